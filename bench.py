@@ -17,9 +17,19 @@ primary workload (C4 = 3840x2160 at 1024 spp is the one named for 8 GPUs).
 
 stdout carries ONE compact JSON line (< 2000 characters: the contract's keys, `roofline` and `cpu_baseline` as objects of a
 few scalars, the other legs as rows of numbers); the FULL record -- everything described below -- goes to --detail-out
-(default gpurun_out/bench_detail_n<N>.json; the line names it in `detail`).
+(the line names it in `detail`; with --full and no --detail-out, a default file under the repository root).
 
-At N = 1 with the default config the record also carries
+A plain run does only what the headline figure needs: set-up, the W warm-up steps, the K timed steps, the outputs of
+--dump-outputs DIR, the line (its roofline from the stats of the timed steps, and the stored counters of
+profiles/pmc_counters.json when they match the kernel sources).  --full adds every other leg: the live rocprofv3
+counters, the legs below and the full record.
+
+--dump-outputs DIR writes what the timed path returned in its last step (rank 0's frame, img[y][x] = (r, g, b), f64) as
+DIR/image.npy; a frame above DUMP_LIMIT bytes is written as a fixed, seeded sample of its pixels instead
+(DIR/image_sample.npy, and their flat indices y * width + x as DIR/image_sample_pixels.npy).  Scene and render seeds are
+fixed, so the same arguments give the same inputs in every run.
+
+With --full, at N = 1 with the default config, the record also carries
   other_configs   C3 full frame (at its named 64 spp) + the band rank 0 of 8 owns of C3, C4 and C5 + the C5 full frame + J1 (a joint
                   tree: 5k spheres + 50k triangles, not a BASELINE config), at a stated spp: rate + roofline each
   lds_sweep       the LDS-staged f32-filter sweep BASELINE.json's configs[1] describes, same frame, same bits
@@ -49,7 +59,7 @@ counts once, as the hardware counters count it.
              and issued lane-instructions, lanes
   traffic    HBM-side bytes per launch from rocprofv3 FETCH_SIZE / WRITE_SIZE (separate passes; FETCH doubled as the
              guide prescribes for gfx950, raw figure beside it); hbm_gbs = traffic / launch time, hbm_frac = / 8 TB/s
-The counters are collected IN THIS RUN when rocprofv3 is on the PATH (child processes `rocprofv3 --pmc ... -- python3
+With --full the counters are collected IN THIS RUN when rocprofv3 is on the PATH (child processes `rocprofv3 --pmc ... -- python3
 bench.py --pmc-leg ...` after the timed region; --no-pmc skips them); otherwise they are read from profiles/pmc_counters.json
 if its kernel-source hash matches this tree, else the fields are null and `counters_source` says so.
 """
@@ -108,6 +118,9 @@ KERNEL_SYMBOL = {1: ("trace_exact_kernel",), 2: ("trace_mixed_kernel",), 3: ("tr
                  6: ("wf_trace_packet_kernel", "wf_trace_kernel", "wf_shade_kernel", "wf_generate_kernel", "trace_bvh_mesh_kernel",
                      "wf_trace_spheres_kernel", "wf_shade_spheres_kernel", "wf_generate_spheres_kernel")}
 PMC_LEG_RENDERS = 2                # renders of the workload a --pmc-leg child does (pmc_leg)
+DUMP_LIMIT = 64 << 20              # bytes --dump-outputs may write; C2's frame (1920 x 1080 x 3 f64, 49.8 MB) fits whole
+DUMP_SAMPLE_PIXELS = 1 << 20       # pixels of the seeded sample of a larger frame (24 MB of values + 8 MB of indices)
+DUMP_SAMPLE_SEED = 0
 # Prices of the algorithmic counts in lane-INSTRUCTIONS (what the chosen algorithm needs at least; a packed instruction
 # counts once, an f64 instruction once -- the scale of SQ_THREAD_CYCLES_VALU).  box test: 6 fma + 9 min/max + 2 widen + 2 cmp;
 # sphere leaf bound (closest-approach terms, rtx_traverse.h): 30; triangle filter: 16; exact sphere test (sphere.rs:19-30):
@@ -134,9 +147,15 @@ def parse():
     ap.add_argument("--no-pmc", action="store_true", help="do not collect rocprofv3 counters in this run")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU time budget of each cpu_baseline mode")
     ap.add_argument("--other-spp", default="C3=64,C3band=64,C4=64,C5=1,C5band=4,J1=8", help="rays per pixel of the other_configs legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline figure (live rocprofv3 counters, the LDS sweep, other configs, "
+                         "partition balance, cpu_baseline) and write the full record; the --no-* options above select among them")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the frame the last timed step returned to DIR/image.npy (f64; a seeded sample of it above %d MB)"
+                         % (DUMP_LIMIT >> 20))
     ap.add_argument("--detail-out", default=None,
-                    help="file that receives the FULL record (per-kernel counters, every leg's roofline object, the log); default "
-                         "gpurun_out/bench_detail_n<N>.json under the repo root.  stdout carries ONE compact line (< 2000 characters)")
+                    help="file that receives the FULL record (per-kernel counters, every leg's roofline object, the log); with --full "
+                         "it defaults to a file under the repository root.  stdout carries ONE compact line (< 2000 characters)")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="N>1 rehearsal on a 1-GPU box: every rank renders on cuda:0 and the gather goes through gloo on host "
                          "copies (RCCL refuses two ranks on one device); the line is marked and is not a measurement")
@@ -453,6 +472,24 @@ def write_detail(full, path, n_gpus):
     return None
 
 
+def dump_outputs(img, out_dir):
+    """--dump-outputs: the (height, width, 3) f64 frame as out_dir/image.npy, or a seeded sample of its pixels when the whole
+    frame is above DUMP_LIMIT bytes; returns the names written."""
+    import numpy as np
+    img = np.ascontiguousarray(img, dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    if img.nbytes <= DUMP_LIMIT:
+        arrays = {"image": img}
+    else:
+        n_px = img.shape[0] * img.shape[1]
+        pick = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n_px, size=min(DUMP_SAMPLE_PIXELS, n_px), replace=False))
+        arrays = {"image_sample": img.reshape(n_px, -1)[pick], "image_sample_pixels": pick.astype(np.float64)}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # rocprofv3 counters, collected in this run
 # ---------------------------------------------------------------------------------------------------------------------
@@ -669,6 +706,8 @@ def main():
     args = parse()
     if args.pmc_leg:
         return pmc_leg(args.pmc_leg)
+    if args.dump_outputs and args.steps < 1:
+        raise SystemExit("--dump-outputs writes the last timed step's frame: it needs --steps >= 1")
     import torch                       # first: one HIP runtime for torch tensors and librtx_hip
     import torch.distributed as dist
 
@@ -758,11 +797,13 @@ def main():
         total_segments = int(tsum[1])
     else:
         total_segments = acc.segments
+    if args.dump_outputs and rank == 0:
+        dump_outputs(full.cpu().numpy(), args.dump_outputs)
 
-    single = world == 1 and args.steps > 0
-    live_pmc = single and not args.no_pmc
+    full_legs = world == 1 and args.steps > 0 and args.full       # the legs beyond the headline figure
+    live_pmc = full_legs and not args.no_pmc
     lds = None
-    if single and args.config == "C2" and not args.no_lds_sweep and acc.kernel != 2:
+    if full_legs and args.config == "C2" and not args.no_lds_sweep and acc.kernel != 2:
         handle.set_config(rcfg.with_kernel(rtx.RTX_KERNEL_MIXED))
         e2, acc2, full2, _ = run(handle, W, H, 0, 1, 1, 2, gather=False)
         c2, pk2, src2 = counters_for("C2:%d:full:2" % spp, KERNEL_SYMBOL[2], live_pmc, log, acc2.launches / max(acc2.n, 1))
@@ -772,7 +813,7 @@ def main():
         handle.set_config(rcfg)
     image_mean = float(full.mean()) if full is not None else float("nan")
     balance = None
-    if single and not args.no_other_configs:
+    if full_legs and not args.no_other_configs:
         # load balance of the 8-way partition (blocks of 8 rows dealt out round-robin): segments of every band of THIS frame, 4 spp
         handle.set_config(rcfg.with_rays_per_pixel(4))
         segs = []
@@ -787,7 +828,7 @@ def main():
     del full
 
     others = None
-    if single and args.config == "C2" and not args.no_other_configs:
+    if full_legs and args.config == "C2" and not args.no_other_configs:
         other_spp = dict(kv.split("=") for kv in args.other_spp.split(","))
         others = []
         full_rate = {}
@@ -856,7 +897,7 @@ def main():
             line["lds_sweep"] = lds
         if others is not None:
             line["other_configs"] = others
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cb = cpu_baseline(args.cpu_seconds)
             line["cpu_baseline"] = cb
             line["speedup_vs_cpu"] = {"primary_rays": value / cb["value"] if cb["value"] > 0 else None,
@@ -867,7 +908,7 @@ def main():
                                               "sweep (which scans the list as the reference does) / the same CPU rate"}
         if log:
             line["log"] = log
-        detail = write_detail(line, args.detail_out, world)
+        detail = write_detail(line, args.detail_out, world) if args.full or args.detail_out else None
         sys.stdout.flush()
         print(compact_line(line, detail), flush=True)          # ONE line, < 2000 characters; the full record is in `detail`
     if world > 1:

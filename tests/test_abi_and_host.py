@@ -485,3 +485,24 @@ def test_bench_roofline_object_is_a_fraction_of_a_real_ceiling(tmp_path, monkeyp
     path = b.write_detail(full, str(tmp_path / "sub" / "detail.json"), 1)
     assert path == os.path.join("sub", "detail.json")               # relative to the repo root (monkeypatched above) when inside it
     assert json.load(open(tmp_path / path))["log"] == full["log"]
+
+
+def test_bench_dump_outputs_whole_frame_or_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs (no GPU): a frame within DUMP_LIMIT is written whole; a larger one as the same seeded pixel sample in
+    every run, with the flat indices it took, in f64 and within the limit."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("_bench", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    img = np.random.default_rng(5).random((9, 16, 3))
+    assert b.dump_outputs(img, str(tmp_path / "whole")) == ["image"]
+    assert np.array_equal(np.load(tmp_path / "whole" / "image.npy"), img)
+    monkeypatch.setattr(b, "DUMP_LIMIT", 1024)
+    monkeypatch.setattr(b, "DUMP_SAMPLE_PIXELS", 32)
+    for run in ("a", "b"):
+        assert b.dump_outputs(img, str(tmp_path / run)) == ["image_sample", "image_sample_pixels"]
+    vals, pix = np.load(tmp_path / "a" / "image_sample.npy"), np.load(tmp_path / "a" / "image_sample_pixels.npy")
+    assert vals.dtype == pix.dtype == np.float64 and vals.shape == (32, 3) and vals.nbytes + pix.nbytes <= 1024
+    assert len(set(pix.tolist())) == 32 and np.array_equal(vals, img.reshape(-1, 3)[pix.astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "b" / "image_sample.npy"), vals) and np.array_equal(np.load(tmp_path / "b" / "image_sample_pixels.npy"), pix)

@@ -1747,7 +1747,7 @@ def test_bench_line_contract(gpu):
     """bench.py at a reduced sample count (counters off: they are the next test): one JSON line with the contract's keys,
     strong scaling by default, roofline objects that are fractions of a real ceiling for the value kernel, the LDS sweep
     and the three other configs, a cpu_baseline on the benchmark's own view, and the two kernels' frames bit-identical."""
-    d = _bench(["--steps", "1", "--warmup", "0", "--spp", "2", "--cpu-seconds", "1", "--other-spp", "C3=1,C3band=8,C4=2,C5=1,C5band=1,J1=1", "--no-pmc",
+    d = _bench(["--full", "--steps", "1", "--warmup", "0", "--spp", "2", "--cpu-seconds", "1", "--other-spp", "C3=1,C3band=8,C4=2,C5=1,C5band=1,J1=1", "--no-pmc",
                 "--detail-out", "gpurun_out/test_bench_detail.json"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "other_configs", "lds_sweep"):
@@ -1793,13 +1793,37 @@ def test_bench_line_contract(gpu):
     assert st[0]["segments"] == 1920 * 1080 * 2 and all(0 < s_["frac"] <= 1 for s_ in st)
 
 
+def test_bench_plain_run_dumps_the_timed_frame(gpu, tmp_path):
+    """A plain bench run (no --full) times exactly --steps steps and runs none of the other legs; --dump-outputs writes the
+    frame of its last timed step, which is the frame the library renders for the same scene and config."""
+    import importlib.util
+    import rust_raytracing_amd as rtx
+    from rust_raytracing_amd import scenes
+    out = tmp_path / "out"
+    d = _bench(["--steps", "2", "--warmup", "1", "--spp", "2", "--dump-outputs", str(out), "--detail-out", str(tmp_path / "detail.json")])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    for key in ("cpu_baseline", "lds_sweep", "other_configs", "partition_balance"):
+        assert key not in d and key not in d["_line"], key
+    assert "of this run" not in d["roofline"]["counters_source"]                  # no rocprofv3 passes
+    assert sorted(os.listdir(out)) == ["image.npy"]
+    img = np.load(out / "image.npy")
+    assert img.shape == (1080, 1920, 3) and img.dtype == np.float64
+    assert abs(float(img.mean()) - d["image_mean"]) <= 1e-12
+    spec = importlib.util.spec_from_file_location("_bench", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    ref = rtx.Scene.from_packed(rtx.Config(rays_per_pixel=2, seed=scenes.RENDER_SEED), rtx.Camera(*scenes.CAMERA),
+                                b.make_objects(b.CONFIGS["C2"])).render(1920, 1080)
+    assert np.array_equal(img, ref)
+
+
 def test_bench_collects_counters_in_the_run(gpu):
     """With rocprofv3 on the PATH the roofline's counters come from this very run (child passes under rocprofv3 --pmc):
     lane-ops issued vs the VALU ceiling, HBM-side bytes vs 8 TB/s -- both fractions below 1."""
     import shutil
     if shutil.which("rocprofv3") is None and not os.path.exists("/opt/rocm/bin/rocprofv3"):
         pytest.skip("rocprofv3 not installed")
-    d = _bench(["--steps", "1", "--warmup", "0", "--spp", "2", "--no-cpu-baseline", "--no-lds-sweep", "--no-other-configs"])
+    d = _bench(["--full", "--steps", "1", "--warmup", "0", "--spp", "2", "--no-cpu-baseline", "--no-lds-sweep", "--no-other-configs"])
     r = d["roofline"]
     assert "of this run" in r["counters_source"], (r["counters_source"], d.get("log"))
     _check_roofline(r)
@@ -1818,7 +1842,7 @@ def test_bench_two_rank_rehearsal_on_one_gpu(gpu):
     (same pixels, same samples), and so is the segment count."""
     import sys
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
-    common = ["--steps", "1", "--warmup", "0", "--spp", "4", "--no-cpu-baseline", "--no-lds-sweep", "--no-other-configs", "--no-pmc"]
+    common = ["--steps", "1", "--warmup", "0", "--spp", "4", "--no-cpu-baseline", "--no-lds-sweep", "--no-other-configs", "--no-pmc", "--full"]
     d2 = _bench(["--gpus", "2", "--rehearse-on-one-gpu"] + common, env=env,
                 launcher=[sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                           "127.0.0.1", "--master-port", "29653"])

@@ -8,8 +8,8 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd $R
-echo "[gpu_profile] bench.py (N=1, default flags)"
-python bench.py --steps 3 --warmup 1 --detail-out $OUT/bench_detail_n1.json > $OUT/bench_n1.json 2> $OUT/bench_n1.err || { tail -30 $OUT/bench_n1.err; exit 1; }
+echo "[gpu_profile] bench.py --full (N=1)"
+python bench.py --full --steps 3 --warmup 1 --detail-out $OUT/bench_detail_n1.json > $OUT/bench_n1.json 2> $OUT/bench_n1.err || { tail -30 $OUT/bench_n1.err; exit 1; }
 python - <<PY
 import json
 line = open("$OUT/bench_n1.json").read().strip().splitlines()[-1]
@@ -33,7 +33,7 @@ PY
 export TMPDIR=/tmp
 cd /tmp
 echo "[gpu_profile] rocprofv3 --kernel-trace --stats of the same command"
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-pmc --no-other-configs > $OUT/trace.log 2>&1 || { tail -20 $OUT/trace.log; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-pmc --no-other-configs > $OUT/trace.log 2>&1 || { tail -20 $OUT/trace.log; exit 1; }
 find $OUT/trace -name "*kernel_stats.csv" | head -3
 f=$(find $OUT/trace -name "*kernel_stats.csv" | head -1)
 head -8 "$f" | cut -c1-200
