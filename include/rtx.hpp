@@ -229,6 +229,18 @@ public:
         return out;
     }
 
+    // closest_object (scene.rs:243-251) for each ray (rtx_closest_hits: upload to device 0, query, copy back).  A miss has
+    // object == -1, distance == +inf and NaN position / normal.  Directions are used as given.
+    std::vector<RtxHit> closest_hits(const std::vector<RtxRay> &rays) const
+    {
+        std::vector<RtxHit> hits(rays.size());
+        std::vector<RtxObject> packed = pack();
+        RtxScene sc = to_c(packed);
+        int32_t rc = rtx_closest_hits(&sc, rays.data(), rays.size(), hits.data());
+        if (rc != RTX_OK) throw Panic(rc, rtx_last_error());
+        return hits;
+    }
+
     std::vector<RtxObject> pack() const
     {
         std::vector<RtxObject> packed(objects.size());
@@ -331,6 +343,17 @@ public:
         return st;
     }
     void set_scratch_limit(std::uint64_t bytes) { check(rtx_scene_set_scratch_limit(h_, bytes)); }
+    // closest_object for n rays of DEVICE memory (d_rays[n] -> d_hits[n], not overlapping), on the HIP stream it names; with
+    // stats = nullptr the call returns once the work is enqueued
+    void closest_hits(const RtxRay *d_rays, std::size_t n, RtxHit *d_hits, void *hip_stream = nullptr, RtxStats *stats = nullptr)
+    {
+        check(rtx_scene_closest_hits(h_, d_rays, n, d_hits, hip_stream, stats));
+    }
+    // the pick buffer: d_hits[height][width] = the hit of each pixel's primary ray without the focal / non-focal offsets
+    void primary_hits(std::size_t width, std::size_t height, RtxHit *d_hits, void *hip_stream = nullptr, RtxStats *stats = nullptr)
+    {
+        check(rtx_scene_primary_hits(h_, (uint32_t)width, (uint32_t)height, d_hits, hip_stream, stats));
+    }
 
 private:
     friend class Scene;

@@ -202,6 +202,20 @@ typedef struct RtxStats {
 
 typedef struct RtxSceneHandle_ *RtxSceneHandle;
 
+/* Ray queries (rtx_scene_closest_hits, rtx_scene_primary_hits, rtx_closest_hits): one ray, and the answer of closest_object
+ * (scene.rs:243-251) for it. */
+typedef struct RtxRay {
+    double position[3];
+    double direction[3];         /* used as given: no hidden norm() (the shape tests normalise where the reference does) */
+} RtxRay;
+
+typedef struct RtxHit {
+    double  position[3];         /* position + direction * distance (scene.rs:234); NaN when nothing is hit */
+    double  normal[3];           /* Object::normal_at(position) of the winner (object.rs:37-39); NaN when nothing is hit */
+    double  distance;            /* the winning Object::distance; +inf when nothing is hit */
+    int64_t object;              /* the winner's index in Scene.objects (the first minimal distance wins); -1: nothing is hit */
+} RtxHit;
+
 /* The layouts a binding has to reproduce (rust/src/raytracing/hip.rs: #[repr(C)]; rust-raytracing_amd/abi.py: ctypes;
  * tests/test_abi_and_host.py checks both against these numbers). */
 #ifdef __cplusplus
@@ -220,6 +234,9 @@ RTX_STATIC_ASSERT(sizeof(RtxScene) == 272 && offsetof(RtxScene, camera) == 56 &&
 RTX_STATIC_ASSERT(sizeof(RtxStats) == 104 && offsetof(RtxStats, trace_ms) == 32 && offsetof(RtxStats, box_tests) == 56 &&
                   offsetof(RtxStats, trace_launches) == 64 && offsetof(RtxStats, kernel) == 68 && offsetof(RtxStats, stage1_ms) == 72 &&
                   offsetof(RtxStats, stage1_exact_tests) == 96, "RtxStats layout");
+RTX_STATIC_ASSERT(sizeof(RtxRay) == 48 && offsetof(RtxRay, direction) == 24, "RtxRay layout");
+RTX_STATIC_ASSERT(sizeof(RtxHit) == 64 && offsetof(RtxHit, normal) == 24 && offsetof(RtxHit, distance) == 48 &&
+                  offsetof(RtxHit, object) == 56, "RtxHit layout");
 
 /* -- library ----------------------------------------------------------------------------- */
 int32_t     rtx_version(void);
@@ -307,6 +324,30 @@ uint32_t rtx_blocks_row_count(uint32_t height, uint32_t block_rows, uint32_t par
 int32_t rtx_render_blocks(RtxSceneHandle scene, uint32_t width, uint32_t height,
                           uint32_t block_rows, uint32_t part, uint32_t n_parts,
                           double *d_out_rgb, void *stream, RtxStats *stats);
+
+/* -- ray queries on an uploaded scene ----------------------------------------------------------
+ * Each answer is exactly what the reference's closest_object(position, direction) returns over Scene.objects (the first minimal
+ * distance wins, is_normal && is_sign_positive filter), filled in as RtxHit describes; a scene without objects hits nothing.
+ * RtxConfig.kernel of the handle picks the path: RTX_KERNEL_EXACT tests every shape of every ray in f64; any other id walks the
+ * scene's tree (query_closest_kernel, DESIGN.md "Ray queries") where it has one -- the same bits.  Rays the walk's f32 bounds were
+ * not derived for (|d.d - 1| > 2^-40 or a non-finite component, an origin beyond the tree's far range) are swept exhaustively:
+ * slower, the same bits.  The "Streams" rules apply; RtxConfig.tuning bits of RTX_TUNE_LAB_MASK are refused as for renders.
+ * With stats == NULL the call returns once the work is enqueued on `stream`; else it synchronises and fills stats: segments = n,
+ * exact_tests, filter_tests, box_tests, trace_ms, trace_launches = 1, kernel = RTX_KERNEL_BVH (a tree walk) or RTX_KERNEL_EXACT.
+ *
+ * rtx_scene_closest_hits: d_rays / d_hits are DEVICE arrays of n entries (must not overlap); n < 2^32. */
+int32_t rtx_scene_closest_hits(RtxSceneHandle scene, const RtxRay *d_rays, uint64_t n, RtxHit *d_hits,
+                               void *stream, RtxStats *stats);
+
+/* The pick buffer: per pixel of a width x height frame, the hit of the ray render_pixel builds when focal_offset =
+ * non_focal_offset = 0 (scene.rs:196-209): position = camera.position, direction = ((p + get_ray_dir(x/w, y/h, vfov) *
+ * focal_length) - p).norm().  d_hits: DEVICE array [y][x], row 0 = the reference's row 0 (as rtx_render); width * height < 2^32.
+ * Independent of the RNG, the seed and both offsets of the handle's config. */
+int32_t rtx_scene_primary_hits(RtxSceneHandle scene, uint32_t width, uint32_t height, RtxHit *d_hits,
+                               void *stream, RtxStats *stats);
+
+/* One-shot host form (as rtx_render is to rtx_render_rows): uploads to device 0, queries, copies back.  rays / hits: HOST arrays. */
+int32_t rtx_closest_hits(const RtxScene *scene, const RtxRay *rays, uint64_t n, RtxHit *hits);
 
 /* Device epilogue of render_to_image on a full device image (scene.rs:175-178):
  * d_rgb height*width*3 doubles -> d_rgb8 height*width*3 bytes, flipped vertically. */

@@ -22,11 +22,12 @@ from . import abi
 from .abi import (RTX_TUNE_NO_TILES, RTX_TUNE_BVH_CLASSIC, RTX_TUNE_NO_QNODES, RTX_TUNE_NO_PACKETS, RTX_TUNE_WF_PURE, RTX_TUNE_ONE_STAGE,
                   RTX_TUNE_TWO_STAGE, RTX_TUNE_BVH_MEDIAN, RTX_TUNE_TRI_LEAF_SHIFT, RTX_TUNE_THRESH_SHIFT, RTX_TUNE_SORT_SURVIVORS, RTX_TUNE_PK_LDS_STACK, RTX_TUNE_STAGE2_POOL, RTX_TUNE_STAGE2_PAIR, RTX_TUNE_NO_CUT, RTX_TUNE_BEAMS, RTX_TUNE_INLINE_LEAVES, RTX_TUNE_STAGE2_SLOTS, RTX_TUNE_HALVES, RTX_TUNE_NO_HALVES, RTX_TUNE_NO_TILE_LISTS)
 from .abi import (OBJECT_DTYPE, RTX_KERNEL_WAVEFRONT, RTX_KERNEL_AUTO, RTX_KERNEL_BVH, RTX_KERNEL_EXACT, RTX_KERNEL_MIXED, RTX_KERNEL_MIXED_VERIFY, RTX_KERNEL_BVH_REGROUP,
-                  RTX_PLANE, RTX_SPHERE, RTX_TRIANGLE, RtxError, load_library)
+                  RTX_PLANE, RTX_SPHERE, RTX_TRIANGLE, RtxError, load_library, RAY_DTYPE, HIT_DTYPE)
 
 __all__ = ["LabKernel", "Vector3", "Material", "Sphere", "Plane", "Triangle", "Object", "Config", "Camera", "Scene",
            "SceneHandle", "RtxError", "device_count", "pack_objects", "OBJECT_DTYPE",
-           "RTX_KERNEL_AUTO", "RTX_KERNEL_EXACT", "RTX_KERNEL_MIXED", "RTX_KERNEL_MIXED_VERIFY", "RTX_KERNEL_BVH", "RTX_KERNEL_BVH_REGROUP", "RTX_KERNEL_WAVEFRONT", "debug_host_scene"]
+           "RTX_KERNEL_AUTO", "RTX_KERNEL_EXACT", "RTX_KERNEL_MIXED", "RTX_KERNEL_MIXED_VERIFY", "RTX_KERNEL_BVH", "RTX_KERNEL_BVH_REGROUP", "RTX_KERNEL_WAVEFRONT", "debug_host_scene",
+           "RAY_DTYPE", "HIT_DTYPE", "make_rays"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -299,6 +300,24 @@ def device_count():
     return int(load_library().rtx_device_count())
 
 
+def make_rays(origins, directions):
+    """(n, 3) origins and (n, 3) directions (or one of either, broadcast) -> a RAY_DTYPE array of n RtxRay.  Directions are used as
+    given (no normalisation)."""
+    o = np.asarray(origins, dtype=np.float64)
+    d = np.asarray(directions, dtype=np.float64)
+    o, d = np.broadcast_arrays(o.reshape(-1, 3) if o.ndim != 1 else o, d.reshape(-1, 3) if d.ndim != 1 else d)
+    o, d = np.atleast_2d(o), np.atleast_2d(d)
+    rays = np.zeros(len(o), dtype=RAY_DTYPE)
+    rays["position"] = o
+    rays["direction"] = d
+    return rays
+
+
+def _split_hits(hits):
+    """RtxHit records -> (distance, object, position, normal) numpy arrays"""
+    return (hits["distance"].copy(), hits["object"].copy(), hits["position"].copy(), hits["normal"].copy())
+
+
 class Scene:
     def __init__(self, config=None, camera=None):                   # Scene::new scene.rs:112-118 / Default :86-94
         self.config = config if config is not None else Config()
@@ -353,6 +372,17 @@ class Scene:
     def upload(self, device=0, lab=None):
         """lab: None = the library the config asks for (Config.wants_lab()); True = librtx_hip_lab.so whatever the config says."""
         return SceneHandle(self, device, lab)
+
+    def closest_hits(self, origins, directions):
+        """closest_object (scene.rs:243-251) for each ray (rtx_closest_hits: upload to device 0, query, copy back).  Returns numpy
+        (distance (n,), object (n,) int64 -- -1: nothing hit, position (n, 3), normal (n, 3)); a miss has +inf and NaNs."""
+        rays = make_rays(origins, directions)
+        hits = np.zeros(len(rays), dtype=HIT_DTYPE)
+        packed = self.packed()
+        sc = _scene_c(self.config, self.camera, packed)
+        lib = load_library(self.config.wants_lab())
+        abi.check(lib.rtx_closest_hits(C.byref(sc), rays.ctypes.data, len(rays), hits.ctypes.data), lib)
+        return _split_hits(hits)
 
 
 class SceneHandle:
@@ -418,6 +448,44 @@ class SceneHandle:
                                               C.c_void_p(int(d_out_ptr)), C.c_void_p(int(stream)) if stream else None,
                                               C.byref(stats) if want_stats else None))
         return stats if want_stats else None
+
+    def closest_hits(self, d_rays_ptr, n, d_hits_ptr, stream=None, want_stats=True):
+        """closest_object for n rays: d_rays_ptr / d_hits_ptr are device addresses of n RtxRay (48 B) / RtxHit (64 B) records (e.g.
+        torch tensors' data_ptr()).  want_stats=False: asynchronous on `stream`."""
+        stats = abi.RtxStats()
+        self._check(self._lib.rtx_scene_closest_hits(self._h, C.c_void_p(int(d_rays_ptr)), int(n), C.c_void_p(int(d_hits_ptr)),
+                                                     C.c_void_p(int(stream)) if stream else None, C.byref(stats) if want_stats else None))
+        return stats if want_stats else None
+
+    def primary_hits(self, width, height, d_hits_ptr, stream=None, want_stats=True):
+        """The pick buffer: the hit of every pixel's zero-offset primary ray, width * height RtxHit records [y][x] at d_hits_ptr."""
+        stats = abi.RtxStats()
+        self._check(self._lib.rtx_scene_primary_hits(self._h, int(width), int(height), C.c_void_p(int(d_hits_ptr)),
+                                                     C.c_void_p(int(stream)) if stream else None, C.byref(stats) if want_stats else None))
+        return stats if want_stats else None
+
+    def query(self, origins, directions):
+        """Host convenience of closest_hits (device buffers through torch): numpy (distance, object, position, normal)."""
+        import torch
+        rays = make_rays(origins, directions)
+        n = len(rays)
+        dev = torch.device("cuda", self.device)
+        d_rays = torch.from_numpy(rays.view(np.uint8)).to(dev)
+        d_hits = torch.empty(max(n, 1) * HIT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        self.closest_hits(d_rays.data_ptr(), n, d_hits.data_ptr(), want_stats=True)          # (synchronises)
+        hits = d_hits[:n * HIT_DTYPE.itemsize].cpu().numpy().view(HIT_DTYPE)
+        return _split_hits(hits)
+
+    def pick(self, width, height):
+        """Host convenience of primary_hits: numpy (distance, object, position, normal), each indexed [y][x]."""
+        import torch
+        n = int(width) * int(height)
+        d_hits = torch.empty(max(n, 1) * HIT_DTYPE.itemsize, dtype=torch.uint8, device=torch.device("cuda", self.device))
+        torch.cuda.synchronize(self.device)
+        self.primary_hits(width, height, d_hits.data_ptr(), want_stats=True)
+        hits = d_hits[:n * HIT_DTYPE.itemsize].cpu().numpy().view(HIT_DTYPE).reshape(int(height), int(width))
+        return _split_hits(hits)
 
     def close(self):
         if self._h:

@@ -71,6 +71,20 @@ class RtxStats(C.Structure):
                 ("stage1_exact_tests", C.c_uint64)]
 
 
+class RtxRay(C.Structure):
+    _fields_ = [("position", C.c_double * 3), ("direction", C.c_double * 3)]
+
+
+class RtxHit(C.Structure):
+    _fields_ = [("position", C.c_double * 3), ("normal", C.c_double * 3), ("distance", C.c_double), ("object", C.c_int64)]
+
+
+# the same layouts as numpy records (arrays of rays / answers)
+RAY_DTYPE = np.dtype([("position", "<f8", (3,)), ("direction", "<f8", (3,))])
+HIT_DTYPE = np.dtype([("position", "<f8", (3,)), ("normal", "<f8", (3,)), ("distance", "<f8"), ("object", "<i8")])
+assert RAY_DTYPE.itemsize == C.sizeof(RtxRay) == 48 and HIT_DTYPE.itemsize == C.sizeof(RtxHit) == 64
+
+
 # every symbol include/rtx_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("rtx_version", C.c_int32, []),
@@ -94,6 +108,9 @@ SYMBOLS = [
     ("rtx_blocks_row_count", C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     ("rtx_render_blocks", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                       C.c_void_p, C.c_void_p, C.POINTER(RtxStats)]),
+    ("rtx_scene_closest_hits", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(RtxStats)]),
+    ("rtx_scene_primary_hits", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(RtxStats)]),
+    ("rtx_closest_hits", C.c_int32, [C.POINTER(RtxScene), C.c_void_p, C.c_uint64, C.c_void_p]),
     ("rtx_quantize_image_device", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p]),
     ("rtx_debug_math", C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
     ("rtx_debug_paths", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),

@@ -24,7 +24,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librtx_hip.so")
 LAB_LIB = os.path.join(HERE, "librtx_hip_lab.so")
 OBJ_DIR = os.path.join(HERE, "build")
-SOURCES = ["rtx_kernels.hip", "rtx_bvh_spheres.hip", "rtx_bvh_mesh.hip", "rtx_wavefront.hip", "rtx_api.hip"]
+SOURCES = ["rtx_kernels.hip", "rtx_bvh_spheres.hip", "rtx_bvh_mesh.hip", "rtx_wavefront.hip", "rtx_query.hip", "rtx_api.hip"]
 LAB_SOURCES = SOURCES + ["rtx_bvh.hip", "rtx_bvh_spheres_pool.hip", "rtx_bvh_regroup.hip", "rtx_wavefront_spheres.hip"]
 HEADERS = ["rtx_math.h", "rtx_scene.h", "rtx_bvh.h", "rtx_device.h", "rtx_traverse.h", "rtx_mesh_step.h", "rtx_wavefront.h",
            "rtx_launch.h", "rtx_bvh_spheres_lab.h"]

@@ -722,6 +722,53 @@ static uint32_t blocks_row_count(uint32_t height, uint32_t block, uint32_t part,
     return (uint32_t)rows;
 }
 
+// ---- trig tables of get_ray_dir (scene.rs:213-220) for the rows of a band (render_band, the pick buffer of rtx_scene_primary_hits)
+static int32_t ensure_tables(RtxSceneHandle_ *h, uint32_t width, uint32_t height, uint32_t row_begin, uint32_t row_stride,
+                             uint32_t row_block, uint32_t n_rows, hipStream_t stream)
+{
+    // host libm, one value per column / local row.
+    // glibc's sincos(), called by name: the reference takes f64::sin and f64::cos of the same angle, and a compiler on a GNU target
+    // turns such a pair into ONE sincos call (LLVM does for rustc's output, gcc does for the test suite's CPU checker) -- whose results
+    // differ from sin() / cos() in the last place on ~0.07 % of arguments (glibc 2.35).  Left to the optimiser, this code had one loop
+    // merged and one not: one image row in ~100 started its primary rays an ulp off the CPU's (found by the path transcripts,
+    // rtx_debug_paths).  Spelled out, both sides call the same function whatever the optimiser does.
+    const size_t tdbl = 2 * (size_t)width + 2 * (size_t)n_rows;
+    const bool t_same = h->t_valid && h->t_w == width && h->t_h == height && h->t_rb == row_begin &&
+                        h->t_rs == row_stride && h->t_blk == row_block && h->t_nr == n_rows && h->t_fov == h->cam.fov;
+    if (!t_same) {
+        if (h->have_done) RTX_HIP_CHECK(hipEventSynchronize(h->ev_done));   // an earlier render's enqueued copy may still read h_tables
+        if (h->h_tables_doubles < tdbl) {
+            if (h->h_tables) RTX_HIP_CHECK(hipHostFree(h->h_tables));
+            h->h_tables = nullptr; h->h_tables_doubles = 0;
+            RTX_HIP_CHECK(hipHostMalloc((void **)&h->h_tables, tdbl * sizeof(double), hipHostMallocDefault));
+            h->h_tables_doubles = tdbl;
+        }
+        {
+            size_t have = h->tables_doubles * sizeof(double);
+            if (int32_t rc = grow((void **)&h->tables, &have, tdbl * sizeof(double))) return rc;
+            h->tables_doubles = have / sizeof(double);
+        }
+        const double fov = h->cam.fov;
+        const double vertical_fov = (double)height / (double)width * fov;             // scene.rs:145
+        double *sx = h->h_tables, *cx = sx + width, *sy = cx + width, *cy = sy + n_rows;
+        for (uint32_t x = 0; x < width; ++x) {
+            double u = (double)x / (double)width;                                       // scene.rs:157
+            double angle_x = fov * (u - 0.5);                                           // scene.rs:214
+            ::sincos(angle_x, &sx[x], &cx[x]);
+        }
+        for (uint32_t k = 0; k < n_rows; ++k) {
+            const uint32_t kb = k / row_block;
+            double v = (double)(row_begin + kb * row_stride + (k - kb * row_block)) / (double)height;   // scene.rs:153 (image_row)
+            double angle_y = vertical_fov * (v - 0.5);                                  // scene.rs:215
+            ::sincos(angle_y, &sy[k], &cy[k]);
+        }
+        RTX_HIP_CHECK(hipMemcpyAsync(h->tables, h->h_tables, tdbl * sizeof(double), hipMemcpyHostToDevice, stream));
+        h->t_w = width; h->t_h = height; h->t_rb = row_begin; h->t_rs = row_stride; h->t_blk = row_block; h->t_nr = n_rows;
+        h->t_fov = fov; h->t_valid = true;
+    }
+    return RTX_OK;
+}
+
 // The band local row k -> image row row_begin + (k / row_block) * row_stride + k % row_block, k < n_rows (rtx_device.h, image_row).
 static int32_t render_band(RtxSceneHandle h, uint32_t width, uint32_t height, uint32_t row_begin, uint32_t row_stride,
                            uint32_t row_block, uint32_t n_rows, double *d_out_rgb, void *stream_, RtxStats *stats)
@@ -848,46 +895,7 @@ static int32_t render_band(RtxSceneHandle h, uint32_t width, uint32_t height, ui
         if (batch > fit32) batch = fit32;
     }
 
-    // ---- trig tables of get_ray_dir (scene.rs:213-220), host libm, one value per column / local row.
-    // glibc's sincos(), called by name: the reference takes f64::sin and f64::cos of the same angle, and a compiler on a GNU target
-    // turns such a pair into ONE sincos call (LLVM does for rustc's output, gcc does for the test suite's CPU checker) -- whose results
-    // differ from sin() / cos() in the last place on ~0.07 % of arguments (glibc 2.35).  Left to the optimiser, this code had one loop
-    // merged and one not: one image row in ~100 started its primary rays an ulp off the CPU's (found by the path transcripts,
-    // rtx_debug_paths).  Spelled out, both sides call the same function whatever the optimiser does.
-    const size_t tdbl = 2 * (size_t)width + 2 * (size_t)n_rows;
-    const bool t_same = h->t_valid && h->t_w == width && h->t_h == height && h->t_rb == row_begin &&
-                        h->t_rs == row_stride && h->t_blk == row_block && h->t_nr == n_rows && h->t_fov == h->cam.fov;
-    if (!t_same) {
-        if (h->have_done) RTX_HIP_CHECK(hipEventSynchronize(h->ev_done));   // an earlier render's enqueued copy may still read h_tables
-        if (h->h_tables_doubles < tdbl) {
-            if (h->h_tables) RTX_HIP_CHECK(hipHostFree(h->h_tables));
-            h->h_tables = nullptr; h->h_tables_doubles = 0;
-            RTX_HIP_CHECK(hipHostMalloc((void **)&h->h_tables, tdbl * sizeof(double), hipHostMallocDefault));
-            h->h_tables_doubles = tdbl;
-        }
-        {
-            size_t have = h->tables_doubles * sizeof(double);
-            if (int32_t rc = grow((void **)&h->tables, &have, tdbl * sizeof(double))) return rc;
-            h->tables_doubles = have / sizeof(double);
-        }
-        const double fov = h->cam.fov;
-        const double vertical_fov = (double)height / (double)width * fov;             // scene.rs:145
-        double *sx = h->h_tables, *cx = sx + width, *sy = cx + width, *cy = sy + n_rows;
-        for (uint32_t x = 0; x < width; ++x) {
-            double u = (double)x / (double)width;                                       // scene.rs:157
-            double angle_x = fov * (u - 0.5);                                           // scene.rs:214
-            ::sincos(angle_x, &sx[x], &cx[x]);
-        }
-        for (uint32_t k = 0; k < n_rows; ++k) {
-            const uint32_t kb = k / row_block;
-            double v = (double)(row_begin + kb * row_stride + (k - kb * row_block)) / (double)height;   // scene.rs:153 (image_row)
-            double angle_y = vertical_fov * (v - 0.5);                                  // scene.rs:215
-            ::sincos(angle_y, &sy[k], &cy[k]);
-        }
-        RTX_HIP_CHECK(hipMemcpyAsync(h->tables, h->h_tables, tdbl * sizeof(double), hipMemcpyHostToDevice, stream));
-        h->t_w = width; h->t_h = height; h->t_rb = row_begin; h->t_rs = row_stride; h->t_blk = row_block; h->t_nr = n_rows;
-        h->t_fov = fov; h->t_valid = true;
-    }
+    if (int32_t rc = ensure_tables(h, width, height, row_begin, row_stride, row_block, n_rows, stream)) return rc;
 
     // ---- scratch: one RGB per ray of a sample batch, the running per-pixel sum, the SoA ray state
     if (spp > 0) {
@@ -1217,6 +1225,88 @@ static int32_t render_band(RtxSceneHandle h, uint32_t width, uint32_t height, ui
     return RTX_OK;
 }
 
+// ---- ray queries: closest_object (scene.rs:243-251) for the caller's rays (width == 0) or for the zero-offset primary ray of every
+// pixel of a width x height frame (the pick buffer).  The handle's conventions: status codes, "Streams", stats == NULL = asynchronous.
+static int32_t query_run(RtxSceneHandle_ *h, const RtxRay *d_rays, uint32_t width, uint32_t height, uint64_t n, RtxHit *d_hits,
+                         void *stream_, RtxStats *stats)
+{
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (n == 0) return RTX_OK;
+    RTX_HIP_CHECK(hipSetDevice(h->device));
+    if (int32_t rc = check_watchdog(h, false)) return rc;
+    if (int32_t rc = adopt_stream(h, stream)) return rc;
+    struct DoneGuard {                       // (render_band's: whatever way this call leaves, a later call on another stream waits for it)
+        RtxSceneHandle_ *h; hipStream_t stream;
+        ~DoneGuard() {
+            if (hipEventRecord(h->ev_done, stream) == hipSuccess) h->have_done = true;
+            else { (void)hipGetLastError(); (void)hipDeviceSynchronize(); h->have_done = false; }
+        }
+    } done_guard{h, stream};
+
+    // RTX_KERNEL_EXACT sweeps every ray; any other id walks the tree when the scene has one a query kernel can walk
+    const bool walk = h->cfg.kernel != RTX_KERNEL_EXACT && query_tree_kind(h->sv) != 0u;
+    RowsView rv{};
+    if (width != 0) {                        // the pick buffer: one band of all rows, ray i = pixel i (row-major, row 0 = the reference's)
+        if (int32_t rc = ensure_tables(h, width, height, 0u, 1u, 1u, height, stream)) return rc;
+        rv.width = width; rv.height = height;
+        rv.row_begin = 0; rv.row_stride = 1; rv.n_rows = height; rv.row_block = 1;
+        rv.npix = width * height;
+        rv.div_width = make_fastdiv(width); rv.div_row_block = make_fastdiv(1u); rv.div_npix = make_fastdiv(rv.npix);
+        rv.div_tiles_x = make_fastdiv(0u); rv.div_per_sample = make_fastdiv(rv.npix);
+        rv.sin_x = h->tables; rv.cos_x = h->tables + width;
+        rv.sin_y = h->tables + 2 * (size_t)width; rv.cos_y = rv.sin_y + height;
+        rv.n_samples = 1; rv.n_rays = n;
+        RTX_HIP_CHECK(hipMemcpyAsync(h->d_rv, &rv, sizeof(RowsView), hipMemcpyHostToDevice, stream));   // pageable: staged before return
+    }
+    // the walk's HBM stack columns, within the handle's scratch cap (fewer entries than a deep tree wants: the rays whose stack
+    // overflows are swept -- the same bits)
+    uint32_t spill_entries = walk ? query_spill_entries(h->sv) : 0u;
+    if (spill_entries != 0u) {
+        size_t cap_bytes = h->scratch_limit ? h->scratch_limit : kDefaultScratchBytes;
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+            const size_t avail = (free_b + h->state_bytes) / 4 * 3;
+            if (cap_bytes > avail) cap_bytes = avail;
+        } else (void)hipGetLastError();
+        const size_t per_entry = query_spill_bytes(1u, h->n_cus);
+        if ((size_t)spill_entries * per_entry > cap_bytes) spill_entries = (uint32_t)(cap_bytes / per_entry);
+        if (int32_t rc = grow((void **)&h->state, &h->state_bytes, query_spill_bytes(spill_entries, h->n_cus))) return rc;
+    }
+    if (h->sv_dirty) {
+        RTX_HIP_CHECK(hipMemcpyAsync(h->d_sv, &h->sv, sizeof(SceneView), hipMemcpyHostToDevice, stream));
+        h->sv_dirty = false;
+    }
+    RTX_HIP_CHECK(hipMemsetAsync(h->counters, 0, sizeof(Counters) * kCounterShards, stream));
+    RTX_HIP_CHECK(hipMemsetAsync(h->work_counter, 0, sizeof(unsigned long long), stream));
+    QueryArgs qa{};
+    qa.rays = reinterpret_cast<const QueryRay *>(d_rays);
+    qa.rv = width != 0 ? h->d_rv : nullptr;
+    qa.hits = reinterpret_cast<QueryHit *>(d_hits);
+    qa.n = n;
+    if (stats) RTX_HIP_CHECK(hipEventRecord(h->ev[0], stream));
+    RTX_HIP_CHECK(launch_query_closest(h->d_sv, h->sv, qa, walk, spill_entries ? reinterpret_cast<uint32_t *>(h->state) : nullptr,
+                                       spill_entries, h->n_cus, h->counters, h->work_counter, stream));
+    if (stats) {
+        RTX_HIP_CHECK(hipEventRecord(h->ev[1], stream));
+        RTX_HIP_CHECK(hipEventSynchronize(h->ev[1]));
+        float ms = 0.f;
+        RTX_HIP_CHECK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+        Counters host[kCounterShards];
+        RTX_HIP_CHECK(hipMemcpy(host, h->counters, sizeof host, hipMemcpyDeviceToHost));
+        for (int k = 0; k < kCounterShards; ++k) {
+            stats->segments += host[k].segments;
+            stats->exact_tests += host[k].exact_tests;
+            stats->filter_tests += host[k].filter_tests;
+        }
+        for (int k = 2; k < kCounterShards; ++k) stats->box_tests += host[k].pad_;
+        stats->trace_ms = ms;
+        stats->trace_launches = 1;
+        stats->kernel = walk ? RTX_KERNEL_BVH : RTX_KERNEL_EXACT;
+    }
+    return RTX_OK;
+}
+
 extern "C" {
 
 int32_t rtx_render_rows(RtxSceneHandle h, uint32_t width, uint32_t height, uint32_t row_begin, uint32_t row_stride,
@@ -1337,7 +1427,7 @@ static int32_t render_common(const RtxScene *scene, uint32_t width, uint32_t hei
                 std::fprintf(stderr, "[rtx_hip] device %d band %u/%u: rays %llu segments %llu exact %llu filter %llu mismatches %llu trace %.3f ms resolve %.3f ms\n",
                              dev, k, n_dev, (unsigned long long)st.primary_rays, (unsigned long long)st.segments, (unsigned long long)st.exact_tests,
                              (unsigned long long)st.filter_tests, (unsigned long long)st.filter_mismatches, st.trace_ms, st.resolve_ms);
-            if (w.rc == RTX_OK && n_rows && as_u8) hip(launch_quantize_values(d_band, d_band8, n_vals, stream), "quantize_values_kernel");
+            if (w.rc == RTX_OK && n_rows && as_u8) hip(launch_quantize_values(d_band, d_band8, width, n_rows, stream), "quantize_kernel");
             if (w.rc == RTX_OK && n_rows && !local)
                 hip(hipMemcpyPeerAsync(dst, dev0, as_u8 ? (const void *)d_band8 : (const void *)d_band, dev, n_vals * val_bytes, stream),
                     "hipMemcpyPeerAsync");
@@ -1603,6 +1693,56 @@ int32_t rtx_debug_math(int32_t op, const double *a, const double *b, double *out
     RTX_HIP_CHECK(hipMemcpy(out, d.p[2], n * sizeof(double), hipMemcpyDeviceToHost));
     return RTX_OK;
 #endif
+}
+
+int32_t rtx_scene_closest_hits(RtxSceneHandle h, const RtxRay *d_rays, uint64_t n, RtxHit *d_hits, void *stream, RtxStats *stats)
+{
+    if (!h) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_closest_hits: null scene");
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (n == 0) return RTX_OK;
+    if (!d_rays || !d_hits) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_closest_hits: null rays or hits");
+    if (n >= 0xFFFFFFFFull) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_closest_hits: n must be below 2^32");
+    const uintptr_t r0 = (uintptr_t)d_rays, r1 = r0 + n * sizeof(RtxRay), o0 = (uintptr_t)d_hits, o1 = o0 + n * sizeof(RtxHit);
+    if (r0 < o1 && o0 < r1) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_closest_hits: rays and hits overlap");
+    return query_run(h, d_rays, 0u, 0u, n, d_hits, stream, stats);
+}
+
+int32_t rtx_scene_primary_hits(RtxSceneHandle h, uint32_t width, uint32_t height, RtxHit *d_hits, void *stream, RtxStats *stats)
+{
+    if (!h) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_primary_hits: null scene");
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    const uint64_t n = (uint64_t)width * height;
+    if (n == 0) return RTX_OK;
+    if (!d_hits) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_primary_hits: null hits");
+    if (n >= 0xFFFFFFFFull) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_primary_hits: more than 2^32 pixels");
+    return query_run(h, nullptr, width, height, n, d_hits, stream, stats);
+}
+
+int32_t rtx_closest_hits(const RtxScene *scene, const RtxRay *rays, uint64_t n, RtxHit *hits)
+{
+    if (int32_t rc = check_scene_args(scene, "rtx_closest_hits")) return rc;
+    if (n == 0) return RTX_OK;
+    if (!rays || !hits) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_closest_hits: null rays or hits");
+    if (n >= 0xFFFFFFFFull) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_closest_hits: n must be below 2^32");
+    if (int32_t rc = check_device(0, "rtx_closest_hits")) return rc;
+    RtxSceneHandle h = nullptr;
+    if (int32_t rc = rtx_scene_upload(scene, 0, &h)) return rc;
+    RtxRay *d_rays = nullptr;
+    RtxHit *d_hits = nullptr;
+    hipError_t e = hipMalloc((void **)&d_rays, n * sizeof(RtxRay));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_hits, n * sizeof(RtxHit));
+    if (e == hipSuccess) e = hipMemcpy(d_rays, rays, n * sizeof(RtxRay), hipMemcpyHostToDevice);
+    int32_t rc = e == hipSuccess ? RTX_OK : fail(e == hipErrorOutOfMemory ? RTX_ERR_OUT_OF_MEMORY : RTX_ERR_HIP,
+                                                std::string("rtx_closest_hits: ") + hipGetErrorString(e));
+    if (!rc) rc = query_run(h, d_rays, 0u, 0u, n, d_hits, nullptr, nullptr);
+    if (!rc) {
+        e = hipMemcpy(hits, d_hits, n * sizeof(RtxHit), hipMemcpyDeviceToHost);       // (the null stream: after the query)
+        if (e != hipSuccess) rc = fail(RTX_ERR_HIP, std::string("rtx_closest_hits: ") + hipGetErrorString(e));
+    }
+    if (d_rays) (void)hipFree(d_rays);
+    if (d_hits) (void)hipFree(d_hits);
+    const int32_t frc = rtx_scene_free(h);
+    return rc ? rc : frc;
 }
 
 }  // extern "C"

@@ -557,37 +557,32 @@ __device__ __forceinline__ uint8_t rust_as_u8(double v)
     return (uint8_t)v;
 }
 
+// flip = 1: render_to_image's rows, output row y from row height - 1 - y (scene.rs:176) -- the whole-frame epilogue.
+// flip = 0: the rows of a band in place order (before it travels over xGMI: 3 bytes per pixel instead of 24; the gather
+// epilogue puts rows where they belong).
 __global__ __launch_bounds__(256) void quantize_kernel(const double *__restrict__ rgb, uint8_t *__restrict__ rgb8,
-                                                       uint32_t width, uint32_t height)
+                                                       uint32_t width, uint32_t height, uint32_t flip)
 {
     uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint64_t npix = (uint64_t)width * height;
     if (p >= npix) return;
     uint32_t y = (uint32_t)(p / width);
     uint32_t x = (uint32_t)(p - (uint64_t)y * width);
-    const double *c = rgb + 3 * ((uint64_t)(height - y - 1) * width + x);
+    const double *c = rgb + 3 * ((uint64_t)(flip ? height - y - 1 : y) * width + x);
     uint8_t *o = rgb8 + 3 * p;
     o[0] = rust_as_u8(c[0] * 256.0);
     o[1] = rust_as_u8(c[1] * 256.0);
     o[2] = rust_as_u8(c[2] * 256.0);
 }
 
-// render_to_image's `* 256` + saturating `as u8` (scene.rs:175-178) on the rows of a band, WITHOUT the flip (the gather
-// epilogue puts rows where they belong): what a device sends over xGMI is then 3 bytes per pixel instead of 24.
-__global__ __launch_bounds__(256) void quantize_values_kernel(const double *__restrict__ rgb, uint8_t *__restrict__ rgb8, uint64_t n)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) rgb8[i] = rust_as_u8(rgb[i] * 256.0);
-}
-
 // ------------------------------------------------------------------------------------------
 // multi-device gather epilogue: parts[p] (cap_rows rows each) holds band p of n: the blocks of `block` image rows
-// b = p, p + n, ... in order.  flip: output row height - 1 - y (render_to_image, scene.rs:176).
+// b = p, p + n, ... in order.  flip: output row height - 1 - y (render_to_image, scene.rs:176).  A value is elem_bytes
+// bytes (8: the f64 frame, 1: the quantised one), moved as one load and one store.
 // ------------------------------------------------------------------------------------------
-template <class T>
-__global__ __launch_bounds__(256) void deinterleave_kernel(const T *__restrict__ parts, T *__restrict__ full,
+__global__ __launch_bounds__(256) void deinterleave_kernel(const uint8_t *__restrict__ parts, uint8_t *__restrict__ full,
                                                            uint32_t width, uint32_t height, uint32_t n, uint32_t cap_rows,
-                                                           uint32_t block, uint32_t flip)
+                                                           uint32_t block, uint32_t flip, uint32_t elem_bytes)
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;       // one value of the frame
     const uint64_t row_vals = (uint64_t)width * 3;
@@ -596,7 +591,9 @@ __global__ __launch_bounds__(256) void deinterleave_kernel(const T *__restrict__
     const uint64_t c = i - (uint64_t)yo * row_vals;
     const uint32_t y = flip ? height - 1u - yo : yo;
     const uint32_t b = y / block, p = b % n, k = (b / n) * block + (y - b * block);
-    full[i] = parts[((uint64_t)p * cap_rows + k) * row_vals + c];
+    const uint64_t src = ((uint64_t)p * cap_rows + k) * row_vals + c;
+    if (elem_bytes == 8u) reinterpret_cast<unsigned long long *>(full)[i] = reinterpret_cast<const unsigned long long *>(parts)[src];
+    else full[i] = parts[src];
 }
 
 #ifdef RTX_LAB
@@ -740,14 +737,16 @@ hipError_t launch_quantize(const double *rgb, uint8_t *rgb8, uint32_t width, uin
     uint64_t npix = (uint64_t)width * height;
     if (npix == 0) return hipSuccess;
     hipLaunchKernelGGL(quantize_kernel, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, stream, rgb, rgb8, width,
-                       height);
+                       height, 1u);
     return hipGetLastError();
 }
 
-hipError_t launch_quantize_values(const double *rgb, uint8_t *rgb8, uint64_t n, hipStream_t stream)
+hipError_t launch_quantize_values(const double *rgb, uint8_t *rgb8, uint32_t width, uint32_t n_rows, hipStream_t stream)
 {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(quantize_values_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, rgb, rgb8, n);
+    uint64_t npix = (uint64_t)width * n_rows;
+    if (npix == 0) return hipSuccess;
+    hipLaunchKernelGGL(quantize_kernel, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, stream, rgb, rgb8, width,
+                       n_rows, 0u);
     return hipGetLastError();
 }
 
@@ -756,8 +755,8 @@ hipError_t launch_deinterleave(const double *parts, double *full, uint32_t width
 {
     const uint64_t total = (uint64_t)width * height * 3;
     if (total == 0) return hipSuccess;
-    hipLaunchKernelGGL(deinterleave_kernel<double>, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, stream, parts, full, width,
-                       height, n, cap_rows, block, 0u);
+    hipLaunchKernelGGL(deinterleave_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, stream,
+                       reinterpret_cast<const uint8_t *>(parts), reinterpret_cast<uint8_t *>(full), width, height, n, cap_rows, block, 0u, 8u);
     return hipGetLastError();
 }
 
@@ -766,8 +765,8 @@ hipError_t launch_deinterleave_u8(const uint8_t *parts, uint8_t *full, uint32_t 
 {
     const uint64_t total = (uint64_t)width * height * 3;
     if (total == 0) return hipSuccess;
-    hipLaunchKernelGGL(deinterleave_kernel<uint8_t>, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, stream, parts, full, width,
-                       height, n, cap_rows, block, flip ? 1u : 0u);
+    hipLaunchKernelGGL(deinterleave_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, stream, parts, full, width,
+                       height, n, cap_rows, block, flip ? 1u : 0u, 1u);
     return hipGetLastError();
 }
 

@@ -150,8 +150,28 @@ hipError_t launch_deinterleave(const double *parts, double *full, uint32_t width
                                uint32_t block, hipStream_t stream);
 hipError_t launch_deinterleave_u8(const uint8_t *parts, uint8_t *full, uint32_t width, uint32_t height, uint32_t n, uint32_t cap_rows,
                                   uint32_t block, bool flip, hipStream_t stream);
-// `* 256`, saturating `as u8` (scene.rs:175-178) of n values in place order (a band before it travels: no flip)
-hipError_t launch_quantize_values(const double *rgb, uint8_t *rgb8, uint64_t n, hipStream_t stream);
+// `* 256`, saturating `as u8` (scene.rs:175-178) of the n_rows x width pixels of a band in place order (before it travels: no flip)
+hipError_t launch_quantize_values(const double *rgb, uint8_t *rgb8, uint32_t width, uint32_t n_rows, hipStream_t stream);
+
+// ---- ray queries (rtx_query.hip): closest_object for caller rays or for the pick buffer's zero-offset primary rays
+struct QueryRay { double position[3], direction[3]; };                                      // = RtxRay (include/rtx_hip.h)
+struct QueryHit { double position[3], normal[3], distance; long long object; };            // = RtxHit
+static_assert(sizeof(QueryRay) == 48 && sizeof(QueryHit) == 64, "QueryRay / QueryHit");
+struct QueryArgs {
+    const QueryRay *rays;          // n rays (null in the pick form)
+    const RowsView *rv;            // the pick form: the frame's RowsView (one band of all rows), ray i = pixel i; else null
+    QueryHit *hits;                // n answers
+    unsigned long long n;
+    uint32_t walk;                 // 0: every ray is swept (RTX_KERNEL_EXACT / no usable tree); set by the launcher
+    uint32_t pad_;
+};
+uint32_t query_tree_kind(const SceneView &sv);        // 0 no walk, 1 sphere tree, 2 a tree that holds triangles
+uint32_t query_spill_entries(const SceneView &sv);    // HBM stack entries per lane a walk may need beyond its LDS rows
+size_t query_spill_bytes(uint32_t entries, int n_cus);
+// head: a zeroed u64 (the ray queue's head); spill: query_spill_bytes(spill_entries, n_cus) bytes (fewer entries than
+// query_spill_entries: a deeper stack overflows, that ray is swept -- the same bits)
+hipError_t launch_query_closest(const SceneView *d_sv, const SceneView &sv, const QueryArgs &qa, bool walk, uint32_t *spill,
+                                uint32_t spill_entries, int n_cus, Counters *counters, unsigned long long *head, hipStream_t stream);
 
 // device evaluation of single f64 ops (tests: are / and sqrt correctly rounded, how far are sin/cos)
 // op: 0 a/b, 1 sqrt(a), 2 sin(a), 3 cos(a)

@@ -1,0 +1,302 @@
+// rtx_query.hip -- query_closest_kernel: closest_object (scene.rs:243-251) for rays the caller brings (rtx_scene_closest_hits)
+// or for the zero-offset primary ray of every pixel of a frame (rtx_scene_primary_hits, the pick buffer).
+//
+// Persistent waves; a wave takes rays from the launch's atomic head in chunks (wf_take) and each lane owns one ray: the
+// segment body of trace_bvh_kernel (rtx_bvh.hip) -- the origin-range gate, the walk, the exhaustive fallback, planes and
+// shapes outside the tree swept for every ray, the (t, scene index) minimum -- on the product's faster steps:
+//   TRIS = false  a sphere tree: the 64-byte nodes, node and leaf visits apart (sphere_walk_phased), candidates queued with
+//                 their f32 lower bound, the exact tests after the walk;
+//   TRIS = true   a tree that holds triangles (a pure footprint tree with its 64-byte nodes, or a joint tree): mesh_step with
+//                 tri_bounds, the queue flushed into the exact tests whenever it fills.
+// The walk does not know which surface the ray starts on: no self-hit pre-test (the render's mesh kernel has one; here the
+// triangle a ray sits on is found like any other, its t_lo bound is ~0 and it always reaches the exact test).
+//
+// Exactness ("Ray queries").  The f32 code only selects candidates; every reported hit is the f64 test in the
+// reference's operation order.  The f32 bounds were derived for unit directions, so a ray takes the walk only when
+// |d.d - 1| <= kQueryDirTol and d is finite; anything else (a non-unit or non-finite direction, an origin beyond
+// bvh_origin_limit * kBvhRange64, a NaN origin, RTX_KERNEL_EXACT, a scene without a usable tree, a stack or candidate
+// overflow) tests every shape exactly -- every triangle, not just the ones with a filter record, since upload drops the
+// triangles the cull test rejects for every UNIT direction.
+#include "rtx_launch.h"
+#include "rtx_mesh_step.h"
+#include "rtx_wavefront.h"
+
+namespace rtx {
+
+constexpr int kQueryWaves = 4;                                   // workgroups per CU (4 waves each)
+constexpr int kQuerySphStack = 30;                               // LDS stack rows: (30 + 1 sink + 2 * kSphQueue) KB per workgroup
+constexpr int kQueryMeshStack = 38 - 2 * kMeshQueue;             // (26 + 1 sink + 2 * kMeshQueue) KB per workgroup
+constexpr uint32_t kQueryLeafLanes = 8;                          // sphere_walk_phased: a leaf visit runs for this many lanes
+// |d.d - 1| at most this: 2^-40.  A normalised f64 vector is within a few 2^-53 of unit length; the f32 bounds budget their
+// errors in units of u = 2^-24 with at least a factor 2 to spare, and converting d to f32 alone moves it by u.
+constexpr double kQueryDirTol = 9.094947017729282e-13;
+
+__device__ __forceinline__ bool query_dir_ok(V3 d)
+{
+    const double n2 = d.x * d.x + d.y * d.y + d.z * d.z;
+    return fabs(n2 - 1.0) <= kQueryDirTol;                        // (NaN / inf components: false)
+}
+
+// every shape exactly (spheres, planes, then every triangle -- Scene.objects order decides ties through hit_consider)
+__device__ __forceinline__ void query_sweep(const SceneView &sv, const LeafArrays &la, const RayX &rx, bool spheres, bool tris, Hit &h,
+                                            unsigned long long &exact)
+{
+    if (spheres) {
+        for (uint32_t k = 0; k < sv.n_spheres; ++k) {
+            double t;
+            if (sphere_distance(la.spheres[k], rx, &t)) hit_consider(h, t, la.sphere_ids[k], 0, k);
+        }
+        exact += sv.n_spheres;
+    }
+    for (uint32_t k = 0; k < sv.n_planes; ++k) {
+        double t;
+        if (plane_distance(sv.planes[k], rx, &t)) hit_consider(h, t, sv.planes[k].id, 1, k);
+    }
+    exact += sv.n_planes;
+    if (tris) {
+        for (uint32_t k = 0; k < sv.n_tris; ++k) {
+            double t;
+            if (triangle_distance(la.tris[k], rx, &t)) hit_consider(h, t, la.tris[k].id, 2, k);
+        }
+        exact += sv.n_tris;
+    }
+}
+
+// the exact tests of the queued candidates that can still win
+__device__ __forceinline__ void query_flush(const LeafArrays &la, const RayX &rx, const uint32_t *lq, uint32_t tid, uint32_t queue,
+                                            uint32_t qcnt, float best_up, Hit &h, unsigned long long &exact)
+{
+#pragma unroll 1
+    for (uint32_t e = 0; e < qcnt; ++e) {
+        if (__uint_as_float(lq[(size_t)(queue + e) * kBvhThreads + tid]) <= best_up) {
+            const uint32_t idx = lq[(size_t)e * kBvhThreads + tid];
+            double t;
+            if (idx & kQueueTri) {
+                const uint32_t tk = la.tri_fidx[idx & ~kQueueTri];
+                if (triangle_distance(la.tris[tk], rx, &t)) hit_consider(h, t, la.tris[tk].id, 2, tk);
+            } else {
+                if (sphere_distance(la.spheres[idx], rx, &t)) hit_consider(h, t, la.sphere_ids[idx], 0, idx);
+            }
+            exact += 1;
+        }
+    }
+}
+
+// one walk of a tree that holds triangles (PLAIN 2: 64-byte footprint nodes; 0: joint nodes), flushing whenever the queue is full
+template <int PLAIN, class RAY>
+__device__ __forceinline__ void query_mesh_walk(const float4 *__restrict__ nodes, const LeafArrays &la, const MeshArrays &ma, const RAY &q,
+                                                const SphereRay &sr, const TriFilterParams &tpar, const RayX &rx, uint32_t root, bool &overflow,
+                                                Hit &h, uint32_t *ls, uint32_t *lq, uint32_t tid, uint32_t *__restrict__ spill,
+                                                uint32_t spill_entries, size_t spill_stride, size_t glane, unsigned long long &exact,
+                                                uint32_t &nbox, uint32_t &nleaf)
+{
+    float best_up = __builtin_inff();
+    uint32_t node = root, sp = 0, qcnt = 0, resume = 0, resume_node = 0;
+    float4 nd[MeshNode<PLAIN>::n];
+    if constexpr (kMeshPipe) mesh_load_node<PLAIN>(nodes, node, nd);
+    while (node != kNone || resume != 0u) {
+        if (mesh_step<true, PLAIN, kQueryMeshStack>(nodes, ma, q, sr, tpar, nd, node, sp, qcnt, overflow, best_up, resume, resume_node, ls, lq,
+                                                     tid, spill, spill_entries, spill_stride, glane, nbox, nleaf))
+            continue;
+        query_flush(la, rx, lq, tid, kMeshQueue, qcnt, best_up, h, exact);
+        qcnt = 0;
+        if (h.id != kNone) best_up = fminf(best_up, round_up32(h.t));
+        if constexpr (kMeshPipe) mesh_load_node<PLAIN>(nodes, resume_node, nd);
+    }
+    query_flush(la, rx, lq, tid, kMeshQueue, qcnt, best_up, h, exact);
+}
+
+template <bool TRIS>
+__global__ __launch_bounds__(kBvhThreads, kQueryWaves) void query_closest_kernel(const SceneView *__restrict__ svp, const QueryArgs qa,
+                                                                                 const float4 *__restrict__ nodes, const LeafArrays la,
+                                                                                 const MeshArrays ma, uint32_t *__restrict__ spill,
+                                                                                 uint32_t spill_entries, Counters *__restrict__ ctr,
+                                                                                 unsigned long long *__restrict__ head)
+{
+    constexpr int STACK = TRIS ? kQueryMeshStack : kQuerySphStack;
+    constexpr int QUEUE = TRIS ? kMeshQueue : kSphQueue;
+    const SceneView &sv = *svp;
+    __shared__ uint32_t lds_stack[STACK + 1][kBvhThreads];             // + the sink row of the branch-free pushes
+    __shared__ uint32_t lds_q[2 * QUEUE][kBvhThreads];                 // candidate entries, then their t_lo
+    uint32_t *const ls = &lds_stack[0][0];
+    uint32_t *const lq = &lds_q[0][0];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t lane = tid & 63u;
+    const size_t spill_stride = (size_t)gridDim.x * kBvhThreads, glane = (size_t)blockIdx.x * kBvhThreads + tid;
+    const unsigned long long grab = wf_grab_size(qa.n);
+    unsigned long long segs = 0, box_tests = 0, leaf_filters = 0, exact = 0;
+    WfChunk ch{0ull, 0ull, false};
+
+    for (;;) {
+        unsigned long long i = 0;
+        const bool mine = wf_take(ch, head, grab, qa.n, true, i);         // (every lane of the wave is here: lane 0 takes the chunk)
+        if (ch.drained && __ballot(mine) == 0ull) break;                 // wave-uniform
+        if (!mine) continue;
+        V3 pos, dir;
+        if (qa.rv) {                                                     // the pick buffer: render_pixel's ray without the offsets
+            pos = sv.cam_pos;
+            dir = vnorm(vsub(primary_focal_point(sv, *qa.rv, (uint32_t)i), pos));      // scene.rs:203-207, i = y * width + x
+        } else {
+            const QueryRay &qr = qa.rays[i];
+            pos = mk(qr.position[0], qr.position[1], qr.position[2]);
+            dir = mk(qr.direction[0], qr.direction[1], qr.direction[2]);
+        }
+        const RayX rx = make_rayx(pos, dir);
+        Hit h;
+        hit_init(h);
+        ++segs;
+        const float omax = fmaxf(fmaxf(__builtin_fabsf((float)pos.x), __builtin_fabsf((float)pos.y)), __builtin_fabsf((float)pos.z));
+        const bool in32 = omax <= sv.bvh_origin_limit;                                      // NaN origin -> exhaustive branch
+        const bool walk = qa.walk && query_dir_ok(dir) && (in32 || omax <= sv.bvh_origin_limit * kBvhRange64);
+        bool covered = false;
+        if (walk) {
+            bool overflow = false;
+            uint32_t nbox = 0, nleaf = 0;
+            if constexpr (TRIS) {
+                SphereRay sr;
+                sr.px = sr.py = sr.pz = sr.dx = sr.dy = sr.dz = sr.Kg = sr.K = 0.f; sr.c0 = __builtin_inff();
+                if (sv.bvh_flags & 1u) sphere_ray_from(sv, pos, dir, sr);
+                TriFilterParams tpar;
+                tri_filter_from_ray(sv, pos, dir, tpar);
+                const bool plain = (sv.bvh_flags & 4u) != 0u;
+                if (in32) {
+                    Ray32 q;
+                    make_ray32(pos, rx.dirn, (double)sv.bvh_inv_max, q);
+                    if (plain) query_mesh_walk<2>(nodes, la, ma, q, sr, tpar, rx, sv.bvh_root, overflow, h, ls, lq, tid, spill, spill_entries,
+                                                  spill_stride, glane, exact, nbox, nleaf);
+                    else query_mesh_walk<0>(nodes, la, ma, q, sr, tpar, rx, sv.bvh_root, overflow, h, ls, lq, tid, spill, spill_entries,
+                                            spill_stride, glane, exact, nbox, nleaf);
+                } else {                                  // origin far outside the scene: the same walk with an f64 slab test
+                    Ray64 q;
+                    make_ray64(pos, rx.dirn, (double)sv.bvh_inv_max, q);
+                    if (plain) query_mesh_walk<2>(nodes, la, ma, q, sr, tpar, rx, sv.bvh_root, overflow, h, ls, lq, tid, spill, spill_entries,
+                                                  spill_stride, glane, exact, nbox, nleaf);
+                    else query_mesh_walk<0>(nodes, la, ma, q, sr, tpar, rx, sv.bvh_root, overflow, h, ls, lq, tid, spill, spill_entries,
+                                            spill_stride, glane, exact, nbox, nleaf);
+                }
+            } else {
+                SphereRay sr;
+                sphere_ray_from(sv, pos, dir, sr);
+                Ray32 q0;
+                make_ray32(pos, rx.dirn, (double)sv.bvh_inv_max, q0);
+                Ray32S q;                                 // (a far origin: Ray32's planes widened by the slack of noi's rounding)
+                q.ix = q0.ix; q.iy = q0.iy; q.iz = q0.iz; q.nx = q0.nx; q.ny = q0.ny; q.nz = q0.nz;
+                q.e = ray32_slack(q0.nx, q0.ny, q0.nz, in32);
+                float best_up = __builtin_inff();
+                uint32_t node = sv.bvh_root, sp = 0, qcnt = 0;
+                sphere_walk_phased<kQuerySphStack, true>(nodes, la.sphere_f32, la.sphere_prims, q, sr, node, sp, ls, lq, tid, spill,
+                                                         spill_entries, spill_stride, glane, best_up, qcnt, overflow, nbox, nleaf,
+                                                         0u, 0u, 0u, kQueryLeafLanes);
+                if (!overflow) query_flush(la, rx, lq, tid, kSphQueue, qcnt, best_up, h, exact);
+            }
+            box_tests += nbox;
+            leaf_filters += nleaf;
+            covered = !overflow;
+        }
+        if (covered) {
+            // the tree answered for its shapes: the spheres outside it, every plane, the triangle records outside it
+            query_sweep(sv, la, rx, (sv.bvh_flags & 1u) == 0u, false, h, exact);
+            const uint32_t from = (sv.bvh_flags & 2u) ? sv.n_tri_tree : 0u;
+            for (uint32_t k = from; k < sv.n_tri_filter; ++k) {
+                const uint32_t tk = la.tri_fidx[k];
+                double t;
+                if (triangle_distance(la.tris[tk], rx, &t)) hit_consider(h, t, la.tris[tk].id, 2, tk);
+            }
+            exact += sv.n_tri_filter - from;
+        } else {
+            hit_init(h);                                  // (a walk cut short: start over, every shape exactly)
+            query_sweep(sv, la, rx, true, true, h, exact);
+        }
+        // the answer: scene.rs:234's hit point and object.rs:37-39's normal there (what advance_and_shade hands the bounce)
+        QueryHit out;
+        if (h.id != kNone) {
+            const V3 p = vadd(pos, vmuls(dir, h.t));
+            const V3 n = normal_at(sv, h, p);
+            out.position[0] = p.x; out.position[1] = p.y; out.position[2] = p.z;
+            out.normal[0] = n.x; out.normal[1] = n.y; out.normal[2] = n.z;
+            out.distance = h.t;
+            out.object = (long long)h.id;
+        } else {
+            const double nan = __builtin_nan("");
+            out.position[0] = out.position[1] = out.position[2] = nan;
+            out.normal[0] = out.normal[1] = out.normal[2] = nan;
+            out.distance = __builtin_inf();
+            out.object = -1;
+        }
+        qa.hits[i] = out;
+    }
+    unsigned long long filt = box_tests + leaf_filters;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        segs += __shfl_xor(segs, off, 64);
+        exact += __shfl_xor(exact, off, 64);
+        filt += __shfl_xor(filt, off, 64);
+        box_tests += __shfl_xor(box_tests, off, 64);
+    }
+    if (lane == 0) {
+        const uint32_t shard = (blockIdx.x * (kBvhThreads >> 6) + (tid >> 6)) & (kCounterShards - 1);
+        if (segs) atomicAdd(&ctr[shard].segments, segs);
+        if (exact) atomicAdd(&ctr[shard].exact_tests, exact);
+        if (filt) atomicAdd(&ctr[shard].filter_tests, filt);
+        if (box_tests) atomicAdd(&ctr[2 + (shard % (kCounterShards - 2))].pad_, box_tests);   // shards 0,1 carry debug flags
+    }
+}
+
+// which walk a scene's tree allows: 1 a sphere tree with its 64-byte nodes, 2 a tree that holds triangles (a pure footprint tree
+// only with its 64-byte nodes), 0 none (every ray is swept)
+uint32_t query_tree_kind(const SceneView &sv)
+{
+    if (sv.n_bvh_nodes == 0) return 0u;
+    if ((sv.bvh_flags & 19u) == 17u && sv.bvh_q3nodes != nullptr) return 1u;
+    if ((sv.bvh_flags & 2u) != 0u && ((sv.bvh_flags & 4u) == 0u || ((sv.bvh_flags & 8u) != 0u && sv.bvh_qnodes != nullptr))) return 2u;
+    return 0u;
+}
+
+uint32_t query_spill_entries(const SceneView &sv)
+{
+    const uint32_t kind = query_tree_kind(sv);
+    if (kind == 0u) return 0u;
+    const uint32_t need = 3u * sv.bvh_depth + 2u;                   // a 4-wide node pushes at most 3 entries per level
+    const uint32_t rows = (uint32_t)(kind == 1u ? kQuerySphStack : kQueryMeshStack);
+    return need > rows ? need - rows : 0u;
+}
+
+uint32_t query_blocks(uint64_t n, int n_cus)
+{
+    const uint64_t want = (n + kBvhThreads - 1) / kBvhThreads;
+    const uint64_t cap = (uint64_t)n_cus * kQueryWaves;
+    return (uint32_t)(want < cap ? want : cap);
+}
+
+size_t query_spill_bytes(uint32_t entries, int n_cus)
+{
+    return (size_t)entries * (size_t)n_cus * kQueryWaves * kBvhThreads * sizeof(uint32_t);
+}
+
+hipError_t launch_query_closest(const SceneView *d_sv, const SceneView &sv, const QueryArgs &qa, bool walk, uint32_t *spill,
+                                uint32_t spill_entries, int n_cus, Counters *counters, unsigned long long *head, hipStream_t stream)
+{
+    const uint32_t blocks = query_blocks(qa.n, n_cus);
+    if (blocks == 0) return hipSuccess;
+    const uint32_t kind = walk ? query_tree_kind(sv) : 0u;
+    QueryArgs a = qa;
+    a.walk = kind != 0u ? 1u : 0u;
+    LeafArrays la;
+    la.sphere_f32 = sv.bvh_leaf_cr; la.sphere_prims = sv.bvh_prims; la.spheres = sv.spheres; la.sphere_ids = sv.sphere_id;
+    la.tri_f32 = sv.tri_f32; la.tri_fidx = sv.tri_fidx; la.tris = sv.tris;
+    MeshArrays ma;
+    ma.sphere_cr = sv.bvh_leaf_cr; ma.sphere_prims = sv.bvh_prims; ma.tri_f32 = sv.tri_f32; ma.tri_geo = sv.tri_geo;
+    const float4 *nodes = kind == 1u ? reinterpret_cast<const float4 *>(sv.bvh_q3nodes)
+                        : (kind == 2u && (sv.bvh_flags & 4u) != 0u) ? reinterpret_cast<const float4 *>(sv.bvh_qnodes)
+                        : reinterpret_cast<const float4 *>(sv.bvh_nodes);
+    if (!spill) spill_entries = 0u;
+    if (kind == 2u)
+        hipLaunchKernelGGL(query_closest_kernel<true>, dim3(blocks), dim3(kBvhThreads), 0, stream, d_sv, a, nodes, la, ma, spill, spill_entries,
+                           counters, head);
+    else
+        hipLaunchKernelGGL(query_closest_kernel<false>, dim3(blocks), dim3(kBvhThreads), 0, stream, d_sv, a, nodes, la, ma, spill, spill_entries,
+                           counters, head);
+    return hipGetLastError();
+}
+
+}  // namespace rtx

@@ -76,6 +76,25 @@ pub struct RtxStats {
     pub stage1_exact_tests: u64,
 }
 
+/// One ray of a closest-hit query (`rtx_scene_closest_hits`, `rtx_closest_hits`); the direction is used as given.  48 bytes.
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct RtxRay {
+    pub position: [f64; 3],
+    pub direction: [f64; 3],
+}
+
+/// The answer of `closest_object` (scene.rs:243-251) for one ray: hit point, `normal_at` there, distance, index in
+/// `Scene.objects` (-1, +inf and NaNs when nothing is hit).  64 bytes.
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct RtxHit {
+    pub position: [f64; 3],
+    pub normal: [f64; 3],
+    pub distance: f64,
+    pub object: i64,
+}
+
 #[repr(C)]
 pub struct RtxSceneHandleOpaque {
     _private: [u8; 0],
@@ -101,6 +120,9 @@ extern "C" {
     pub fn rtx_render_rows(scene: RtxSceneHandle, width: u32, height: u32, row_begin: u32, row_stride: u32, n_rows: u32, d_out_rgb: *mut f64, stream: *mut c_void, stats: *mut RtxStats) -> i32;
     pub fn rtx_blocks_row_count(height: u32, block_rows: u32, part: u32, n_parts: u32) -> u32;
     pub fn rtx_render_blocks(scene: RtxSceneHandle, width: u32, height: u32, block_rows: u32, part: u32, n_parts: u32, d_out_rgb: *mut f64, stream: *mut c_void, stats: *mut RtxStats) -> i32;
+    pub fn rtx_scene_closest_hits(scene: RtxSceneHandle, d_rays: *const RtxRay, n: u64, d_hits: *mut RtxHit, stream: *mut c_void, stats: *mut RtxStats) -> i32;
+    pub fn rtx_scene_primary_hits(scene: RtxSceneHandle, width: u32, height: u32, d_hits: *mut RtxHit, stream: *mut c_void, stats: *mut RtxStats) -> i32;
+    pub fn rtx_closest_hits(scene: *const RtxScene, rays: *const RtxRay, n: u64, hits: *mut RtxHit) -> i32;
     pub fn rtx_quantize_image_device(d_rgb: *const f64, width: u32, height: u32, d_rgb8: *mut u8, device: i32, stream: *mut c_void) -> i32;
 }
 
