@@ -216,7 +216,7 @@ class Config:
         return self._with(seed=int(v))
 
     def with_kernel(self, v):
-        return self._with(kernel=int(v))
+        return self._with(kernel=int(v), lab=self.lab or bool(getattr(v, "lab", False)))   # (a LabKernel id keeps asking for the lab library)
 
     def with_tuning(self, v):
         return self._with(tuning=int(v))

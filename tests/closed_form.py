@@ -211,3 +211,346 @@ def hemisphere_check(mean, n_samples, p, value, sigmas=5.0):
     mu = p * value
     bound = sigmas * value * math.sqrt(p * (1.0 - p) / n_samples)
     return abs(mean - mu), bound
+
+
+# ---- the first part of Scene::render (scene.rs:144-170, :194-222; camera.rs:42-49), pinned without the oracle ------------------
+# Every scene above is a 1 x 1 image with a 1e-12 rad field of view and no jitter.  The scenes below are not: a half-pixel shift
+# of the pixel -> angle map, vfov = fov, a flipped row order, another camera basis, a centred or halved lens jitter or one draw
+# serving both offsets changes their pixels.
+MARK_DISTANCE, MARK_SHARE, MARK_MARGIN = 50.0, 0.3, 2.0
+PIXEL_MAP_CAMERAS = [("default", ((0.0, 0.0, 0.0), (1.0, 0.0, 0.0), math.pi / 2)),
+                     ("z in the direction", ((0.0, 0.0, 0.0), (1.0, 0.2, 0.5), 1.2)),               # |right| = 0.90
+                     ("off the origin, looking down", ((0.3, -0.2, 0.1), (0.6, -0.3, -0.7), 0.9))]  # |right| = 0.69
+PIXEL_MAP_FRAMES = [(24, 10), (17, 16), (9, 20)]                 # non-square, partial 8 x 8 tiles, h > w (vfov > fov)
+PIXEL_MAP_BIG = 1024                                             # 2^20 primary rays: AUTO runs two stages and builds tile lists
+
+
+def _cross(a, b):
+    return (a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0])     # vector.rs:89-95
+
+
+def camera_basis(direction):
+    """Camera::derive_to_world_space_mat (camera.rs:42-49), in the reference's operation order: cam_forward = direction.norm()
+    (vector.rs:101-107: self / sqrt(x x + y y + z z)), cam_right = cam_forward x (0, 0, -1) and cam_up = cam_forward x cam_right,
+    NEITHER normalised: |right| = |up| = sqrt(1 - forward.z^2).  The matrix' columns are (right, up, forward), so a camera-space
+    vector (a, b, c) becomes right * a + up * b + forward * c (mat/mul.rs:42-50 sums in that order)."""
+    x, y, z = (float(c) for c in direction)
+    n = math.sqrt(x * x + y * y + z * z)
+    fwd = (x / n, y / n, z / n)
+    right = _cross(fwd, (0.0, 0.0, -1.0))
+    up = _cross(fwd, right)
+    return np.array(right), np.array(up), np.array(fwd)
+
+
+def pixel_ray(cam, w, h, x, y):
+    """The un-normalised direction Scene::render gives pixel (x, y) of a w x h frame: u = x / w, v = y / h -- the pixel's CORNER,
+    not its centre (scene.rs:153,157) --, vertical_fov = h / w * fov (scene.rs:145), angle_x = fov * (u - 0.5), angle_y =
+    vertical_fov * (v - 0.5), camera-space (sin angle_x, sin angle_y, cos angle_x * cos angle_y) rotated to world space
+    (scene.rs:213-221).  x and y may lie outside the frame (a pixel's neighbours)."""
+    _, _, fov = cam
+    right, up, fwd = camera_basis(cam[1])
+    ax = fov * (x / w - 0.5)
+    ay = (h / w * fov) * (y / h - 0.5)
+    return right * math.sin(ax) + up * math.sin(ay) + fwd * (math.cos(ax) * math.cos(ay))
+
+
+def _all_pixel_rays(cam, w, h):
+    """[h][w] unit ray directions of the whole frame (the same formulas, vectorised: for the margin checks only)."""
+    _, _, fov = cam
+    right, up, fwd = camera_basis(cam[1])
+    ax = fov * (np.arange(w) / w - 0.5)
+    ay = (h / w * fov) * (np.arange(h) / h - 0.5)
+    D = (right * np.sin(ax)[None, :, None] + up * np.sin(ay)[:, None, None]
+         + fwd * (np.cos(ax)[None, :, None] * np.cos(ay)[:, None, None]))
+    return D / np.sqrt((D * D).sum(axis=2))[:, :, None]
+
+
+def _angle(a, b):
+    """angle between unit vectors a [..., 3] and b [3] (atan2 of |a x b| and a . b: exact enough at 1e-4 rad and at pi / 2)"""
+    c = np.cross(a, b)
+    return np.arctan2(np.sqrt((c * c).sum(axis=-1)), a @ b)
+
+
+def _tri_rows(v0, v1, v2):
+    """The two rows of a r + b s = p that Triangle::contains ends up solving (triangle.rs:55-96): (x, y) unless a zero pivot
+    swaps rows (r.x == 0: the y row first, or the z row; then a zero in the eliminated second row: the third).  None: "can't
+    handle LGS" (never contains)."""
+    r, s = v1 - v0, v2 - v0
+    rows = [0, 1, 2]
+    if r[0] == 0.0:
+        if r[1] == 0.0:
+            if r[2] == 0.0:
+                return None
+            rows = [2, 1, 0]
+        else:
+            rows = [1, 0, 2]
+    i0, i1, i2 = rows
+    q = s[i0] / r[i0]
+    if s[i1] - q * r[i1] == 0.0:
+        if s[i2] - q * r[i2] == 0.0:
+            return None
+        i1 = i2
+    return i0, i1
+
+
+def _tri_min_barycentric(v0, v1, v2, pos, dirs):
+    """Triangle::distance as the text has it (triangle.rs:108-127), for unit directions dirs [..., 3] from pos: the plane distance
+    t = n . (v0 - pos) / (dir . n), its ABSOLUTE value, hit point pos + dir * |t| (in front of the ray also when the plane is
+    behind it), and `contains` solving two rows for (a, b).  Returns min(a, b, 1 - a - b) per direction: >= 0 where the triangle
+    is hit, < (1 - k) / 3 where the hit point lies outside the triangle enlarged k times about its centroid; -inf where the text
+    reports no distance (dir . n == 0, or an unsolvable system).  (The cull of triangle.rs:115 is left to the caller.)"""
+    n = _norm(np.cross(v1 - v0, v2 - v0))
+    rows = _tri_rows(v0, v1, v2)
+    out = np.full(dirs.shape[:-1], -np.inf)
+    if rows is None:
+        return out
+    dn = dirs @ n
+    ok = dn != 0.0
+    t = np.abs(float(n @ (v0 - pos)) / np.where(ok, dn, 1.0))
+    p = (pos - v0) + dirs * t[..., None]
+    r, s = v1 - v0, v2 - v0
+    i0, i1 = rows
+    det = r[i0] * s[i1] - s[i0] * r[i1]
+    a = (p[..., i0] * s[i1] - s[i0] * p[..., i1]) / det
+    b = (r[i0] * p[..., i1] - p[..., i0] * r[i1]) / det
+    return np.where(ok, np.minimum(np.minimum(a, b), 1.0 - a - b), out)
+
+
+def pixel_map_marks(w, h):
+    """The pixels that get a mark: the four corners ((0, 0) is where a pixel-CENTRE convention goes dark: its mark would sit half
+    a pixel outside the frame), the centre and its neighbours, and pixels on both sides of the borders of the 8 x 8 ray tiles --
+    there a mark's ray is the extreme ray of its tile's beam and the mark straddles into the next tile's."""
+    cand = [(0, 0), (w - 1, 0), (0, h - 1), (w - 1, h - 1), (w // 2, h // 2), (w // 2 - 1, h // 2), (w // 2, h // 2 - 2),
+            (8, 8), (7, 8), (16, 7), (15, 16), (w - 1 - 7, 7), (w - 1 - 8, 8), (7, h - 1 - 7), (8, h - 1 - 8),
+            (w // 8 * 8, h // 8 * 8), (w // 8 * 8 - 1, h // 8 * 8 - 1), ((w - 1) // 8 * 8, 3), (3, (h - 1) // 8 * 8),
+            (w - 1, h // 2 + 1), (w // 2 + 3, h - 1)]
+    out = []
+    for x, y in cand:
+        if 0 <= x < w and 0 <= y < h and (x, y) not in out:
+            out.append((x, y))
+    return out
+
+
+def mark_emission(k):
+    """distinct dyadic emissions (k < 63), every channel in (0, 1]: exact under any sum and average, and nonzero as u8"""
+    return ((k + 1) / 64.0, ((7 * k) % 64 + 1) / 64.0, ((13 * k) % 64 + 1) / 64.0)
+
+
+_pixel_map_cache = {}
+
+
+def pixel_map_case(dtype, cam, w, h, marks=None, shape="sphere", fillers=0):
+    """One emissive shape (base colour 0: the path ends there; emission mark_emission(k)) per marked pixel, MARK_DISTANCE along
+    that pixel's ray D = norm(pixel_ray(...)) (scene.rs:207 normalises; no lens: focal_offset = non_focal_offset = 0), of angular
+    radius rho = MARK_SHARE x the smallest angle between the pixel's ray and any of its eight neighbours':
+      "sphere":   centre pos + 50 D, radius 50 sin rho (near root 50 - r, sphere.rs:29);
+      "triangle": equilateral, circumradius 50 tan rho about pos + 50 D in the plane perpendicular to D, rotated in that plane by a
+                  generic angle so that `contains` solves the (x, y) rows (triangle.rs:55-56), wound so that n . v0 > 1 in absolute
+                  coordinates: triangle.rs:115's n . (v0 - dir) < 0 then never culls it, whatever unit dir.  Two exceptions, both
+                  on the middle row of an even-height frame of a camera with forward.z = 0, where D.z = 0: (i) D = +x exactly
+                  (the centre pixel of an even-width frame): the mark lies in x = const and the zero-pivot swaps solve (y, z)
+                  (triangle.rs:60-71,81-87); (ii) any other such D: the perpendicular plane contains the z direction, its (x, y)
+                  projection is a segment and the two rows the text solves are singular but for rounding (Triangle::contains is
+                  noise there) -- the triangle is tilted by 0.3 rad about its horizontal in-plane axis, inside the same
+                  sphere of radius 50 tan rho (the margin below is asserted on the tilted triangle).  The same tilt, or half a
+                  radian more of in-plane rotation, is taken wherever the two rows would otherwise be badly conditioned (the
+                  (x, y) projection under 5 % of the area, or the first pivot r.x under 0.2 % of its edge).
+    Expected image ([y][x], scene.rs:136: row 0 is v = 0): the mark's emission at its pixel -- every sample is 0 + 1 * e and the
+    average of n equal dyadic values is that value --, exactly 0 everywhere else; closest_object is called once per ray.
+    The closed form's margin is ASSERTED here, in f64: every other pixel's ray (marked or not) misses a sphere mark by at least
+    MARK_MARGIN x its angular radius, and for a triangle mark the hit point the text computes (|t|: also for a plane behind the ray)
+    lies outside the triangle enlarged MARK_MARGIN x about its centroid; the construction gives 1 / MARK_SHARE = 3.3.
+    `fillers` > 0 (the two-stage frame; needs fov < pi): that many more black shapes of the same kind BEHIND the camera, so that the
+    tree is a real one (and, for triangles, large enough for AUTO to take the wavefront form).  A black shape changes nothing
+    where it replaces a miss; that no MARKED pixel's ray meets one is asserted (spheres: they lie in the half space behind
+    the camera, which no ray with D . forward = cos angle_x cos angle_y > 0 enters; triangles: Triangle::distance's text per
+    marked ray, phantom hits included).
+    Returns (objects, config kwargs, expected [h][w][3], info) -- info: marks, the un-normalised D per mark, rho and sphere radius."""
+    marks = list(marks) if marks is not None else pixel_map_marks(w, h)
+    key = (str(dtype), cam, w, h, tuple(marks), shape, fillers)
+    if key in _pixel_map_cache:
+        objs, cfg, expected, info = _pixel_map_cache[key]
+        return objs.copy(), dict(cfg), expected.copy(), info
+    assert shape in ("sphere", "triangle") and len(marks) < 63 and len(set(marks)) == len(marks)
+    pos = np.asarray(cam[0], dtype=np.float64)
+    right, up, fwd = camera_basis(cam[1])
+    rays = _all_pixel_rays(cam, w, h)
+    o = _obj(dtype, len(marks) + fillers)
+    o["roughness"] = 1.0
+    expected = np.zeros((h, w, 3))
+    info = dict(marks=marks, D=[], rho=[], radius=[])
+    for k, (x, y) in enumerate(marks):
+        D = pixel_ray(cam, w, h, x, y)
+        d = _norm(D)
+        rho = MARK_SHARE * min(float(_angle(_norm(pixel_ray(cam, w, h, x + i, y + j)), d))
+                               for i in (-1, 0, 1) for j in (-1, 0, 1) if (i, j) != (0, 0))
+        assert 1e-5 < rho < 0.2
+        centre = pos + d * MARK_DISTANCE
+        own = np.zeros((h, w), dtype=bool)
+        own[y, x] = True
+        if shape == "sphere":
+            r = MARK_DISTANCE * math.sin(rho)
+            o[k]["kind"] = 0
+            o[k]["geom"][:4] = (*centre, r)
+            assert float(_angle(rays, d)[~own].min()) >= MARK_MARGIN * rho and float(_angle(rays[y, x], d)) < 1e-9
+            info["radius"].append(r)
+        else:
+            e1 = _norm(np.cross(d, (0.0, 0.0, 1.0) if abs(d[2]) < 0.9 else (0.0, 1.0, 0.0)))
+            e2 = np.cross(d, e1)
+            R, phi = MARK_DISTANCE * math.tan(rho), 0.37 + 0.61 * k
+            for tilt, turn in ((0.0, 0.0), (0.0, 0.5), (0.3, 0.0), (0.3, 0.5)):
+                f2 = math.cos(tilt) * e2 + math.sin(tilt) * d
+                v = [centre + R * (math.cos(phi + turn + j * 2.0 * math.pi / 3.0) * e1 + math.sin(phi + turn + j * 2.0 * math.pi / 3.0) * f2) for j in range(3)]
+                if float(_norm(np.cross(v[1] - v[0], v[2] - v[0])) @ v[0]) < 0.0:
+                    v[1], v[2] = v[2], v[1]
+                nz = abs(float(_norm(np.cross(v[1] - v[0], v[2] - v[0]))[2]))
+                pivot = abs(v[1][0] - v[0][0]) / float(np.linalg.norm(v[1] - v[0]))
+                if _tri_rows(v[0], v[1], v[2]) != (0, 1) or (nz >= 0.05 and pivot >= 0.002):
+                    break
+            # the two rows solved are a well-conditioned system: the (x, y) projection keeps >= 5 % of the area, the first pivot >= 0.2 % of its edge
+            # (elimination without pivoting then loses at most three of f64's sixteen digits; the margin needs one)
+            assert _tri_rows(v[0], v[1], v[2]) != (0, 1) or (nz >= 0.05 and pivot >= 0.002)
+            assert float(_norm(np.cross(v[1] - v[0], v[2] - v[0])) @ v[0]) > 1.0                    # never culled (triangle.rs:115)
+            o[k]["kind"] = 2
+            o[k]["geom"] = np.concatenate(v)
+            m = _tri_min_barycentric(v[0], v[1], v[2], pos, rays)
+            assert float(m[~own].max()) < (1.0 - MARK_MARGIN) / 3.0 and float(m[y, x]) > 0.3        # (its own ray: the centroid, 1/3 each)
+            info["radius"].append(R)
+        o[k]["emission_color"] = mark_emission(k)
+        expected[y, x] = mark_emission(k)
+        info["D"].append(D)
+        info["rho"].append(rho)
+    if fillers:
+        assert cam[2] < math.pi and h / w * cam[2] < math.pi
+        ru, uu = _norm(right), _norm(up)
+        mark_dirs = np.array([_norm(D) for D in info["D"]])
+        for i in range(fillers):
+            k = len(marks) + i
+            c = pos - fwd * (20.0 + 0.013 * i) + ru * (i % 35 - 17.0) + uu * (i // 35 - 17.0)
+            if shape == "sphere":
+                o[k]["kind"] = 0
+                o[k]["geom"][:4] = (*c, 0.4)
+                assert float((c - pos) @ fwd) + 0.4 < 0.0
+            else:
+                # its normal within ~30 degrees of c's direction (varied, and with a z component: an (x, y) footprint), so that
+                # n . v0 > 1: never culled (triangle.rs:115) -- the upload would drop a triangle that always is
+                for sign in (1.0, -1.0):
+                    n = _norm(_norm(c) + sign * 0.5 * np.array([math.sin(1.0 + i), math.cos(2.0 + 0.7 * i), 0.8]))
+                    if abs(n[2]) >= 0.05:
+                        break
+                a1 = _norm(np.cross(n, (math.sin(0.3 * i), 0.4, 1.0)))
+                a2 = np.cross(n, a1)
+                v = [c, c + 0.3 * a1, c + 0.3 * a2]
+                assert abs(n[2]) >= 0.05 and float(_norm(np.cross(v[1] - v[0], v[2] - v[0])) @ v[0]) > 1.0
+                o[k]["kind"] = 2
+                o[k]["geom"] = np.concatenate(v)
+                assert float(_tri_min_barycentric(v[0], v[1], v[2], pos, mark_dirs).max()) < (1.0 - MARK_MARGIN) / 3.0
+    cfg = dict(rays_per_pixel=1 if w * h >= 1 << 20 else 2, focal_offset=0.0, non_focal_offset=0.0, seed=7)
+    _pixel_map_cache[key] = (o, cfg, expected, info)
+    return o.copy(), dict(cfg), expected.copy(), info
+
+
+def pixel_map_cases(dtype, big=False):
+    """(name, objects, camera, config kwargs, w, h, expected, info, shape): every camera x every small frame x both shapes; big:
+    the two-stage frame instead, sphere and triangle marks from two cameras each, with fillers behind the camera."""
+    for cname, cam in (PIXEL_MAP_CAMERAS[::2] if big else PIXEL_MAP_CAMERAS):
+        for w, h in ([(PIXEL_MAP_BIG, PIXEL_MAP_BIG)] if big else PIXEL_MAP_FRAMES):
+            for shape in ("sphere", "triangle"):
+                objs, cfg, expected, info = pixel_map_case(dtype, cam, w, h, None, shape, fillers=(200 if shape == "sphere" else 1190) if big else 0)
+                yield "%s, %dx%d, %s marks" % (cname, w, h, shape), objs, cam, cfg, w, h, expected, info, shape
+
+
+def quantized(expected):
+    """render_to_image (scene.rs:173-178) of an image with values in [0, 1]: x 256, `as u8` (truncating, saturating), image row y
+    = render row height - y - 1."""
+    return np.minimum(np.floor(expected * 256.0), 255.0).astype(np.uint8)[::-1]
+
+
+# ---- the lens (scene.rs:202-207) ------------------------------------------------------------------------------------------------------
+LENS_EMIT = (4.0, 2.0, 1.0)
+LENS_W, LENS_H, LENS_SPP = 24, 16, 5                             # the exact cases' frame
+
+
+def _occluder(dtype, X, axis, edge, side):
+    """A black triangle (emission 0, base colour 0) in the plane x = X that covers coordinate[axis] >= edge (side +1) or <= edge
+    (side -1) wherever a ray of these scenes can pass (|other coordinate| <= 999, up to 1 beyond the edge), wound so that its
+    normal is +x: n . v0 = X > 1 and triangle.rs:115 never culls it.  All three x are X: `contains` takes the zero-pivot swaps and
+    solves the (y, z) rows; its coefficient along the axis is (hit[axis] - edge) / (+-1000), and a difference has the sign of the
+    exact one -- the edge is sharp."""
+    other = 3 - axis
+    H = 1000.0
+    v = np.zeros((3, 3))
+    v[:, 0] = X
+    v[0, axis], v[0, other] = edge, -H
+    v[1, axis], v[1, other] = edge, H
+    v[2, axis], v[2, other] = edge + side * H, 0.0
+    if np.cross(v[1] - v[0], v[2] - v[0])[0] < 0.0:
+        v[[1, 2]] = v[[2, 1]]
+    assert X > 1.0 and set(_tri_rows(v[0], v[1], v[2])) == {1, 2}
+    o = _obj(dtype, 1)
+    o[0]["kind"] = 2
+    o[0]["geom"] = v.reshape(9)
+    return o
+
+
+def _lens_scene(dtype, occluders, light_x):
+    light = _obj(dtype, 1)
+    light[0]["kind"] = 1
+    light[0]["geom"][:6] = (light_x, 0.0, 0.0, -1.0, 0.0, 0.0)   # faces the camera (plane.rs:25), behind everything
+    light[0]["emission_color"] = LENS_EMIT
+    o = np.concatenate([light] + list(occluders) + [_fillers(dtype, (-60.0, 35.0, 20.0), (-1.0, 0.0, 0.0))])
+    o["roughness"] = 1.0
+    return o
+
+
+def lens_cases(dtype):
+    """scene.rs:202-207: ray_position = position + U * non_focal_offset, target = position + direction * focal_length + U' *
+    focal_offset, direction = norm(target - ray_position), with U and U' = Vector3::random() (vector.rs:29-35): SIX independent
+    draws, each uniform on [0, 1) -- not centred.  The camera sits at the origin and looks along +x with a 1e-12 rad field of view
+    (right = +y, up = +z; every pixel's direction is +x to 1e-12); a light plane (emission LENS_EMIT, base colour 0) faces the camera
+    behind everything, and one black occluder (a triangle in a plane x = X with a sharp edge, _occluder; or a one-sided plane)
+    covers one side: a sample is LENS_EMIT if its ray passes and 0 if not.  Fillers behind the camera give the tree kernels trees.
+    With a = non_focal_offset, b = focal_offset, L = focal_length:
+      * b = 0, L = 1e12: the ray runs parallel to +x at lateral offset a U_y, a U_z (its slope is below (a + 1) / L: 1e-11 at x = 5);
+      * a = 0, L = 10: at x = 5 the ray is at 5 (10 d + b U')_yz / (10 d_x + b U'_x), inside [-3e-12, b / 2);
+      * a = b, an occluder at x = L / 2: y = a (U_y + U'_y) / 2 + e with |e| <= a^2 / (L - a) + 1e-8 (the coupling through U_x, U'_x
+        and the pixel's 1e-12 rad).
+    EXACT cases (the occluder is never hit: the image is LENS_EMIT bit for bit, for any seed): an occluder over axis <= -1e-9 (a
+    centred jitter hits it half the time) and one over axis >= a (1 + 1e-9) resp. b / 2 (1 + 1e-9) (the support's far end), for the
+    origin's and the target's jitter, in y and in z; and for the origin's x a black plane at x = -a / 4 that faces AWAY from the
+    camera's view (normal -x: plane.rs:25 lets only a ray that starts behind it and heads +x hit it) -- an origin that can
+    fall behind it sees black, the reference's never does.
+    STATISTICAL cases (Bernoulli; lit share p): a = 1, L = 1e12, occluder over axis >= a / 2 resp. a / 4: p = 1/2 resp. 1/4
+    (uniformity and scale: U / 2 gives 1 resp. 1/2); and a = b = 1, L = 2e4, occluder at x = L / 2 over axis >= a / 4: p =
+    P(U + U' < 1/2) = 1/8 where ONE draw serving both offsets gives P(2U < 1/2) = 1/4.
+    Yields (name, objects, camera, config kwargs, p, exact, systematic) -- systematic: a bound on |lit share - p| from the terms
+    neglected above, for lens_check."""
+    cam = ((0.0, 0.0, 0.0), (1.0, 0.0, 0.0), 1e-12)
+    a = b = 1.0
+    tiny = 1e-11                                                 # lateral drift of a "parallel" ray at x = 5: 5 (a + 1/2) / (1e12 - a)
+    for axis, ax in ((1, "y"), (2, "z")):
+        par = dict(non_focal_offset=a, focal_offset=0.0, focal_length=1e12)
+        foc = dict(non_focal_offset=0.0, focal_offset=b, focal_length=10.0)
+        yield ("origin jitter never below 0, " + ax, _lens_scene(dtype, [_occluder(dtype, 5.0, axis, -1e-9, -1)], 20.0), cam, par, 1.0, True, 0.0)
+        yield ("origin jitter never reaches a, " + ax, _lens_scene(dtype, [_occluder(dtype, 5.0, axis, a * (1.0 + 1e-9), +1)], 20.0), cam, par, 1.0, True, 0.0)
+        yield ("target jitter never below 0, " + ax, _lens_scene(dtype, [_occluder(dtype, 5.0, axis, -1e-9, -1)], 20.0), cam, foc, 1.0, True, 0.0)
+        yield ("target jitter never reaches b, " + ax, _lens_scene(dtype, [_occluder(dtype, 5.0, axis, 0.5 * b * (1.0 + 1e-9), +1)], 20.0), cam, foc, 1.0, True, 0.0)
+        # P(a U < a / 2 + drift): U is k / 2^52, so the share is 1/2 resp. 1/4 exactly but for the drift
+        yield ("origin jitter uniform: half, " + ax, _lens_scene(dtype, [_occluder(dtype, 5.0, axis, a / 2, +1)], 20.0), cam, par, 0.5, False, tiny / a)
+        yield ("origin jitter uniform: quarter, " + ax, _lens_scene(dtype, [_occluder(dtype, 5.0, axis, a / 4, +1)], 20.0), cam, par, 0.25, False, tiny / a)
+        # lit iff (U + U') / 2 + e / a < 1/4, i.e. S = U + U' < 1/2 + eta with |eta| <= 2 |e| / a; P(S < s) = s^2 / 2 for s <= 1
+        L = 2.0e4
+        eta = 2.0 * (a * a / (L - a) + 1e-8) / a
+        yield ("the two jitters are independent, " + ax, _lens_scene(dtype, [_occluder(dtype, L / 2, axis, a / 4, +1)], 4.0 * L), cam,
+               dict(non_focal_offset=a, focal_offset=a, focal_length=L), 0.125, False, ((0.5 + eta) ** 2 - 0.25) / 2.0)
+    back = _obj(dtype, 1)
+    back[0]["kind"] = 1
+    back[0]["geom"][:6] = (-a / 4, 0.0, 0.0, -1.0, 0.0, 0.0)
+    yield ("origin jitter never below 0, x", _lens_scene(dtype, [back], 20.0), cam, dict(non_focal_offset=a, focal_offset=0.0, focal_length=1e12), 1.0, True, 0.0)
+
+
+def lens_check(mean, n_samples, p, systematic, sigmas=5.0):
+    """(|mean - p|, bound) for the lit share `mean` (the image divided by LENS_EMIT, averaged) of n_samples samples: hemisphere_check's
+    5 sigma of a Bernoulli(p), plus the case's systematic term."""
+    err, bound = hemisphere_check(mean, n_samples, p, 1.0, sigmas)
+    return err, bound + systematic

@@ -286,6 +286,17 @@ def test_config_material_and_packing(rtx):
         rtx.Object(Custom(), M.mirror())
 
 
+def test_lab_kernel_id_keeps_the_lab_flag(rtx):
+    """A LabKernel id asks for the lab library however it reaches the config -- with_kernel used to drop the flag, and an A / B run or
+    a test over _kernels() built that way compared the product library with itself."""
+    for k in (rtx.RTX_KERNEL_BVH, rtx.RTX_KERNEL_BVH_REGROUP, rtx.RTX_KERNEL_WAVEFRONT):
+        assert rtx.Config().with_kernel(rtx.LabKernel(k)).wants_lab() and rtx.Config().with_kernel(rtx.LabKernel(k)).kernel == k
+        assert rtx.Config(kernel=rtx.LabKernel(k)).with_seed(1).wants_lab()
+        assert rtx.Config().with_kernel(rtx.LabKernel(k)).with_rays_per_pixel(2).wants_lab()
+        assert not rtx.Config().with_kernel(k).wants_lab() and not rtx.Config(kernel=k).with_seed(1).wants_lab()
+        assert rtx.Config(lab=True).with_kernel(k).wants_lab()                      # (a plain id does not take an explicit flag away)
+
+
 def test_render_fails_loudly_without_a_gpu(rtx):
     if rtx.device_count() > 0:
         pytest.skip("a gfx950 device is present")

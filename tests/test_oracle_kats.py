@@ -332,6 +332,89 @@ def test_bounce_direction_is_pinned_without_the_kernels(oracle, rtx):
     assert bound < 0.01 * p * value                     # the test can tell 0.2 from the nearest wrong answer (0.1, 0.36) by far
 
 
+# ---- the first part of Scene::render -- the pixel -> angle map, vertical_fov, get_ray_dir, the camera's un-normalised basis, the
+#      [y][x] layout and render_to_image's flip, the lens -- against frames the reference's text determines (tests/closed_form.py)
+def _check_pixel_map(oracle, case):
+    import closed_form as cf
+    name, objs, cam, cfg, w, h, expected, info, shape = case
+    img, seg = oracle_render(oracle, objs, w, h, cam=cam, want_segments=True, **cfg)
+    assert np.array_equal(img, expected), name
+    assert int(seg.sum()) == w * h * cfg["rays_per_pixel"] and int(seg.min()) == int(seg.max()), name   # one closest_object call per ray
+    q = oracle.quantize_image(img)
+    assert np.array_equal(q, cf.quantized(expected)), name
+    lit = sorted(set(np.nonzero(q.any(axis=2))[0].tolist()))
+    assert lit == sorted({h - 1 - y for _, y in info["marks"]}), name                                   # scene.rs:176
+
+
+def test_pixel_map_and_orientation_are_pinned_without_the_kernels(oracle, rtx):
+    """Scene::render's u = x / w, v = y / h (the pixel's corner), vertical_fov = h / w * fov, get_ray_dir, the camera's un-normalised
+    right / up, img[y][x] and render_to_image's height - y - 1 (scene.rs:145-157,176,213-221; camera.rs:42-49): one small light per
+    marked pixel where the TEXT puts that pixel's ray (closed_form.pixel_map_case) -- the image is the marks' emissions at their
+    pixels and exactly 0 elsewhere; three cameras x 24x10, 17x16, 9x20 x sphere and triangle marks."""
+    import closed_form as cf
+    n = 0
+    for case in cf.pixel_map_cases(rtx.OBJECT_DTYPE):
+        _check_pixel_map(oracle, case)
+        n += 1
+    assert n == 18
+
+
+def test_pixel_map_at_two_stage_size_is_pinned_without_the_kernels(oracle, rtx):
+    """The same at 1024 x 1024 (the frame the device path builds its per-tile candidate lists for), two cameras x both shapes."""
+    import closed_form as cf
+    n = 0
+    for case in cf.pixel_map_cases(rtx.OBJECT_DTYPE, big=True):
+        _check_pixel_map(oracle, case)
+        n += 1
+    assert n == 4
+
+
+def test_get_ray_dir_equals_the_text(oracle, rtx):
+    """rtxo_get_ray_dir(x / w, y / h, vfov) against closed_form.pixel_ray, un-normalised, for every mark of every small frame.  Bound:
+    both sides evaluate right * sin ax + up * sin ay + forward * (cos ax * cos ay) from the same basis and angles; what may differ is
+    the last place of a sin / cos (glibc's sincos there, sin and cos here) -- three products and two sums of magnitudes <= 1 per
+    component: 4 * 2^-52."""
+    import closed_form as cf
+    worst = 0.0
+    for name, objs, cam, cfg, w, h, expected, info, shape in cf.pixel_map_cases(rtx.OBJECT_DTYPE):
+        if shape != "sphere":
+            continue
+        sc = oracle.make_scene(objs, cam, **cfg)
+        vfov = h / w * cam[2]
+        for (x, y), D in zip(info["marks"], info["D"]):
+            got = np.array(oracle.lib().rtxo_get_ray_dir(C.byref(sc), x / w, y / h, vfov).tuple())
+            worst = max(worst, float(np.abs(got - D).max()))
+            assert np.abs(got - D).max() <= 4 * 2.0 ** -52, (name, x, y)
+    print("get_ray_dir: worst |difference| %.3g" % worst)
+
+
+def test_lens_is_pinned_without_the_kernels(oracle, rtx):
+    """The lens of render_pixel (scene.rs:202-207) against closed_form.lens_cases: the jitters' support is [0, offset) -- occluders just
+    outside it are never hit, for the origin in x, y, z and for the target in y, z: the image is the light's emission bit for bit --,
+    they are uniform on it (an occluder over the upper half / upper three quarters of the origin's range leaves 1/2 / 1/4 lit), and
+    the origin's and the target's draws are independent (P(U + U' < 1/2) = 1/8, not 1/4); 5 sigma of the Bernoulli plus the case's
+    analytic systematic term."""
+    import closed_form as cf
+    E = np.array(cf.LENS_EMIT)
+    n_exact = n_stat = 0
+    for name, objs, cam, cfg, p, exact, systematic in cf.lens_cases(rtx.OBJECT_DTYPE):
+        if exact:
+            for seed in (1, 99):
+                img = oracle_render(oracle, objs, cf.LENS_W, cf.LENS_H, cam=cam, rays_per_pixel=cf.LENS_SPP, seed=seed, **cfg)
+                assert np.all(img == E), (name, seed)
+            n_exact += 1
+            continue
+        spp = 128 if p > 0.2 else 1024                       # 5.2e5 samples tell 1/2 from 1 and 1/4 from 1/2; 4.2e6 keep the systematic term of 1/8 under a sigma
+        means = [float((oracle_render(oracle, objs, 32, 32, cam=cam, rays_per_pixel=spp, seed=seed, **cfg) / E).mean()) for seed in (31, 32, 33, 34)]
+        n = 4 * 32 * 32 * spp
+        err, bound = cf.lens_check(float(np.mean(means)), n, p, systematic)
+        print("%s: lit share %.6f, |error| %.3g, bound %.3g" % (name, float(np.mean(means)), err, bound))
+        assert err <= bound, (name, err, bound)
+        assert bound < 0.02 * p and systematic < math.sqrt(p * (1 - p) / n)        # far from the nearest wrong value; the systematic term under one sigma
+        n_stat += 1
+    assert n_exact == 9 and n_stat == 6
+
+
 @pytest.mark.parametrize("name", ["c1_three_spheres_32x32", "spheres200_48x27", "mixed_40x24", "tris300_32x18"])
 def test_oracle_reproduces_golden(oracle, name):
     z = np.load(os.path.join(GOLDEN, name + ".npz"))
