@@ -496,6 +496,9 @@ __device__ __forceinline__ void sphere_step(const float4 *__restrict__ nodes, co
 #ifndef RTX_Q3_SORT64
 #define RTX_Q3_SORT64 1
 #endif
+#ifndef RTX_Q3_PUSH_ALL
+#define RTX_Q3_PUSH_ALL 1                     // sphere_node_step_q3: 1 = all four links written, the nearest read back; 0 = the counted pushes
+#endif
 template <int STACK, bool SPILL, class RAY>
 __device__ __forceinline__ void sphere_step_q3(const float4 *__restrict__ qnodes, const float4 *__restrict__ leaf_f32,
                                                const uint32_t *__restrict__ leaf_prims, const RAY &q, const SphereRay &sr,
@@ -690,6 +693,9 @@ __device__ __forceinline__ void sphere_node_step_q3(const float4 *__restrict__ q
     const uint32_t nyw = gy ? hiy : loy, fyw = gy ? loy : hiy;
     const uint32_t nzw = gz ? hiz : loz, fzw = gz ? loz : hiz;
     double kd[4];
+#if RTX_Q3_PUSH_ALL
+    uint32_t n_enter = 0;
+#endif
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         const float x0 = __builtin_fmaf((float)((nxw >> (8 * c)) & 255u), Sx, Ox), x1 = __builtin_fmaf((float)((fxw >> (8 * c)) & 255u), Sx, Ox);
@@ -701,10 +707,57 @@ __device__ __forceinline__ void sphere_node_step_q3(const float4 *__restrict__ q
         const float tf_hi = __builtin_fmaf(tf, 1.0f + 4.76837158e-7f, e);
         // (one compare against the smaller of the two limits; type 7 is an empty slot: one select for both conditions)
         const bool enter = (tn_lo <= fminf(tf_hi, best_up)) & (lk[c] < 0xE0000000u);
+#if RTX_Q3_PUSH_ALL
+        n_enter += enter ? 1u : 0u;
+        const float key = enter ? tn_lo : -__builtin_inff();
+#else
         const float key = enter ? tn_lo : __builtin_inff();
+#endif
         kd[c] = __hiloint2double((int)__float_as_uint(key), (int)lk[c]);
     }
     nbox += 4;
+#if RTX_Q3_PUSH_ALL
+    // (key, link) pairs ordered as f64 values (sphere_step_q3), FARTHEST first, the children not entered (key -inf) last: all four
+    // links are written to the rows sp .. sp + 3 as they stand -- the rows above the new top are nobody's -- and the nearest child is
+    // read back as the top of the stack, by the same read that pops when no child was entered.  Same visiting order as pushing the
+    // far children and keeping the nearest in a register, without the counting, the row selects and the separate pop.
+    // (An entered key is finite or +inf, never -inf: tn >= 0 and the slack is finite.  One difference to the counted form: a child
+    // entered with tn_lo == +inf -- possible only when tf_hi and best_up are +inf as well -- is visited here, where the counted form's
+    // "key < inf" tests dropped it: conservative, it cannot change the image.)
+#define RTX_CSWAP(i, j) { double lo_, hi_; rtx_minmax_f64_bits(kd[i], kd[j], lo_, hi_); kd[i] = hi_; kd[j] = lo_; }
+    RTX_CSWAP(0, 1) RTX_CSWAP(2, 3) RTX_CSWAP(0, 2) RTX_CSWAP(1, 3) RTX_CSWAP(1, 2)
+#undef RTX_CSWAP
+    if (sp + 3u <= (uint32_t)STACK) {                    // (row STACK, the sink of the other form, is the fourth row of sp = STACK - 3)
+        uint32_t *const row = lds_stack + ((size_t)sp * kBvhThreads + tid);
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i) row[i * kBvhThreads] = (uint32_t)__double2loint(kd[i]);
+        const uint32_t top = sp + n_enter;
+        node = kNone;
+        if (top != 0u) {
+            sp = top - 1u;
+            node = lds_stack[(size_t)sp * kBvhThreads + tid];
+        }
+    } else {
+#define RTX_PUSH(v)                                                                                  \
+        {                                                                                            \
+            if (sp < (uint32_t)STACK) { lds_stack[(size_t)sp * kBvhThreads + tid] = (v); sp += 1; } \
+            else if (SPILL && sp - (uint32_t)STACK < spill_entries) {                                \
+                spill[(size_t)(sp - (uint32_t)STACK) * spill_stride + glane] = (v); sp += 1;         \
+            } else overflow = true;                                                                  \
+        }
+#pragma unroll
+        for (uint32_t i = 0; i < 3; ++i)
+            if (i + 1u < n_enter) RTX_PUSH((uint32_t)__double2loint(kd[i]))
+#undef RTX_PUSH
+        const double near_ = n_enter >= 3u ? (n_enter == 4u ? kd[3] : kd[2]) : (n_enter == 2u ? kd[1] : kd[0]);
+        node = n_enter != 0u ? (uint32_t)__double2loint(near_) : kNone;
+        if (node == kNone && sp != 0u) {
+            sp -= 1;
+            node = (!SPILL || sp < (uint32_t)STACK) ? lds_stack[(size_t)sp * kBvhThreads + tid]
+                                                    : spill[(size_t)(sp - (uint32_t)STACK) * spill_stride + glane];
+        }
+    }
+#else
     // (key, link) pairs ordered as f64 values (sphere_step_q3)
 #define RTX_CSWAP(i, j) { double lo_, hi_; rtx_minmax_f64_bits(kd[i], kd[j], lo_, hi_); kd[i] = lo_; kd[j] = hi_; }
     RTX_CSWAP(0, 1) RTX_CSWAP(2, 3) RTX_CSWAP(0, 2) RTX_CSWAP(1, 3) RTX_CSWAP(1, 2)
@@ -741,6 +794,7 @@ __device__ __forceinline__ void sphere_node_step_q3(const float4 *__restrict__ q
         node = (!SPILL || sp < (uint32_t)STACK) ? lds_stack[(size_t)sp * kBvhThreads + tid]
                                                 : spill[(size_t)(sp - (uint32_t)STACK) * spill_stride + glane];
     }
+#endif
 }
 
 // The leaf `ref` (type << 29 | first record, type = its 1..6 spheres): sphere_step's bounds for each record, then the next entry.
