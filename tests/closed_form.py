@@ -554,3 +554,82 @@ def lens_check(mean, n_samples, p, systematic, sigmas=5.0):
     5 sigma of a Bernoulli(p), plus the case's systematic term."""
     err, bound = hemisphere_check(mean, n_samples, p, 1.0, sigmas)
     return err, bound + systematic
+
+
+# ---- ray_hit's two colour updates and avg (scene.rs:276-277, :253-259; iter_ops.rs:4-8; div.rs:11-20) on values that are NOT dyadic ---------
+# Dyadic values come out the same under any summation order, any fused multiply-add and any `* (1 / n)`; these do not.
+# (0.1, 0.7, 1/3) as emission would do for the summation, but with these base colours a fused `res = fma(light, e, res)` happens to
+# round to the same values as the two-rounding form at every step up to 10 bounces, in all three channels; with the emission below it
+# differs in every channel at 3 and at 10 bounces (tests/test_text_shapes.py checks that).
+COLOUR_EMIT, COLOUR_BASE = (0.13, 0.6, 1.0 / 7.0), (0.9, 0.3, 0.77)
+COLOUR_BOUNCES, COLOUR_SPP = (0, 3, 10), (1, 3, 7, 10, 64)
+LENS_COLOUR_SPP, LENS_COLOUR_FRAME = (7, 10, 64, 257), 64
+
+
+def closed_box_coloured(dtype, n_spheres=0, seed=5):
+    """closed_box with emission COLOUR_EMIT and base colour COLOUR_BASE on EVERY object: every ray still hits something at every
+    iteration, so every sample is the same value whatever the seed, the directions or the objects hit."""
+    o = closed_box(dtype, n_spheres, seed)
+    o["emission_color"] = COLOUR_EMIT
+    o["base_color"] = COLOUR_BASE
+    return o
+
+
+def coloured_sample(max_bounces, emit=COLOUR_EMIT, base=COLOUR_BASE):
+    """render_ray's value per channel, plain Python floats: resulting_color = 0, light_color = 1 (ray.rs:18-19), then max_bounces + 1
+    times (scene.rs:227) resulting_color += light_color * emission; light_color *= base_color (scene.rs:276-277) -- a product, then
+    a sum: two roundings, nothing fused."""
+    out = []
+    for e, b in zip(emit, base):
+        res, light = 0.0, 1.0
+        for _ in range(max_bounces + 1):
+            res = res + light * e
+            light = light * b
+        out.append(res)
+    return tuple(out)
+
+
+def fold(value, k):
+    """`value` added k times from zero, left to right (iter_ops.rs:4-8)"""
+    total = 0.0
+    for _ in range(k):
+        total = total + value
+    return total
+
+
+def coloured_pixel(max_bounces, n):
+    """avg of n equal samples (scene.rs:253-259): the fold, then / (n as f64) (div.rs:11-20)"""
+    return tuple(fold(v, n) / float(n) for v in coloured_sample(max_bounces))
+
+
+def lens_coloured_cases(dtype):
+    """The "origin jitter uniform: half, y" scene of lens_cases with the light's emission COLOUR_EMIT: a sample is E = 0 + 1 * e or 0
+    (the occluder is black), adding 0 is exact, so a pixel is fold(E, k) / n in all three channels for ONE k in 0..n -- the number
+    of lit samples, Binomial(n, 1/2).  A binomial count with p = 1/2 stays within a few sqrt(n) / 2 of n / 2, so on its own it
+    cannot reach half of 0..n for n >= 64: the quarter scene (z) and the same scene with the edge moved to 3/4 (lit share 3/4) cover the
+    rest of the range.  Yields (name, objects, camera, config kwargs without seed / rays_per_pixel)."""
+    cases = {name: (objs, cam, cfg) for name, objs, cam, cfg, _, _, _ in lens_cases(dtype)}
+    objs, cam, cfg = cases["origin jitter uniform: half, y"]
+    out = [("half, y", objs, cam, cfg)]
+    objs, cam, cfg = cases["origin jitter uniform: quarter, z"]
+    out.append(("quarter, z", objs, cam, cfg))
+    out.append(("three quarters, z", _lens_scene(dtype, [_occluder(dtype, 5.0, 2, 0.75, +1)], 20.0), cam, cfg))
+    for name, objs, cam, cfg in out:
+        objs = objs.copy()
+        assert tuple(objs[0]["emission_color"]) == LENS_EMIT
+        objs[0]["emission_color"] = COLOUR_EMIT
+        yield name, objs, cam, dict(cfg)
+
+
+def lens_allowed(n, emit=COLOUR_EMIT):
+    """[n + 1][3]: row k is the pixel with k lit samples, (fold(E_c, k) / n for the three channels)"""
+    return np.array([[fold(e, k) / float(n) for e in emit] for k in range(n + 1)])
+
+
+def lens_lit_counts(img, n):
+    """per pixel the k whose row of lens_allowed equals the pixel in ALL THREE channels bit for bit, -1 where there is none"""
+    allowed = lens_allowed(n)
+    px = np.asarray(img, dtype=np.float64).reshape(-1, 3)
+    k = np.clip(np.searchsorted(allowed[:, 0], px[:, 0]), 0, n)
+    ok = (allowed[k].view(np.uint64) == np.ascontiguousarray(px).view(np.uint64)).all(axis=1)
+    return np.where(ok, k, -1).reshape(np.asarray(img).shape[:-1])

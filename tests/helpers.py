@@ -81,3 +81,62 @@ def sincos_args():
     near = np.concatenate([np.arange(0, 9) * (math.pi / 4) + d for d in (0.0, 1e-17, -1e-17, 1e-12, -1e-12, 1e-7, -1e-7, 3e-4, -3e-4)])
     near = near[(near >= 0) & (near <= 2 * math.pi)]
     return np.concatenate([th, edges[(edges >= 0) & (edges <= 2 * math.pi)], near, 10.0 ** rng.uniform(-300, 0, 4096)])
+
+
+def bits(a):
+    """raw f64 patterns, with every NaN made one pattern (NaN matches NaN)"""
+    a = np.array(a, dtype=np.float64, copy=True)
+    a[np.isnan(a)] = np.nan
+    return a.view(np.uint64)
+
+
+def same(a, b):
+    return np.array_equal(bits(a), bits(b))
+
+
+def check_equal(got, want, what):
+    names = ("distance", "object", "position", "normal")
+    for g, w, nm in zip(got, want, names):
+        if not same(g, w):
+            bad = np.nonzero(~np.all((bits(g) == bits(w)).reshape(len(g), -1), axis=1))[0]
+            raise AssertionError("%s: %s differs on %d rays, first %s: got %r want %r" % (what, nm, len(bad), bad[:5], g[bad[0]], w[bad[0]]))
+
+
+def fuzz_rays(rng, objs, n):
+    """origins inside / outside the scene box, inside spheres, on triangle vertices and faces, far away; unit, non-unit and axis
+    directions, a few zero and NaN ones"""
+    g = objs["geom"]
+    pts = [np.zeros((1, 3))]
+    sph = g[objs["kind"] == 0]
+    tri = g[objs["kind"] == 2]
+    if len(sph):
+        pts.append(sph[:, :3])
+    if len(tri):
+        pts.append(tri[:, :9].reshape(-1, 3))
+    allp = np.concatenate(pts)
+    lo, hi = allp.min(axis=0) - 1.0, allp.max(axis=0) + 1.0
+    kind = rng.integers(0, 7, n)
+    o = lo + (hi - lo) * rng.uniform(-0.5, 1.5, (n, 3))                         # inside and outside the box
+    if len(sph):
+        k = rng.integers(0, len(sph), n)
+        inside = sph[k, :3] + rng.normal(size=(n, 3)) * (0.3 * np.abs(sph[k, 3:4]))
+        o = np.where((kind == 1)[:, None], inside, o)
+    if len(tri):
+        k = rng.integers(0, len(tri), n)
+        v = tri[k].reshape(n, 3, 3)
+        vert = v[np.arange(n), rng.integers(0, 3, n)]
+        w = rng.dirichlet((1.0, 1.0, 1.0), n)
+        face = v[:, 0] * w[:, :1] + v[:, 1] * w[:, 1:2] + v[:, 2] * w[:, 2:3]
+        o = np.where((kind == 2)[:, None], vert, o)
+        o = np.where((kind == 3)[:, None], face, o)
+    o = np.where((kind == 4)[:, None], o * rng.choice([1e6, 1e9, 1e15], (n, 1)), o)       # far outside any origin limit
+    d = rng.normal(size=(n, 3))
+    d /= np.linalg.norm(d, axis=1)[:, None]
+    dk = rng.integers(0, 10, n)
+    d = np.where((dk == 1)[:, None], d * rng.uniform(0.05, 20.0, (n, 1)), d)             # non-unit
+    ax = np.eye(3)[rng.integers(0, 3, n)] * rng.choice([-1.0, 1.0], (n, 1))
+    d = np.where((dk == 2)[:, None], ax, d)                                              # axis-aligned
+    d = np.where((dk == 3)[:, None], (lo + hi) / 2 - o, d)                               # at the scene (non-unit)
+    d[rng.random(n) < 0.004] = 0.0
+    d[rng.random(n) < 0.004, rng.integers(0, 3)] = np.nan
+    return np.ascontiguousarray(o), np.ascontiguousarray(d)

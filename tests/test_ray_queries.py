@@ -11,7 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from helpers import DEFAULT_CAM, fuzz_scene, hip_scene
+from helpers import DEFAULT_CAM, check_equal, fuzz_rays, fuzz_scene, hip_scene, same
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "rtx_hip.h")
@@ -23,17 +23,6 @@ def gpu(rtx):
     if rtx.device_count() < 1:
         pytest.fail("no gfx950 device: the gpu tests must run on an MI355X (there is no CPU fallback to test)")
     return rtx
-
-
-def bits(a):
-    """raw f64 patterns, with every NaN made one pattern (NaN matches NaN)"""
-    a = np.array(a, dtype=np.float64, copy=True)
-    a[np.isnan(a)] = np.nan
-    return a.view(np.uint64)
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
 
 
 def oracle_answers(oracle, objs, sc, origins, dirs):
@@ -56,54 +45,6 @@ def oracle_answers(oracle, objs, sc, origins, dirs):
         pos[k] = p
         nrm[k] = L.rtxo_object_normal_at(objs.ctypes.data + i * objs.itemsize, oracle.vec(p)).tuple()
     return dist, obj, pos, nrm
-
-
-def check_equal(got, want, what):
-    names = ("distance", "object", "position", "normal")
-    for g, w, nm in zip(got, want, names):
-        if not same(g, w):
-            bad = np.nonzero(~np.all((bits(g) == bits(w)).reshape(len(g), -1), axis=1))[0]
-            raise AssertionError("%s: %s differs on %d rays, first %s: got %r want %r" % (what, nm, len(bad), bad[:5], g[bad[0]], w[bad[0]]))
-
-
-def fuzz_rays(rng, objs, n):
-    """origins inside / outside the scene box, inside spheres, on triangle vertices and faces, far away; unit, non-unit and axis
-    directions, a few zero and NaN ones"""
-    g = objs["geom"]
-    pts = [np.zeros((1, 3))]
-    sph = g[objs["kind"] == 0]
-    tri = g[objs["kind"] == 2]
-    if len(sph):
-        pts.append(sph[:, :3])
-    if len(tri):
-        pts.append(tri[:, :9].reshape(-1, 3))
-    allp = np.concatenate(pts)
-    lo, hi = allp.min(axis=0) - 1.0, allp.max(axis=0) + 1.0
-    kind = rng.integers(0, 7, n)
-    o = lo + (hi - lo) * rng.uniform(-0.5, 1.5, (n, 3))                         # inside and outside the box
-    if len(sph):
-        k = rng.integers(0, len(sph), n)
-        inside = sph[k, :3] + rng.normal(size=(n, 3)) * (0.3 * np.abs(sph[k, 3:4]))
-        o = np.where((kind == 1)[:, None], inside, o)
-    if len(tri):
-        k = rng.integers(0, len(tri), n)
-        v = tri[k].reshape(n, 3, 3)
-        vert = v[np.arange(n), rng.integers(0, 3, n)]
-        w = rng.dirichlet((1.0, 1.0, 1.0), n)
-        face = v[:, 0] * w[:, :1] + v[:, 1] * w[:, 1:2] + v[:, 2] * w[:, 2:3]
-        o = np.where((kind == 2)[:, None], vert, o)
-        o = np.where((kind == 3)[:, None], face, o)
-    o = np.where((kind == 4)[:, None], o * rng.choice([1e6, 1e9, 1e15], (n, 1)), o)       # far outside any origin limit
-    d = rng.normal(size=(n, 3))
-    d /= np.linalg.norm(d, axis=1)[:, None]
-    dk = rng.integers(0, 10, n)
-    d = np.where((dk == 1)[:, None], d * rng.uniform(0.05, 20.0, (n, 1)), d)             # non-unit
-    ax = np.eye(3)[rng.integers(0, 3, n)] * rng.choice([-1.0, 1.0], (n, 1))
-    d = np.where((dk == 2)[:, None], ax, d)                                              # axis-aligned
-    d = np.where((dk == 3)[:, None], (lo + hi) / 2 - o, d)                               # at the scene (non-unit)
-    d[rng.random(n) < 0.004] = 0.0
-    d[rng.random(n) < 0.004, rng.integers(0, 3)] = np.nan
-    return np.ascontiguousarray(o), np.ascontiguousarray(d)
 
 
 def incoherent_rays(rng, objs, n):
