@@ -283,7 +283,12 @@ int32_t rtx_scene_set_config(RtxSceneHandle scene, const RtxConfig *config);
  * sample batches -- same bits (the fold continues across batches).  For several handles, ranks or frameworks sharing a GPU.
  * What a launch allocates whatever its batch (a queue chunk per resident wave, counters, stack columns: 0.15-0.3 GB on a
  * 256-CU part) is taken off the limit before the batch is sized.  The floor is ONE sample of the band per launch: a limit
- * below that size is exceeded by that one sample's records + the fixed part (a frame cannot be cut finer). */
+ * below that size is exceeded by that one sample's records + the fixed part (a frame cannot be cut finer).
+ * The largest single launch the default yields, by what a ray of the launch holds: 32 B (the LDS sweep, the exhaustive kernel, the
+ * mesh megakernel): ~800 M rays; 101 B (a sphere tree's two stages: + the survivors' queue): ~255 M; 408 B (the wavefront form: + two
+ * sets of ray state, two record queues, candidates): ~63 M -- and never 2^32 ray slots or more.  Observed by tests/test_launch_sizes.py,
+ * which holds such launches to the bits of small ones: one launch for 165.9 M rays (1920 x 1080 x 80) of the first two families and for
+ * 180.4 M (16384 x 11008 x 1) of the second; the wavefront form takes 33.2 M (16 spp) in one launch and 132.7 M (64 spp) in three. */
 int32_t rtx_scene_set_scratch_limit(RtxSceneHandle scene, uint64_t bytes);
 
 /* Scene::add_object (scene.rs:126-128) on an uploaded scene: the objects are appended in order (they get the next scene
@@ -359,8 +364,15 @@ int32_t rtx_quantize_image_device(const double *d_rgb, uint32_t width, uint32_t 
  * 2: sin(a), 3: cos(a), 4 / 5: sincos(a)'s two results; 6: the packet walks' v_writelane -- out[i] = (int)b[0] in lane (int)b[1]
  * of every wave, (int)a[i] elsewhere; 7 / 8: v_min_f64 / v_max_f64 on the raw bits of a[i], b[i] -- the child sort's (key, link)
  * pairs are denormal f64 patterns when the key is +0.0 and must come back bit for bit; 9 / 10: the sin / cos the path itself uses
- * for Vector3::random_direction's angle in [0, 2 pi] -- rtx_math.h sincos_2pi); a, b, out are HOST arrays of n doubles.  Used by tests/ to check that the
- * device's / and sqrt are correctly rounded and to measure how far its sin/cos are from libm. */
+ * for Vector3::random_direction's angle in [0, 2 pi] -- rtx_math.h sincos_2pi; 11-16: the trace kernels' ray index -> pixel arithmetic
+ * (rtx_device.h) on 32-bit integers held in doubles, the divisors built on the host and passed as a kernel argument as the renders
+ * pass theirs -- 11: fastdiv(a[i], make_fastdiv(b[0])); 12 / 13: ray_index_to_pixel's local pixel / sample of ray index a[i] in a band
+ * of b[0] pixels; 14 / 15 / 16: ray_index_to_pixel_tiled's local pixel / sample / 1.0 unless the lane is the padding of a partial 8x8
+ * tile, in a band of b[0] columns x b[1] rows; 17-21: the HOST forms, evaluated without a device -- 17: fastdiv(a[i],
+ * make_fastdiv(b[0])); 18: image_row of local row a[i] for row_begin, row_stride, row_block = b[0], b[1], b[2]; 19 / 20 / 21: m, s1, s2
+ * of make_fastdiv(a[i])); a, b, out are HOST arrays of n doubles.  Used by tests/ to check that the
+ * device's / and sqrt are correctly rounded, to measure how far its sin/cos are from libm, and to hold the index arithmetic to
+ * "exact for every 32-bit n" at ray counts no test can afford to allocate. */
 int32_t rtx_debug_math(int32_t op, const double *a, const double *b, double *out, uint64_t n);
 
 /* Test hook (lab library; the product returns RTX_ERR_UNSUPPORTED): the TRANSCRIPT of every path of one image row, as the exhaustive

@@ -528,3 +528,40 @@ def debug_math(op, a, b=None):
     lib = load_library(True)
     abi.check(lib.rtx_debug_math(int(op), a.ctypes.data, b.ctypes.data, out.ctypes.data, a.size), lib)
     return out
+
+
+def _debug_index(op, values, params):
+    """one of rtx_debug_math's index ops (11-21) on uint32 `values`: b carries `params` in its first entries -> uint32 array"""
+    v = np.ascontiguousarray(values, dtype=np.uint32).ravel()
+    a = np.zeros(max(v.size, len(params)), dtype=np.float64)
+    a[:v.size] = v
+    b = np.zeros_like(a)
+    b[:len(params)] = [int(p) for p in params]
+    return debug_math(op, a, b)[:v.size].astype(np.uint32)
+
+
+def debug_fastdiv(n, d, host=False):
+    """fastdiv(n[i], make_fastdiv(d)) as the kernels evaluate it (rtx_device.h); host=True: the host form, no device needed"""
+    return _debug_index(17 if host else 11, n, (d,))
+
+
+def debug_ray_index_to_pixel(i, npix):
+    """(local pixel, sample) of ray indices i in a band of npix pixels: the device's ray_index_to_pixel"""
+    return _debug_index(12, i, (npix,)), _debug_index(13, i, (npix,))
+
+
+def debug_ray_index_to_pixel_tiled(i, width, n_rows):
+    """(local pixel, sample, live) of ray indices i of a width x n_rows band whose queue runs over 8x8 tiles (live False: the padding of
+    a partial tile, whose pixel means nothing): the device's ray_index_to_pixel_tiled"""
+    p = (width, n_rows)
+    return _debug_index(14, i, p), _debug_index(15, i, p), _debug_index(16, i, p) != 0
+
+
+def debug_image_row(k, row_begin, row_stride, row_block):
+    """image_row of local rows k (rtx_device.h), the host form: needs no device"""
+    return _debug_index(18, k, (row_begin, row_stride, row_block))
+
+
+def debug_make_fastdiv(d):
+    """(m, s1, s2) of make_fastdiv(d[i]), host code: needs no device"""
+    return _debug_index(19, d, ()), _debug_index(20, d, ()), _debug_index(21, d, ())

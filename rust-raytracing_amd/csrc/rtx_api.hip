@@ -1680,6 +1680,8 @@ int32_t rtx_debug_math(int32_t op, const double *a, const double *b, double *out
 #else
     if (n == 0) return RTX_OK;
     if (!a || !out) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_math: null argument");
+    if (op >= 17 && op <= 21)                       // the host forms of the index arithmetic: no device is touched
+        return debug_math_host(op, a, b ? b : a, out, n) ? RTX_OK : fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_math: op 18 takes three values in b");
     if (usable_device_count() == 0) return fail(RTX_ERR_NO_DEVICE, "no gfx950 device");
     struct Bufs {                                   // freed on every return path
         double *p[3] = { nullptr, nullptr, nullptr };
@@ -1689,7 +1691,7 @@ int32_t rtx_debug_math(int32_t op, const double *a, const double *b, double *out
     for (double *&q : d.p) RTX_HIP_CHECK(hipMalloc((void **)&q, n * sizeof(double)));
     RTX_HIP_CHECK(hipMemcpy(d.p[0], a, n * sizeof(double), hipMemcpyHostToDevice));
     RTX_HIP_CHECK(hipMemcpy(d.p[1], b ? b : a, n * sizeof(double), hipMemcpyHostToDevice));
-    RTX_HIP_CHECK(launch_debug_math(op, d.p[0], d.p[1], d.p[2], n, nullptr));
+    RTX_HIP_CHECK(launch_debug_math(op, d.p[0], d.p[1], d.p[2], n, b ? b : a, nullptr));
     RTX_HIP_CHECK(hipMemcpy(out, d.p[2], n * sizeof(double), hipMemcpyDeviceToHost));
     return RTX_OK;
 #endif

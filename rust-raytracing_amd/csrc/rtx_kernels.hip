@@ -597,7 +597,9 @@ __global__ __launch_bounds__(256) void deinterleave_kernel(const uint8_t *__rest
 }
 
 #ifdef RTX_LAB
-__global__ void debug_math_kernel(int op, const double *a, const double *b, double *out, uint64_t n)
+// ops 11-16: a ray index -> pixel arithmetic of the trace kernels (rtx_device.h) on the RowsView the host built for the op, passed
+// by value as the renders pass their divisors: out[i] for the index / numerator (uint32_t)a[i]
+__global__ void debug_math_kernel(int op, const double *a, const double *b, double *out, uint64_t n, RowsView rv)
 {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -612,6 +614,17 @@ __global__ void debug_math_kernel(int op, const double *a, const double *b, doub
             r = (double)rtx_writelane(__builtin_amdgcn_readfirstlane((int)b[0]), __builtin_amdgcn_readfirstlane((int)b[1]), (int)a[i]);
             break;
         case 9: case 10: { double sn, cs; sincos_2pi(a[i], &sn, &cs); r = (op == 9) ? sn : cs; } break;     // random_direction's sin / cos (rtx_math.h)
+        case 11: r = (double)fastdiv((uint32_t)a[i], rv.div_npix); break;
+        case 12: case 13: {                              // ray_index_to_pixel: the local pixel / the sample
+            uint32_t pl, s_local;
+            ray_index_to_pixel(rv, (uint64_t)a[i], pl, s_local);
+            r = (double)(op == 12 ? pl : s_local);
+        } break;
+        case 14: case 15: case 16: {                     // ray_index_to_pixel_tiled: the local pixel / the sample / 1.0 unless the lane is padding
+            uint32_t pl, s_local;
+            const bool live = ray_index_to_pixel_tiled(rv, (uint64_t)a[i], pl, s_local);
+            r = op == 14 ? (double)pl : (op == 15 ? (double)s_local : (live ? 1.0 : 0.0));
+        } break;
         default: {                                       // 7 / 8: the child sort's v_min_f64 / v_max_f64 on raw bit patterns
             double lo, hi;
             rtx_minmax_f64_bits(a[i], b[i], lo, hi);
@@ -771,11 +784,51 @@ hipError_t launch_deinterleave_u8(const uint8_t *parts, uint8_t *full, uint32_t 
 }
 
 #ifdef RTX_LAB
-hipError_t launch_debug_math(int op, const double *a, const double *b, double *out, uint64_t n, hipStream_t stream)
+// The RowsView of the index ops, sized as render_band sizes a launch's: 11-13 take the divisor / npix from b[0], 14-16 a band of
+// b[0] columns x b[1] rows whose ray queue runs over 8x8 tiles.
+static RowsView debug_index_view(int op, const double *b_host, uint64_t n)
+{
+    RowsView rv{};
+    const uint32_t b0 = b_host ? (uint32_t)b_host[0] : 0u, b1 = (b_host && n > 1) ? (uint32_t)b_host[1] : 0u;
+    if (op >= 11 && op <= 13) {
+        rv.npix = b0;
+        rv.div_npix = make_fastdiv(b0);
+    } else if (op >= 14 && op <= 16) {
+        rv.width = b0; rv.n_rows = b1; rv.npix = b0 * b1;
+        rv.tiles_x = (b0 + 7u) / 8u;
+        rv.div_width = make_fastdiv(b0); rv.div_npix = make_fastdiv(rv.npix); rv.div_tiles_x = make_fastdiv(rv.tiles_x);
+        rv.div_per_sample = make_fastdiv((uint32_t)((uint64_t)rv.tiles_x * ((b1 + 7u) / 8u) * 64u));
+    }
+    return rv;
+}
+
+hipError_t launch_debug_math(int op, const double *a, const double *b, double *out, uint64_t n, const double *b_host, hipStream_t stream)
 {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(debug_math_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, op, a, b, out, n);
+    hipLaunchKernelGGL(debug_math_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, op, a, b, out, n,
+                       debug_index_view(op, b_host, n));
     return hipGetLastError();
+}
+
+// ops 17-21 need no kernel: the HOST forms (RTX_HD) that size launches and fill the row tables.  17: fastdiv(a[i], make_fastdiv(b[0]));
+// 18: image_row of local row a[i] in a band with row_begin, row_stride, row_block = b[0], b[1], b[2]; 19 / 20 / 21: m, s1, s2 of
+// make_fastdiv(a[i])
+bool debug_math_host(int op, const double *a, const double *b, double *out, uint64_t n)
+{
+    if (op < 17 || op > 21) return false;
+    RowsView rv{};
+    if (op == 18) {
+        if (n < 3) return false;
+        rv.row_begin = (uint32_t)b[0]; rv.row_stride = (uint32_t)b[1]; rv.row_block = (uint32_t)b[2];
+        rv.div_row_block = make_fastdiv(rv.row_block);
+    }
+    const FastDiv f17 = make_fastdiv((uint32_t)b[0]);
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint32_t v = (uint32_t)a[i];
+        const FastDiv f = make_fastdiv(v);
+        out[i] = op == 17 ? (double)fastdiv(v, f17) : op == 18 ? (double)image_row(rv, v) : op == 19 ? (double)f.m : op == 20 ? (double)f.s1 : (double)f.s2;
+    }
+    return true;
 }
 #endif
 

@@ -180,7 +180,8 @@ hipError_t launch_trace_transcript(const SceneView *d_sv, const RowsView *d_rv, 
                                    uint32_t max_steps, hipStream_t stream);
 #endif
 #ifdef RTX_LAB
-hipError_t launch_debug_math(int op, const double *a, const double *b, double *out, uint64_t n, hipStream_t stream);
+hipError_t launch_debug_math(int op, const double *a, const double *b, double *out, uint64_t n, const double *b_host, hipStream_t stream);
+bool debug_math_host(int op, const double *a, const double *b, double *out, uint64_t n);      // ops 17-21: host forms, no device
 #endif
 
 }  // namespace rtx

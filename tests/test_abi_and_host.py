@@ -517,3 +517,32 @@ def test_bench_dump_outputs_whole_frame_or_seeded_sample(tmp_path, monkeypatch):
     assert vals.dtype == pix.dtype == np.float64 and vals.shape == (32, 3) and vals.nbytes + pix.nbytes <= 1024
     assert len(set(pix.tolist())) == 32 and np.array_equal(vals, img.reshape(-1, 3)[pix.astype(np.int64)])
     assert np.array_equal(np.load(tmp_path / "b" / "image_sample.npy"), vals) and np.array_equal(np.load(tmp_path / "b" / "image_sample_pixels.npy"), pix)
+
+
+def test_host_index_arithmetic_is_exact_for_every_32_bit_value(rtx):
+    """make_fastdiv / fastdiv / image_row as the HOST evaluates them (rtx_device.h's RTX_HD forms: they size launches and fill the row
+    tables), through rtx_debug_math ops 17-21 of the lab library -- no device.  make_fastdiv's constants against Granlund & Montgomery's
+    round-up multiplier (l = ceil(log2 d), m = floor(2^32 (2^l - d) / d) + 1, s1 = min(l, 1), s2 = max(l - 1, 0)); the five-instruction
+    quotient, evaluated on those constants in Python integers, never leaves 32 bits; fastdiv == n // d on 0, d - 1, d, the multiples
+    of d next to 2^32, the 2^27 and 2^31 edges and 2^20 random numerators per divisor; image_row against its definition."""
+    from helpers import FASTDIV_DIVISORS, index_values, tiled_slots
+    rng = np.random.default_rng(5)
+    legs = [1920 * 1080, tiled_slots(1920, 1080), 3840 * 272, tiled_slots(3840, 272), 16384 * 11008, 8192 * 8192, tiled_slots(1003, 9)]
+    divisors = list(FASTDIV_DIVISORS) + legs + [int(v) for v in rng.integers(1, 1 << 32, 64)]
+    m, s1, s2 = rtx.debug_make_fastdiv(divisors)
+    for d, mm, a, b in zip(divisors, m, s1, s2):
+        l = (d - 1).bit_length()
+        assert (int(mm), int(a), int(b)) == ((((1 << l) - d) << 32) // d + 1, min(l, 1), max(l - 1, 0)), d
+        assert int(mm) < 1 << 32
+        for n in index_values(d, 1 << 32, 64, rng).tolist():
+            t = (int(mm) * n) >> 32
+            assert t <= n and t + ((n - t) >> int(a)) < 1 << 32 and (t + ((n - t) >> int(a))) >> int(b) == n // d, (d, n)
+    for d in list(FASTDIV_DIVISORS) + legs:
+        n = index_values(d, 1 << 32, 1 << 20, rng)
+        got = rtx.debug_fastdiv(n, d, host=True)
+        bad = np.nonzero(got != n // np.uint32(d))[0]
+        assert len(bad) == 0, (d, int(n[bad[0]]), int(got[bad[0]]))
+    for begin, stride, block in ((0, 1, 1), (3, 8, 1), (5, 64, 8), (0, 8, 8), (2, 10, 5), (7, 0x10000, 8)):
+        k = np.concatenate([np.arange(0, 4 * block + 2), rng.integers(0, 1 << 16, 4096)]).astype(np.uint32)
+        want = begin + (k.astype(np.int64) // block) * stride + k.astype(np.int64) % block
+        assert np.array_equal(rtx.debug_image_row(k, begin, stride, block).astype(np.int64), want), (begin, stride, block)

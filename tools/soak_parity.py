@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Soak: the tree kernels (BVH lock-step, BVH regroup, wavefront form) and the LDS sweep against the exhaustive f64 kernel, bit for bit, on
-the full-size C2 / C3 scenes from several cameras (outside, inside the cloud, looking along each axis).  Prints one line
+the full-size C2 / C3 scenes from several cameras (outside, inside the cloud, looking along each axis).  Full-size in PIXELS, at 1 spp
+(SPP=3 in the environment: 3): launches of 2-6 M rays.  The size of a launch -- the 64-spp frames bench.py times, launches past 2^27
+rays and 4 GiB per buffer -- is tests/test_launch_sizes.py's subject.  Prints one line
 per (scene, camera) with the number of segments compared; exits non-zero on the first difference."""
 import sys, os, math
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, R)
