@@ -53,6 +53,9 @@ int usable_device_count()
 // queue -- and 59 M rays of the wavefront form run as one launch; fewer, larger launches measured 3-10 % faster)
 constexpr size_t kDefaultScratchBytes = (size_t)24576 << 20;
 
+// the non-zero mask of a launch's sample records (store_sample, rtx_device.h): one bit per ray-queue slot, in whole 32-bit words
+static size_t nonzero_mask_bytes(uint64_t n_rays) { return (size_t)((n_rays + 31) / 32) * sizeof(uint32_t); }
+
 // Triangles per BVH leaf (RTX_TUNE_TRI_LEAF_SHIFT bits of RtxConfig.tuning: 1..6 -- a leaf must fit the walk's 6-entry
 // candidate queue, or every visit of it ends in the exhaustive sweep).  A tree of (x, y) footprints alone (`plain`: C3, C5)
 // gets 5: a packet tests a leaf's records for 64 rays at once and the regrouping kernel's leaf half reads one leaf per lane
@@ -862,7 +865,7 @@ static int32_t render_band(RtxSceneHandle h, uint32_t width, uint32_t height, ui
     // build_mesh_tile_lists_kernel) -- 2 KB resp. 4 KB per tile, so only where they stay a small part of the scratch cap (decided below)
     uint64_t tile_list_bytes = 0;
     {
-        // bytes per ray of a batch: the 32-byte sample record (+ the wavefront kernels' state, ~270 B)
+        // bytes per ray of a batch: the 32-byte sample record and its bit of the non-zero mask (+ the wavefront kernels' state, ~270 B)
         // (+ the survivors' queue of the sphere kernel's two-stage form, 64 B)
         const bool sph2 = kernel == RTX_KERNEL_BVH && (h->sv.bvh_flags & 2u) == 0u && h->sv.n_bvh_nodes != 0;
         const uint64_t per_ray = 4 * sizeof(double) + (kernel == RTX_KERNEL_WAVEFRONT ? wavefront_state_bytes(1u << 20, 1) >> 20 : 0) +
@@ -889,7 +892,7 @@ static int32_t render_band(RtxSceneHandle h, uint32_t width, uint32_t height, ui
                                (kernel == RTX_KERNEL_WAVEFRONT ? (uint64_t)wavefront_state_bytes(0, 1) + wavefront_spill_bytes(h->sv, h->n_cus) : 0) +
                                (kernel == RTX_KERNEL_MIXED || kernel == RTX_KERNEL_MIXED_VERIFY ? (uint64_t)mixed_state_bytes(h->n_cus) : 0);
         const uint64_t room = cap_bytes > fixed ? cap_bytes - fixed : 0;
-        const uint64_t fit = room / (per_sample64 * per_ray);
+        const uint64_t fit = room * 8 / (per_sample64 * (per_ray * 8 + 1));      // (in bits: the mask's one per ray)
         const uint64_t fit32 = 0xFFFFFFF0ull / per_sample64;
         if (batch > fit) batch = fit ? fit : 1;
         if (batch > fit32) batch = fit32;
@@ -899,7 +902,9 @@ static int32_t render_band(RtxSceneHandle h, uint32_t width, uint32_t height, ui
 
     // ---- scratch: one RGB per ray of a sample batch, the running per-pixel sum, the SoA ray state
     if (spp > 0) {
-        if (int32_t rc = grow((void **)&h->samples, &h->samples_bytes, (size_t)(batch * per_sample64 * 4 * sizeof(double)))) return rc;
+        // the records of a batch, then one bit per record: which of them store_sample wrote (the others are zero samples)
+        if (int32_t rc = grow((void **)&h->samples, &h->samples_bytes,
+                              (size_t)(batch * per_sample64 * 4 * sizeof(double)) + nonzero_mask_bytes(batch * per_sample64))) return rc;
     }
     if (batch < spp) {
         if (int32_t rc = grow((void **)&h->acc, &h->acc_bytes, (size_t)npix * 3 * sizeof(double))) return rc;
@@ -973,6 +978,8 @@ static int32_t render_band(RtxSceneHandle h, uint32_t width, uint32_t height, ui
     rv.div_tiles_x = make_fastdiv(tiles_x); rv.div_per_sample = make_fastdiv(per_sample);
     rv.sin_x = h->tables; rv.cos_x = h->tables + width;
     rv.sin_y = h->tables + 2 * (size_t)width; rv.cos_y = rv.sin_y + n_rows;
+    rv.nonzero = spp > 0 ? reinterpret_cast<uint32_t *>(h->samples + (size_t)(batch * per_sample64) * 4) : nullptr;
+    rv.nonzero_base = 0;
 
     if (h->sv_dirty) {
         RTX_HIP_CHECK(hipMemcpyAsync(h->d_sv, &h->sv, sizeof(SceneView), hipMemcpyHostToDevice, stream));
@@ -1038,6 +1045,7 @@ static int32_t render_band(RtxSceneHandle h, uint32_t width, uint32_t height, ui
             }
         } join{h, stream};
         RTX_HIP_CHECK(hipMemsetAsync(b.counters, 0, sizeof(Counters) * kCounterShards, stream));
+        RTX_HIP_CHECK(hipMemsetAsync(rv.nonzero, 0, nonzero_mask_bytes(per_sample64 * spp), stream));     // (both halves' bits, before the fork)
         if (stats) RTX_HIP_CHECK(hipEventRecord(h->ev[0], stream));
         RTX_HIP_CHECK(hipEventRecord(b.fork, stream));                 // (behind the tables, the scene descriptor and the zeroed counters)
         RTX_HIP_CHECK(hipStreamWaitEvent(b.stream, b.fork, 0));
@@ -1048,6 +1056,7 @@ static int32_t render_band(RtxSceneHandle h, uint32_t width, uint32_t height, ui
             r.sample_begin = k == 0 ? 0u : (uint32_t)ns[0];
             r.n_samples = (uint32_t)ns[k];
             r.n_rays = per_sample64 * ns[k];
+            r.nonzero_base = k == 0 ? 0 : per_sample64 * ns[0];          // (the second half's records and bits lie behind the first's)
             r.tiles_x = tiles_x;
             const uint64_t per_wave = r.n_rays / ((uint64_t)h->n_cus * 16u * (RTX_GRABS_PER_WAVE / 2));   // (half the rays: half the grabs)
             r.grab = (uint32_t)(per_wave >= 512 ? 512 : (per_wave <= 64 ? 64 : (per_wave & ~(uint64_t)63)));
@@ -1099,6 +1108,7 @@ static int32_t render_band(RtxSceneHandle h, uint32_t width, uint32_t height, ui
             rv.grab = (uint32_t)(per_wave >= 512 ? 512 : (per_wave <= 64 ? 64 : (per_wave & ~(uint64_t)63)));
         }
         RTX_HIP_CHECK(hipMemcpyAsync(h->d_rv, &rv, sizeof(RowsView), hipMemcpyHostToDevice, stream));   // pageable: staged before return
+        RTX_HIP_CHECK(hipMemsetAsync(rv.nonzero, 0, nonzero_mask_bytes(rv.n_rays), stream));            // no record yet: the last batch's bits go
         if (stats) RTX_HIP_CHECK(hipEventRecord(h->ev[0], stream));
         if (kernel == RTX_KERNEL_EXACT) {
             RTX_HIP_CHECK(launch_trace_exact(h->d_sv, h->d_rv, rv, h->samples, h->counters, stream));

@@ -102,6 +102,8 @@ struct RowsView {
     // host-libm trig tables (scene.rs:214-220): sin/cos(fov*(x/w-0.5)) per column,
     // sin/cos(vfov*(y/h-0.5)) per LOCAL row
     const double *sin_x, *cos_x, *sin_y, *cos_y;
+    uint32_t *nonzero;             // one bit per slot of the ray queue, cleared before the launch: set where store_sample wrote a
+    uint64_t nonzero_base;         // record (slot ridx is bit nonzero_base + ridx: a launch of a later part of the samples has a base)
     FastDiv div_width, div_row_block, div_npix, div_tiles_x, div_per_sample;    // per_sample = tiles_x * tiles_y * 64 (the host keeps n_rays < 2^32)
 };
 
@@ -181,11 +183,18 @@ __device__ __forceinline__ bool ray_index_to_pixel_tiled(const RowsView &rv, uin
 // whole 32-byte sector, which is what the memory side writes anyway.  Measured on C2 at 64 spp (WRITE_SIZE per launch
 // for 3.19 GB of samples): [pixel][3] doubles, 24 B across two sectors: 9.4 GB; three 8-byte planes: 13.6 GB (one
 // sector per 8-byte store -- L2 does not merge them before they leave); this layout: see profiles/.
+// A sample that is zero in all three components (+0.0 or -0.0: the IEEE compare, so NaN and infinities are not zero) is not
+// written at all: resolve_kernel's fold does not change when it adds one (the proof stands above that kernel), and most
+// samples are zero (a path that never reaches a light: ~95 % of C2's).  Every other sample is written as before and sets its
+// slot's bit in rv.nonzero, which the host clears before each launch; resolve_kernel reads a record only where the bit is
+// set, so whatever an earlier launch left under a clear bit is never read.
 __device__ __forceinline__ void store_sample(double *__restrict__ samples, const RowsView &rv, uint64_t ridx, V3 c)
 {
-    (void)rv;
+    if (c.x == 0.0 && c.y == 0.0 && c.z == 0.0) return;
     double4 *rec = reinterpret_cast<double4 *>(samples) + ridx;
     *rec = make_double4(c.x, c.y, c.z, 0.0);
+    const uint64_t bit = rv.nonzero_base + ridx;
+    atomicOr(rv.nonzero + (bit >> 5), 1u << (uint32_t)(bit & 31u));
 }
 
 // focal_point of a local pixel: get_ray_dir (scene.rs:213-222, with the host-computed trig values) and scene.rs:203

@@ -516,8 +516,16 @@ __global__ __launch_bounds__(THREADS, WAVES_PER_EU) void trace_mixed_kernel(cons
 // resolve: avg() (scene.rs:253-259) = left fold from zeros (iter_ops.rs:4-8), then / len
 // One thread per slot of a sample's queue order (tiles_x != 0: 8x8 pixel tiles, padding slots skipped); consecutive
 // threads read consecutive 32-byte records {r, g, b, 0}, sample after sample.
+// Zero samples are skipped: store_sample (rtx_device.h) writes no record for them and leaves their bit of `nonzero` clear, and
+// a record is read only where the bit is set.  Why the sum keeps its bits:
+//   The left fold starts at +0.0 and never becomes -0.0.
+//   Round-to-nearest gives +0.0 for x + (-x) and for +0.0 + -0.0.
+//   So s + 0.0 == s bit for bit for every addend of either sign.
+// (The running sum of an earlier batch, acc, is such a fold's value too.)  The bits of a sample's slots are read a word per
+// thread, eight samples ahead of the records, so that the records of those samples are in flight together.
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void resolve_kernel(const double *__restrict__ samples, double *__restrict__ acc,
+__global__ __launch_bounds__(256) void resolve_kernel(const double *__restrict__ samples, const uint32_t *__restrict__ nonzero,
+                                                      double *__restrict__ acc,
                                                       double *__restrict__ out, uint32_t width, uint32_t n_rows, uint32_t tiles_x,
                                                       uint32_t per_sample, uint32_t n_samples,
                                                       double divisor, int first, int last)
@@ -534,9 +542,27 @@ __global__ __launch_bounds__(256) void resolve_kernel(const double *__restrict__
     }
     double sx = 0.0, sy = 0.0, sz = 0.0;
     if (!first) { sx = acc[3 * (uint64_t)p]; sy = acc[3 * (uint64_t)p + 1]; sz = acc[3 * (uint64_t)p + 2]; }
-    for (uint32_t s = 0; s < n_samples; ++s) {
-        const double4 c = reinterpret_cast<const double4 *>(samples)[(uint64_t)s * per_sample + t];
-        sx = sx + c.x; sy = sy + c.y; sz = sz + c.z;
+    constexpr uint32_t kAhead = 8;
+    for (uint32_t s0 = 0; s0 < n_samples; s0 += kAhead) {
+        const uint32_t n = n_samples - s0 < kAhead ? n_samples - s0 : kAhead;
+        uint32_t set = 0;                             // bit j: sample s0 + j of this slot has a record
+#pragma unroll
+        for (uint32_t j = 0; j < kAhead; ++j) {
+            if (j < n) {
+                const uint64_t slot = (uint64_t)(s0 + j) * per_sample + t;
+                set |= ((nonzero[slot >> 5] >> (uint32_t)(slot & 31u)) & 1u) << j;
+            }
+        }
+        if (set == 0u) continue;
+        double4 c[kAhead];
+#pragma unroll
+        for (uint32_t j = 0; j < kAhead; ++j) {
+            c[j] = make_double4(0.0, 0.0, 0.0, 0.0);
+            if ((set >> j) & 1u) c[j] = reinterpret_cast<const double4 *>(samples)[(uint64_t)(s0 + j) * per_sample + t];
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < kAhead; ++j)
+            if ((set >> j) & 1u) { sx = sx + c[j].x; sy = sy + c[j].y; sz = sz + c[j].z; }
     }
     if (last) {
         double *o = out + 3 * (uint64_t)p;
@@ -740,7 +766,7 @@ hipError_t launch_resolve(const double *samples, double *acc, double *out, const
                           uint64_t rays_per_pixel, bool first, bool last, hipStream_t stream)
 {
     if (per_sample == 0) return hipSuccess;
-    hipLaunchKernelGGL(resolve_kernel, dim3((per_sample + 255) / 256), dim3(256), 0, stream, samples, acc, out, rv.width, rv.n_rows,
+    hipLaunchKernelGGL(resolve_kernel, dim3((per_sample + 255) / 256), dim3(256), 0, stream, samples, rv.nonzero, acc, out, rv.width, rv.n_rows,
                        rv.tiles_x, per_sample, rv.n_samples, (double)rays_per_pixel, first ? 1 : 0, last ? 1 : 0);
     return hipGetLastError();
 }
