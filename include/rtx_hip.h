@@ -391,6 +391,39 @@ typedef struct RtxPathStep {
 int32_t rtx_debug_paths(RtxSceneHandle scene, uint32_t width, uint32_t height, uint32_t row, uint32_t max_steps,
                         RtxPathStep *steps, uint32_t *counts);
 
+/* Test hooks of the sample store, the fold and the gather epilogues (lab library; the product returns RTX_ERR_UNSUPPORTED).  Each runs
+ * the product's own device function or launcher on the caller's data: every argument is a HOST array, the hook allocates on device 0,
+ * copies, launches, copies back and synchronises.  tests/test_support_kernels.py holds them to plain references, bit for bit.
+ *
+ * rtx_debug_store_samples: entry i < n is the sample rgb[3 i .. 3 i + 2] of ray-queue slot slots[i]; one thread per entry calls the
+ * trace kernels' store_sample (rtx_device.h) on it, with `records` (n_records records of 4 doubles) as the launch's sample buffer and
+ * `mask` (n_words 32-bit words) as its non-zero mask with base nonzero_base: a sample that is not zero leaves {r, g, b, 0.0} in record
+ * slots[i] and sets bit nonzero_base + slots[i] of the mask, a zero sample touches neither.  records and mask are read (the caller
+ * pre-fills them) and written back whole.  The slots must be distinct and every record and bit inside the buffers: else
+ * RTX_ERR_INVALID_ARGUMENT, nothing runs. */
+int32_t rtx_debug_store_samples(const double *rgb, const uint64_t *slots, uint64_t n, uint64_t nonzero_base, double *records,
+                                uint64_t n_records, uint32_t *mask, uint64_t n_words);
+
+/* rtx_debug_resolve: launch_resolve -- the launcher every render calls -- on a band of width x n_rows pixels whose ray queue runs in
+ * image rows (tiles_x = 0: per_sample = width * n_rows slots per sample) or over 8x8 pixel tiles (tiles_x = ceil(width / 8): per_sample =
+ * tiles_x * ceil(n_rows / 8) * 64, the padding of partial tiles included).  records: n_samples * per_sample records of 4 doubles in queue
+ * order; mask: one bit per record (bit 0 of word 0 = record 0), ceil(n_samples * per_sample / 32) words; both may be null when n_samples
+ * is 0.  first: the fold starts from zero, else from acc; last: out[3 p + c] = sum / rays_per_pixel, else the sum goes to acc (p = k *
+ * width + x, local row k).  acc (acc_doubles >= 3 * width * n_rows doubles; may be null when first and last) and out (out_doubles >= 3 *
+ * width * n_rows; may be null unless last) are read and written back whole: what lies behind the pixels must come back untouched.  On the device one more sample's worth of NaN
+ * records under set bits lies behind the caller's records and mask, so a fold that reads a sample too many shows in the frame. */
+int32_t rtx_debug_resolve(const double *records, const uint32_t *mask, uint32_t width, uint32_t n_rows, uint32_t tiles_x,
+                          uint32_t n_samples, uint64_t rays_per_pixel, int32_t first, int32_t last, double *acc, uint64_t acc_doubles,
+                          double *out, uint64_t out_doubles);
+
+/* rtx_debug_gather: the epilogues of rtx_render_devices / rtx_render_to_image_devices on a caller's staging buffer.  form 0:
+ * launch_deinterleave, parts = n bands of cap_rows rows of width * 3 doubles (band p = the blocks of `block` image rows p, p + n, ... in
+ * order) -> full, height * width * 3 doubles; form 1: launch_deinterleave_u8, the same on bytes, flip != 0: output row y is image row
+ * height - 1 - y; form 2: launch_quantize_values, parts = a band of height x width x 3 doubles -> full, as many bytes (`* 256`,
+ * saturating `as u8`, rows in place; n, cap_rows, block and flip are not read).  cap_rows below a part's row count is refused. */
+int32_t rtx_debug_gather(int32_t form, const void *parts, uint32_t width, uint32_t height, uint32_t n, uint32_t cap_rows,
+                         uint32_t block, int32_t flip, void *full);
+
 /* Test hook, needs no GPU: runs the host half of rtx_scene_upload (scene packing, filter records, the SAH build of
  * the flat BVH -- SURVEY 8f row N2; the reference's analogue is gpu_state.rs:53-77) and checks the tree's
  * invariants: every child box inside its parent's, every sphere / triangle-footprint inside its leaf's box, every

@@ -565,3 +565,64 @@ def debug_image_row(k, row_begin, row_stride, row_block):
 def debug_make_fastdiv(d):
     """(m, s1, s2) of make_fastdiv(d[i]), host code: needs no device"""
     return _debug_index(19, d, ()), _debug_index(20, d, ()), _debug_index(21, d, ())
+
+
+def debug_store_samples(rgb, slots, nonzero_base, records, mask):
+    """The trace kernels' store_sample on sample rgb[i] for ray-queue slot slots[i], one thread per entry (include/rtx_hip.h,
+    rtx_debug_store_samples; lab library).  records (n, 4) float64 and mask uint32 are the launch's sample buffer and non-zero mask as
+    the caller pre-filled them; returns what the kernel left of both, as new arrays."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.float64).reshape(-1, 3)
+    slots = np.ascontiguousarray(slots, dtype=np.uint64).ravel()
+    records = np.array(records, dtype=np.float64, order="C").reshape(-1, 4)
+    mask = np.array(mask, dtype=np.uint32, order="C").ravel()
+    if len(slots) != len(rgb):
+        raise ValueError("one slot per sample")
+    lib = load_library(True)
+    abi.check(lib.rtx_debug_store_samples(rgb.ctypes.data, slots.ctypes.data, len(slots), int(nonzero_base), records.ctypes.data,
+                                          len(records), mask.ctypes.data, mask.size), lib)
+    return records, mask
+
+
+def debug_resolve(records, mask, width, n_rows, tiled, n_samples, rays_per_pixel, first=True, last=True, acc=None, out=None):
+    """launch_resolve on a width x n_rows band (include/rtx_hip.h, rtx_debug_resolve; lab library): records (n_samples * per_sample, 4)
+    float64 in ray-queue order (tiled: 8x8 pixel tiles, else image rows), mask one bit per record; acc / out are the running sum and the
+    output as the caller pre-filled them (flat float64, at least 3 per pixel).  Returns (out, acc) as the kernel left them, as new arrays
+    (None for one that was not given)."""
+    rec = None if records is None else np.ascontiguousarray(records, dtype=np.float64)
+    msk = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint32)
+    acc = None if acc is None else np.array(acc, dtype=np.float64, order="C").ravel()
+    out = None if out is None else np.array(out, dtype=np.float64, order="C").ravel()
+    tiles_x = (int(width) + 7) // 8 if tiled else 0
+    per_sample = tiles_x * ((int(n_rows) + 7) // 8) * 64 if tiled else int(width) * int(n_rows)
+    if n_samples and (rec is None or msk is None or rec.size != int(n_samples) * per_sample * 4 or msk.size * 32 < int(n_samples) * per_sample):
+        raise ValueError("records / mask do not hold n_samples * per_sample slots")
+    lib = load_library(True)
+    abi.check(lib.rtx_debug_resolve(rec.ctypes.data if rec is not None else None, msk.ctypes.data if msk is not None else None,
+                                    int(width), int(n_rows), tiles_x, int(n_samples), int(rays_per_pixel), int(bool(first)), int(bool(last)),
+                                    acc.ctypes.data if acc is not None else None, acc.size if acc is not None else 0,
+                                    out.ctypes.data if out is not None else None, out.size if out is not None else 0), lib)
+    return out, acc
+
+
+def debug_gather(parts, width, height, n, cap_rows, block, flip=False):
+    """The gather epilogue of the multi-device renders on a caller's staging buffer (include/rtx_hip.h, rtx_debug_gather; lab library):
+    parts (n, cap_rows, width, 3), float64 (launch_deinterleave; no flip) or uint8 (launch_deinterleave_u8) -> (height, width, 3)."""
+    parts = np.ascontiguousarray(parts)
+    if parts.dtype not in (np.float64, np.uint8) or parts.shape != (int(n), int(cap_rows), int(width), 3):
+        raise ValueError("parts is (n, cap_rows, width, 3) float64 or uint8")
+    full = np.zeros((int(height), int(width), 3), dtype=parts.dtype)
+    lib = load_library(True)
+    abi.check(lib.rtx_debug_gather(0 if parts.dtype == np.float64 else 1, parts.ctypes.data, int(width), int(height), int(n), int(cap_rows),
+                                   int(block), int(bool(flip)), full.ctypes.data), lib)
+    return full
+
+
+def debug_quantize_band(band):
+    """launch_quantize_values -- `* 256`, Rust's saturating `as u8`, rows in place: a band before it travels -- on a (n_rows, width, 3)
+    float64 array (rtx_debug_gather, form 2; lab library) -> uint8 of the same shape."""
+    band = np.ascontiguousarray(band, dtype=np.float64)
+    n_rows, width, _ = band.shape
+    out = np.zeros(band.shape, dtype=np.uint8)
+    lib = load_library(True)
+    abi.check(lib.rtx_debug_gather(2, band.ctypes.data, int(width), int(n_rows), 0, 0, 0, 0, out.ctypes.data), lib)
+    return out

@@ -1707,6 +1707,153 @@ int32_t rtx_debug_math(int32_t op, const double *a, const double *b, double *out
 #endif
 }
 
+#ifdef RTX_LAB
+namespace {
+// device copies of the host arrays of rtx_debug_store_samples / _resolve / _gather: freed on every return path
+struct DebugBufs {
+    std::vector<void *> p;
+    ~DebugBufs() { for (void *q : p) if (q) (void)hipFree(q); }
+    // a device buffer of `bytes` bytes holding `host`'s, and `tail` bytes of 0xFF behind them (null host or 0 bytes: a null pointer,
+    // nothing is allocated)
+    hipError_t up(const void *host, size_t bytes, void **out, size_t tail = 0)
+    {
+        *out = nullptr;
+        if (!host || bytes == 0) return hipSuccess;
+        hipError_t e = hipMalloc(out, bytes + tail);
+        if (e != hipSuccess) return e;
+        p.push_back(*out);
+        if (tail && (e = hipMemset(static_cast<char *>(*out) + bytes, 0xFF, tail)) != hipSuccess) return e;
+        return hipMemcpy(*out, host, bytes, hipMemcpyHostToDevice);
+    }
+};
+}  // namespace
+#endif
+
+int32_t rtx_debug_store_samples(const double *rgb, const uint64_t *slots, uint64_t n, uint64_t nonzero_base, double *records,
+                                uint64_t n_records, uint32_t *mask, uint64_t n_words)
+{
+#ifndef RTX_LAB
+    (void)rgb; (void)slots; (void)n; (void)nonzero_base; (void)records; (void)n_records; (void)mask; (void)n_words;
+    return fail(RTX_ERR_UNSUPPORTED, "rtx_debug_store_samples: a lab-library hook (librtx_hip_lab.so)");
+#else
+    if (n == 0) return RTX_OK;
+    if (!rgb || !slots || !records || !mask) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_store_samples: null argument");
+    if (n > (1ull << 24) || n_records > (1ull << 26) || n_words > (1ull << 26) || nonzero_base > (1ull << 40))
+        return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_store_samples: too large");
+    {   // every record and every bit inside the caller's buffers, no slot twice
+        std::vector<uint64_t> seen(slots, slots + n);
+        std::sort(seen.begin(), seen.end());
+        for (uint64_t i = 0; i < n; ++i) {
+            if (seen[i] >= n_records || ((nonzero_base + seen[i]) >> 5) >= n_words)
+                return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_store_samples: a slot's record or bit lies outside the buffers");
+            if (i && seen[i] == seen[i - 1]) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_store_samples: a slot appears twice");
+        }
+    }
+    if (usable_device_count() == 0) return fail(RTX_ERR_NO_DEVICE, "no gfx950 device");
+    RTX_HIP_CHECK(hipSetDevice(0));
+    DebugBufs d;
+    void *d_rgb, *d_slots, *d_rec, *d_mask;
+    RTX_HIP_CHECK(d.up(rgb, n * 3 * sizeof(double), &d_rgb));
+    RTX_HIP_CHECK(d.up(slots, n * sizeof(uint64_t), &d_slots));
+    RTX_HIP_CHECK(d.up(records, n_records * 4 * sizeof(double), &d_rec));
+    RTX_HIP_CHECK(d.up(mask, n_words * sizeof(uint32_t), &d_mask));
+    RowsView rv{};
+    rv.nonzero = static_cast<uint32_t *>(d_mask);
+    rv.nonzero_base = nonzero_base;
+    RTX_HIP_CHECK(launch_debug_store_samples(static_cast<const double *>(d_rgb), static_cast<const uint64_t *>(d_slots), n,
+                                             static_cast<double *>(d_rec), rv, nullptr));
+    RTX_HIP_CHECK(hipMemcpy(records, d_rec, n_records * 4 * sizeof(double), hipMemcpyDeviceToHost));   // (the null stream: after the kernel)
+    RTX_HIP_CHECK(hipMemcpy(mask, d_mask, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return RTX_OK;
+#endif
+}
+
+int32_t rtx_debug_resolve(const double *records, const uint32_t *mask, uint32_t width, uint32_t n_rows, uint32_t tiles_x,
+                          uint32_t n_samples, uint64_t rays_per_pixel, int32_t first, int32_t last, double *acc, uint64_t acc_doubles,
+                          double *out, uint64_t out_doubles)
+{
+#ifndef RTX_LAB
+    (void)records; (void)mask; (void)width; (void)n_rows; (void)tiles_x; (void)n_samples; (void)rays_per_pixel; (void)first; (void)last;
+    (void)acc; (void)acc_doubles; (void)out; (void)out_doubles;
+    return fail(RTX_ERR_UNSUPPORTED, "rtx_debug_resolve: a lab-library hook (librtx_hip_lab.so)");
+#else
+    const uint64_t npix = (uint64_t)width * n_rows;
+    if (npix == 0) return RTX_OK;
+    if (tiles_x != 0 && tiles_x != (width + 7u) / 8u) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_resolve: tiles_x is 0 or ceil(width / 8)");
+    const uint64_t per_sample64 = tiles_x ? (uint64_t)tiles_x * ((n_rows + 7u) / 8u) * 64u : npix;     // as render_band sizes a sample
+    if (per_sample64 * ((uint64_t)n_samples + 1) > (1ull << 26)) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_resolve: too large");
+    if (n_samples != 0 && (!records || !mask)) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_resolve: null records or mask");
+    if ((!first || !last) && (!acc || acc_doubles < 3 * npix)) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_resolve: acc holds 3 doubles per pixel");
+    if (last && (!out || out_doubles < 3 * npix)) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_resolve: out holds 3 doubles per pixel");
+    if (usable_device_count() == 0) return fail(RTX_ERR_NO_DEVICE, "no gfx950 device");
+    RTX_HIP_CHECK(hipSetDevice(0));
+    const uint64_t n_rays = per_sample64 * n_samples;
+    DebugBufs d;
+    void *d_rec, *d_mask, *d_acc, *d_out;
+    // behind the caller's records and bits lie one more sample's worth of NaN records under set bits: a fold that reads a sample
+    // too many stays inside the buffers and shows in the frame
+    const size_t rec_bytes = n_rays * 4 * sizeof(double), mask_bytes = (size_t)((n_rays + 31) / 32) * sizeof(uint32_t);
+    RTX_HIP_CHECK(d.up(records, rec_bytes, &d_rec, per_sample64 * 4 * sizeof(double)));
+    RTX_HIP_CHECK(d.up(mask, mask_bytes, &d_mask, nonzero_mask_bytes(per_sample64) + sizeof(uint32_t)));
+    RTX_HIP_CHECK(d.up(acc, acc_doubles * sizeof(double), &d_acc));
+    RTX_HIP_CHECK(d.up(out, out_doubles * sizeof(double), &d_out));
+    RowsView rv{};                                     // the fields launch_resolve reads, as render_band fills them
+    rv.width = width; rv.n_rows = n_rows; rv.npix = (uint32_t)npix; rv.tiles_x = tiles_x;
+    rv.n_samples = n_samples; rv.n_rays = n_rays;
+    rv.nonzero = static_cast<uint32_t *>(d_mask); rv.nonzero_base = 0;
+    RTX_HIP_CHECK(launch_resolve(static_cast<const double *>(d_rec), static_cast<double *>(d_acc), static_cast<double *>(d_out), rv,
+                                 (uint32_t)per_sample64, rays_per_pixel, first != 0, last != 0, nullptr));
+    if (d_acc) RTX_HIP_CHECK(hipMemcpy(acc, d_acc, acc_doubles * sizeof(double), hipMemcpyDeviceToHost));
+    if (d_out) RTX_HIP_CHECK(hipMemcpy(out, d_out, out_doubles * sizeof(double), hipMemcpyDeviceToHost));
+    RTX_HIP_CHECK(hipDeviceSynchronize());
+    return RTX_OK;
+#endif
+}
+
+int32_t rtx_debug_gather(int32_t form, const void *parts, uint32_t width, uint32_t height, uint32_t n, uint32_t cap_rows,
+                         uint32_t block, int32_t flip, void *full)
+{
+#ifndef RTX_LAB
+    (void)form; (void)parts; (void)width; (void)height; (void)n; (void)cap_rows; (void)block; (void)flip; (void)full;
+    return fail(RTX_ERR_UNSUPPORTED, "rtx_debug_gather: a lab-library hook (librtx_hip_lab.so)");
+#else
+    if (form < 0 || form > 2) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_gather: form is 0, 1 or 2");
+    const uint64_t vals = (uint64_t)width * height * 3;
+    if (vals == 0) return RTX_OK;
+    if (!parts || !full) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_gather: null argument");
+    if (vals > (1ull << 26)) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_gather: too large");
+    uint64_t in_vals = vals;                            // form 2: the band itself
+    if (form != 2) {
+        if (n == 0 || block == 0 || cap_rows == 0 || (uint64_t)n * cap_rows * width * 3 > (1ull << 26))
+            return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_gather: bad partition");
+        if (form == 0 && flip) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_gather: the f64 form has no flip");
+        for (uint32_t y = 0; y < height; ++y) {        // every row the kernel reads lies inside its part's cap_rows
+            const uint32_t b = y / block;
+            if ((uint64_t)(b / n) * block + (y - b * block) >= cap_rows)
+                return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_gather: cap_rows is below a part's row count");
+        }
+        in_vals = (uint64_t)n * cap_rows * width * 3;
+    }
+    if (usable_device_count() == 0) return fail(RTX_ERR_NO_DEVICE, "no gfx950 device");
+    RTX_HIP_CHECK(hipSetDevice(0));
+    const size_t in_bytes = form == 1 ? 1 : sizeof(double), out_bytes = form == 0 ? sizeof(double) : 1;
+    DebugBufs d;
+    void *d_parts, *d_full;
+    RTX_HIP_CHECK(d.up(parts, in_vals * in_bytes, &d_parts));
+    RTX_HIP_CHECK(d.up(full, vals * out_bytes, &d_full));
+    if (form == 0)
+        RTX_HIP_CHECK(launch_deinterleave(static_cast<const double *>(d_parts), static_cast<double *>(d_full), width, height, n, cap_rows,
+                                          block, nullptr));
+    else if (form == 1)
+        RTX_HIP_CHECK(launch_deinterleave_u8(static_cast<const uint8_t *>(d_parts), static_cast<uint8_t *>(d_full), width, height, n,
+                                             cap_rows, block, flip != 0, nullptr));
+    else
+        RTX_HIP_CHECK(launch_quantize_values(static_cast<const double *>(d_parts), static_cast<uint8_t *>(d_full), width, height, nullptr));
+    RTX_HIP_CHECK(hipMemcpy(full, d_full, vals * out_bytes, hipMemcpyDeviceToHost));
+    return RTX_OK;
+#endif
+}
+
 int32_t rtx_scene_closest_hits(RtxSceneHandle h, const RtxRay *d_rays, uint64_t n, RtxHit *d_hits, void *stream, RtxStats *stats)
 {
     if (!h) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_closest_hits: null scene");

@@ -659,6 +659,15 @@ __global__ void debug_math_kernel(int op, const double *a, const double *b, doub
     }
     out[i] = r;
 }
+
+// rtx_debug_store_samples: entry i is the sample rgb[3 i .. 3 i + 2] of ray-queue slot slots[i], stored by the trace kernels' own
+// store_sample (rtx_device.h) under the RowsView the host built for the call (nonzero, nonzero_base), passed by value
+__global__ void debug_store_samples_kernel(const double *rgb, const uint64_t *slots, uint64_t n, double *samples, RowsView rv)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    store_sample(samples, rv, slots[i], mk(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]));
+}
 #endif
 
 // ------------------------------------------------------------------------------------------
@@ -833,6 +842,14 @@ hipError_t launch_debug_math(int op, const double *a, const double *b, double *o
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(debug_math_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, op, a, b, out, n,
                        debug_index_view(op, b_host, n));
+    return hipGetLastError();
+}
+
+hipError_t launch_debug_store_samples(const double *rgb, const uint64_t *slots, uint64_t n, double *samples, const RowsView &rv,
+                                      hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(debug_store_samples_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, rgb, slots, n, samples, rv);
     return hipGetLastError();
 }
 

@@ -183,6 +183,9 @@ hipError_t launch_trace_transcript(const SceneView *d_sv, const RowsView *d_rv, 
 #ifdef RTX_LAB
 hipError_t launch_debug_math(int op, const double *a, const double *b, double *out, uint64_t n, const double *b_host, hipStream_t stream);
 bool debug_math_host(int op, const double *a, const double *b, double *out, uint64_t n);      // ops 17-21: host forms, no device
+// rtx_debug_store_samples: one thread per entry calls store_sample(samples, rv, slots[i], rgb[3 i .. 3 i + 2]) (rtx_device.h)
+hipError_t launch_debug_store_samples(const double *rgb, const uint64_t *slots, uint64_t n, double *samples, const RowsView &rv,
+                                      hipStream_t stream);
 #endif
 
 }  // namespace rtx
