@@ -241,6 +241,19 @@ public:
         return hits;
     }
 
+    // Occlusion: out[i] = 1 when some object's distance is normal, positive and < t_max[i] (rtx_any_hits); an empty t_max
+    // means +inf for every ray (any hit at all).  Limits are compared as given: NaN, zero or negative is never occluded.
+    std::vector<uint8_t> any_hits(const std::vector<RtxRay> &rays, const std::vector<double> &t_max = {}) const
+    {
+        if (!t_max.empty() && t_max.size() != rays.size()) throw Panic(RTX_ERR_INVALID_ARGUMENT, "any_hits: one limit per ray, or none");
+        std::vector<uint8_t> out(rays.size());
+        std::vector<RtxObject> packed = pack();
+        RtxScene sc = to_c(packed);
+        int32_t rc = rtx_any_hits(&sc, rays.data(), t_max.empty() ? nullptr : t_max.data(), rays.size(), out.data());
+        if (rc != RTX_OK) throw Panic(rc, rtx_last_error());
+        return out;
+    }
+
     std::vector<RtxObject> pack() const
     {
         std::vector<RtxObject> packed(objects.size());
@@ -348,6 +361,12 @@ public:
     void closest_hits(const RtxRay *d_rays, std::size_t n, RtxHit *d_hits, void *hip_stream = nullptr, RtxStats *stats = nullptr)
     {
         check(rtx_scene_closest_hits(h_, d_rays, n, d_hits, hip_stream, stats));
+    }
+    // occlusion for n rays of DEVICE memory: d_out[i] = 1 when something lies before d_t_max[i] (nullptr: anywhere along the ray)
+    void any_hits(const RtxRay *d_rays, const double *d_t_max, std::size_t n, uint8_t *d_out, void *hip_stream = nullptr,
+                  RtxStats *stats = nullptr)
+    {
+        check(rtx_scene_any_hits(h_, d_rays, d_t_max, n, d_out, hip_stream, stats));
     }
     // the pick buffer: d_hits[height][width] = the hit of each pixel's primary ray without the focal / non-focal offsets
     void primary_hits(std::size_t width, std::size_t height, RtxHit *d_hits, void *hip_stream = nullptr, RtxStats *stats = nullptr)

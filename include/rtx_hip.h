@@ -354,6 +354,26 @@ int32_t rtx_scene_primary_hits(RtxSceneHandle scene, uint32_t width, uint32_t he
 /* One-shot host form (as rtx_render is to rtx_render_rows): uploads to device 0, queries, copies back.  rays / hits: HOST arrays. */
 int32_t rtx_closest_hits(const RtxScene *scene, const RtxRay *rays, uint64_t n, RtxHit *hits);
 
+/* Occlusion (any-hit) queries: shadow rays, ambient occlusion, line of sight.  For ray i with limit t_max[i]:
+ *   occluded[i] = 1 iff some object of Scene.objects has Object::distance(position, direction) = Some(t) with t.is_normal() &&
+ *   t.is_sign_positive() (closest_object's filter, scene.rs:249) and t < t_max[i] (strict); else 0
+ * -- exactly (rtx_scene_closest_hits' distance < t_max[i]), without the search for the nearest surface: the limit prunes the walk,
+ * and a ray stops at the first surface that certainly lies before it (DESIGN.md "Occlusion queries").
+ *  - t_max is compared as given: +inf asks for any hit at all; NaN, zero or a negative limit is never occluded (0, nothing is tested).
+ *  - d_t_max == NULL means +inf for every ray.
+ *  - Directions are used as given, exactly as for closest hits.  A surface the ray starts on is found like any other -- the
+ *    reference's |t| ~ 1e-16 self-hits included: callers who do not want that offset their origins.  No hidden epsilon, no t_min.
+ *  - A scene without objects answers 0 everywhere (one memset, no launch: stats has segments = n and nothing else).
+ * d_rays: n RtxRay; d_t_max: n doubles or NULL; d_occluded: n bytes, 1 / 0.  DEVICE arrays, pairwise non-overlapping; n < 2^32.
+ * Streams, stats == NULL asynchrony, RtxConfig.tuning bits of RTX_TUNE_LAB_MASK, RTX_KERNEL_EXACT (every shape of every ray in f64,
+ * up to the first one before the limit): as rtx_scene_closest_hits.  stats: segments = n, exact_tests, filter_tests, box_tests (the
+ * tests actually made), trace_ms, trace_launches = 1, kernel = RTX_KERNEL_BVH | RTX_KERNEL_EXACT. */
+int32_t rtx_scene_any_hits(RtxSceneHandle scene, const RtxRay *d_rays, const double *d_t_max, uint64_t n, uint8_t *d_occluded,
+                           void *stream, RtxStats *stats);
+
+/* One-shot host form (upload to device 0, query, copy back), as rtx_closest_hits.  rays / t_max (or NULL) / occluded: HOST arrays. */
+int32_t rtx_any_hits(const RtxScene *scene, const RtxRay *rays, const double *t_max, uint64_t n, uint8_t *occluded);
+
 /* Device epilogue of render_to_image on a full device image (scene.rs:175-178):
  * d_rgb height*width*3 doubles -> d_rgb8 height*width*3 bytes, flipped vertically. */
 int32_t rtx_quantize_image_device(const double *d_rgb, uint32_t width, uint32_t height,

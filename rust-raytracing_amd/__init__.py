@@ -313,6 +313,13 @@ def make_rays(origins, directions):
     return rays
 
 
+def _limits(t_max, n):
+    """t_max of an occlusion query -> None (+inf for every ray) or n float64 limits (a scalar is broadcast)"""
+    if t_max is None:
+        return None
+    return np.array(np.broadcast_to(np.asarray(t_max, dtype=np.float64), (n,)))          # (a copy: contiguous and writable)
+
+
 def _split_hits(hits):
     """RtxHit records -> (distance, object, position, normal) numpy arrays"""
     return (hits["distance"].copy(), hits["object"].copy(), hits["position"].copy(), hits["normal"].copy())
@@ -383,6 +390,20 @@ class Scene:
         lib = load_library(self.config.wants_lab())
         abi.check(lib.rtx_closest_hits(C.byref(sc), rays.ctypes.data, len(rays), hits.ctypes.data), lib)
         return _split_hits(hits)
+
+    def any_hits(self, origins, directions, t_max=None):
+        """Occlusion: for each ray, whether some object's distance is normal, positive and < t_max[i] (rtx_any_hits: upload to
+        device 0, query, copy back).  t_max: None (= +inf: any hit at all), a scalar or n limits, compared as given -- NaN, zero or
+        negative: never occluded.  Returns a bool array (n,)."""
+        rays = make_rays(origins, directions)
+        lim = _limits(t_max, len(rays))
+        occ = np.zeros(len(rays), dtype=np.uint8)
+        packed = self.packed()
+        sc = _scene_c(self.config, self.camera, packed)
+        lib = load_library(self.config.wants_lab())
+        abi.check(lib.rtx_any_hits(C.byref(sc), rays.ctypes.data, lim.ctypes.data if lim is not None else None, len(rays),
+                                   occ.ctypes.data), lib)
+        return occ.astype(bool)
 
 
 class SceneHandle:
@@ -463,6 +484,30 @@ class SceneHandle:
         self._check(self._lib.rtx_scene_primary_hits(self._h, int(width), int(height), C.c_void_p(int(d_hits_ptr)),
                                                      C.c_void_p(int(stream)) if stream else None, C.byref(stats) if want_stats else None))
         return stats if want_stats else None
+
+    def any_hits(self, d_rays_ptr, d_t_max_ptr, n, d_out_ptr, stream=None, want_stats=True):
+        """Occlusion for n rays: d_rays_ptr / d_t_max_ptr / d_out_ptr are device addresses of n RtxRay (48 B), n doubles (or None:
+        +inf for every ray) and n result bytes (1 / 0).  want_stats=False: asynchronous on `stream`."""
+        stats = abi.RtxStats()
+        self._check(self._lib.rtx_scene_any_hits(self._h, C.c_void_p(int(d_rays_ptr)),
+                                                 C.c_void_p(int(d_t_max_ptr)) if d_t_max_ptr else None, int(n), C.c_void_p(int(d_out_ptr)),
+                                                 C.c_void_p(int(stream)) if stream else None, C.byref(stats) if want_stats else None))
+        return stats if want_stats else None
+
+    def occluded(self, origins, directions, t_max=None):
+        """Host convenience of any_hits (device buffers through torch): a bool array (n,), True where some object lies before t_max
+        (None: anywhere along the ray; a scalar or n limits)."""
+        import torch
+        rays = make_rays(origins, directions)
+        n = len(rays)
+        lim = _limits(t_max, n)
+        dev = torch.device("cuda", self.device)
+        d_rays = torch.from_numpy(rays.view(np.uint8)).to(dev)
+        d_lim = torch.from_numpy(lim).to(dev) if lim is not None and n else None
+        d_out = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        self.any_hits(d_rays.data_ptr(), d_lim.data_ptr() if d_lim is not None else None, n, d_out.data_ptr(), want_stats=True)
+        return d_out[:n].cpu().numpy().astype(bool)
 
     def query(self, origins, directions):
         """Host convenience of closest_hits (device buffers through torch): numpy (distance, object, position, normal)."""

@@ -1237,8 +1237,10 @@ static int32_t render_band(RtxSceneHandle h, uint32_t width, uint32_t height, ui
 
 // ---- ray queries: closest_object (scene.rs:243-251) for the caller's rays (width == 0) or for the zero-offset primary ray of every
 // pixel of a width x height frame (the pick buffer).  The handle's conventions: status codes, "Streams", stats == NULL = asynchronous.
+// d_occluded != null: the any-hit mode of the same kernel (rtx_scene_any_hits) -- one byte per ray instead of d_hits, d_t_max the
+// per-ray limits (null: +inf).
 static int32_t query_run(RtxSceneHandle_ *h, const RtxRay *d_rays, uint32_t width, uint32_t height, uint64_t n, RtxHit *d_hits,
-                         void *stream_, RtxStats *stats)
+                         void *stream_, RtxStats *stats, const double *d_t_max = nullptr, uint8_t *d_occluded = nullptr)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (stats) std::memset(stats, 0, sizeof *stats);
@@ -1256,6 +1258,15 @@ static int32_t query_run(RtxSceneHandle_ *h, const RtxRay *d_rays, uint32_t widt
 
     // RTX_KERNEL_EXACT sweeps every ray; any other id walks the tree when the scene has one a query kernel can walk
     const bool walk = h->cfg.kernel != RTX_KERNEL_EXACT && query_tree_kind(h->sv) != 0u;
+    if (d_occluded && h->sv.n_objects == 0) {          // nothing can occlude: no launch (stats: segments = n, nothing else counted)
+        RTX_HIP_CHECK(hipMemsetAsync(d_occluded, 0, n, stream));
+        if (stats) {
+            RTX_HIP_CHECK(hipStreamSynchronize(stream));
+            stats->segments = n;
+            stats->kernel = RTX_KERNEL_EXACT;
+        }
+        return RTX_OK;
+    }
     RowsView rv{};
     if (width != 0) {                        // the pick buffer: one band of all rows, ray i = pixel i (row-major, row 0 = the reference's)
         if (int32_t rc = ensure_tables(h, width, height, 0u, 1u, 1u, height, stream)) return rc;
@@ -1294,6 +1305,9 @@ static int32_t query_run(RtxSceneHandle_ *h, const RtxRay *d_rays, uint32_t widt
     qa.rv = width != 0 ? h->d_rv : nullptr;
     qa.hits = reinterpret_cast<QueryHit *>(d_hits);
     qa.n = n;
+    qa.any_hit = d_occluded ? 1u : 0u;
+    qa.t_max = d_t_max;
+    qa.occluded = d_occluded;
     if (stats) RTX_HIP_CHECK(hipEventRecord(h->ev[0], stream));
     RTX_HIP_CHECK(launch_query_closest(h->d_sv, h->sv, qa, walk, spill_entries ? reinterpret_cast<uint32_t *>(h->state) : nullptr,
                                        spill_entries, h->n_cus, h->counters, h->work_counter, stream));
@@ -1866,6 +1880,22 @@ int32_t rtx_scene_closest_hits(RtxSceneHandle h, const RtxRay *d_rays, uint64_t 
     return query_run(h, d_rays, 0u, 0u, n, d_hits, stream, stats);
 }
 
+int32_t rtx_scene_any_hits(RtxSceneHandle h, const RtxRay *d_rays, const double *d_t_max, uint64_t n, uint8_t *d_occluded, void *stream,
+                           RtxStats *stats)
+{
+    if (!h) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_any_hits: null scene");
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (n == 0) return RTX_OK;
+    if (!d_rays || !d_occluded) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_any_hits: null rays or output");
+    if (n >= 0xFFFFFFFFull) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_any_hits: n must be below 2^32");
+    const uintptr_t b[3] = { (uintptr_t)d_rays, (uintptr_t)d_occluded, (uintptr_t)d_t_max };
+    const uintptr_t e[3] = { b[0] + n * sizeof(RtxRay), b[1] + n, b[2] + n * sizeof(double) };
+    for (int i = 0; i < 3; ++i)
+        for (int j = i + 1; j < (d_t_max ? 3 : 2); ++j)
+            if (b[i] < e[j] && b[j] < e[i]) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_any_hits: rays, limits and output overlap");
+    return query_run(h, d_rays, 0u, 0u, n, nullptr, stream, stats, d_t_max, d_occluded);
+}
+
 int32_t rtx_scene_primary_hits(RtxSceneHandle h, uint32_t width, uint32_t height, RtxHit *d_hits, void *stream, RtxStats *stats)
 {
     if (!h) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_primary_hits: null scene");
@@ -1900,6 +1930,37 @@ int32_t rtx_closest_hits(const RtxScene *scene, const RtxRay *rays, uint64_t n, 
     }
     if (d_rays) (void)hipFree(d_rays);
     if (d_hits) (void)hipFree(d_hits);
+    const int32_t frc = rtx_scene_free(h);
+    return rc ? rc : frc;
+}
+
+int32_t rtx_any_hits(const RtxScene *scene, const RtxRay *rays, const double *t_max, uint64_t n, uint8_t *occluded)
+{
+    if (int32_t rc = check_scene_args(scene, "rtx_any_hits")) return rc;
+    if (n == 0) return RTX_OK;
+    if (!rays || !occluded) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_any_hits: null rays or output");
+    if (n >= 0xFFFFFFFFull) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_any_hits: n must be below 2^32");
+    if (int32_t rc = check_device(0, "rtx_any_hits")) return rc;
+    RtxSceneHandle h = nullptr;
+    if (int32_t rc = rtx_scene_upload(scene, 0, &h)) return rc;
+    RtxRay *d_rays = nullptr;
+    double *d_t_max = nullptr;
+    uint8_t *d_occ = nullptr;
+    hipError_t e = hipMalloc((void **)&d_rays, n * sizeof(RtxRay));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_occ, n);
+    if (e == hipSuccess && t_max) e = hipMalloc((void **)&d_t_max, n * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(d_rays, rays, n * sizeof(RtxRay), hipMemcpyHostToDevice);
+    if (e == hipSuccess && t_max) e = hipMemcpy(d_t_max, t_max, n * sizeof(double), hipMemcpyHostToDevice);
+    int32_t rc = e == hipSuccess ? RTX_OK : fail(e == hipErrorOutOfMemory ? RTX_ERR_OUT_OF_MEMORY : RTX_ERR_HIP,
+                                                std::string("rtx_any_hits: ") + hipGetErrorString(e));
+    if (!rc) rc = query_run(h, d_rays, 0u, 0u, n, nullptr, nullptr, nullptr, d_t_max, d_occ);
+    if (!rc) {
+        e = hipMemcpy(occluded, d_occ, n, hipMemcpyDeviceToHost);                      // (the null stream: after the query)
+        if (e != hipSuccess) rc = fail(RTX_ERR_HIP, std::string("rtx_any_hits: ") + hipGetErrorString(e));
+    }
+    if (d_rays) (void)hipFree(d_rays);
+    if (d_t_max) (void)hipFree(d_t_max);
+    if (d_occ) (void)hipFree(d_occ);
     const int32_t frc = rtx_scene_free(h);
     return rc ? rc : frc;
 }

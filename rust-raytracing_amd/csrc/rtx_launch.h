@@ -154,17 +154,20 @@ hipError_t launch_deinterleave_u8(const uint8_t *parts, uint8_t *full, uint32_t 
 // `* 256`, saturating `as u8` (scene.rs:175-178) of the n_rows x width pixels of a band in place order (before it travels: no flip)
 hipError_t launch_quantize_values(const double *rgb, uint8_t *rgb8, uint32_t width, uint32_t n_rows, hipStream_t stream);
 
-// ---- ray queries (rtx_query.hip): closest_object for caller rays or for the pick buffer's zero-offset primary rays
+// ---- ray queries (rtx_query.hip): closest_object for caller rays or for the pick buffer's zero-offset primary rays, or -- the
+// any-hit mode, a launch-uniform switch of the same kernel -- whether any object lies before a per-ray distance limit
 struct QueryRay { double position[3], direction[3]; };                                      // = RtxRay (include/rtx_hip.h)
 struct QueryHit { double position[3], normal[3], distance; long long object; };            // = RtxHit
 static_assert(sizeof(QueryRay) == 48 && sizeof(QueryHit) == 64, "QueryRay / QueryHit");
 struct QueryArgs {
     const QueryRay *rays;          // n rays (null in the pick form)
     const RowsView *rv;            // the pick form: the frame's RowsView (one band of all rows), ray i = pixel i; else null
-    QueryHit *hits;                // n answers
+    QueryHit *hits;                // n answers (null in the any-hit mode)
     unsigned long long n;
     uint32_t walk;                 // 0: every ray is swept (RTX_KERNEL_EXACT / no usable tree); set by the launcher
-    uint32_t pad_;
+    uint32_t any_hit;              // != 0: occluded[i] = some object's distance is normal, positive and < t_max[i]; no QueryHit is written
+    const double *t_max;           // any-hit: n limits, compared as given (null: +inf for every ray)
+    uint8_t *occluded;             // any-hit: n answers, 1 / 0
 };
 uint32_t query_tree_kind(const SceneView &sv);        // 0 no walk, 1 sphere tree, 2 a tree that holds triangles
 uint32_t query_spill_entries(const SceneView &sv);    // HBM stack entries per lane a walk may need beyond its LDS rows

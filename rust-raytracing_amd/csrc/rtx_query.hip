@@ -17,6 +17,14 @@
 // bvh_origin_limit * kBvhRange64, a NaN origin, RTX_KERNEL_EXACT, a scene without a usable tree, a stack or candidate
 // overflow) tests every shape exactly -- every triangle, not just the ones with a filter record, since upload drops the
 // triangles the cull test rejects for every UNIT direction.
+//
+// The any-hit mode (QueryArgs.any_hit, rtx_scene_any_hits; DESIGN.md "Occlusion queries"): occluded[i] = some object's distance is
+// normal, positive and < t_max[i] -- closest_object's distance < t_max[i], without the search for the nearest.  A launch-uniform
+// switch of the same two instances, taken once per launch (the mode has its own ray loop: the closest-hit loop carries none of its
+// arguments -- with the branch inside the shared loop the closest-hit rates fell by 0.5-2 %): the limit seeds best_up, so the walk
+// prunes what starts behind it; planes and the shapes outside the tree are tested BEFORE the walk; and a lane retires -- drops its stack and
+// its queued candidates -- as soon as a hit before the limit is certain: best_up, which only certain hits lower (the sphere
+// leaves' t_lo > K bound, tri_bounds' upper bound), has fallen below t_max, or an exact test said so.
 #include "rtx_launch.h"
 #include "rtx_mesh_step.h"
 #include "rtx_wavefront.h"
@@ -106,6 +114,195 @@ __device__ __forceinline__ void query_mesh_walk(const float4 *__restrict__ nodes
     query_flush(la, rx, lq, tid, kMeshQueue, qcnt, best_up, h, exact);
 }
 
+// ---- the any-hit mode ---------------------------------------------------------------------------------------------------------
+// closest_object's filter (scene.rs:249) and the caller's limit, strict
+__device__ __forceinline__ bool query_before(double t, double t_max) { return is_normal_positive(t) && t < t_max; }
+
+// query_sweep, stopping at the first hit before the limit (planes first: one of them often settles the ray)
+__device__ __forceinline__ bool query_sweep_any(const SceneView &sv, const LeafArrays &la, const RayX &rx, bool spheres, bool tris, double t_max,
+                                                unsigned long long &exact)
+{
+    double t;
+    for (uint32_t k = 0; k < sv.n_planes; ++k) {
+        exact += 1;
+        if (plane_distance(sv.planes[k], rx, &t) && query_before(t, t_max)) return true;
+    }
+    if (spheres) {
+        for (uint32_t k = 0; k < sv.n_spheres; ++k) {
+            exact += 1;
+            if (sphere_distance(la.spheres[k], rx, &t) && query_before(t, t_max)) return true;
+        }
+    }
+    if (tris) {
+        for (uint32_t k = 0; k < sv.n_tris; ++k) {
+            exact += 1;
+            if (triangle_distance(la.tris[k], rx, &t) && query_before(t, t_max)) return true;
+        }
+    }
+    return false;
+}
+
+// query_flush, stopping at the first hit before the limit
+__device__ __forceinline__ bool query_flush_any(const LeafArrays &la, const RayX &rx, const uint32_t *lq, uint32_t tid, uint32_t queue,
+                                                uint32_t qcnt, float best_up, double t_max, unsigned long long &exact)
+{
+#pragma unroll 1
+    for (uint32_t e = 0; e < qcnt; ++e) {
+        if (__uint_as_float(lq[(size_t)(queue + e) * kBvhThreads + tid]) <= best_up) {
+            const uint32_t idx = lq[(size_t)e * kBvhThreads + tid];
+            double t;
+            bool hit;
+            if (idx & kQueueTri) hit = triangle_distance(la.tris[la.tri_fidx[idx & ~kQueueTri]], rx, &t);
+            else hit = sphere_distance(la.spheres[idx], rx, &t);
+            exact += 1;
+            if (hit && query_before(t, t_max)) return true;
+        }
+    }
+    return false;
+}
+
+// query_mesh_walk's loop with best_up seeded by the limit; the lane leaves it -- its stack, the leaf children still to be read and
+// its queue dropped -- once a hit before the limit is certain.  Returns whether one is.
+template <int PLAIN, class RAY>
+__device__ __forceinline__ bool query_mesh_walk_any(const float4 *__restrict__ nodes, const LeafArrays &la, const MeshArrays &ma, const RAY &q,
+                                                    const SphereRay &sr, const TriFilterParams &tpar, const RayX &rx, uint32_t root, float best_up,
+                                                    double t_max, bool &overflow, uint32_t *ls, uint32_t *lq, uint32_t tid,
+                                                    uint32_t *__restrict__ spill, uint32_t spill_entries, size_t spill_stride, size_t glane,
+                                                    unsigned long long &exact, uint32_t &nbox, uint32_t &nleaf)
+{
+    uint32_t node = root, sp = 0, qcnt = 0, resume = 0, resume_node = 0;
+    float4 nd[MeshNode<PLAIN>::n];
+    if constexpr (kMeshPipe) mesh_load_node<PLAIN>(nodes, node, nd);
+    while (node != kNone || resume != 0u) {
+        const bool go = mesh_step<true, PLAIN, kQueryMeshStack>(nodes, ma, q, sr, tpar, nd, node, sp, qcnt, overflow, best_up, resume, resume_node,
+                                                                ls, lq, tid, spill, spill_entries, spill_stride, glane, nbox, nleaf);
+        if ((double)best_up < t_max) return true;                     // a certain hit's upper bound lies before the limit
+        if (go) continue;
+        if (query_flush_any(la, rx, lq, tid, kMeshQueue, qcnt, best_up, t_max, exact)) return true;
+        qcnt = 0;
+        if constexpr (kMeshPipe) mesh_load_node<PLAIN>(nodes, resume_node, nd);
+    }
+    return query_flush_any(la, rx, lq, tid, kMeshQueue, qcnt, best_up, t_max, exact);
+}
+
+// One ray of the any-hit mode, t_max > 0 (the caller's gate): 1 when some object's distance is normal, positive and < t_max.
+template <bool TRIS>
+__device__ __forceinline__ uint32_t query_any_ray(const SceneView &sv, const float4 *__restrict__ nodes, const LeafArrays &la, const MeshArrays &ma,
+                                                  V3 pos, V3 dir, const RayX &rx, bool walk, bool in32, double t_max, uint32_t *ls, uint32_t *lq,
+                                                  uint32_t tid, uint32_t *__restrict__ spill, uint32_t spill_entries, size_t spill_stride,
+                                                  size_t glane, unsigned long long &exact, unsigned long long &box_tests,
+                                                  unsigned long long &leaf_filters)
+{
+    if (!walk) return query_sweep_any(sv, la, rx, true, true, t_max, exact) ? 1u : 0u;
+    // the shapes the tree does not answer for, before the walk: every plane, the spheres and the triangle records outside it
+    if (query_sweep_any(sv, la, rx, (sv.bvh_flags & 1u) == 0u, false, t_max, exact)) return 1u;
+    for (uint32_t k = (sv.bvh_flags & 2u) ? sv.n_tri_tree : 0u; k < sv.n_tri_filter; ++k) {
+        double t;
+        exact += 1;
+        if (triangle_distance(la.tris[la.tri_fidx[k]], rx, &t) && query_before(t, t_max)) return 1u;
+    }
+    // the walk prunes with the limit from its first box on: t_lo <= best_up keeps every hit with t < t_max <= best_up
+    const float best0 = fmaxf(round_up32(t_max), 1.17549435e-38f);      // (+inf when t_max is; never a denormal a compare may flush)
+    bool overflow = false, occ = false;
+    uint32_t nbox = 0, nleaf = 0;
+    if constexpr (TRIS) {
+        SphereRay sr;
+        sr.px = sr.py = sr.pz = sr.dx = sr.dy = sr.dz = sr.Kg = sr.K = 0.f; sr.c0 = __builtin_inff();
+        if (sv.bvh_flags & 1u) sphere_ray_from(sv, pos, dir, sr);
+        TriFilterParams tpar;
+        tri_filter_from_ray(sv, pos, dir, tpar);
+        const bool plain = (sv.bvh_flags & 4u) != 0u;
+        if (in32) {
+            Ray32 q;
+            make_ray32(pos, rx.dirn, (double)sv.bvh_inv_max, q);
+            if (plain) occ = query_mesh_walk_any<2>(nodes, la, ma, q, sr, tpar, rx, sv.bvh_root, best0, t_max, overflow, ls, lq, tid, spill,
+                                                    spill_entries, spill_stride, glane, exact, nbox, nleaf);
+            else occ = query_mesh_walk_any<0>(nodes, la, ma, q, sr, tpar, rx, sv.bvh_root, best0, t_max, overflow, ls, lq, tid, spill,
+                                              spill_entries, spill_stride, glane, exact, nbox, nleaf);
+        } else {
+            Ray64 q;
+            make_ray64(pos, rx.dirn, (double)sv.bvh_inv_max, q);
+            if (plain) occ = query_mesh_walk_any<2>(nodes, la, ma, q, sr, tpar, rx, sv.bvh_root, best0, t_max, overflow, ls, lq, tid, spill,
+                                                    spill_entries, spill_stride, glane, exact, nbox, nleaf);
+            else occ = query_mesh_walk_any<0>(nodes, la, ma, q, sr, tpar, rx, sv.bvh_root, best0, t_max, overflow, ls, lq, tid, spill,
+                                              spill_entries, spill_stride, glane, exact, nbox, nleaf);
+        }
+    } else {
+        SphereRay sr;
+        sphere_ray_from(sv, pos, dir, sr);
+        Ray32 q0;
+        make_ray32(pos, rx.dirn, (double)sv.bvh_inv_max, q0);
+        Ray32S q;
+        q.ix = q0.ix; q.iy = q0.iy; q.iz = q0.iz; q.nx = q0.nx; q.ny = q0.ny; q.nz = q0.nz;
+        q.e = ray32_slack(q0.nx, q0.ny, q0.nz, in32);
+        float best_up = best0;
+        uint32_t node = sv.bvh_root, sp = 0, qcnt = 0;
+        // sphere_walk_phased's iteration -- node visits and leaf visits apart, chosen for the wave -- with the retirement check after
+        // a leaf visit, the only place best_up falls
+        while (node != kNone) {
+            const bool at_leaf = (node >> 29) != 0u;
+            const unsigned long long lm = __ballot(at_leaf), am = __ballot(true);
+            if ((uint32_t)__popcll(lm) >= kQueryLeafLanes || lm == am) {
+                if (at_leaf) {
+                    sphere_leaf_step<kQuerySphStack, true>(la.sphere_f32, la.sphere_prims, sr, node, sp, ls, lq, tid, spill, spill_stride, glane,
+                                                           best_up, qcnt, overflow, nleaf);
+                    if ((double)best_up < t_max) { occ = true; node = kNone; sp = 0; qcnt = 0; }
+                }
+            } else if (!at_leaf) {
+                sphere_node_step_q3<kQuerySphStack, true>(nodes, q, node, sp, ls, tid, spill, spill_entries, spill_stride, glane, best_up,
+                                                          overflow, nbox);
+            }
+        }
+        if (!occ && !overflow) occ = query_flush_any(la, rx, lq, tid, kSphQueue, qcnt, best_up, t_max, exact);
+    }
+    box_tests += nbox;
+    leaf_filters += nleaf;
+    // a walk cut short by a full stack or queue, no certain hit seen: every shape exactly (a certain hit stays one whatever overflowed)
+    if (!occ && overflow) occ = query_sweep_any(sv, la, rx, true, true, t_max, exact);
+    return occ ? 1u : 0u;
+}
+
+// whether the ray may take the walk (its f32 bounds hold for it) and which slab test it gets: query_closest_kernel's gate
+__device__ __forceinline__ bool query_walkable(const SceneView &sv, uint32_t tree, V3 pos, V3 dir, bool &in32)
+{
+    const float omax = fmaxf(fmaxf(__builtin_fabsf((float)pos.x), __builtin_fabsf((float)pos.y)), __builtin_fabsf((float)pos.z));
+    in32 = omax <= sv.bvh_origin_limit;                                                 // NaN origin -> exhaustive branch
+    return tree && query_dir_ok(dir) && (in32 || omax <= sv.bvh_origin_limit * kBvhRange64);
+}
+
+// The kernel's ray loop in the any-hit mode: the same persistent waves and chunks, one byte per ray.  A loop of its own, entered
+// once per launch, so that the closest-hit loop carries none of this mode's arguments or state.
+template <bool TRIS>
+__device__ __forceinline__ void query_any_loop(const SceneView &sv, const QueryArgs &qa, const float4 *__restrict__ nodes, const LeafArrays &la,
+                                               const MeshArrays &ma, uint32_t *ls, uint32_t *lq, uint32_t tid, uint32_t *__restrict__ spill,
+                                               uint32_t spill_entries, size_t spill_stride, size_t glane, unsigned long long *__restrict__ head,
+                                               unsigned long long &segs, unsigned long long &exact, unsigned long long &box_tests,
+                                               unsigned long long &leaf_filters)
+{
+    const unsigned long long grab = wf_grab_size(qa.n);
+    WfChunk ch{0ull, 0ull, false};
+    for (;;) {
+        unsigned long long i = 0;
+        const bool mine = wf_take(ch, head, grab, qa.n, true, i);
+        if (ch.drained && __ballot(mine) == 0ull) break;
+        if (!mine) continue;
+        ++segs;
+        const double t_max = qa.t_max ? qa.t_max[i] : __builtin_inf();
+        uint32_t occ = 0;
+        if (t_max > 0.0) {                                               // (NaN, zero, negative: never occluded, nothing is tested)
+            const QueryRay &qr = qa.rays[i];
+            const V3 pos = mk(qr.position[0], qr.position[1], qr.position[2]);
+            const V3 dir = mk(qr.direction[0], qr.direction[1], qr.direction[2]);
+            const RayX rx = make_rayx(pos, dir);
+            bool in32;
+            const bool walk = query_walkable(sv, qa.walk, pos, dir, in32);
+            occ = query_any_ray<TRIS>(sv, nodes, la, ma, pos, dir, rx, walk, in32, t_max, ls, lq, tid, spill, spill_entries, spill_stride,
+                                      glane, exact, box_tests, leaf_filters);
+        }
+        qa.occluded[i] = (uint8_t)occ;
+    }
+}
+
 template <bool TRIS>
 __global__ __launch_bounds__(kBvhThreads, kQueryWaves) void query_closest_kernel(const SceneView *__restrict__ svp, const QueryArgs qa,
                                                                                  const float4 *__restrict__ nodes, const LeafArrays la,
@@ -127,7 +324,10 @@ __global__ __launch_bounds__(kBvhThreads, kQueryWaves) void query_closest_kernel
     unsigned long long segs = 0, box_tests = 0, leaf_filters = 0, exact = 0;
     WfChunk ch{0ull, 0ull, false};
 
-    for (;;) {
+    if (qa.any_hit)                                                      // launch-uniform: the any-hit mode has its own ray loop
+        query_any_loop<TRIS>(sv, qa, nodes, la, ma, ls, lq, tid, spill, spill_entries, spill_stride, glane, head, segs, exact, box_tests,
+                             leaf_filters);
+    else for (;;) {
         unsigned long long i = 0;
         const bool mine = wf_take(ch, head, grab, qa.n, true, i);         // (every lane of the wave is here: lane 0 takes the chunk)
         if (ch.drained && __ballot(mine) == 0ull) break;                 // wave-uniform

@@ -1,13 +1,19 @@
 #!/usr/bin/env python3
-"""Closest-hit query rates (rtx_scene_closest_hits / rtx_scene_primary_hits), in Mrays/s from RtxStats.trace_ms, on the scenes of the
+"""Closest-hit and any-hit query rates (rtx_scene_closest_hits / rtx_scene_primary_hits / rtx_scene_any_hits), in Mrays/s from
+RtxStats.trace_ms, on the scenes of the
 benchmark's C2 (10k spheres), C3 (100k triangles) and J1 (5k spheres + 50k triangles: a joint tree), built with scenes.py's
 generators and the same parameters:
 
   incoherent   2^24 rays, origins uniform in the scene's box, unit directions uniform on the sphere (the tree walk)
   pick         the 1920x1080 pick buffer (rtx_scene_primary_hits)
   exact        the incoherent set with RTX_KERNEL_EXACT (every shape of every ray in f64)
+  any          rtx_scene_any_hits on the incoherent set, t_max = +inf (any hit at all)
+  any_short    the same with t_max = 1.0 (the median closest distance in these boxes is ~25)
+  any_aimed    t_max = +inf on rays with the incoherent set's origins, each aimed at a random sphere centre / triangle centroid
 
-    tools/query_rate.py [--rays 24] [--scenes C2,C3,J1] [--reps 3] [--exact-rays 20]
+    tools/query_rate.py [--rays 24] [--scenes C2,C3,J1] [--reps 3] [--exact-rays 20] [--legs incoherent,pick,...]
+
+The library is the package's (RTX_HIP_LIB selects another build, e.g. one of the parent commit: its any legs are then skipped).
 
 The exact leg runs 2^--exact-rays of the rays (the sweep is ~n_objects tests per ray) and reports its rate on those.  One JSON line per
 scene and leg; the best of --reps timed runs after one warm-up.
@@ -41,12 +47,26 @@ def incoherent(objs, n, seed=1):
     return o, d
 
 
+def aimed(objs, o, seed=2):
+    """unit directions from the origins o toward a random sphere centre or triangle centroid each"""
+    rng = np.random.default_rng(seed)
+    g = objs["geom"]
+    targets = np.concatenate([g[objs["kind"] == 0][:, :3], g[objs["kind"] == 2][:, :9].reshape(-1, 3, 3).mean(axis=1)])
+    d = targets[rng.integers(0, len(targets), len(o))] - o
+    d /= np.linalg.norm(d, axis=1)[:, None]
+    return d
+
+
+LEGS = ("incoherent", "pick", "exact", "any", "any_short", "any_aimed")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rays", type=int, default=24, help="log2 of the incoherent set's size")
     ap.add_argument("--exact-rays", type=int, default=20, help="log2 of the rays the exact leg runs")
     ap.add_argument("--scenes", default="C2,C3,J1")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--legs", default=",".join(LEGS))
     args = ap.parse_args()
     import torch
 
@@ -54,12 +74,26 @@ def main():
     from rust_raytracing_amd import scenes
     dev = torch.device("cuda", 0)
     n = 1 << args.rays
+    legs = [l for l in args.legs.split(",") if l]
+    assert all(l in LEGS for l in legs), legs
+    if os.environ.get("RTX_HIP_LIB"):           # maybe a build of an older commit: bind what it exports, skip the legs it lacks
+        import ctypes
+        rtx.abi._share_hip_runtime_with_torch()
+        probe = ctypes.CDLL(rtx.abi.LIB_PATH)
+        rtx.abi.SYMBOLS[:] = [sym for sym in rtx.abi.SYMBOLS if hasattr(probe, sym[0])]
+        if not hasattr(probe, "rtx_scene_any_hits"):
+            legs = [l for l in legs if not l.startswith("any")]
     for name in args.scenes.split(","):
         objs = SCENES[name](scenes)
         o, d = incoherent(objs, n)
         rays = rtx.make_rays(o, d)
         d_rays = torch.from_numpy(rays.view(np.uint8)).to(dev)
         d_hits = torch.empty(n * 64, dtype=torch.uint8, device=dev)
+        d_aimed = d_lim = None
+        if "any_aimed" in legs:
+            d_aimed = torch.from_numpy(rtx.make_rays(o, aimed(objs, o)).view(np.uint8)).to(dev)
+        if "any_short" in legs:
+            d_lim = torch.full((n,), 1.0, dtype=torch.float64, device=dev)
         torch.cuda.synchronize(dev)
 
         def best(fn):
@@ -67,8 +101,20 @@ def main():
             runs = [fn() for _ in range(args.reps)]
             return min(runs, key=lambda s: s.trace_ms)
 
-        for leg, kernel in (("incoherent", rtx.RTX_KERNEL_AUTO), ("pick", rtx.RTX_KERNEL_AUTO), ("exact", rtx.RTX_KERNEL_EXACT)):
+        for leg in legs:
+            kernel = rtx.RTX_KERNEL_EXACT if leg == "exact" else rtx.RTX_KERNEL_AUTO
             hnd = rtx.Scene.from_packed(rtx.Config(rays_per_pixel=1, kernel=kernel), rtx.Camera(*scenes.CAMERA), objs).upload(0)
+            if leg.startswith("any"):
+                k = n
+                src = d_aimed if leg == "any_aimed" else d_rays
+                lim = d_lim.data_ptr() if leg == "any_short" else None
+                st = best(lambda: hnd.any_hits(src.data_ptr(), lim, k, d_hits.data_ptr()))
+                print(json.dumps({"scene": name, "leg": leg, "rays": k, "trace_ms": round(st.trace_ms, 3),
+                                  "mrays_per_s": round(k / (st.trace_ms * 1e-3) / 1e6, 1), "kernel": int(st.kernel),
+                                  "exact_tests_per_ray": round(st.exact_tests / k, 2), "box_tests_per_ray": round(st.box_tests / k, 2),
+                                  "occluded_fraction": round(float(d_hits[:k].float().mean().item()), 4)}), flush=True)
+                hnd.close()
+                continue
             if leg == "pick":
                 k = 1920 * 1080
                 st = best(lambda: hnd.primary_hits(1920, 1080, d_hits.data_ptr()))
