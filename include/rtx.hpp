@@ -254,6 +254,23 @@ public:
         return out;
     }
 
+    // render_ray (scene.rs:223-242) from each ray, with the config's max_bounces and seed (rtx_trace_paths): rgb[3 i .. 3 i + 2] =
+    // the path's resulting_color, unclamped.  ids: empty (entry i draws as pixel i, sample 0) or 2 per ray, (pixel index, sample
+    // index); segments (optional): the closest_object calls of each path.
+    std::vector<double> trace_paths(const std::vector<RtxRay> &rays, const std::vector<uint64_t> &ids = {},
+                                    std::vector<uint32_t> *segments = nullptr) const
+    {
+        if (!ids.empty() && ids.size() != 2 * rays.size()) throw Panic(RTX_ERR_INVALID_ARGUMENT, "trace_paths: two ids per ray, or none");
+        std::vector<double> rgb(3 * rays.size());
+        if (segments) segments->assign(rays.size(), 0u);
+        std::vector<RtxObject> packed = pack();
+        RtxScene sc = to_c(packed);
+        int32_t rc = rtx_trace_paths(&sc, rays.data(), ids.empty() ? nullptr : ids.data(), rays.size(), rgb.data(),
+                                     segments ? segments->data() : nullptr);
+        if (rc != RTX_OK) throw Panic(rc, rtx_last_error());
+        return rgb;
+    }
+
     std::vector<RtxObject> pack() const
     {
         std::vector<RtxObject> packed(objects.size());
@@ -367,6 +384,13 @@ public:
                   RtxStats *stats = nullptr)
     {
         check(rtx_scene_any_hits(h_, d_rays, d_t_max, n, d_out, hip_stream, stats));
+    }
+    // render_ray from n rays of DEVICE memory: d_rgb[3 n] = each path's colour, d_ids (nullptr: (i, 0)) the (pixel, sample) pairs that
+    // key the RNG, d_segments (or nullptr) the closest_object calls of each path
+    void trace_paths(const RtxRay *d_rays, const uint64_t *d_ids, std::size_t n, double *d_rgb, uint32_t *d_segments = nullptr,
+                     void *hip_stream = nullptr, RtxStats *stats = nullptr)
+    {
+        check(rtx_scene_trace_paths(h_, d_rays, d_ids, n, d_rgb, d_segments, hip_stream, stats));
     }
     // the pick buffer: d_hits[height][width] = the hit of each pixel's primary ray without the focal / non-focal offsets
     void primary_hits(std::size_t width, std::size_t height, RtxHit *d_hits, void *hip_stream = nullptr, RtxStats *stats = nullptr)

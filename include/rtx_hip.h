@@ -374,6 +374,35 @@ int32_t rtx_scene_any_hits(RtxSceneHandle scene, const RtxRay *d_rays, const dou
 /* One-shot host form (upload to device 0, query, copy back), as rtx_closest_hits.  rays / t_max (or NULL) / occluded: HOST arrays. */
 int32_t rtx_any_hits(const RtxScene *scene, const RtxRay *rays, const double *t_max, uint64_t n, uint8_t *occluded);
 
+/* Path-radiance queries: render_ray (scene.rs:223-242), the bounce loop that turns a ray into a colour, for the caller's rays -- the
+ * path tracer without the reference's camera (panoramas, stereo pairs, light probes at pick() / query() points, debug rays).
+ * For entry i, with the handle's RtxConfig supplying max_bounces and seed (rays_per_pixel, focal_* and the camera are not read):
+ *  - ray = Ray::new(position, direction), the direction used as given (no hidden norm()); resulting_color = 0, light_color = 1.
+ *  - Up to max_bounces + 1 times: stop if light_color == zeros; closest_object -- on None, stop; else position += direction * dst
+ *    and ray_hit (scene.rs:260-278).
+ *  - d_rgb[3 i .. 3 i + 2] = resulting_color, unclamped.  d_segments[i] = the closest_object calls the path made; d_segments may
+ *    be NULL.
+ *  - Randomness: key = rng_key(config.seed, d_ids[2 i], d_ids[2 i + 1]), a (pixel index, sample index) pair; d_ids == NULL means
+ *    (i, 0).  Bounce b draws indices 6 + 2 b and 7 + 2 b; indices 0..5 stay the lens jitter's.  So a caller who brings
+ *    render_pixel's own ray for (pixel, sample) gets that sample of rtx_render bit for bit, and summing S samples in sample order
+ *    and dividing by S gives the render's pixel.  A path's result depends only on its ray, its id pair and the scene -- never on
+ *    n, on its position in the batch or on its neighbours.
+ *  - A scene without objects (scene.rs:224): zeros, nothing is asked -- one memset of d_rgb (and of d_segments), no launch,
+ *    stats->segments = 0.
+ *  - A segment whose ray the walk's f32 bounds were not derived for (a non-unit or non-finite direction, a far or NaN origin) is
+ *    swept exhaustively, as for closest hits; bounced directions are normalised, so later segments walk.  RTX_KERNEL_EXACT: every
+ *    segment swept -- the same bits.  No self-hit pre-test and no epsilon, as for the other queries.
+ * d_rays: n RtxRay; d_ids: 2 n uint64 or NULL; d_rgb: 3 n doubles; d_segments: n uint32 or NULL.  DEVICE arrays, pairwise
+ * non-overlapping; n < 2^32.  Streams, stats == NULL asynchrony, RtxConfig.tuning bits of RTX_TUNE_LAB_MASK: as rtx_scene_any_hits.
+ * stats: primary_rays = n, segments = all closest_object calls, exact_tests, filter_tests, box_tests, trace_ms,
+ * trace_launches = 1, kernel = RTX_KERNEL_BVH | RTX_KERNEL_EXACT.  (DESIGN.md "Path queries".) */
+int32_t rtx_scene_trace_paths(RtxSceneHandle scene, const RtxRay *d_rays, const uint64_t *d_ids, uint64_t n,
+                              double *d_rgb, uint32_t *d_segments, void *stream, RtxStats *stats);
+
+/* One-shot host form (upload to device 0, trace, copy back), as rtx_closest_hits.  rays / ids (or NULL) / rgb / segments (or NULL):
+ * HOST arrays. */
+int32_t rtx_trace_paths(const RtxScene *scene, const RtxRay *rays, const uint64_t *ids, uint64_t n, double *rgb, uint32_t *segments);
+
 /* Device epilogue of render_to_image on a full device image (scene.rs:175-178):
  * d_rgb height*width*3 doubles -> d_rgb8 height*width*3 bytes, flipped vertically. */
 int32_t rtx_quantize_image_device(const double *d_rgb, uint32_t width, uint32_t height,

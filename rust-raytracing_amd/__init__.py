@@ -320,6 +320,16 @@ def _limits(t_max, n):
     return np.array(np.broadcast_to(np.asarray(t_max, dtype=np.float64), (n,)))          # (a copy: contiguous and writable)
 
 
+def _path_ids(ids, n):
+    """ids of a path query -> None ((i, 0) for entry i) or an (n, 2) uint64 array of (pixel index, sample index) pairs"""
+    if ids is None:
+        return None
+    a = np.ascontiguousarray(ids, dtype=np.uint64)
+    if a.shape != (n, 2):
+        raise ValueError("ids is (n, 2): one (pixel index, sample index) pair per ray")
+    return a
+
+
 def _split_hits(hits):
     """RtxHit records -> (distance, object, position, normal) numpy arrays"""
     return (hits["distance"].copy(), hits["object"].copy(), hits["position"].copy(), hits["normal"].copy())
@@ -404,6 +414,22 @@ class Scene:
         abi.check(lib.rtx_any_hits(C.byref(sc), rays.ctypes.data, lim.ctypes.data if lim is not None else None, len(rays),
                                    occ.ctypes.data), lib)
         return occ.astype(bool)
+
+    def trace_paths(self, origins, directions, ids=None):
+        """render_ray (scene.rs:223-242) from each ray, with the config's max_bounces and seed (rtx_trace_paths: upload to device 0,
+        trace, copy back).  ids: None (entry i draws as (pixel i, sample 0)) or (n, 2) (pixel index, sample index) pairs.  Returns
+        numpy (rgb (n, 3) float64, unclamped; segments (n,) uint32 -- the closest_object calls of each path)."""
+        rays = make_rays(origins, directions)
+        n = len(rays)
+        pid = _path_ids(ids, n)
+        rgb = np.zeros((n, 3), dtype=np.float64)
+        seg = np.zeros(n, dtype=np.uint32)
+        packed = self.packed()
+        sc = _scene_c(self.config, self.camera, packed)
+        lib = load_library(self.config.wants_lab())
+        abi.check(lib.rtx_trace_paths(C.byref(sc), rays.ctypes.data, pid.ctypes.data if pid is not None else None, n, rgb.ctypes.data,
+                                      seg.ctypes.data), lib)
+        return rgb, seg
 
 
 class SceneHandle:
@@ -508,6 +534,50 @@ class SceneHandle:
         torch.cuda.synchronize(dev)
         self.any_hits(d_rays.data_ptr(), d_lim.data_ptr() if d_lim is not None else None, n, d_out.data_ptr(), want_stats=True)
         return d_out[:n].cpu().numpy().astype(bool)
+
+    def trace_paths(self, d_rays_ptr, d_ids_ptr, n, d_rgb_ptr, d_segments_ptr=None, stream=None, want_stats=True):
+        """render_ray from n rays: d_rays_ptr / d_ids_ptr / d_rgb_ptr / d_segments_ptr are device addresses of n RtxRay (48 B), n
+        (pixel index, sample index) uint64 pairs (or None: (i, 0)), 3 n doubles and n uint32 (or None).  want_stats=False:
+        asynchronous on `stream`."""
+        stats = abi.RtxStats()
+        self._check(self._lib.rtx_scene_trace_paths(self._h, C.c_void_p(int(d_rays_ptr)), C.c_void_p(int(d_ids_ptr)) if d_ids_ptr else None,
+                                                    int(n), C.c_void_p(int(d_rgb_ptr)),
+                                                    C.c_void_p(int(d_segments_ptr)) if d_segments_ptr else None,
+                                                    C.c_void_p(int(stream)) if stream else None, C.byref(stats) if want_stats else None))
+        return stats if want_stats else None
+
+    def radiance(self, origins, directions, ids=None, samples=1):
+        """Host convenience of trace_paths (device buffers through torch): the (n, 3) float64 radiance along each ray, unclamped.
+        samples == 1: ids is None (ray i draws as pixel i, sample 0) or (n, 2) (pixel index, sample index) pairs.  samples > 1: ids
+        is None or (n,) pixel indices; ray i is traced with the ids (pixel, s) for s = 0 .. samples - 1 and the results are folded
+        as the render folds a pixel's samples: summed in sample order from zero, divided by samples."""
+        import torch
+        rays = make_rays(origins, directions)
+        n, samples = len(rays), int(samples)
+        if samples < 1:
+            raise ValueError("samples >= 1")
+        if samples == 1:
+            pid = _path_ids(ids, n)
+        else:
+            pix = np.arange(n, dtype=np.uint64) if ids is None else np.ascontiguousarray(ids, dtype=np.uint64)
+            if pix.shape != (n,):
+                raise ValueError("with samples > 1, ids is (n,): one pixel index per ray (the sample index runs over the samples)")
+            pid = np.stack([np.tile(pix, samples), np.repeat(np.arange(samples, dtype=np.uint64), n)], axis=1)      # sample-major
+            rays = np.tile(rays, samples)
+        m = len(rays)
+        dev = torch.device("cuda", self.device)
+        d_rays = torch.from_numpy(rays.view(np.uint8)).to(dev)
+        d_ids = torch.from_numpy(pid.view(np.int64)).to(dev) if pid is not None and m else None
+        d_rgb = torch.empty(max(m, 1) * 3, dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        self.trace_paths(d_rays.data_ptr(), d_ids.data_ptr() if d_ids is not None else None, m, d_rgb.data_ptr(), want_stats=True)
+        rgb = d_rgb[:m * 3].cpu().numpy().reshape(samples, n, 3)
+        if samples == 1:
+            return rgb[0]
+        acc = np.zeros((n, 3), dtype=np.float64)
+        for s in range(samples):                                                         # iter_ops.rs:4-8: a left fold from zeros
+            acc = acc + rgb[s]
+        return acc / float(samples)
 
     def query(self, origins, directions):
         """Host convenience of closest_hits (device buffers through torch): numpy (distance, object, position, normal)."""

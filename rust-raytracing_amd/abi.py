@@ -113,6 +113,8 @@ SYMBOLS = [
     ("rtx_closest_hits", C.c_int32, [C.POINTER(RtxScene), C.c_void_p, C.c_uint64, C.c_void_p]),
     ("rtx_scene_any_hits", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(RtxStats)]),
     ("rtx_any_hits", C.c_int32, [C.POINTER(RtxScene), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    ("rtx_scene_trace_paths", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtxStats)]),
+    ("rtx_trace_paths", C.c_int32, [C.POINTER(RtxScene), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("rtx_quantize_image_device", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p]),
     ("rtx_debug_math", C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
     ("rtx_debug_paths", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),

@@ -1238,9 +1238,11 @@ static int32_t render_band(RtxSceneHandle h, uint32_t width, uint32_t height, ui
 // ---- ray queries: closest_object (scene.rs:243-251) for the caller's rays (width == 0) or for the zero-offset primary ray of every
 // pixel of a width x height frame (the pick buffer).  The handle's conventions: status codes, "Streams", stats == NULL = asynchronous.
 // d_occluded != null: the any-hit mode of the same kernel (rtx_scene_any_hits) -- one byte per ray instead of d_hits, d_t_max the
-// per-ray limits (null: +inf).
+// per-ray limits (null: +inf).  d_rgb != null: the path mode (rtx_scene_trace_paths) -- render_ray's colour of the path each ray
+// starts, d_ids the (pixel, sample) pairs that key the RNG (null: (i, 0)), d_segments its closest_object calls (or null).
 static int32_t query_run(RtxSceneHandle_ *h, const RtxRay *d_rays, uint32_t width, uint32_t height, uint64_t n, RtxHit *d_hits,
-                         void *stream_, RtxStats *stats, const double *d_t_max = nullptr, uint8_t *d_occluded = nullptr)
+                         void *stream_, RtxStats *stats, const double *d_t_max = nullptr, uint8_t *d_occluded = nullptr,
+                         const uint64_t *d_ids = nullptr, double *d_rgb = nullptr, uint32_t *d_segments = nullptr)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (stats) std::memset(stats, 0, sizeof *stats);
@@ -1263,6 +1265,16 @@ static int32_t query_run(RtxSceneHandle_ *h, const RtxRay *d_rays, uint32_t widt
         if (stats) {
             RTX_HIP_CHECK(hipStreamSynchronize(stream));
             stats->segments = n;
+            stats->kernel = RTX_KERNEL_EXACT;
+        }
+        return RTX_OK;
+    }
+    if (d_rgb && h->sv.n_objects == 0) {               // scene.rs:224: the colour is zero and nothing is asked -- no launch
+        RTX_HIP_CHECK(hipMemsetAsync(d_rgb, 0, n * 3 * sizeof(double), stream));
+        if (d_segments) RTX_HIP_CHECK(hipMemsetAsync(d_segments, 0, n * sizeof(uint32_t), stream));
+        if (stats) {
+            RTX_HIP_CHECK(hipStreamSynchronize(stream));
+            stats->primary_rays = n;
             stats->kernel = RTX_KERNEL_EXACT;
         }
         return RTX_OK;
@@ -1305,9 +1317,8 @@ static int32_t query_run(RtxSceneHandle_ *h, const RtxRay *d_rays, uint32_t widt
     qa.rv = width != 0 ? h->d_rv : nullptr;
     qa.hits = reinterpret_cast<QueryHit *>(d_hits);
     qa.n = n;
-    qa.any_hit = d_occluded ? 1u : 0u;
-    qa.t_max = d_t_max;
-    qa.occluded = d_occluded;
+    if (d_occluded) { qa.mode = kQueryAnyHit; qa.occluded = d_occluded; qa.t_max = d_t_max; }
+    else if (d_rgb) { qa.mode = kQueryPaths; qa.rgb = d_rgb; qa.ids = reinterpret_cast<const unsigned long long *>(d_ids); qa.segments = d_segments; }
     if (stats) RTX_HIP_CHECK(hipEventRecord(h->ev[0], stream));
     RTX_HIP_CHECK(launch_query_closest(h->d_sv, h->sv, qa, walk, spill_entries ? reinterpret_cast<uint32_t *>(h->state) : nullptr,
                                        spill_entries, h->n_cus, h->counters, h->work_counter, stream));
@@ -1324,6 +1335,7 @@ static int32_t query_run(RtxSceneHandle_ *h, const RtxRay *d_rays, uint32_t widt
             stats->filter_tests += host[k].filter_tests;
         }
         for (int k = 2; k < kCounterShards; ++k) stats->box_tests += host[k].pad_;
+        if (d_rgb) stats->primary_rays = n;
         stats->trace_ms = ms;
         stats->trace_launches = 1;
         stats->kernel = walk ? RTX_KERNEL_BVH : RTX_KERNEL_EXACT;
@@ -1896,6 +1908,23 @@ int32_t rtx_scene_any_hits(RtxSceneHandle h, const RtxRay *d_rays, const double 
     return query_run(h, d_rays, 0u, 0u, n, nullptr, stream, stats, d_t_max, d_occluded);
 }
 
+int32_t rtx_scene_trace_paths(RtxSceneHandle h, const RtxRay *d_rays, const uint64_t *d_ids, uint64_t n, double *d_rgb, uint32_t *d_segments,
+                              void *stream, RtxStats *stats)
+{
+    if (!h) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_trace_paths: null scene");
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (n == 0) return RTX_OK;
+    if (!d_rays || !d_rgb) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_trace_paths: null rays or rgb");
+    if (n >= 0xFFFFFFFFull) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_trace_paths: n must be below 2^32");
+    const uintptr_t b[4] = { (uintptr_t)d_rays, (uintptr_t)d_rgb, (uintptr_t)d_ids, (uintptr_t)d_segments };
+    const uintptr_t e[4] = { b[0] + n * sizeof(RtxRay), b[1] + n * 3 * sizeof(double), b[2] + n * 2 * sizeof(uint64_t), b[3] + n * sizeof(uint32_t) };
+    for (int i = 0; i < 4; ++i)
+        for (int j = i + 1; j < 4; ++j)
+            if (b[i] && b[j] && b[i] < e[j] && b[j] < e[i])
+                return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_trace_paths: rays, ids, rgb and segments overlap");
+    return query_run(h, d_rays, 0u, 0u, n, nullptr, stream, stats, nullptr, nullptr, d_ids, d_rgb, d_segments);
+}
+
 int32_t rtx_scene_primary_hits(RtxSceneHandle h, uint32_t width, uint32_t height, RtxHit *d_hits, void *stream, RtxStats *stats)
 {
     if (!h) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_primary_hits: null scene");
@@ -1961,6 +1990,41 @@ int32_t rtx_any_hits(const RtxScene *scene, const RtxRay *rays, const double *t_
     if (d_rays) (void)hipFree(d_rays);
     if (d_t_max) (void)hipFree(d_t_max);
     if (d_occ) (void)hipFree(d_occ);
+    const int32_t frc = rtx_scene_free(h);
+    return rc ? rc : frc;
+}
+
+int32_t rtx_trace_paths(const RtxScene *scene, const RtxRay *rays, const uint64_t *ids, uint64_t n, double *rgb, uint32_t *segments)
+{
+    if (int32_t rc = check_scene_args(scene, "rtx_trace_paths")) return rc;
+    if (n == 0) return RTX_OK;
+    if (!rays || !rgb) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_trace_paths: null rays or rgb");
+    if (n >= 0xFFFFFFFFull) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_trace_paths: n must be below 2^32");
+    if (int32_t rc = check_device(0, "rtx_trace_paths")) return rc;
+    RtxSceneHandle h = nullptr;
+    if (int32_t rc = rtx_scene_upload(scene, 0, &h)) return rc;
+    RtxRay *d_rays = nullptr;
+    uint64_t *d_ids = nullptr;
+    double *d_rgb = nullptr;
+    uint32_t *d_seg = nullptr;
+    hipError_t e = hipMalloc((void **)&d_rays, n * sizeof(RtxRay));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_rgb, n * 3 * sizeof(double));
+    if (e == hipSuccess && ids) e = hipMalloc((void **)&d_ids, n * 2 * sizeof(uint64_t));
+    if (e == hipSuccess && segments) e = hipMalloc((void **)&d_seg, n * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemcpy(d_rays, rays, n * sizeof(RtxRay), hipMemcpyHostToDevice);
+    if (e == hipSuccess && ids) e = hipMemcpy(d_ids, ids, n * 2 * sizeof(uint64_t), hipMemcpyHostToDevice);
+    int32_t rc = e == hipSuccess ? RTX_OK : fail(e == hipErrorOutOfMemory ? RTX_ERR_OUT_OF_MEMORY : RTX_ERR_HIP,
+                                                std::string("rtx_trace_paths: ") + hipGetErrorString(e));
+    if (!rc) rc = query_run(h, d_rays, 0u, 0u, n, nullptr, nullptr, nullptr, nullptr, nullptr, d_ids, d_rgb, d_seg);
+    if (!rc) {
+        e = hipMemcpy(rgb, d_rgb, n * 3 * sizeof(double), hipMemcpyDeviceToHost);      // (the null stream: after the query)
+        if (e == hipSuccess && segments) e = hipMemcpy(segments, d_seg, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(RTX_ERR_HIP, std::string("rtx_trace_paths: ") + hipGetErrorString(e));
+    }
+    if (d_rays) (void)hipFree(d_rays);
+    if (d_ids) (void)hipFree(d_ids);
+    if (d_rgb) (void)hipFree(d_rgb);
+    if (d_seg) (void)hipFree(d_seg);
     const int32_t frc = rtx_scene_free(h);
     return rc ? rc : frc;
 }

@@ -155,20 +155,30 @@ hipError_t launch_deinterleave_u8(const uint8_t *parts, uint8_t *full, uint32_t 
 hipError_t launch_quantize_values(const double *rgb, uint8_t *rgb8, uint32_t width, uint32_t n_rows, hipStream_t stream);
 
 // ---- ray queries (rtx_query.hip): closest_object for caller rays or for the pick buffer's zero-offset primary rays, or -- the
-// any-hit mode, a launch-uniform switch of the same kernel -- whether any object lies before a per-ray distance limit
+// any-hit mode, a launch-uniform switch of the same kernel -- whether any object lies before a per-ray distance limit, or -- the
+// path mode, a third switch -- render_ray's colour of the path that starts with the ray
 struct QueryRay { double position[3], direction[3]; };                                      // = RtxRay (include/rtx_hip.h)
 struct QueryHit { double position[3], normal[3], distance; long long object; };            // = RtxHit
 static_assert(sizeof(QueryRay) == 48 && sizeof(QueryHit) == 64, "QueryRay / QueryHit");
 struct QueryArgs {
     const QueryRay *rays;          // n rays (null in the pick form)
     const RowsView *rv;            // the pick form: the frame's RowsView (one band of all rows), ray i = pixel i; else null
-    QueryHit *hits;                // n answers (null in the any-hit mode)
+    union {                        // the answers, by mode (the modes share the slots: one kernel argument layout for the three loops)
+        QueryHit *hits;            // closest hits: n records
+        uint8_t *occluded;         // any-hit: n bytes, 1 / 0
+        double *rgb;               // paths: 3 n doubles, rgb[3 i .. 3 i + 2] = resulting_color of the path that starts with ray i
+    };
     unsigned long long n;
     uint32_t walk;                 // 0: every ray is swept (RTX_KERNEL_EXACT / no usable tree); set by the launcher
-    uint32_t any_hit;              // != 0: occluded[i] = some object's distance is normal, positive and < t_max[i]; no QueryHit is written
-    const double *t_max;           // any-hit: n limits, compared as given (null: +inf for every ray)
-    uint8_t *occluded;             // any-hit: n answers, 1 / 0
+    uint32_t mode;                 // kQueryClosest; kQueryAnyHit: occluded[i] = some object's distance is normal, positive and < t_max[i];
+                                   // kQueryPaths: render_ray (scene.rs:223-242) from ray i
+    union {
+        const double *t_max;       // any-hit: n limits, compared as given (null: +inf for every ray)
+        const unsigned long long *ids;   // paths: n (pixel index, sample index) pairs that key the RNG (null: (i, 0))
+    };
+    uint32_t *segments;            // paths: n closest_object counts, or null
 };
+constexpr uint32_t kQueryClosest = 0u, kQueryAnyHit = 1u, kQueryPaths = 2u;
 uint32_t query_tree_kind(const SceneView &sv);        // 0 no walk, 1 sphere tree, 2 a tree that holds triangles
 uint32_t query_spill_entries(const SceneView &sv);    // HBM stack entries per lane a walk may need beyond its LDS rows
 size_t query_spill_bytes(uint32_t entries, int n_cus);

@@ -18,13 +18,17 @@
 // overflow) tests every shape exactly -- every triangle, not just the ones with a filter record, since upload drops the
 // triangles the cull test rejects for every UNIT direction.
 //
-// The any-hit mode (QueryArgs.any_hit, rtx_scene_any_hits; DESIGN.md "Occlusion queries"): occluded[i] = some object's distance is
+// The any-hit mode (QueryArgs.mode, rtx_scene_any_hits; DESIGN.md "Occlusion queries"): occluded[i] = some object's distance is
 // normal, positive and < t_max[i] -- closest_object's distance < t_max[i], without the search for the nearest.  A launch-uniform
 // switch of the same two instances, taken once per launch (the mode has its own ray loop: the closest-hit loop carries none of its
 // arguments -- with the branch inside the shared loop the closest-hit rates fell by 0.5-2 %): the limit seeds best_up, so the walk
 // prunes what starts behind it; planes and the shapes outside the tree are tested BEFORE the walk; and a lane retires -- drops its stack and
 // its queued candidates -- as soon as a hit before the limit is certain: best_up, which only certain hits lower (the sphere
 // leaves' t_lo > K bound, tri_bounds' upper bound), has fallen below t_max, or an exact test said so.
+//
+// The path mode (QueryArgs.mode, rtx_scene_trace_paths; DESIGN.md "Path queries"): render_ray for the caller's rays -- the third
+// launch-uniform loop of the same two instances.  A lane owns a path and is refilled at the segment boundary; a segment is the
+// closest-hit loop's body (query_closest_ray) followed by advance_and_shade, with the render's draws 6 + 2b, 7 + 2b for bounce b.
 #include "rtx_launch.h"
 #include "rtx_mesh_step.h"
 #include "rtx_wavefront.h"
@@ -270,6 +274,80 @@ __device__ __forceinline__ bool query_walkable(const SceneView &sv, uint32_t tre
     return tree && query_dir_ok(dir) && (in32 || omax <= sv.bvh_origin_limit * kBvhRange64);
 }
 
+// One closest_object call (scene.rs:243-251) for the ray (pos, dir): the origin-range gate, the walk, the flush, planes and the
+// shapes outside the tree, or the sweep of every shape -- the segment body of the closest-hit loop and of the path loop.
+template <bool TRIS>
+__device__ __forceinline__ void query_closest_ray(const SceneView &sv, uint32_t tree, const float4 *__restrict__ nodes, const LeafArrays &la,
+                                                  const MeshArrays &ma, V3 pos, V3 dir, const RayX &rx, Hit &h, uint32_t *ls, uint32_t *lq,
+                                                  uint32_t tid, uint32_t *__restrict__ spill, uint32_t spill_entries, size_t spill_stride,
+                                                  size_t glane, unsigned long long &exact, unsigned long long &box_tests,
+                                                  unsigned long long &leaf_filters)
+{
+    hit_init(h);
+    const float omax = fmaxf(fmaxf(__builtin_fabsf((float)pos.x), __builtin_fabsf((float)pos.y)), __builtin_fabsf((float)pos.z));
+    const bool in32 = omax <= sv.bvh_origin_limit;                                      // NaN origin -> exhaustive branch
+    const bool walk = tree && query_dir_ok(dir) && (in32 || omax <= sv.bvh_origin_limit * kBvhRange64);
+    bool covered = false;
+    if (walk) {
+        bool overflow = false;
+        uint32_t nbox = 0, nleaf = 0;
+        if constexpr (TRIS) {
+            SphereRay sr;
+            sr.px = sr.py = sr.pz = sr.dx = sr.dy = sr.dz = sr.Kg = sr.K = 0.f; sr.c0 = __builtin_inff();
+            if (sv.bvh_flags & 1u) sphere_ray_from(sv, pos, dir, sr);
+            TriFilterParams tpar;
+            tri_filter_from_ray(sv, pos, dir, tpar);
+            const bool plain = (sv.bvh_flags & 4u) != 0u;
+            if (in32) {
+                Ray32 q;
+                make_ray32(pos, rx.dirn, (double)sv.bvh_inv_max, q);
+                if (plain) query_mesh_walk<2>(nodes, la, ma, q, sr, tpar, rx, sv.bvh_root, overflow, h, ls, lq, tid, spill, spill_entries,
+                                              spill_stride, glane, exact, nbox, nleaf);
+                else query_mesh_walk<0>(nodes, la, ma, q, sr, tpar, rx, sv.bvh_root, overflow, h, ls, lq, tid, spill, spill_entries,
+                                        spill_stride, glane, exact, nbox, nleaf);
+            } else {                                  // origin far outside the scene: the same walk with an f64 slab test
+                Ray64 q;
+                make_ray64(pos, rx.dirn, (double)sv.bvh_inv_max, q);
+                if (plain) query_mesh_walk<2>(nodes, la, ma, q, sr, tpar, rx, sv.bvh_root, overflow, h, ls, lq, tid, spill, spill_entries,
+                                              spill_stride, glane, exact, nbox, nleaf);
+                else query_mesh_walk<0>(nodes, la, ma, q, sr, tpar, rx, sv.bvh_root, overflow, h, ls, lq, tid, spill, spill_entries,
+                                        spill_stride, glane, exact, nbox, nleaf);
+            }
+        } else {
+            SphereRay sr;
+            sphere_ray_from(sv, pos, dir, sr);
+            Ray32 q0;
+            make_ray32(pos, rx.dirn, (double)sv.bvh_inv_max, q0);
+            Ray32S q;                                 // (a far origin: Ray32's planes widened by the slack of noi's rounding)
+            q.ix = q0.ix; q.iy = q0.iy; q.iz = q0.iz; q.nx = q0.nx; q.ny = q0.ny; q.nz = q0.nz;
+            q.e = ray32_slack(q0.nx, q0.ny, q0.nz, in32);
+            float best_up = __builtin_inff();
+            uint32_t node = sv.bvh_root, sp = 0, qcnt = 0;
+            sphere_walk_phased<kQuerySphStack, true>(nodes, la.sphere_f32, la.sphere_prims, q, sr, node, sp, ls, lq, tid, spill,
+                                                     spill_entries, spill_stride, glane, best_up, qcnt, overflow, nbox, nleaf,
+                                                     0u, 0u, 0u, kQueryLeafLanes);
+            if (!overflow) query_flush(la, rx, lq, tid, kSphQueue, qcnt, best_up, h, exact);
+        }
+        box_tests += nbox;
+        leaf_filters += nleaf;
+        covered = !overflow;
+    }
+    if (covered) {
+        // the tree answered for its shapes: the spheres outside it, every plane, the triangle records outside it
+        query_sweep(sv, la, rx, (sv.bvh_flags & 1u) == 0u, false, h, exact);
+        const uint32_t from = (sv.bvh_flags & 2u) ? sv.n_tri_tree : 0u;
+        for (uint32_t k = from; k < sv.n_tri_filter; ++k) {
+            const uint32_t tk = la.tri_fidx[k];
+            double t;
+            if (triangle_distance(la.tris[tk], rx, &t)) hit_consider(h, t, la.tris[tk].id, 2, tk);
+        }
+        exact += sv.n_tri_filter - from;
+    } else {
+        hit_init(h);                                  // (a walk cut short: start over, every shape exactly)
+        query_sweep(sv, la, rx, true, true, h, exact);
+    }
+}
+
 // The kernel's ray loop in the any-hit mode: the same persistent waves and chunks, one byte per ray.  A loop of its own, entered
 // once per launch, so that the closest-hit loop carries none of this mode's arguments or state.
 template <bool TRIS>
@@ -303,6 +381,68 @@ __device__ __forceinline__ void query_any_loop(const SceneView &sv, const QueryA
     }
 }
 
+// ---- the path mode -------------------------------------------------------------------------------------------------------------
+// render_ray (scene.rs:223-242) for the caller's rays: a lane owns one PATH, a variable number of segments, and is refilled at the
+// segment boundary -- at the top of every iteration each lane without a path takes the next ray of the wave's chunk (wf_take compacts
+// the takers by ballot), so no lane waits for the wave's longest path.  One iteration is one closest_object call (query_closest_ray)
+// and advance_and_shade, or the end of the path: a miss, max_bounces + 1 segments, or light_color == 0 (scene.rs:227-231).  A loop of
+// its own, entered once per launch: the closest-hit and any-hit loops carry none of its arguments or state.
+template <bool TRIS>
+__device__ __forceinline__ void query_path_loop(const SceneView &sv, const QueryArgs &qa, const float4 *__restrict__ nodes, const LeafArrays &la,
+                                                const MeshArrays &ma, uint32_t *ls, uint32_t *lq, uint32_t tid, uint32_t *__restrict__ spill,
+                                                uint32_t spill_entries, size_t spill_stride, size_t glane, unsigned long long *__restrict__ head,
+                                                unsigned long long &segs, unsigned long long &exact, unsigned long long &box_tests,
+                                                unsigned long long &leaf_filters)
+{
+    const unsigned long long grab = wf_grab_size(qa.n);
+    const uint32_t bounce_limit = sv.max_bounces >= 0xFFFFFFF0ull ? 0xFFFFFFF0u : (uint32_t)sv.max_bounces + 1u;     // scene.rs:227
+    WfChunk ch{0ull, 0ull, false};
+    RayState r;
+    uint32_t idx = 0;                                                    // the path's entry (n < 2^32)
+    bool have = false;
+    r.pos = r.dir = r.result = r.light = mk(0.0, 0.0, 0.0);
+    r.key = 0; r.draw = 6; r.bounce = 0;
+    for (;;) {
+        unsigned long long i = 0;
+        bool got = wf_take(ch, head, grab, qa.n, !have, i);
+        if (!ch.drained && __ballot(!have && !got) != 0ull) {            // the chunk ran out under the takers: the next one, now
+            unsigned long long i2 = 0;
+            if (wf_take(ch, head, grab, qa.n, !have && !got, i2)) { got = true; i = i2; }
+        }
+        if (got) {
+            const QueryRay &qr = qa.rays[i];
+            r.pos = mk(qr.position[0], qr.position[1], qr.position[2]);                      // Ray::new (ray.rs:14-21): no norm()
+            r.dir = mk(qr.direction[0], qr.direction[1], qr.direction[2]);
+            r.result = mk(0.0, 0.0, 0.0);
+            r.light = mk(1.0, 1.0, 1.0);
+            r.key = qa.ids ? rng_key(sv.seed, qa.ids[2 * i], qa.ids[2 * i + 1]) : rng_key(sv.seed, i, 0ull);
+            r.draw = 6;                                                  // (draws 0..5 are the lens jitter's: a render's sample continues here)
+            r.bounce = 0;
+            idx = (uint32_t)i;
+            have = true;
+        }
+        if (ch.drained && __ballot(have) == 0ull) break;                 // wave-uniform
+        if (!have) continue;
+        const RayX rx = make_rayx(r.pos, r.dir);
+        Hit h;
+        ++segs;
+        query_closest_ray<TRIS>(sv, qa.walk, nodes, la, ma, r.pos, r.dir, rx, h, ls, lq, tid, spill, spill_entries, spill_stride, glane, exact,
+                                box_tests, leaf_filters);
+        uint32_t nseg = r.bounce + 1u;                                   // closest_object calls so far
+        bool done = true;                                                // scene.rs:232: None ends the path
+        if (h.id != kNone) {
+            advance_and_shade(sv, h, r);
+            done = (r.bounce >= bounce_limit) || light_is_zero(r);       // scene.rs:227-228
+        }
+        if (done) {
+            double *out = qa.rgb + 3ull * idx;
+            out[0] = r.result.x; out[1] = r.result.y; out[2] = r.result.z;
+            if (qa.segments) qa.segments[idx] = nseg;
+            have = false;
+        }
+    }
+}
+
 template <bool TRIS>
 __global__ __launch_bounds__(kBvhThreads, kQueryWaves) void query_closest_kernel(const SceneView *__restrict__ svp, const QueryArgs qa,
                                                                                  const float4 *__restrict__ nodes, const LeafArrays la,
@@ -324,9 +464,12 @@ __global__ __launch_bounds__(kBvhThreads, kQueryWaves) void query_closest_kernel
     unsigned long long segs = 0, box_tests = 0, leaf_filters = 0, exact = 0;
     WfChunk ch{0ull, 0ull, false};
 
-    if (qa.any_hit)                                                      // launch-uniform: the any-hit mode has its own ray loop
+    if (qa.mode == kQueryAnyHit)                                         // launch-uniform: the any-hit mode has its own ray loop
         query_any_loop<TRIS>(sv, qa, nodes, la, ma, ls, lq, tid, spill, spill_entries, spill_stride, glane, head, segs, exact, box_tests,
                              leaf_filters);
+    else if (qa.mode == kQueryPaths)                                     // launch-uniform: so has the path mode
+        query_path_loop<TRIS>(sv, qa, nodes, la, ma, ls, lq, tid, spill, spill_entries, spill_stride, glane, head, segs, exact, box_tests,
+                              leaf_filters);
     else for (;;) {
         unsigned long long i = 0;
         const bool mine = wf_take(ch, head, grab, qa.n, true, i);         // (every lane of the wave is here: lane 0 takes the chunk)
@@ -343,70 +486,9 @@ __global__ __launch_bounds__(kBvhThreads, kQueryWaves) void query_closest_kernel
         }
         const RayX rx = make_rayx(pos, dir);
         Hit h;
-        hit_init(h);
         ++segs;
-        const float omax = fmaxf(fmaxf(__builtin_fabsf((float)pos.x), __builtin_fabsf((float)pos.y)), __builtin_fabsf((float)pos.z));
-        const bool in32 = omax <= sv.bvh_origin_limit;                                      // NaN origin -> exhaustive branch
-        const bool walk = qa.walk && query_dir_ok(dir) && (in32 || omax <= sv.bvh_origin_limit * kBvhRange64);
-        bool covered = false;
-        if (walk) {
-            bool overflow = false;
-            uint32_t nbox = 0, nleaf = 0;
-            if constexpr (TRIS) {
-                SphereRay sr;
-                sr.px = sr.py = sr.pz = sr.dx = sr.dy = sr.dz = sr.Kg = sr.K = 0.f; sr.c0 = __builtin_inff();
-                if (sv.bvh_flags & 1u) sphere_ray_from(sv, pos, dir, sr);
-                TriFilterParams tpar;
-                tri_filter_from_ray(sv, pos, dir, tpar);
-                const bool plain = (sv.bvh_flags & 4u) != 0u;
-                if (in32) {
-                    Ray32 q;
-                    make_ray32(pos, rx.dirn, (double)sv.bvh_inv_max, q);
-                    if (plain) query_mesh_walk<2>(nodes, la, ma, q, sr, tpar, rx, sv.bvh_root, overflow, h, ls, lq, tid, spill, spill_entries,
-                                                  spill_stride, glane, exact, nbox, nleaf);
-                    else query_mesh_walk<0>(nodes, la, ma, q, sr, tpar, rx, sv.bvh_root, overflow, h, ls, lq, tid, spill, spill_entries,
-                                            spill_stride, glane, exact, nbox, nleaf);
-                } else {                                  // origin far outside the scene: the same walk with an f64 slab test
-                    Ray64 q;
-                    make_ray64(pos, rx.dirn, (double)sv.bvh_inv_max, q);
-                    if (plain) query_mesh_walk<2>(nodes, la, ma, q, sr, tpar, rx, sv.bvh_root, overflow, h, ls, lq, tid, spill, spill_entries,
-                                                  spill_stride, glane, exact, nbox, nleaf);
-                    else query_mesh_walk<0>(nodes, la, ma, q, sr, tpar, rx, sv.bvh_root, overflow, h, ls, lq, tid, spill, spill_entries,
-                                            spill_stride, glane, exact, nbox, nleaf);
-                }
-            } else {
-                SphereRay sr;
-                sphere_ray_from(sv, pos, dir, sr);
-                Ray32 q0;
-                make_ray32(pos, rx.dirn, (double)sv.bvh_inv_max, q0);
-                Ray32S q;                                 // (a far origin: Ray32's planes widened by the slack of noi's rounding)
-                q.ix = q0.ix; q.iy = q0.iy; q.iz = q0.iz; q.nx = q0.nx; q.ny = q0.ny; q.nz = q0.nz;
-                q.e = ray32_slack(q0.nx, q0.ny, q0.nz, in32);
-                float best_up = __builtin_inff();
-                uint32_t node = sv.bvh_root, sp = 0, qcnt = 0;
-                sphere_walk_phased<kQuerySphStack, true>(nodes, la.sphere_f32, la.sphere_prims, q, sr, node, sp, ls, lq, tid, spill,
-                                                         spill_entries, spill_stride, glane, best_up, qcnt, overflow, nbox, nleaf,
-                                                         0u, 0u, 0u, kQueryLeafLanes);
-                if (!overflow) query_flush(la, rx, lq, tid, kSphQueue, qcnt, best_up, h, exact);
-            }
-            box_tests += nbox;
-            leaf_filters += nleaf;
-            covered = !overflow;
-        }
-        if (covered) {
-            // the tree answered for its shapes: the spheres outside it, every plane, the triangle records outside it
-            query_sweep(sv, la, rx, (sv.bvh_flags & 1u) == 0u, false, h, exact);
-            const uint32_t from = (sv.bvh_flags & 2u) ? sv.n_tri_tree : 0u;
-            for (uint32_t k = from; k < sv.n_tri_filter; ++k) {
-                const uint32_t tk = la.tri_fidx[k];
-                double t;
-                if (triangle_distance(la.tris[tk], rx, &t)) hit_consider(h, t, la.tris[tk].id, 2, tk);
-            }
-            exact += sv.n_tri_filter - from;
-        } else {
-            hit_init(h);                                  // (a walk cut short: start over, every shape exactly)
-            query_sweep(sv, la, rx, true, true, h, exact);
-        }
+        query_closest_ray<TRIS>(sv, qa.walk, nodes, la, ma, pos, dir, rx, h, ls, lq, tid, spill, spill_entries, spill_stride, glane, exact,
+                                box_tests, leaf_filters);
         // the answer: scene.rs:234's hit point and object.rs:37-39's normal there (what advance_and_shade hands the bounce)
         QueryHit out;
         if (h.id != kNone) {

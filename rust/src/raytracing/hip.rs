@@ -125,6 +125,8 @@ extern "C" {
     pub fn rtx_closest_hits(scene: *const RtxScene, rays: *const RtxRay, n: u64, hits: *mut RtxHit) -> i32;
     pub fn rtx_scene_any_hits(scene: RtxSceneHandle, d_rays: *const RtxRay, d_t_max: *const f64, n: u64, d_occluded: *mut u8, stream: *mut c_void, stats: *mut RtxStats) -> i32;
     pub fn rtx_any_hits(scene: *const RtxScene, rays: *const RtxRay, t_max: *const f64, n: u64, occluded: *mut u8) -> i32;
+    pub fn rtx_scene_trace_paths(scene: RtxSceneHandle, d_rays: *const RtxRay, d_ids: *const u64, n: u64, d_rgb: *mut f64, d_segments: *mut u32, stream: *mut c_void, stats: *mut RtxStats) -> i32;
+    pub fn rtx_trace_paths(scene: *const RtxScene, rays: *const RtxRay, ids: *const u64, n: u64, rgb: *mut f64, segments: *mut u32) -> i32;
     pub fn rtx_quantize_image_device(d_rgb: *const f64, width: u32, height: u32, d_rgb8: *mut u8, device: i32, stream: *mut c_void) -> i32;
 }
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Closest-hit and any-hit query rates (rtx_scene_closest_hits / rtx_scene_primary_hits / rtx_scene_any_hits), in Mrays/s from
-RtxStats.trace_ms, on the scenes of the
+"""Closest-hit, any-hit and path query rates (rtx_scene_closest_hits / rtx_scene_primary_hits / rtx_scene_any_hits /
+rtx_scene_trace_paths), in Mrays/s (the path legs: Msegments/s) from RtxStats.trace_ms, on the scenes of the
 benchmark's C2 (10k spheres), C3 (100k triangles) and J1 (5k spheres + 50k triangles: a joint tree), built with scenes.py's
 generators and the same parameters:
 
@@ -10,10 +10,14 @@ generators and the same parameters:
   any          rtx_scene_any_hits on the incoherent set, t_max = +inf (any hit at all)
   any_short    the same with t_max = 1.0 (the median closest distance in these boxes is ~25)
   any_aimed    t_max = +inf on rays with the incoherent set's origins, each aimed at a random sphere centre / triangle centroid
+  paths        rtx_scene_trace_paths on the incoherent set at the scene's config (max_bounces = 10), ids (i, 0)
+  paths_1seg   the same rays at max_bounces = 0: one segment per path -- against `incoherent`, the price of the shade and the refill
+  paths_pick   the 1920x1080 zero-offset primary rays (built on the host from the camera) with ids (pixel, 0)
+  render_pick  rtx_render_rows of the same frame at 1 spp with both offsets 0: paths_pick's segments, with the render's tile packets
 
     tools/query_rate.py [--rays 24] [--scenes C2,C3,J1] [--reps 3] [--exact-rays 20] [--legs incoherent,pick,...]
 
-The library is the package's (RTX_HIP_LIB selects another build, e.g. one of the parent commit: its any legs are then skipped).
+The library is the package's (RTX_HIP_LIB selects another build, e.g. one of the parent commit: the legs it lacks are then skipped).
 
 The exact leg runs 2^--exact-rays of the rays (the sweep is ~n_objects tests per ray) and reports its rate on those.  One JSON line per
 scene and leg; the best of --reps timed runs after one warm-up.
@@ -57,7 +61,20 @@ def aimed(objs, o, seed=2):
     return d
 
 
-LEGS = ("incoherent", "pick", "exact", "any", "any_short", "any_aimed")
+def primary_rays(rtx, cam, width, height):
+    """the zero-offset primary ray of every pixel (scene.rs:196-222 with focal_offset = non_focal_offset = 0), row-major"""
+    c = rtx.Camera(*cam)
+    m = np.array(c._to_world, dtype=np.float64).reshape(3, 3)
+    ax = c.fov * (np.arange(width) / width - 0.5)
+    ay = (height / width * c.fov) * (np.arange(height) / height - 0.5)
+    v = np.stack([np.broadcast_to(np.sin(ax)[None, :], (height, width)), np.broadcast_to(np.sin(ay)[:, None], (height, width)),
+                  np.cos(ax)[None, :] * np.cos(ay)[:, None]], axis=2).reshape(-1, 3)
+    d = v @ m.T                                                        # mat/mul.rs:42-50: rhs.dot(row)
+    d /= np.linalg.norm(d, axis=1)[:, None]
+    return np.broadcast_to(np.array(list(c.position), dtype=np.float64), d.shape), d
+
+
+LEGS = ("incoherent", "pick", "exact", "any", "any_short", "any_aimed", "paths", "paths_1seg", "paths_pick", "render_pick")
 
 
 def main():
@@ -83,13 +100,19 @@ def main():
         rtx.abi.SYMBOLS[:] = [sym for sym in rtx.abi.SYMBOLS if hasattr(probe, sym[0])]
         if not hasattr(probe, "rtx_scene_any_hits"):
             legs = [l for l in legs if not l.startswith("any")]
+        if not hasattr(probe, "rtx_scene_trace_paths"):
+            legs = [l for l in legs if not l.startswith("paths")]
     for name in args.scenes.split(","):
         objs = SCENES[name](scenes)
         o, d = incoherent(objs, n)
         rays = rtx.make_rays(o, d)
         d_rays = torch.from_numpy(rays.view(np.uint8)).to(dev)
         d_hits = torch.empty(n * 64, dtype=torch.uint8, device=dev)
-        d_aimed = d_lim = None
+        d_aimed = d_lim = d_prim = d_prim_ids = None
+        W, H = 1920, 1080
+        if "paths_pick" in legs:
+            d_prim = torch.from_numpy(rtx.make_rays(*primary_rays(rtx, scenes.CAMERA, W, H)).view(np.uint8)).to(dev)
+            d_prim_ids = torch.stack([torch.arange(W * H, dtype=torch.int64, device=dev), torch.zeros(W * H, dtype=torch.int64, device=dev)], dim=1).contiguous()
         if "any_aimed" in legs:
             d_aimed = torch.from_numpy(rtx.make_rays(o, aimed(objs, o)).view(np.uint8)).to(dev)
         if "any_short" in legs:
@@ -103,7 +126,28 @@ def main():
 
         for leg in legs:
             kernel = rtx.RTX_KERNEL_EXACT if leg == "exact" else rtx.RTX_KERNEL_AUTO
-            hnd = rtx.Scene.from_packed(rtx.Config(rays_per_pixel=1, kernel=kernel), rtx.Camera(*scenes.CAMERA), objs).upload(0)
+            cfg = rtx.Config(rays_per_pixel=1, kernel=kernel, max_bounces=0 if leg == "paths_1seg" else 10)
+            if leg == "render_pick":
+                cfg = cfg.with_focal_offset(0.0).with_non_focal_offset(0.0)
+            hnd = rtx.Scene.from_packed(cfg, rtx.Camera(*scenes.CAMERA), objs).upload(0)
+            if leg.startswith("paths") or leg == "render_pick":
+                d_rgb = d_hits.view(torch.float64)                       # (n * 8 doubles: room for 3 per ray or pixel)
+                if leg == "paths_pick":
+                    k = W * H
+                    st = best(lambda: hnd.trace_paths(d_prim.data_ptr(), d_prim_ids.data_ptr(), k, d_rgb.data_ptr()))
+                elif leg == "render_pick":
+                    k = W * H
+                    st = best(lambda: hnd.render_rows(W, H, 0, 1, H, d_rgb.data_ptr()))
+                else:
+                    k = n
+                    st = best(lambda: hnd.trace_paths(d_rays.data_ptr(), None, k, d_rgb.data_ptr()))
+                print(json.dumps({"scene": name, "leg": leg, "rays": k, "segments": int(st.segments), "trace_ms": round(st.trace_ms, 3),
+                                  "msegments_per_s": round(st.segments / (st.trace_ms * 1e-3) / 1e6, 1), "kernel": int(st.kernel),
+                                  "segments_per_ray": round(st.segments / k, 3), "exact_tests_per_ray": round(st.exact_tests / k, 2),
+                                  "box_tests_per_ray": round(st.box_tests / k, 2),
+                                  "lit_fraction": round(float((d_rgb[:3 * k].view(-1, 3) != 0).any(dim=1).float().mean().item()), 4)}), flush=True)
+                hnd.close()
+                continue
             if leg.startswith("any"):
                 k = n
                 src = d_aimed if leg == "any_aimed" else d_rays
