@@ -266,7 +266,8 @@ __device__ __forceinline__ uint32_t query_any_ray(const SceneView &sv, const flo
     return occ ? 1u : 0u;
 }
 
-// whether the ray may take the walk (its f32 bounds hold for it) and which slab test it gets: query_closest_kernel's gate
+// whether the ray may take the walk (its f32 bounds hold for it) and which slab test it gets: the gate of query_closest_ray (the
+// closest-hit and the path loop) and of the any-hit loop
 __device__ __forceinline__ bool query_walkable(const SceneView &sv, uint32_t tree, V3 pos, V3 dir, bool &in32)
 {
     const float omax = fmaxf(fmaxf(__builtin_fabsf((float)pos.x), __builtin_fabsf((float)pos.y)), __builtin_fabsf((float)pos.z));
@@ -284,9 +285,8 @@ __device__ __forceinline__ void query_closest_ray(const SceneView &sv, uint32_t 
                                                   unsigned long long &leaf_filters)
 {
     hit_init(h);
-    const float omax = fmaxf(fmaxf(__builtin_fabsf((float)pos.x), __builtin_fabsf((float)pos.y)), __builtin_fabsf((float)pos.z));
-    const bool in32 = omax <= sv.bvh_origin_limit;                                      // NaN origin -> exhaustive branch
-    const bool walk = tree && query_dir_ok(dir) && (in32 || omax <= sv.bvh_origin_limit * kBvhRange64);
+    bool in32;
+    const bool walk = query_walkable(sv, tree, pos, dir, in32);
     bool covered = false;
     if (walk) {
         bool overflow = false;

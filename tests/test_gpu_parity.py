@@ -838,6 +838,37 @@ def test_two_halves_in_flight_keep_the_bits(gpu, oracle):
     hnd.close()
 
 
+def test_stage1_stats_do_not_depend_on_the_batching(gpu):
+    """The counters accumulate over the sample batches of a call and stage 1's share of each batch is what its snapshot holds beyond
+    the totals of the batches before it (render_band): the two-stage sphere kernel's frame and every counter of RtxStats, stage 1's
+    included, are the same whether the 4 samples run as one launch or as two batches of 2."""
+    import torch
+    from rust_raytracing_amd import scenes
+    objs = scenes.random_spheres(200, 1)
+    w, h, spp = 64, 64, 4
+    res = {}
+    for tag in ("one", "batched"):
+        hnd = hip_scene(gpu, objs, cam=scenes.CAMERA, kernel=gpu.RTX_KERNEL_AUTO, rays_per_pixel=spp, max_bounces=4, seed=42,
+                        tuning=gpu.RTX_TUNE_TWO_STAGE | gpu.RTX_TUNE_NO_TILE_LISTS).upload(0)
+        if tag == "batched":
+            # 128 MiB + 32.5 KiB of the limit are the queue's fixed part (a chunk of 512 64-byte records per resident wave of 256 CUs,
+            # as in test_c4_shaped_band_of_one_rank); 8*8*64 slots * (32 + 64 + 5) B + their mask bits = 414 KB per sample: the
+            # remaining ~0.97 MiB hold 2 samples -> 2 batches
+            hnd.set_scratch_limit(129 << 20)
+        buf = torch.zeros((h, w, 3), dtype=torch.float64, device="cuda:0")
+        st = hnd.render_rows(w, h, 0, 1, h, buf.data_ptr())
+        hnd.close()
+        res[tag] = (buf.cpu().numpy(), st)
+    (a, sa), (b, sb) = res["one"], res["batched"]
+    assert sa.kernel == gpu.RTX_KERNEL_BVH and sa.trace_launches == 1 and sa.stage1_ms > 0
+    assert sb.kernel == gpu.RTX_KERNEL_BVH and sb.trace_launches >= 2 and sb.stage1_ms > 0
+    assert a.tobytes() == b.tobytes()
+    for f in ("segments", "exact_tests", "filter_tests", "box_tests", "stage1_exact_tests", "stage1_filter_tests", "stage1_box_tests"):
+        print(f, getattr(sa, f), getattr(sb, f))
+        assert getattr(sa, f) == getattr(sb, f), (f, getattr(sa, f), getattr(sb, f))
+    assert sa.stage1_box_tests + sa.stage1_filter_tests + sa.stage1_exact_tests > 0          # (the walking packets of stage 1 counted)
+
+
 def test_tile_lists_of_the_primary_rays_keep_the_bits(gpu, oracle):
     """Stage 1 of the sphere path: what an 8x8 tile's primary rays can hit is found once per tile (build_tile_lists_kernel: a walk
     with an interval origin and an interval direction) and every packet of the tile runs the walk's leaf test over that list
