@@ -254,6 +254,18 @@ public:
         return out;
     }
 
+    // The denoising guide buffers of a width x height frame (rtx_pixel_features): per pixel [y][x] the first hits of render_pixel's own
+    // lens-jittered rays, folded in sample order -- mean albedo / emission / normal, mean depth, coverage, sample 0's object.
+    std::vector<RtxPixelFeatures> pixel_features(std::size_t width, std::size_t height) const
+    {
+        std::vector<RtxPixelFeatures> out(width * height);
+        std::vector<RtxObject> packed = pack();
+        RtxScene sc = to_c(packed);
+        int32_t rc = rtx_pixel_features(&sc, (uint32_t)width, (uint32_t)height, out.data());
+        if (rc != RTX_OK) throw Panic(rc, rtx_last_error());
+        return out;
+    }
+
     // render_ray (scene.rs:223-242) from each ray, with the config's max_bounces and seed (rtx_trace_paths): rgb[3 i .. 3 i + 2] =
     // the path's resulting_color, unclamped.  ids: empty (entry i draws as pixel i, sample 0) or 2 per ray, (pixel index, sample
     // index); segments (optional): the closest_object calls of each path.
@@ -396,6 +408,17 @@ public:
     void primary_hits(std::size_t width, std::size_t height, RtxHit *d_hits, void *hip_stream = nullptr, RtxStats *stats = nullptr)
     {
         check(rtx_scene_primary_hits(h_, (uint32_t)width, (uint32_t)height, d_hits, hip_stream, stats));
+    }
+    // the denoising guide buffers: d_features[height][width] = each pixel's folded first hits over the render's own rays
+    void pixel_features(std::size_t width, std::size_t height, RtxPixelFeatures *d_features, void *hip_stream = nullptr, RtxStats *stats = nullptr)
+    {
+        check(rtx_scene_pixel_features(h_, (uint32_t)width, (uint32_t)height, d_features, hip_stream, stats));
+    }
+    // the same for the band of part `part` of `n_parts` (blocks of block_rows rows, as render_blocks): rtx_blocks_row_count() rows
+    void pixel_features_blocks(std::size_t width, std::size_t height, std::uint32_t block_rows, std::uint32_t part, std::uint32_t n_parts,
+                               RtxPixelFeatures *d_features, void *hip_stream = nullptr, RtxStats *stats = nullptr)
+    {
+        check(rtx_scene_pixel_features_blocks(h_, (uint32_t)width, (uint32_t)height, block_rows, part, n_parts, d_features, hip_stream, stats));
     }
 
 private:

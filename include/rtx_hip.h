@@ -216,6 +216,17 @@ typedef struct RtxHit {
     int64_t object;              /* the winner's index in Scene.objects (the first minimal distance wins); -1: nothing is hit */
 } RtxHit;
 
+/* Denoising guide buffers (rtx_scene_pixel_features, rtx_scene_pixel_features_blocks, rtx_pixel_features): one pixel's first hits over
+ * render_pixel's own lens-jittered rays, folded as the render folds its samples. */
+typedef struct RtxPixelFeatures {
+    double  albedo[3];           /* mean Material.base_color of the samples' first hits (a miss adds zero) */
+    double  emission[3];         /* mean Material.emission_color, likewise */
+    double  normal[3];           /* mean Object::normal_at(hit point), likewise; NOT renormalised */
+    double  depth;               /* mean distance over the samples that hit; +inf when none did */
+    double  coverage;            /* samples that hit / rays_per_pixel */
+    int64_t object;              /* sample 0's winner in Scene.objects; -1: it missed (or rays_per_pixel == 0) */
+} RtxPixelFeatures;
+
 /* The layouts a binding has to reproduce (rust/src/raytracing/hip.rs: #[repr(C)]; rust-raytracing_amd/abi.py: ctypes;
  * tests/test_abi_and_host.py checks both against these numbers). */
 #ifdef __cplusplus
@@ -237,6 +248,9 @@ RTX_STATIC_ASSERT(sizeof(RtxStats) == 104 && offsetof(RtxStats, trace_ms) == 32 
 RTX_STATIC_ASSERT(sizeof(RtxRay) == 48 && offsetof(RtxRay, direction) == 24, "RtxRay layout");
 RTX_STATIC_ASSERT(sizeof(RtxHit) == 64 && offsetof(RtxHit, normal) == 24 && offsetof(RtxHit, distance) == 48 &&
                   offsetof(RtxHit, object) == 56, "RtxHit layout");
+RTX_STATIC_ASSERT(sizeof(RtxPixelFeatures) == 96 && offsetof(RtxPixelFeatures, emission) == 24 && offsetof(RtxPixelFeatures, normal) == 48 &&
+                  offsetof(RtxPixelFeatures, depth) == 72 && offsetof(RtxPixelFeatures, coverage) == 80 &&
+                  offsetof(RtxPixelFeatures, object) == 88, "RtxPixelFeatures layout");
 
 /* -- library ----------------------------------------------------------------------------- */
 int32_t     rtx_version(void);
@@ -402,6 +416,40 @@ int32_t rtx_scene_trace_paths(RtxSceneHandle scene, const RtxRay *d_rays, const 
 /* One-shot host form (upload to device 0, trace, copy back), as rtx_closest_hits.  rays / ids (or NULL) / rgb / segments (or NULL):
  * HOST arrays. */
 int32_t rtx_trace_paths(const RtxScene *scene, const RtxRay *rays, const uint64_t *ids, uint64_t n, double *rgb, uint32_t *segments);
+
+/* Denoising guide buffers: the per-pixel first-hit albedo, emission, normal and depth (the "auxiliary feature" / AOV buffers a
+ * denoiser reads next to the beauty frame), taken over the SAME lens-jittered primary rays as the render, so that depth-of-field blur
+ * and edge coverage in the guides line up with the image (the pick buffer of rtx_scene_primary_hits uses the zero-offset ray: it is
+ * sharp where the render is blurred).  For pixel (x, y) of the width x height frame, with S = the handle's rays_per_pixel, for
+ * s = 0 .. S - 1 in order:
+ *  - the ray is exactly render_pixel's (scene.rs:196-207): key = rng_key(seed, y * width + x, s), draws 0..5; non_focal_offset,
+ *    focal_offset, focal_length and the camera come from the handle; max_bounces is not read.
+ *  - closest_object of that ray.  On Some((dst, obj)): albedo sum += base_color, emission sum += emission_color, normal sum +=
+ *    obj.normal_at(position + direction * dst), depth sum += dst, hits += 1 -- component-wise f64 adds from +0.0, in sample order.  On
+ *    None nothing is added.
+ * Then albedo, emission, normal = sum / (double)S (a division, as the render's fold: iter_ops.rs:4-8); coverage = (double)hits /
+ * (double)S; depth = depth sum / (double)hits, +inf when hits == 0; object = sample 0's winner, -1 when it missed.  S == 0: 0 / 0 = NaN
+ * for the four means (as the render's NaN pixels), depth = +inf, object = -1.  S >= 2^32: RTX_ERR_INVALID_ARGUMENT.
+ *  - `emission` is, bit for bit, the pixel rtx_render_rows produces with max_bounces = 0 and the same config: a one-segment render_ray
+ *    returns 0 + 1 * emission_color, and the fold is the same left sum from zero divided by S (0 + 1 * e differs from e only for
+ *    e = -0.0, and added to a sum that started at +0.0 both give the same sum).
+ *  - d_features: DEVICE array [y][x], row 0 = the reference's row 0.  The blocks form writes the rows of part `part` of `n_parts`
+ *    (blocks of block_rows rows dealt out round-robin) in increasing image order, exactly as rtx_render_blocks does:
+ *    rtx_blocks_row_count(height, block_rows, part, n_parts) * width records.  Pixels do not depend on the partition;
+ *    rtx_scene_pixel_features(h, w, hgt, ...) == rtx_scene_pixel_features_blocks(h, w, hgt, 8, 0, 1, ...).  Pixels per call < 2^32 - 16,
+ *    as for renders.
+ *  - A scene without objects is no special case: the launch runs and every sample misses (zeros, depth +inf, object -1, coverage 0).
+ * Streams, stats == NULL asynchrony, RtxConfig.tuning bits of RTX_TUNE_LAB_MASK, RTX_KERNEL_EXACT (every ray swept, the same bits): as
+ * rtx_scene_closest_hits.  stats: primary_rays = segments = pixels * S, exact_tests, filter_tests, box_tests, trace_ms,
+ * trace_launches = 1, kernel = RTX_KERNEL_BVH | RTX_KERNEL_EXACT.  (DESIGN.md "Pixel features".) */
+int32_t rtx_scene_pixel_features(RtxSceneHandle scene, uint32_t width, uint32_t height, RtxPixelFeatures *d_features,
+                                 void *stream, RtxStats *stats);
+int32_t rtx_scene_pixel_features_blocks(RtxSceneHandle scene, uint32_t width, uint32_t height,
+                                        uint32_t block_rows, uint32_t part, uint32_t n_parts,
+                                        RtxPixelFeatures *d_features, void *stream, RtxStats *stats);
+
+/* One-shot host form (upload to device 0, query, copy back), as rtx_closest_hits.  features: HOST array of width * height records. */
+int32_t rtx_pixel_features(const RtxScene *scene, uint32_t width, uint32_t height, RtxPixelFeatures *features);
 
 /* Device epilogue of render_to_image on a full device image (scene.rs:175-178):
  * d_rgb height*width*3 doubles -> d_rgb8 height*width*3 bytes, flipped vertically. */

@@ -22,12 +22,12 @@ from . import abi
 from .abi import (RTX_TUNE_NO_TILES, RTX_TUNE_BVH_CLASSIC, RTX_TUNE_NO_QNODES, RTX_TUNE_NO_PACKETS, RTX_TUNE_WF_PURE, RTX_TUNE_ONE_STAGE,
                   RTX_TUNE_TWO_STAGE, RTX_TUNE_BVH_MEDIAN, RTX_TUNE_TRI_LEAF_SHIFT, RTX_TUNE_THRESH_SHIFT, RTX_TUNE_SORT_SURVIVORS, RTX_TUNE_PK_LDS_STACK, RTX_TUNE_STAGE2_POOL, RTX_TUNE_STAGE2_PAIR, RTX_TUNE_NO_CUT, RTX_TUNE_BEAMS, RTX_TUNE_INLINE_LEAVES, RTX_TUNE_STAGE2_SLOTS, RTX_TUNE_HALVES, RTX_TUNE_NO_HALVES, RTX_TUNE_NO_TILE_LISTS)
 from .abi import (OBJECT_DTYPE, RTX_KERNEL_WAVEFRONT, RTX_KERNEL_AUTO, RTX_KERNEL_BVH, RTX_KERNEL_EXACT, RTX_KERNEL_MIXED, RTX_KERNEL_MIXED_VERIFY, RTX_KERNEL_BVH_REGROUP,
-                  RTX_PLANE, RTX_SPHERE, RTX_TRIANGLE, RtxError, load_library, RAY_DTYPE, HIT_DTYPE)
+                  RTX_PLANE, RTX_SPHERE, RTX_TRIANGLE, RtxError, load_library, RAY_DTYPE, HIT_DTYPE, FEATURE_DTYPE)
 
 __all__ = ["LabKernel", "Vector3", "Material", "Sphere", "Plane", "Triangle", "Object", "Config", "Camera", "Scene",
            "SceneHandle", "RtxError", "device_count", "pack_objects", "OBJECT_DTYPE",
            "RTX_KERNEL_AUTO", "RTX_KERNEL_EXACT", "RTX_KERNEL_MIXED", "RTX_KERNEL_MIXED_VERIFY", "RTX_KERNEL_BVH", "RTX_KERNEL_BVH_REGROUP", "RTX_KERNEL_WAVEFRONT", "debug_host_scene",
-           "RAY_DTYPE", "HIT_DTYPE", "make_rays"]
+           "RAY_DTYPE", "HIT_DTYPE", "FEATURE_DTYPE", "make_rays"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -335,6 +335,11 @@ def _split_hits(hits):
     return (hits["distance"].copy(), hits["object"].copy(), hits["position"].copy(), hits["normal"].copy())
 
 
+def _split_features(f):
+    """RtxPixelFeatures records -> (albedo, emission, normal, depth, coverage, object) numpy arrays"""
+    return (f["albedo"].copy(), f["emission"].copy(), f["normal"].copy(), f["depth"].copy(), f["coverage"].copy(), f["object"].copy())
+
+
 class Scene:
     def __init__(self, config=None, camera=None):                   # Scene::new scene.rs:112-118 / Default :86-94
         self.config = config if config is not None else Config()
@@ -430,6 +435,20 @@ class Scene:
         abi.check(lib.rtx_trace_paths(C.byref(sc), rays.ctypes.data, pid.ctypes.data if pid is not None else None, n, rgb.ctypes.data,
                                       seg.ctypes.data), lib)
         return rgb, seg
+
+
+    def features(self, width, height):
+        """The denoising guide buffers of a width x height frame over the render's own lens-jittered rays (rtx_pixel_features: upload
+        to device 0, query, copy back).  Returns numpy (albedo, emission, normal (height, width, 3) float64 -- the means of the
+        samples' first hits, a miss adding zero; depth (height, width) -- the mean distance of the samples that hit, +inf: none;
+        coverage (height, width) -- hits / rays_per_pixel; object (height, width) int64 -- sample 0's winner, -1: it missed)."""
+        width, height = int(width), int(height)
+        out = np.zeros((height, width), dtype=FEATURE_DTYPE)
+        packed = self.packed()
+        sc = _scene_c(self.config, self.camera, packed)
+        lib = load_library(self.config.wants_lab())
+        abi.check(lib.rtx_pixel_features(C.byref(sc), width, height, out.ctypes.data), lib)
+        return _split_features(out)
 
 
 class SceneHandle:
@@ -601,6 +620,33 @@ class SceneHandle:
         self.primary_hits(width, height, d_hits.data_ptr(), want_stats=True)
         hits = d_hits[:n * HIT_DTYPE.itemsize].cpu().numpy().view(HIT_DTYPE).reshape(int(height), int(width))
         return _split_hits(hits)
+
+    def pixel_features(self, width, height, d_ptr, stream=None, want_stats=True):
+        """The denoising guide buffers: width * height RtxPixelFeatures records (96 B) [y][x] at the device address d_ptr, each pixel's
+        first hits over the render's own rays_per_pixel lens-jittered rays, folded.  want_stats=False: asynchronous on `stream`."""
+        stats = abi.RtxStats()
+        self._check(self._lib.rtx_scene_pixel_features(self._h, int(width), int(height), C.c_void_p(int(d_ptr)),
+                                                       C.c_void_p(int(stream)) if stream else None, C.byref(stats) if want_stats else None))
+        return stats if want_stats else None
+
+    def pixel_features_blocks(self, width, height, block_rows, part, n_parts, d_ptr, stream=None, want_stats=True):
+        """The same for the band of part `part` of `n_parts` (blocks of `block_rows` rows dealt out round-robin, as render_blocks):
+        rtx_blocks_row_count(height, block_rows, part, n_parts) * width records at d_ptr, the part's rows in increasing image order."""
+        stats = abi.RtxStats()
+        self._check(self._lib.rtx_scene_pixel_features_blocks(self._h, int(width), int(height), int(block_rows), int(part), int(n_parts),
+                                                              C.c_void_p(int(d_ptr)), C.c_void_p(int(stream)) if stream else None,
+                                                              C.byref(stats) if want_stats else None))
+        return stats if want_stats else None
+
+    def features(self, width, height):
+        """Host convenience of pixel_features: numpy (albedo, emission, normal [y][x][3], depth, coverage, object [y][x])."""
+        import torch
+        n = int(width) * int(height)
+        d_out = torch.empty(max(n, 1) * FEATURE_DTYPE.itemsize, dtype=torch.uint8, device=torch.device("cuda", self.device))
+        torch.cuda.synchronize(self.device)
+        self.pixel_features(width, height, d_out.data_ptr(), want_stats=True)
+        f = d_out[:n * FEATURE_DTYPE.itemsize].cpu().numpy().view(FEATURE_DTYPE).reshape(int(height), int(width))
+        return _split_features(f)
 
     def close(self):
         if self._h:

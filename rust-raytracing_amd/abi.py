@@ -79,10 +79,18 @@ class RtxHit(C.Structure):
     _fields_ = [("position", C.c_double * 3), ("normal", C.c_double * 3), ("distance", C.c_double), ("object", C.c_int64)]
 
 
+class RtxPixelFeatures(C.Structure):
+    _fields_ = [("albedo", C.c_double * 3), ("emission", C.c_double * 3), ("normal", C.c_double * 3), ("depth", C.c_double),
+                ("coverage", C.c_double), ("object", C.c_int64)]
+
+
 # the same layouts as numpy records (arrays of rays / answers)
 RAY_DTYPE = np.dtype([("position", "<f8", (3,)), ("direction", "<f8", (3,))])
 HIT_DTYPE = np.dtype([("position", "<f8", (3,)), ("normal", "<f8", (3,)), ("distance", "<f8"), ("object", "<i8")])
+FEATURE_DTYPE = np.dtype([("albedo", "<f8", (3,)), ("emission", "<f8", (3,)), ("normal", "<f8", (3,)), ("depth", "<f8"),
+                          ("coverage", "<f8"), ("object", "<i8")])
 assert RAY_DTYPE.itemsize == C.sizeof(RtxRay) == 48 and HIT_DTYPE.itemsize == C.sizeof(RtxHit) == 64
+assert FEATURE_DTYPE.itemsize == C.sizeof(RtxPixelFeatures) == 96
 
 
 # every symbol include/rtx_hip.h declares: (name, restype, argtypes)
@@ -115,6 +123,10 @@ SYMBOLS = [
     ("rtx_any_hits", C.c_int32, [C.POINTER(RtxScene), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     ("rtx_scene_trace_paths", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtxStats)]),
     ("rtx_trace_paths", C.c_int32, [C.POINTER(RtxScene), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("rtx_scene_pixel_features", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(RtxStats)]),
+    ("rtx_scene_pixel_features_blocks", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                    C.c_void_p, C.c_void_p, C.POINTER(RtxStats)]),
+    ("rtx_pixel_features", C.c_int32, [C.POINTER(RtxScene), C.c_uint32, C.c_uint32, C.c_void_p]),
     ("rtx_quantize_image_device", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p]),
     ("rtx_debug_math", C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
     ("rtx_debug_paths", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),

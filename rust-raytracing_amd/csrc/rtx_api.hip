@@ -1347,18 +1347,22 @@ static int32_t render_band(RtxSceneHandle h, uint32_t width, uint32_t height, ui
 }
 
 // ---- ray queries: closest_object (scene.rs:243-251) for the caller's rays or for the zero-offset primary ray of every pixel of a
-// width x height frame (the pick buffer), in one of three modes.  A QueryRequest says which, with that mode's device pointers.
+// width x height frame (the pick buffer), in one of three modes -- or, the fourth, the folded first hits of render_pixel's own rays for
+// every pixel of a band of a frame (the feature buffers).  A QueryRequest says which, with that mode's device pointers.
 namespace {
 
 struct QueryRequest {
     uint32_t mode = kQueryClosest;
-    uint32_t width = 0, height = 0;      // the pick form (rays == null, kQueryClosest): ray i = pixel i of this frame, n = width * height
+    uint32_t width = 0, height = 0;      // the pick form (rays == null, kQueryClosest): ray i = pixel i of this frame, n = width * height;
+                                         // kQueryFeatures: entry i = local pixel i of the band below, n = n_rows * width
+    uint32_t row_begin = 0, row_stride = 1, row_block = 1, n_rows = 0;   // the band of the frame, as render_band takes it (the pick form: every row)
     uint64_t n = 0;
     const RtxRay *rays = nullptr;
     RtxHit *hits = nullptr;                                      // kQueryClosest (rtx_scene_closest_hits, rtx_scene_primary_hits): n records
     uint8_t *occluded = nullptr; const double *t_max = nullptr;  // kQueryAnyHit (rtx_scene_any_hits): one byte per ray; the per-ray limits (null: +inf)
     double *rgb = nullptr;                                       // kQueryPaths (rtx_scene_trace_paths): render_ray's colour of the path each ray starts,
     const uint64_t *ids = nullptr; uint32_t *segments = nullptr; //   the (pixel, sample) pairs that key the RNG (null: (i, 0)), its closest_object calls (or null)
+    RtxPixelFeatures *features = nullptr;                        // kQueryFeatures (rtx_scene_pixel_features_blocks): n records, the band's rows in order
 };
 
 }  // namespace
@@ -1368,7 +1372,7 @@ static int32_t query_run(RtxSceneHandle_ *h, const QueryRequest &req, void *stre
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const uint64_t n = req.n;
-    const bool pick = req.width != 0;
+    const bool pick = req.width != 0;                 // a frame's pixels, not the caller's rays: the pick form, the feature mode
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (n == 0) return RTX_OK;
     RTX_HIP_CHECK(hipSetDevice(h->device));
@@ -1397,9 +1401,10 @@ static int32_t query_run(RtxSceneHandle_ *h, const QueryRequest &req, void *stre
         }
         return RTX_OK;
     }
-    if (pick) {                              // the pick buffer: one band of all rows, ray i = pixel i (row-major, row 0 = the reference's)
-        if (int32_t rc = ensure_tables(h, req.width, req.height, 0u, 1u, 1u, req.height, stream)) return rc;
-        RowsView rv = rows_view(h, req.width, req.height, 0u, 1u, 1u, req.height, 0u, req.width * req.height);
+    if (pick) {                              // the pick buffer: one band of all rows, ray i = pixel i (row-major, row 0 = the reference's);
+                                             // the feature buffers: the caller's band, entry i = its local pixel i
+        if (int32_t rc = ensure_tables(h, req.width, req.height, req.row_begin, req.row_stride, req.row_block, req.n_rows, stream)) return rc;
+        RowsView rv = rows_view(h, req.width, req.height, req.row_begin, req.row_stride, req.row_block, req.n_rows, 0u, (uint32_t)n);
         rv.n_samples = 1; rv.n_rays = n;
         RTX_HIP_CHECK(hipMemcpyAsync(h->d_rv, &rv, sizeof(RowsView), hipMemcpyHostToDevice, stream));   // pageable: staged before return
     }
@@ -1420,6 +1425,7 @@ static int32_t query_run(RtxSceneHandle_ *h, const QueryRequest &req, void *stre
     qa.n = n; qa.mode = req.mode;
     if (req.mode == kQueryAnyHit) { qa.occluded = req.occluded; qa.t_max = req.t_max; }
     else if (req.mode == kQueryPaths) { qa.rgb = req.rgb; qa.ids = reinterpret_cast<const unsigned long long *>(req.ids); qa.segments = req.segments; }
+    else if (req.mode == kQueryFeatures) qa.features = reinterpret_cast<QueryFeatures *>(req.features);
     else qa.hits = reinterpret_cast<QueryHit *>(req.hits);
     if (stats) RTX_HIP_CHECK(hipEventRecord(h->ev[0], stream));
     RTX_HIP_CHECK(launch_query_closest(h->d_sv, h->sv, qa, walk, spill_entries ? reinterpret_cast<uint32_t *>(h->state) : nullptr,
@@ -1433,6 +1439,7 @@ static int32_t query_run(RtxSceneHandle_ *h, const QueryRequest &req, void *stre
         if (int32_t rc = read_counters(h->counters, c)) return rc;
         stats->segments = c.segments; stats->exact_tests = c.exact; stats->filter_tests = c.filter; stats->box_tests = c.box;
         if (req.mode == kQueryPaths) stats->primary_rays = n;
+        if (req.mode == kQueryFeatures) stats->primary_rays = n * h->cfg.rays_per_pixel;
         stats->trace_ms = ms;
         stats->trace_launches = 1;
         stats->kernel = walk ? RTX_KERNEL_BVH : RTX_KERNEL_EXACT;
@@ -2031,8 +2038,40 @@ int32_t rtx_scene_primary_hits(RtxSceneHandle h, uint32_t width, uint32_t height
     if (!d_hits) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_primary_hits: null hits");
     if (n >= 0xFFFFFFFFull) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_primary_hits: more than 2^32 pixels");
     QueryRequest req;
-    req.width = width; req.height = height; req.n = n; req.hits = d_hits;
+    req.width = width; req.height = height; req.n_rows = height; req.n = n; req.hits = d_hits;
     return query_run(h, req, stream, stats);
+}
+
+// The feature buffers of a band (rtx_render_blocks' partition): validation that touches no device, then one query_run.
+static int32_t pixel_features_band(RtxSceneHandle h, const char *who, uint32_t width, uint32_t height, uint32_t block_rows, uint32_t part,
+                                   uint32_t n_parts, RtxPixelFeatures *d_features, void *stream, RtxStats *stats)
+{
+    const std::string w(who);
+    if (!h) return fail(RTX_ERR_INVALID_ARGUMENT, w + ": null scene");
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (block_rows == 0 || n_parts == 0 || part >= n_parts) return fail(RTX_ERR_INVALID_ARGUMENT, w + ": bad partition");
+    if ((uint64_t)block_rows * n_parts > 0xFFFFFFF0ull) return fail(RTX_ERR_INVALID_ARGUMENT, w + ": block_rows * n_parts overflows");
+    const uint32_t n_rows = blocks_row_count(height, block_rows, part, n_parts);
+    const uint64_t n = (uint64_t)n_rows * width;
+    if (n == 0) return RTX_OK;
+    if (!d_features) return fail(RTX_ERR_INVALID_ARGUMENT, w + ": null output");
+    if (n > 0xFFFFFFF0ull) return fail(RTX_ERR_INVALID_ARGUMENT, w + ": more than 2^32 pixels per call");
+    if (h->cfg.rays_per_pixel > 0xFFFFFFFFull) return fail(RTX_ERR_INVALID_ARGUMENT, w + ": rays_per_pixel must be below 2^32");
+    QueryRequest req;
+    req.mode = kQueryFeatures; req.width = width; req.height = height; req.n = n; req.features = d_features;
+    req.row_begin = part * block_rows; req.row_stride = n_parts * block_rows; req.row_block = block_rows; req.n_rows = n_rows;
+    return query_run(h, req, stream, stats);
+}
+
+int32_t rtx_scene_pixel_features_blocks(RtxSceneHandle h, uint32_t width, uint32_t height, uint32_t block_rows, uint32_t part, uint32_t n_parts,
+                                        RtxPixelFeatures *d_features, void *stream, RtxStats *stats)
+{
+    return pixel_features_band(h, "rtx_scene_pixel_features_blocks", width, height, block_rows, part, n_parts, d_features, stream, stats);
+}
+
+int32_t rtx_scene_pixel_features(RtxSceneHandle h, uint32_t width, uint32_t height, RtxPixelFeatures *d_features, void *stream, RtxStats *stats)
+{
+    return pixel_features_band(h, "rtx_scene_pixel_features", width, height, 8u, 0u, 1u, d_features, stream, stats);
 }
 
 }  // extern "C"
@@ -2109,6 +2148,21 @@ int32_t rtx_trace_paths(const RtxScene *scene, const RtxRay *rays, const uint64_
                                  { ids, nullptr, n * 2 * sizeof(uint64_t), (void **)&req.ids },
                                  { nullptr, segments, n * sizeof(uint32_t), (void **)&req.segments } };
     return query_once(scene, "rtx_trace_paths", req, arrays, 4);
+}
+
+int32_t rtx_pixel_features(const RtxScene *scene, uint32_t width, uint32_t height, RtxPixelFeatures *features)
+{
+    if (int32_t rc = check_scene_args(scene, "rtx_pixel_features")) return rc;
+    const uint64_t n = (uint64_t)width * height;
+    if (n == 0) return RTX_OK;
+    if (!features) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_pixel_features: null output");
+    if (n > 0xFFFFFFF0ull) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_pixel_features: more than 2^32 pixels per call");
+    if (scene->config.rays_per_pixel > 0xFFFFFFFFull) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_pixel_features: rays_per_pixel must be below 2^32");
+    QueryRequest req;                                 // rtx_scene_pixel_features' band: blocks of 8 rows, part 0 of 1 = every row in order
+    req.mode = kQueryFeatures; req.width = width; req.height = height; req.n = n;
+    req.row_begin = 0u; req.row_stride = 8u; req.row_block = 8u; req.n_rows = height;
+    const HostArray arrays[] = { { nullptr, features, n * sizeof(RtxPixelFeatures), (void **)&req.features } };
+    return query_once(scene, "rtx_pixel_features", req, arrays, 1);
 }
 
 }  // extern "C"

@@ -156,29 +156,34 @@ hipError_t launch_quantize_values(const double *rgb, uint8_t *rgb8, uint32_t wid
 
 // ---- ray queries (rtx_query.hip): closest_object for caller rays or for the pick buffer's zero-offset primary rays, or -- the
 // any-hit mode, a launch-uniform switch of the same kernel -- whether any object lies before a per-ray distance limit, or -- the
-// path mode, a third switch -- render_ray's colour of the path that starts with the ray
+// path mode, a third switch -- render_ray's colour of the path that starts with the ray, or -- the feature mode, a fourth -- the
+// first-hit albedo / emission / normal / depth of every pixel of a band over render_pixel's own lens-jittered rays
 struct QueryRay { double position[3], direction[3]; };                                      // = RtxRay (include/rtx_hip.h)
 struct QueryHit { double position[3], normal[3], distance; long long object; };            // = RtxHit
-static_assert(sizeof(QueryRay) == 48 && sizeof(QueryHit) == 64, "QueryRay / QueryHit");
+struct QueryFeatures { double albedo[3], emission[3], normal[3], depth, coverage; long long object; };   // = RtxPixelFeatures
+static_assert(sizeof(QueryRay) == 48 && sizeof(QueryHit) == 64 && sizeof(QueryFeatures) == 96, "QueryRay / QueryHit / QueryFeatures");
 struct QueryArgs {
-    const QueryRay *rays;          // n rays (null in the pick form)
-    const RowsView *rv;            // the pick form: the frame's RowsView (one band of all rows), ray i = pixel i; else null
+    const QueryRay *rays;          // n rays (null in the pick form and the feature mode)
+    const RowsView *rv;            // the pick form: the frame's RowsView (one band of all rows), ray i = pixel i; the feature mode: the
+                                   // band's RowsView (row_begin, row_stride, row_block as render_band sets them), entry i = local pixel i; else null
     union {                        // the answers, by mode (the modes share the slots: one kernel argument layout for the three loops)
         QueryHit *hits;            // closest hits: n records
         uint8_t *occluded;         // any-hit: n bytes, 1 / 0
         double *rgb;               // paths: 3 n doubles, rgb[3 i .. 3 i + 2] = resulting_color of the path that starts with ray i
+        QueryFeatures *features;   // features: n records, one per local pixel of the band (the lane that owns the pixel parks its sums here)
     };
     unsigned long long n;
     uint32_t walk;                 // 0: every ray is swept (RTX_KERNEL_EXACT / no usable tree); set by the launcher
     uint32_t mode;                 // kQueryClosest; kQueryAnyHit: occluded[i] = some object's distance is normal, positive and < t_max[i];
-                                   // kQueryPaths: render_ray (scene.rs:223-242) from ray i
+                                   // kQueryPaths: render_ray (scene.rs:223-242) from ray i; kQueryFeatures: the first hits of
+                                   // sv.rays_per_pixel gen_primary rays per pixel, folded (query_feature_loop)
     union {
         const double *t_max;       // any-hit: n limits, compared as given (null: +inf for every ray)
         const unsigned long long *ids;   // paths: n (pixel index, sample index) pairs that key the RNG (null: (i, 0))
     };
     uint32_t *segments;            // paths: n closest_object counts, or null
 };
-constexpr uint32_t kQueryClosest = 0u, kQueryAnyHit = 1u, kQueryPaths = 2u;
+constexpr uint32_t kQueryClosest = 0u, kQueryAnyHit = 1u, kQueryPaths = 2u, kQueryFeatures = 3u;
 uint32_t query_tree_kind(const SceneView &sv);        // 0 no walk, 1 sphere tree, 2 a tree that holds triangles
 uint32_t query_spill_entries(const SceneView &sv);    // HBM stack entries per lane a walk may need beyond its LDS rows
 size_t query_spill_bytes(uint32_t entries, int n_cus);

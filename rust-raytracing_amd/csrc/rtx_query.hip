@@ -29,6 +29,11 @@
 // The path mode (QueryArgs.mode, rtx_scene_trace_paths; DESIGN.md "Path queries"): render_ray for the caller's rays -- the third
 // launch-uniform loop of the same two instances.  A lane owns a path and is refilled at the segment boundary; a segment is the
 // closest-hit loop's body (query_closest_ray) followed by advance_and_shade, with the render's draws 6 + 2b, 7 + 2b for bounce b.
+//
+// The feature mode (QueryArgs.mode, rtx_scene_pixel_features; DESIGN.md "Pixel features"): the denoiser's guide buffers -- the fourth
+// launch-uniform loop of the same two instances.  A lane owns a PIXEL of the band: for every sample it builds render_pixel's own
+// lens-jittered ray (gen_primary), asks query_closest_ray, and adds the winner's colours, normal and distance to the sums, which live in
+// the pixel's output record, not in registers.
 #include "rtx_launch.h"
 #include "rtx_mesh_step.h"
 #include "rtx_wavefront.h"
@@ -443,6 +448,69 @@ __device__ __forceinline__ void query_path_loop(const SceneView &sv, const Query
     }
 }
 
+// ---- the feature mode ----------------------------------------------------------------------------------------------------------
+// Per pixel of the band, over the S = rays_per_pixel rays render_pixel builds for it (scene.rs:196-207: gen_primary with the sample
+// index s, so the RNG key and the draws 0..5 are the render's): the sums of the first hits' base_color, emission_color, normal_at and
+// distance, left folds from +0.0 in sample order (a miss adds nothing), then sum / S -- the render's fold (iter_ops.rs:4-8) -- the
+// distance over the samples that hit, hits / S, and sample 0's winner.  A lane owns a pixel, entry i of the launch = local pixel i of
+// the band, row-major like the pick form (a wave's 64 lanes are a 64 x 1 strip of one sample at a time, as the rows of a caller's
+// primary rays are in the path mode; the 8x8 tiles of ray_index_to_pixel_tiled were not measured against it).  Every lane runs the
+// same S samples, so no lane is refilled inside a pixel.  The ten f64 sums are parked in the pixel's own output record -- the lane
+// owns it -- and read, added to and written back after each sample that hit: held across the walk they would be 20 VGPRs more than
+// the 128 this kernel may have.  Only the hit count stays in a register.  A loop of its own, entered once per launch: the other
+// loops carry none of its arguments or state.
+template <bool TRIS>
+__device__ __forceinline__ void query_feature_loop(const SceneView &sv, const QueryArgs &qa, const float4 *__restrict__ nodes, const LeafArrays &la,
+                                                   const MeshArrays &ma, uint32_t *ls, uint32_t *lq, uint32_t tid, uint32_t *__restrict__ spill,
+                                                   uint32_t spill_entries, size_t spill_stride, size_t glane, unsigned long long *__restrict__ head,
+                                                   unsigned long long &segs, unsigned long long &exact, unsigned long long &box_tests,
+                                                   unsigned long long &leaf_filters)
+{
+    const unsigned long long grab = wf_grab_size(qa.n);
+    const uint32_t n_samples = (uint32_t)sv.rays_per_pixel;             // (the host refuses 2^32 and more)
+    const RowsView &rv = *qa.rv;
+    WfChunk ch{0ull, 0ull, false};
+    for (;;) {
+        unsigned long long i = 0;
+        const bool mine = wf_take(ch, head, grab, qa.n, true, i);
+        if (ch.drained && __ballot(mine) == 0ull) break;
+        if (!mine) continue;
+        QueryFeatures *const out = qa.features + i;
+        for (int c = 0; c < 3; ++c) out->albedo[c] = out->emission[c] = out->normal[c] = 0.0;
+        out->depth = 0.0;
+        out->object = -1;
+        uint32_t hits = 0;
+        for (uint32_t s = 0; s < n_samples; ++s) {
+            RayState r;
+            gen_primary(sv, rv, (uint32_t)i, s, r);
+            const RayX rx = make_rayx(r.pos, r.dir);
+            Hit h;
+            ++segs;
+            query_closest_ray<TRIS>(sv, qa.walk, nodes, la, ma, r.pos, r.dir, rx, h, ls, lq, tid, spill, spill_entries, spill_stride, glane, exact,
+                                    box_tests, leaf_filters);
+            if (h.id != kNone) {
+                const MaterialX m = sv.materials[h.id];
+                const V3 nrm = normal_at(sv, h, vadd(r.pos, vmuls(r.dir, h.t)));             // scene.rs:234, object.rs:37-39
+                out->albedo[0] += m.base_color.x; out->albedo[1] += m.base_color.y; out->albedo[2] += m.base_color.z;
+                out->emission[0] += m.emission_color.x; out->emission[1] += m.emission_color.y; out->emission[2] += m.emission_color.z;
+                out->normal[0] += nrm.x; out->normal[1] += nrm.y; out->normal[2] += nrm.z;
+                out->depth += h.t;
+                if (s == 0u) out->object = (long long)h.id;
+                ++hits;
+            }
+            __asm__ volatile("" ::: "memory");                           // the sums stay in the record: no promotion to registers across the walk
+        }
+        const double ds = (double)n_samples;                             // sum / len (iter_ops.rs:4-8): a division; 0 / 0 = NaN when S == 0
+        for (int c = 0; c < 3; ++c) {
+            out->albedo[c] = out->albedo[c] / ds;
+            out->emission[c] = out->emission[c] / ds;
+            out->normal[c] = out->normal[c] / ds;
+        }
+        out->depth = hits != 0u ? out->depth / (double)hits : __builtin_inf();
+        out->coverage = (double)hits / ds;
+    }
+}
+
 template <bool TRIS>
 __global__ __launch_bounds__(kBvhThreads, kQueryWaves) void query_closest_kernel(const SceneView *__restrict__ svp, const QueryArgs qa,
                                                                                  const float4 *__restrict__ nodes, const LeafArrays la,
@@ -470,6 +538,9 @@ __global__ __launch_bounds__(kBvhThreads, kQueryWaves) void query_closest_kernel
     else if (qa.mode == kQueryPaths)                                     // launch-uniform: so has the path mode
         query_path_loop<TRIS>(sv, qa, nodes, la, ma, ls, lq, tid, spill, spill_entries, spill_stride, glane, head, segs, exact, box_tests,
                               leaf_filters);
+    else if (qa.mode == kQueryFeatures)                                  // launch-uniform: and the feature mode
+        query_feature_loop<TRIS>(sv, qa, nodes, la, ma, ls, lq, tid, spill, spill_entries, spill_stride, glane, head, segs, exact, box_tests,
+                                 leaf_filters);
     else for (;;) {
         unsigned long long i = 0;
         const bool mine = wf_take(ch, head, grab, qa.n, true, i);         // (every lane of the wave is here: lane 0 takes the chunk)

@@ -95,6 +95,20 @@ pub struct RtxHit {
     pub object: i64,
 }
 
+/// One pixel of the denoising guide buffers (`rtx_scene_pixel_features`): the first hits of `render_pixel`'s own rays, folded in
+/// sample order -- mean `base_color`, `emission_color`, `normal_at` (not renormalised), mean distance of the samples that hit (+inf:
+/// none), hits / rays_per_pixel, and sample 0's winner in `Scene.objects` (-1: it missed).  96 bytes.
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct RtxPixelFeatures {
+    pub albedo: [f64; 3],
+    pub emission: [f64; 3],
+    pub normal: [f64; 3],
+    pub depth: f64,
+    pub coverage: f64,
+    pub object: i64,
+}
+
 #[repr(C)]
 pub struct RtxSceneHandleOpaque {
     _private: [u8; 0],
@@ -127,6 +141,9 @@ extern "C" {
     pub fn rtx_any_hits(scene: *const RtxScene, rays: *const RtxRay, t_max: *const f64, n: u64, occluded: *mut u8) -> i32;
     pub fn rtx_scene_trace_paths(scene: RtxSceneHandle, d_rays: *const RtxRay, d_ids: *const u64, n: u64, d_rgb: *mut f64, d_segments: *mut u32, stream: *mut c_void, stats: *mut RtxStats) -> i32;
     pub fn rtx_trace_paths(scene: *const RtxScene, rays: *const RtxRay, ids: *const u64, n: u64, rgb: *mut f64, segments: *mut u32) -> i32;
+    pub fn rtx_scene_pixel_features(scene: RtxSceneHandle, width: u32, height: u32, d_features: *mut RtxPixelFeatures, stream: *mut c_void, stats: *mut RtxStats) -> i32;
+    pub fn rtx_scene_pixel_features_blocks(scene: RtxSceneHandle, width: u32, height: u32, block_rows: u32, part: u32, n_parts: u32, d_features: *mut RtxPixelFeatures, stream: *mut c_void, stats: *mut RtxStats) -> i32;
+    pub fn rtx_pixel_features(scene: *const RtxScene, width: u32, height: u32, features: *mut RtxPixelFeatures) -> i32;
     pub fn rtx_quantize_image_device(d_rgb: *const f64, width: u32, height: u32, d_rgb8: *mut u8, device: i32, stream: *mut c_void) -> i32;
 }
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Closest-hit, any-hit and path query rates (rtx_scene_closest_hits / rtx_scene_primary_hits / rtx_scene_any_hits /
-rtx_scene_trace_paths), in Mrays/s (the path legs: Msegments/s) from RtxStats.trace_ms, on the scenes of the
+"""Closest-hit, any-hit, path and feature query rates (rtx_scene_closest_hits / rtx_scene_primary_hits / rtx_scene_any_hits /
+rtx_scene_trace_paths / rtx_scene_pixel_features), in Mrays/s (the path legs: Msegments/s) from RtxStats.trace_ms, on the scenes of the
 benchmark's C2 (10k spheres), C3 (100k triangles) and J1 (5k spheres + 50k triangles: a joint tree), built with scenes.py's
 generators and the same parameters:
 
@@ -14,6 +14,10 @@ generators and the same parameters:
   paths_1seg   the same rays at max_bounces = 0: one segment per path -- against `incoherent`, the price of the shade and the refill
   paths_pick   the 1920x1080 zero-offset primary rays (built on the host from the camera) with ids (pixel, 0)
   render_pick  rtx_render_rows of the same frame at 1 spp with both offsets 0: paths_pick's segments, with the render's tile packets
+  paths_primary  paths_pick's rays and ids at max_bounces = 0: one segment per pixel -- what a `features` sample does, plus reading a
+               48-byte ray and writing 24 bytes per ray
+  features     rtx_scene_pixel_features of the 1920x1080 frame with the bench camera and the default offsets, at 1 and at 16 samples
+               per pixel (two lines): one segment per (pixel, sample), the ray built on the device, one 96-byte record per pixel
 
     tools/query_rate.py [--rays 24] [--scenes C2,C3,J1] [--reps 3] [--exact-rays 20] [--legs incoherent,pick,...]
 
@@ -74,7 +78,8 @@ def primary_rays(rtx, cam, width, height):
     return np.broadcast_to(np.array(list(c.position), dtype=np.float64), d.shape), d
 
 
-LEGS = ("incoherent", "pick", "exact", "any", "any_short", "any_aimed", "paths", "paths_1seg", "paths_pick", "render_pick")
+LEGS = ("incoherent", "pick", "exact", "any", "any_short", "any_aimed", "paths", "paths_1seg", "paths_pick", "render_pick", "paths_primary",
+        "features")
 
 
 def main():
@@ -102,15 +107,17 @@ def main():
             legs = [l for l in legs if not l.startswith("any")]
         if not hasattr(probe, "rtx_scene_trace_paths"):
             legs = [l for l in legs if not l.startswith("paths")]
+        if not hasattr(probe, "rtx_scene_pixel_features"):
+            legs = [l for l in legs if l != "features"]
     for name in args.scenes.split(","):
         objs = SCENES[name](scenes)
         o, d = incoherent(objs, n)
         rays = rtx.make_rays(o, d)
         d_rays = torch.from_numpy(rays.view(np.uint8)).to(dev)
-        d_hits = torch.empty(n * 64, dtype=torch.uint8, device=dev)
-        d_aimed = d_lim = d_prim = d_prim_ids = None
         W, H = 1920, 1080
-        if "paths_pick" in legs:
+        d_hits = torch.empty(max(n * 64, W * H * 96), dtype=torch.uint8, device=dev)      # (the frame legs' records fit whatever --rays)
+        d_aimed = d_lim = d_prim = d_prim_ids = None
+        if "paths_pick" in legs or "paths_primary" in legs:
             d_prim = torch.from_numpy(rtx.make_rays(*primary_rays(rtx, scenes.CAMERA, W, H)).view(np.uint8)).to(dev)
             d_prim_ids = torch.stack([torch.arange(W * H, dtype=torch.int64, device=dev), torch.zeros(W * H, dtype=torch.int64, device=dev)], dim=1).contiguous()
         if "any_aimed" in legs:
@@ -126,13 +133,26 @@ def main():
 
         for leg in legs:
             kernel = rtx.RTX_KERNEL_EXACT if leg == "exact" else rtx.RTX_KERNEL_AUTO
-            cfg = rtx.Config(rays_per_pixel=1, kernel=kernel, max_bounces=0 if leg == "paths_1seg" else 10)
+            cfg = rtx.Config(rays_per_pixel=1, kernel=kernel, max_bounces=0 if leg in ("paths_1seg", "paths_primary") else 10)
+            if leg == "features":
+                k = W * H
+                for spp in (1, 16):
+                    hnd = rtx.Scene.from_packed(cfg.with_rays_per_pixel(spp), rtx.Camera(*scenes.CAMERA), objs).upload(0)
+                    st = best(lambda: hnd.pixel_features(W, H, d_hits.data_ptr()))           
+                    f = d_hits[:k * 96].cpu().numpy().view(rtx.FEATURE_DTYPE)
+                    print(json.dumps({"scene": name, "leg": leg, "spp": spp, "rays": int(st.segments), "trace_ms": round(st.trace_ms, 3),
+                                      "mrays_per_s": round(st.segments / (st.trace_ms * 1e-3) / 1e6, 1), "kernel": int(st.kernel),
+                                      "exact_tests_per_ray": round(st.exact_tests / st.segments, 2),
+                                      "box_tests_per_ray": round(st.box_tests / st.segments, 2),
+                                      "coverage": round(float(f["coverage"].mean()), 4)}), flush=True)
+                    hnd.close()
+                continue
             if leg == "render_pick":
                 cfg = cfg.with_focal_offset(0.0).with_non_focal_offset(0.0)
             hnd = rtx.Scene.from_packed(cfg, rtx.Camera(*scenes.CAMERA), objs).upload(0)
             if leg.startswith("paths") or leg == "render_pick":
                 d_rgb = d_hits.view(torch.float64)                       # (n * 8 doubles: room for 3 per ray or pixel)
-                if leg == "paths_pick":
+                if leg in ("paths_pick", "paths_primary"):
                     k = W * H
                     st = best(lambda: hnd.trace_paths(d_prim.data_ptr(), d_prim_ids.data_ptr(), k, d_rgb.data_ptr()))
                 elif leg == "render_pick":
