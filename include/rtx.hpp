@@ -384,6 +384,17 @@ public:
                                 d_out_rgb, hip_stream, &st));
         return st;
     }
+    // progressive sampling: the samples [sample_begin, sample_begin + n_samples) of every pixel of the same band ADDED to the running
+    // sums d_sum and d_sum_sq (or nullptr) -- band_rows(...) * width * 3 doubles each, zero bytes before the first call; ranges that tile
+    // [0, S) in order leave d_sum / S == render_blocks at rays_per_pixel = S, bit for bit; (8, 0, 1) is the full frame.  With stats =
+    // nullptr the call returns once the work is enqueued
+    void render_blocks_accumulate(std::size_t width, std::size_t height, std::size_t block_rows, std::size_t part, std::size_t n_parts,
+                                  std::uint64_t sample_begin, std::uint64_t n_samples, double *d_sum, double *d_sum_sq = nullptr,
+                                  void *hip_stream = nullptr, RtxStats *stats = nullptr)
+    {
+        check(rtx_render_blocks_accumulate(h_, (uint32_t)width, (uint32_t)height, (uint32_t)block_rows, (uint32_t)part, (uint32_t)n_parts,
+                                           sample_begin, n_samples, d_sum, d_sum_sq, hip_stream, stats));
+    }
     void set_scratch_limit(std::uint64_t bytes) { check(rtx_scene_set_scratch_limit(h_, bytes)); }
     // closest_object for n rays of DEVICE memory (d_rays[n] -> d_hits[n], not overlapping), on the HIP stream it names; with
     // stats = nullptr the call returns once the work is enqueued
@@ -403,6 +414,13 @@ public:
                      void *hip_stream = nullptr, RtxStats *stats = nullptr)
     {
         check(rtx_scene_trace_paths(h_, d_rays, d_ids, n, d_rgb, d_segments, hip_stream, stats));
+    }
+    // sparse samples of the render: entry i is sample d_ids[2 i + 1] of pixel d_ids[2 i] (= y * width + x) of the width x height frame,
+    // bit for bit the render's; d_rgb[3 n], d_segments (or nullptr) as trace_paths.  An entry outside the frame: NaN, 0 segments
+    void trace_samples(std::size_t width, std::size_t height, const uint64_t *d_ids, std::size_t n, double *d_rgb,
+                       uint32_t *d_segments = nullptr, void *hip_stream = nullptr, RtxStats *stats = nullptr)
+    {
+        check(rtx_scene_trace_samples(h_, (uint32_t)width, (uint32_t)height, d_ids, n, d_rgb, d_segments, hip_stream, stats));
     }
     // the pick buffer: d_hits[height][width] = the hit of each pixel's primary ray without the focal / non-focal offsets
     void primary_hits(std::size_t width, std::size_t height, RtxHit *d_hits, void *hip_stream = nullptr, RtxStats *stats = nullptr)

@@ -344,6 +344,33 @@ int32_t rtx_render_blocks(RtxSceneHandle scene, uint32_t width, uint32_t height,
                           uint32_t block_rows, uint32_t part, uint32_t n_parts,
                           double *d_out_rgb, void *stream, RtxStats *stats);
 
+/*
+ * Progressive sampling: the samples [sample_begin, sample_begin + n_samples) of every pixel of rtx_render_blocks' band (the same
+ * partition, the same row order; the rows form is block_rows = 1, the full frame (8, 0, 1)), ADDED to the caller's running sums.
+ * d_sum and d_sum_sq (may be NULL) are DEVICE buffers of rtx_blocks_row_count(...) * width * 3 doubles, read and written; they must
+ * not overlap.  For every pixel p of the band and s = sample_begin, ..., in order, with c = the render's sample s of that pixel
+ * (render_pixel's ray for the key rng_key(seed, y * width + x, s), then render_ray):
+ *     d_sum[3 p + k]    = d_sum[3 p + k] + c_k
+ *     d_sum_sq[3 p + k] = d_sum_sq[3 p + k] + c_k * c_k        (a rounded multiply, then a rounded add: never fused)
+ * Nothing is divided and RtxConfig.rays_per_pixel is not read; every other field of the handle's config, and its camera, is read as a
+ * render reads it.
+ *  - The contract with the full render: with buffers that start as all-zero bytes and calls whose ranges tile [0, S) in increasing
+ *    order, d_sum / (double)S is the frame rtx_render_blocks gives at rays_per_pixel = S, bit for bit -- for any split of the range,
+ *    any scratch limit (sample batches inside a call) and any kernel id.  It needs a buffer that holds zero bytes or an earlier call's
+ *    output: the fold skips zero samples (which leave a sum that started at +0.0 unchanged), so a caller's -0.0 stays -0.0 where the
+ *    full fold would make it +0.0.
+ *  - n_samples == 0, and a scene without objects (every sample is zero): nothing is touched.
+ *  - sample_begin + n_samples > 2^32 - 1, a NULL d_sum, 2^32 - 16 pixels per call or more: RTX_ERR_INVALID_ARGUMENT.
+ *  - The tile lists of the primary rays are rebuilt by every call (the camera may have changed since the previous range).
+ * Streams, stats == NULL asynchrony, the watchdog word and RtxConfig.tuning follow rtx_render_blocks (RTX_TUNE_HALVES is not used: the
+ * call takes the batch path).  stats: primary_rays = pixels * n_samples and the render's fields.  (DESIGN.md "Progressive and
+ * adaptive sampling".)
+ */
+int32_t rtx_render_blocks_accumulate(RtxSceneHandle scene, uint32_t width, uint32_t height,
+                                     uint32_t block_rows, uint32_t part, uint32_t n_parts,
+                                     uint64_t sample_begin, uint64_t n_samples,
+                                     double *d_sum, double *d_sum_sq, void *stream, RtxStats *stats);
+
 /* -- ray queries on an uploaded scene ----------------------------------------------------------
  * Each answer is exactly what the reference's closest_object(position, direction) returns over Scene.objects (the first minimal
  * distance wins, is_normal && is_sign_positive filter), filled in as RtxHit describes; a scene without objects hits nothing.
@@ -416,6 +443,25 @@ int32_t rtx_scene_trace_paths(RtxSceneHandle scene, const RtxRay *d_rays, const 
 /* One-shot host form (upload to device 0, trace, copy back), as rtx_closest_hits.  rays / ids (or NULL) / rgb / segments (or NULL):
  * HOST arrays. */
 int32_t rtx_trace_paths(const RtxScene *scene, const RtxRay *rays, const uint64_t *ids, uint64_t n, double *rgb, uint32_t *segments);
+
+/* Sparse samples of the render: entry i names (pixel, sample) = (d_ids[2 i], d_ids[2 i + 1]), pixel = y * width + x in the full
+ * width x height frame, and gets that sample of rtx_render bit for bit -- what an adaptive sampler traces where the variance is.
+ *  - The kernel builds render_pixel's own ray (scene.rs:196-207: the key rng_key(seed, pixel, sample), draws 0..5, the handle's
+ *    non_focal_offset, focal_offset, focal_length and camera), then runs render_ray exactly as rtx_scene_trace_paths does (draws from
+ *    6 on): d_rgb[3 i .. 3 i + 2] = resulting_color, d_segments[i] (d_segments may be NULL) = its closest_object calls.
+ *  - The result does not depend on n, on the entry's place in the batch or on its neighbours; repeated ids are allowed.  Adding a
+ *    pixel's samples in sample order to the sums of rtx_render_blocks_accumulate continues that fold.
+ *  - An entry with pixel >= width * height or sample >= 2^32 gets NaN colour and 0 segments; nothing is traced for it.
+ *  - A scene without objects: one memset of d_rgb (and of d_segments), no launch, the ids are not read -- as rtx_scene_trace_paths.
+ * d_ids: 2 n uint64 (required); d_rgb: 3 n doubles; d_segments: n uint32 or NULL.  DEVICE arrays, pairwise non-overlapping; n < 2^32;
+ * 0 < width * height < 2^32 - 16.  Streams, stats == NULL asynchrony, RTX_KERNEL_EXACT, RtxConfig.tuning bits of RTX_TUNE_LAB_MASK and
+ * stats: as rtx_scene_trace_paths.  (DESIGN.md "Progressive and adaptive sampling".) */
+int32_t rtx_scene_trace_samples(RtxSceneHandle scene, uint32_t width, uint32_t height, const uint64_t *d_ids, uint64_t n,
+                                double *d_rgb, uint32_t *d_segments, void *stream, RtxStats *stats);
+
+/* One-shot host form (upload to device 0, trace, copy back), as rtx_closest_hits.  ids / rgb / segments (or NULL): HOST arrays. */
+int32_t rtx_trace_samples(const RtxScene *scene, uint32_t width, uint32_t height, const uint64_t *ids, uint64_t n, double *rgb,
+                          uint32_t *segments);
 
 /* Denoising guide buffers: the per-pixel first-hit albedo, emission, normal and depth (the "auxiliary feature" / AOV buffers a
  * denoiser reads next to the beauty frame), taken over the SAME lens-jittered primary rays as the render, so that depth-of-field blur
@@ -512,6 +558,14 @@ int32_t rtx_debug_store_samples(const double *rgb, const uint64_t *slots, uint64
 int32_t rtx_debug_resolve(const double *records, const uint32_t *mask, uint32_t width, uint32_t n_rows, uint32_t tiles_x,
                           uint32_t n_samples, uint64_t rays_per_pixel, int32_t first, int32_t last, double *acc, uint64_t acc_doubles,
                           double *out, uint64_t out_doubles);
+
+/* rtx_debug_resolve_moments: launch_resolve as rtx_render_blocks_accumulate calls it -- first = last = 0, the caller's sums as the
+ * accumulator, a squares buffer -- on the caller's host arrays: sum[3 p + c] += the set-bit records of pixel p in sample order,
+ * sum_sq[3 p + c] += their squares (sum_sq may be null: the sums alone).  records, mask, width, n_rows, tiles_x, n_samples as
+ * rtx_debug_resolve, the NaN records under set bits behind the caller's data included; sum / sum_sq (at least 3 * width * n_rows doubles)
+ * are read and written back whole. */
+int32_t rtx_debug_resolve_moments(const double *records, const uint32_t *mask, uint32_t width, uint32_t n_rows, uint32_t tiles_x,
+                                  uint32_t n_samples, double *sum, uint64_t sum_doubles, double *sum_sq, uint64_t sum_sq_doubles);
 
 /* rtx_debug_gather: the epilogues of rtx_render_devices / rtx_render_to_image_devices on a caller's staging buffer.  form 0:
  * launch_deinterleave, parts = n bands of cap_rows rows of width * 3 doubles (band p = the blocks of `block` image rows p, p + n, ... in

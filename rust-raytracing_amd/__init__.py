@@ -515,6 +515,35 @@ class SceneHandle:
                                               C.byref(stats) if want_stats else None))
         return stats if want_stats else None
 
+    def render_accumulate(self, width, height, sample_begin, n_samples, d_sum_ptr, d_sum_sq_ptr=None, block_rows=8, part=0, n_parts=1,
+                          stream=None, want_stats=True):
+        """Progressive sampling (rtx_render_blocks_accumulate): the samples [sample_begin, sample_begin + n_samples) of every pixel of
+        the band of part `part` of `n_parts` (default: the full frame) are added to the running sums at the device addresses d_sum_ptr
+        and d_sum_sq_ptr (or None: no second moments) -- rows * width * 3 doubles each, zero bytes before the first call.  Ranges that
+        tile [0, S) in order leave sum / S == the render at rays_per_pixel = S, bit for bit."""
+        stats = abi.RtxStats()
+        self._check(self._lib.rtx_render_blocks_accumulate(self._h, int(width), int(height), int(block_rows), int(part), int(n_parts),
+                                                           int(sample_begin), int(n_samples), C.c_void_p(int(d_sum_ptr)) if d_sum_ptr else None,
+                                                           C.c_void_p(int(d_sum_sq_ptr)) if d_sum_sq_ptr else None,
+                                                           C.c_void_p(int(stream)) if stream else None, C.byref(stats) if want_stats else None))
+        return stats if want_stats else None
+
+    def trace_samples(self, width, height, d_ids_ptr, n, d_rgb_ptr, d_segments_ptr=None, stream=None, want_stats=True):
+        """Sparse samples of the render (rtx_scene_trace_samples): entry i is sample ids[2 i + 1] of pixel ids[2 i] (= y * width + x) of
+        the width x height frame, bit for bit the render's.  d_ids_ptr / d_rgb_ptr / d_segments_ptr are device addresses of n uint64
+        pairs, 3 n doubles and n uint32 (or None).  An entry outside the frame or with a sample index >= 2^32: NaN, 0 segments."""
+        stats = abi.RtxStats()
+        self._check(self._lib.rtx_scene_trace_samples(self._h, int(width), int(height), C.c_void_p(int(d_ids_ptr)) if d_ids_ptr else None, int(n),
+                                                      C.c_void_p(int(d_rgb_ptr)) if d_rgb_ptr else None,
+                                                      C.c_void_p(int(d_segments_ptr)) if d_segments_ptr else None,
+                                                      C.c_void_p(int(stream)) if stream else None, C.byref(stats) if want_stats else None))
+        return stats if want_stats else None
+
+    def progressive(self, width, height, moments=True):
+        """A Progressive accumulator of a width x height frame on this handle: add(n) more samples everywhere, refine(pixels, n) more
+        on chosen pixels, mean() / variance() at any time."""
+        return Progressive(self, width, height, moments)
+
     def closest_hits(self, d_rays_ptr, n, d_hits_ptr, stream=None, want_stats=True):
         """closest_object for n rays: d_rays_ptr / d_hits_ptr are device addresses of n RtxRay (48 B) / RtxHit (64 B) records (e.g.
         torch tensors' data_ptr()).  want_stats=False: asynchronous on `stream`."""
@@ -660,6 +689,80 @@ class SceneHandle:
             pass
 
 
+class Progressive:
+    """Progressive and adaptive sampling of one frame on a resident scene (SceneHandle.progressive).  The running per-channel sums of the
+    samples (and of their squares) live in torch tensors on the handle's device; every pixel carries its own sample count.  A pixel with
+    count n holds the render's samples 0 .. n - 1 folded in sample order, so sum / n is the render's pixel at rays_per_pixel = n bit for
+    bit, however the samples arrived (add(2); add(3) == add(5); refine() continues a pixel's fold)."""
+
+    def __init__(self, handle, width, height, moments=True):
+        import torch
+        self._hnd, self.width, self.height = handle, int(width), int(height)
+        dev = torch.device("cuda", handle.device)
+        self.sum = torch.zeros((self.height, self.width, 3), dtype=torch.float64, device=dev)
+        self.sum_sq = torch.zeros((self.height, self.width, 3), dtype=torch.float64, device=dev) if moments else None
+        self.count = torch.zeros((self.height, self.width), dtype=torch.int64, device=dev)
+        self._uniform = 0                        # samples every pixel has had through add(); refine() makes counts differ
+        self.traced = 0                          # samples traced so far
+
+    def add(self, n):
+        """the next n samples of every pixel (rtx_render_blocks_accumulate); only while no pixel has been refined"""
+        import torch
+        n = int(n)
+        if n <= 0:
+            return None
+        if int(self.count.min()) != self._uniform or int(self.count.max()) != self._uniform:
+            raise ValueError("add() after refine(): the pixels' sample counts differ; refine the others first or start a new Progressive")
+        torch.cuda.synchronize(self.sum.device)
+        st = self._hnd.render_accumulate(self.width, self.height, self._uniform, n, self.sum.data_ptr(),
+                                         self.sum_sq.data_ptr() if self.sum_sq is not None else None)
+        self._uniform += n
+        self.count += n
+        self.traced += n * self.width * self.height
+        return st
+
+    def refine(self, pixels, n):
+        """the next n samples of the chosen pixels only (rtx_scene_trace_samples): `pixels` are indices y * width + x (distinct), each
+        continuing from its own count.  The new samples are added in sample order, one sample index at a time, with f64 torch adds (IEEE
+        adds: the fold keeps the render's bits)."""
+        import torch
+        n = int(n)
+        dev = self.sum.device
+        pix = torch.as_tensor(np.ascontiguousarray(pixels, dtype=np.int64).ravel(), device=dev)
+        m = int(pix.numel())
+        if m == 0 or n <= 0:
+            return None
+        if int(torch.unique(pix).numel()) != m:
+            raise ValueError("refine(): a pixel is named twice")
+        if int(pix.min()) < 0 or int(pix.max()) >= self.width * self.height:
+            raise ValueError("refine(): a pixel outside the frame")
+        start = self.count.view(-1)[pix]
+        ids = torch.stack([pix.repeat(n), (start[None, :] + torch.arange(n, device=dev)[:, None]).reshape(-1)], dim=1).contiguous()   # sample-major
+        rgb = torch.empty((n, m, 3), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        st = self._hnd.trace_samples(self.width, self.height, ids.data_ptr(), n * m, rgb.data_ptr())
+        s, q = self.sum.view(-1, 3), (self.sum_sq.view(-1, 3) if self.sum_sq is not None else None)
+        for k in range(n):                                           # a pixel's samples in sample order
+            s[pix] = s[pix] + rgb[k]
+            if q is not None:
+                q[pix] = q[pix] + rgb[k] * rgb[k]
+        self.count.view(-1)[pix] += n
+        self.traced += n * m
+        return st
+
+    def mean(self):
+        """sum / count per pixel: the render's frame at each pixel's own sample count, bit for bit (0 samples: NaN) -> numpy (h, w, 3)"""
+        return (self.sum / self.count.to(self.sum.dtype)[..., None]).cpu().numpy()
+
+    def variance(self):
+        """the per-channel variance of the mean, (sum_sq - sum^2 / n) / (n - 1) / n -> numpy (h, w, 3).  Plain float arithmetic on the
+        two sums: an estimate for steering samples, not pinned to any bits; NaN or inf below two samples."""
+        if self.sum_sq is None:
+            raise ValueError("variance() needs moments=True")
+        n = self.count.to(self.sum.dtype)[..., None]
+        return ((self.sum_sq - self.sum * self.sum / n) / (n - 1.0) / n).cpu().numpy()
+
+
 HOST_SCENE_STATS = ("spheres", "triangles", "tri_filter_records", "tri_in_tree", "wide_nodes", "depth", "binary_nodes", "flags",
                     "sphere_leaf_entries", "tri_leaf_entries", "largest_leaf", "flat_nodes", "stack_bound", "tri_xy_footprints",
                     "tri_other_footprints", "quantised_nodes")
@@ -763,6 +866,26 @@ def debug_resolve(records, mask, width, n_rows, tiled, n_samples, rays_per_pixel
                                     acc.ctypes.data if acc is not None else None, acc.size if acc is not None else 0,
                                     out.ctypes.data if out is not None else None, out.size if out is not None else 0), lib)
     return out, acc
+
+
+def debug_resolve_moments(records, mask, width, n_rows, tiled, n_samples, total, total_sq=None):
+    """launch_resolve as rtx_render_blocks_accumulate calls it (include/rtx_hip.h, rtx_debug_resolve_moments; lab library): the records
+    under set bits are added to `total`, their squares to `total_sq` (or None), per pixel in sample order.  records / mask / tiled as
+    debug_resolve; returns (total, total_sq) as the kernel left them, as new flat arrays."""
+    rec = None if records is None else np.ascontiguousarray(records, dtype=np.float64)
+    msk = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint32)
+    total = np.array(total, dtype=np.float64, order="C").ravel()
+    total_sq = None if total_sq is None else np.array(total_sq, dtype=np.float64, order="C").ravel()
+    tiles_x = (int(width) + 7) // 8 if tiled else 0
+    per_sample = tiles_x * ((int(n_rows) + 7) // 8) * 64 if tiled else int(width) * int(n_rows)
+    if n_samples and (rec is None or msk is None or rec.size != int(n_samples) * per_sample * 4 or msk.size * 32 < int(n_samples) * per_sample):
+        raise ValueError("records / mask do not hold n_samples * per_sample slots")
+    lib = load_library(True)
+    abi.check(lib.rtx_debug_resolve_moments(rec.ctypes.data if rec is not None else None, msk.ctypes.data if msk is not None else None,
+                                            int(width), int(n_rows), tiles_x, int(n_samples), total.ctypes.data, total.size,
+                                            total_sq.ctypes.data if total_sq is not None else None,
+                                            total_sq.size if total_sq is not None else 0), lib)
+    return total, total_sq
 
 
 def debug_gather(parts, width, height, n, cap_rows, block, flip=False):

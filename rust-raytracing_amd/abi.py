@@ -116,6 +116,8 @@ SYMBOLS = [
     ("rtx_blocks_row_count", C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     ("rtx_render_blocks", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                       C.c_void_p, C.c_void_p, C.POINTER(RtxStats)]),
+    ("rtx_render_blocks_accumulate", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                                 C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtxStats)]),
     ("rtx_scene_closest_hits", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(RtxStats)]),
     ("rtx_scene_primary_hits", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(RtxStats)]),
     ("rtx_closest_hits", C.c_int32, [C.POINTER(RtxScene), C.c_void_p, C.c_uint64, C.c_void_p]),
@@ -123,6 +125,9 @@ SYMBOLS = [
     ("rtx_any_hits", C.c_int32, [C.POINTER(RtxScene), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     ("rtx_scene_trace_paths", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtxStats)]),
     ("rtx_trace_paths", C.c_int32, [C.POINTER(RtxScene), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("rtx_scene_trace_samples", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.POINTER(RtxStats)]),
+    ("rtx_trace_samples", C.c_int32, [C.POINTER(RtxScene), C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("rtx_scene_pixel_features", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(RtxStats)]),
     ("rtx_scene_pixel_features_blocks", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                                     C.c_void_p, C.c_void_p, C.POINTER(RtxStats)]),
@@ -133,6 +138,8 @@ SYMBOLS = [
     ("rtx_debug_store_samples", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
     ("rtx_debug_resolve", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int32,
                                       C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
+    ("rtx_debug_resolve_moments", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
+                                              C.c_void_p, C.c_uint64]),
     ("rtx_debug_gather", C.c_int32, [C.c_int32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32,
                                      C.c_void_p]),
     ("rtx_debug_host_scene", C.c_int32, [C.POINTER(RtxScene), C.POINTER(C.c_uint64)]),

@@ -2,7 +2,8 @@
 // Scene packing (Scene.objects -> per-type device arrays with scene-order ids), the
 // ray-independent precompute, scratch management, kernel launches, timing.
 // There is no CPU fallback in this file: every render path ends in a gfx950 kernel launch.
-// The two launch paths: render_band (a band of a frame: choose_kernel, plan_batch, plan_forms, grow_scratch, launch_halves or
+// The two launch paths: render_band (a band of a frame over a SampleRange -- a render's [0, rays_per_pixel) into the mean, or
+// rtx_render_blocks_accumulate's range into the caller's sums: choose_kernel, plan_batch, plan_forms, grow_scratch, launch_halves or
 // launch_batches, finish_stats over a BandPlan) and query_run (one QueryRequest: the mode, the rays or the pick frame, that mode's
 // pointers); both start with DoneGuard, scratch_cap, rows_view and begin_launches and read their counters through sum_counters.
 #include "../../include/rtx_hip.h"
@@ -889,6 +890,10 @@ struct BandPlan {                                         // what the call decid
     bool spheres_kernel = false, mesh_kernel = false, pool_kernel = false, spheres_two_stage = false, stage2_slots = false;
     bool wf_mesh = false, halves = false;                 // the wavefront form can take this tree; two halves in flight
 };
+// The samples a call traces and where their fold goes.  A render: [0, rays_per_pixel) from zero into out = sum / rays_per_pixel.
+// rtx_render_blocks_accumulate (sum != null): [begin, begin + n) on top of what the caller's sum (and sum_sq, or null) hold; nothing
+// is divided and no accumulator of the handle's is used -- the caller's buffers have its layout.
+struct SampleRange { uint64_t begin = 0, n = 0; double *sum = nullptr, *sum_sq = nullptr; };
 struct BandRun { float trace_ms = 0.f, resolve_ms = 0.f, stage1_ms = 0.f; CounterSums stage1; uint32_t launches = 0; };   // what its launches measured (RtxStats)
 
 // The kernel a band of npix pixels x spp samples runs: RtxConfig.kernel, resolved.  No HIP call in here.
@@ -983,7 +988,7 @@ int32_t plan_batch(const RtxSceneHandle_ *h, BandPlan &plan, uint32_t width, uin
 
 // Which form of plan.kernel runs, once the batch is known.  The lab forms sit behind RTX_TUNE_LAB_MASK bits, which the product
 // library refuses (check_config): there those terms are constant.
-void plan_forms(const RtxSceneHandle_ *h, BandPlan &plan, uint64_t spp)
+void plan_forms(const RtxSceneHandle_ *h, BandPlan &plan, uint64_t spp, bool may_halve)
 {
     const SceneView &sv = h->sv;
     const uint32_t kernel = plan.kernel, tuning = h->cfg.tuning;
@@ -1004,14 +1009,14 @@ void plan_forms(const RtxSceneHandle_ *h, BandPlan &plan, uint64_t spp)
     plan.stage2_slots = kLabBuild && plan.spheres_two_stage && (tuning & RTX_TUNE_STAGE2_SLOTS) != 0u && (sv.bvh_flags & 16u) != 0u &&
                         (tuning & (RTX_TUNE_NO_QNODES | RTX_TUNE_INLINE_LEAVES | RTX_TUNE_STAGE2_POOL | RTX_TUNE_STAGE2_PAIR)) == 0u;
     // two halves in flight (launch_halves): behind RTX_TUNE_HALVES, the whole call in one launch of the plain two-stage form
-    const bool halves_can = plan.spheres_two_stage && plan.batch == spp && spp >= 2 && !plan.stage2_slots &&
+    const bool halves_can = may_halve && plan.spheres_two_stage && plan.batch == spp && spp >= 2 && !plan.stage2_slots &&
                             (tuning & (RTX_TUNE_STAGE2_POOL | RTX_TUNE_STAGE2_PAIR)) == 0u;
     plan.halves = halves_can && (tuning & RTX_TUNE_NO_HALVES) == 0u &&
                   ((tuning & RTX_TUNE_HALVES) != 0u || plan.per_sample64 * spp <= kHalvesBelowRays);
 }
 
 // ---- scratch: one RGB per ray of a sample batch, the running per-pixel sum, the SoA ray state
-int32_t grow_scratch(RtxSceneHandle_ *h, const BandPlan &plan, uint32_t npix, uint64_t spp)
+int32_t grow_scratch(RtxSceneHandle_ *h, const BandPlan &plan, uint32_t npix, uint64_t spp, bool own_acc)
 {
     const uint32_t kernel = plan.kernel;
     const uint64_t batch_rays = plan.batch * plan.per_sample64;
@@ -1019,7 +1024,7 @@ int32_t grow_scratch(RtxSceneHandle_ *h, const BandPlan &plan, uint32_t npix, ui
     if (spp > 0)
         if (int32_t rc = grow((void **)&h->samples, &h->samples_bytes,
                               (size_t)(batch_rays * 4 * sizeof(double)) + nonzero_mask_bytes(batch_rays))) return rc;
-    if (plan.batch < spp)
+    if (own_acc && plan.batch < spp)
         if (int32_t rc = grow((void **)&h->acc, &h->acc_bytes, (size_t)npix * 3 * sizeof(double))) return rc;
     if (kernel == RTX_KERNEL_BVH || kernel == RTX_KERNEL_BVH_REGROUP) {
 #ifdef RTX_LAB
@@ -1160,8 +1165,9 @@ int32_t launch_halves(RtxSceneHandle_ *h, const BandPlan &plan, RowsView rv, dou
     return RTX_OK;
 }
 
-// The trace launch of one sample batch (samples s0 ..: rv), by kernel.
-int32_t launch_batch(RtxSceneHandle_ *h, const BandPlan &plan, const RowsView &rv, uint64_t s0, hipStream_t stream, bool stats)
+// The trace launch of one sample batch (its samples: rv.sample_begin, rv.n_samples), by kernel.  first_batch: the first of THIS call --
+// build the tile lists; the call's later batches reuse them (the camera may have changed since an earlier call: every call rebuilds).
+int32_t launch_batch(RtxSceneHandle_ *h, const BandPlan &plan, const RowsView &rv, bool first_batch, hipStream_t stream, bool stats)
 {
     const uint32_t kernel = plan.kernel, tuning = h->cfg.tuning;
     uint32_t *const state = reinterpret_cast<uint32_t *>(h->state);
@@ -1180,7 +1186,7 @@ int32_t launch_batch(RtxSceneHandle_ *h, const BandPlan &plan, const RowsView &r
         else
 #endif
             RTX_HIP_CHECK(launch_trace_wavefront(h->d_sv, h->sv, h->d_rv, rv, h->samples, h->wf_state, h->counters, state, h->n_cus, stream,
-                                                 plan.wf_mesh && plan.tile_list_bytes != 0 ? h->tile_lists : nullptr, s0 == 0));   // (a frame's later sample batches reuse its lists)
+                                                 plan.wf_mesh && plan.tile_list_bytes != 0 ? h->tile_lists : nullptr, first_batch));   // (a call's later sample batches reuse its lists)
     } else if (kernel == RTX_KERNEL_BVH_REGROUP) {
 #ifdef RTX_LAB
         if (plan.pool_kernel)
@@ -1203,7 +1209,7 @@ int32_t launch_batch(RtxSceneHandle_ *h, const BandPlan &plan, const RowsView &r
                                                    stats && two ? h->counters_stage1 : nullptr, stats && two ? h->ev[3] : nullptr,
                                                    two && (tuning & (RTX_TUNE_STAGE2_POOL | RTX_TUNE_STAGE2_PAIR)) ? h->pool : nullptr,
                                                    plan.stage2_slots ? h->slots : nullptr,
-                                                   two && plan.tile_list_bytes != 0 ? h->tile_lists : nullptr, s0 == 0));
+                                                   two && plan.tile_list_bytes != 0 ? h->tile_lists : nullptr, first_batch));
         }
     } else {
         RTX_HIP_CHECK(launch_trace_mixed(h->d_sv, h->sv, h->d_rv, rv, h->samples, h->state, h->counters, h->work_counter, h->n_cus,
@@ -1213,24 +1219,28 @@ int32_t launch_batch(RtxSceneHandle_ *h, const BandPlan &plan, const RowsView &r
 }
 
 // The samples of a call, plan.batch per launch: a trace launch and a resolve per batch (the left fold over the batches happens in
-// resolve's accumulator).
-int32_t launch_batches(RtxSceneHandle_ *h, const BandPlan &plan, RowsView rv, double *d_out_rgb, hipStream_t stream, bool stats,
-                       BandRun &run)
+// resolve's accumulator: the handle's, or -- sr.sum -- the caller's, which also holds what earlier calls folded).
+int32_t launch_batches(RtxSceneHandle_ *h, const BandPlan &plan, RowsView rv, const SampleRange &sr, double *d_out_rgb, hipStream_t stream,
+                       bool stats, BandRun &run)
 {
-    const uint64_t spp = h->cfg.rays_per_pixel;
+    const uint64_t spp = sr.n;
+    const bool accumulate = sr.sum != nullptr;
     CounterSums before;                                     // the counters after the batch before this one
     for (uint64_t s0 = 0; s0 < spp; s0 += plan.batch) {
         const uint64_t ns = (spp - s0 < plan.batch) ? spp - s0 : plan.batch;
-        rv.sample_begin = (uint32_t)s0; rv.n_samples = (uint32_t)ns;
+        rv.sample_begin = (uint32_t)(sr.begin + s0); rv.n_samples = (uint32_t)ns;
         rv.n_rays = plan.per_sample64 * ns;                 // (the padded tile grid when tiled)
         rv.grab = grab_size(rv.n_rays, h->n_cus, RTX_GRABS_PER_WAVE);
         RTX_HIP_CHECK(hipMemcpyAsync(h->d_rv, &rv, sizeof(RowsView), hipMemcpyHostToDevice, stream));   // pageable: staged before return
         RTX_HIP_CHECK(hipMemsetAsync(rv.nonzero, 0, nonzero_mask_bytes(rv.n_rays), stream));            // no record yet: the last batch's bits go
         if (stats) RTX_HIP_CHECK(hipEventRecord(h->ev[0], stream));
-        if (int32_t rc = launch_batch(h, plan, rv, s0, stream, stats)) return rc;
+        if (int32_t rc = launch_batch(h, plan, rv, s0 == 0, stream, stats)) return rc;
         ++run.launches;
         if (stats) RTX_HIP_CHECK(hipEventRecord(h->ev[1], stream));
-        RTX_HIP_CHECK(launch_resolve(h->samples, h->acc, d_out_rgb, rv, (uint32_t)plan.per_sample64, spp, s0 == 0, s0 + ns == spp, stream));
+        if (accumulate)
+            RTX_HIP_CHECK(launch_resolve(h->samples, sr.sum, nullptr, rv, (uint32_t)plan.per_sample64, spp, false, false, stream, sr.sum_sq));
+        else
+            RTX_HIP_CHECK(launch_resolve(h->samples, h->acc, d_out_rgb, rv, (uint32_t)plan.per_sample64, spp, s0 == 0, s0 + ns == spp, stream));
         if (!stats) continue;
         RTX_HIP_CHECK(hipEventRecord(h->ev[2], stream));
         RTX_HIP_CHECK(hipEventSynchronize(h->ev[2]));
@@ -1295,22 +1305,42 @@ int32_t finish_stats(RtxSceneHandle_ *h, const BandPlan &plan, const BandRun &ru
 }  // namespace
 
 // Renders the band of n_rows rows -- local row k -> image row row_begin + (k / row_block) * row_stride + k % row_block (rtx_device.h,
-// image_row) -- into d_out_rgb on `stream`; stats == NULL: asynchronous.
+// image_row) -- on `stream`; stats == NULL: asynchronous.  accumulate == null: the handle's rays_per_pixel samples, their mean into
+// d_out_rgb (a render); else that range of samples on top of its sums (rtx_render_blocks_accumulate; d_out_rgb is not read).
 static int32_t render_band(RtxSceneHandle h, uint32_t width, uint32_t height, uint32_t row_begin, uint32_t row_stride,
-                           uint32_t row_block, uint32_t n_rows, double *d_out_rgb, void *stream_, RtxStats *stats)
+                           uint32_t row_block, uint32_t n_rows, double *d_out_rgb, void *stream_, RtxStats *stats,
+                           const SampleRange *accumulate = nullptr)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (n_rows == 0 || width == 0) return RTX_OK;
-    if (!d_out_rgb) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_render_rows: null output");
+    if (!accumulate && !d_out_rgb) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_render_rows: null output");
     if ((uint64_t)n_rows * width > 0xFFFFFFF0ull) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_render_rows: more than 2^32 pixels per call");
+    if (accumulate) {                                     // (its range and d_sum: checked by rtx_render_blocks_accumulate)
+        if ((uint64_t)n_rows * width >= 0xFFFFFFF0ull)
+            return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_render_blocks_accumulate: 2^32 - 16 pixels per call or more");
+        const size_t bytes = (size_t)n_rows * width * 3 * sizeof(double);
+        const Range r[2] = { { accumulate->sum, bytes }, { accumulate->sum_sq, bytes } };
+        if (ranges_overlap(r, 2)) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_render_blocks_accumulate: d_sum and d_sum_sq overlap");
+    }
     RTX_HIP_CHECK(hipSetDevice(h->device));
     if (int32_t rc = check_watchdog(h, false)) return rc;
     if (int32_t rc = adopt_stream(h, stream)) return rc;
     DoneGuard done_guard{h, stream};
 
     const uint32_t npix = n_rows * width;
-    const uint64_t spp = h->cfg.rays_per_pixel;
+    SampleRange sr;
+    if (accumulate) sr = *accumulate; else sr.n = h->cfg.rays_per_pixel;
+    const uint64_t spp = sr.n;
+    if (accumulate && h->sv.n_objects == 0) {
+        // every sample of an empty scene is zero (scene.rs:224-226): the sums keep their bits, nothing is touched
+        if (stats) {
+            RTX_HIP_CHECK(hipStreamSynchronize(stream));
+            stats->primary_rays = (uint64_t)npix * spp;
+            stats->kernel = h->cfg.kernel;
+        }
+        return RTX_OK;
+    }
     if (h->sv.n_objects == 0 && spp > 0) {
         // render_ray of an empty scene returns resulting_color = 0 for every sample (scene.rs:224-226) and avg() of
         // zeros is 0/len = +0.0: nothing to trace.  (The sweep kernel's workgroups leave as soon as a round finds no
@@ -1326,9 +1356,9 @@ static int32_t render_band(RtxSceneHandle h, uint32_t width, uint32_t height, ui
     BandPlan plan;
     plan.kernel = choose_kernel(h->sv, h->cfg, npix, spp);
     if (int32_t rc = plan_batch(h, plan, width, n_rows, spp)) return rc;
-    plan_forms(h, plan, spp);
+    plan_forms(h, plan, spp, accumulate == nullptr);       // (an accumulating call takes the batch path: one resolve per batch into the caller's sums)
     if (int32_t rc = ensure_tables(h, width, height, row_begin, row_stride, row_block, n_rows, stream)) return rc;
-    if (int32_t rc = grow_scratch(h, plan, npix, spp)) return rc;
+    if (int32_t rc = grow_scratch(h, plan, npix, spp, accumulate == nullptr)) return rc;
 
     RowsView rv = rows_view(h, width, height, row_begin, row_stride, row_block, n_rows, plan.tiles_x, (uint32_t)plan.per_sample64);
     rv.nonzero = spp > 0 ? reinterpret_cast<uint32_t *>(h->samples + (size_t)(plan.batch * plan.per_sample64) * 4) : nullptr;
@@ -1341,7 +1371,7 @@ static int32_t render_band(RtxSceneHandle h, uint32_t width, uint32_t height, ui
     } else if (plan.halves) {
         if (int32_t rc = launch_halves(h, plan, rv, d_out_rgb, stream, stats != nullptr, run)) return rc;
     } else {
-        if (int32_t rc = launch_batches(h, plan, rv, d_out_rgb, stream, stats != nullptr, run)) return rc;
+        if (int32_t rc = launch_batches(h, plan, rv, sr, d_out_rgb, stream, stats != nullptr, run)) return rc;
     }
     return finish_stats(h, plan, run, (uint64_t)npix * spp, stream, stats);
 }
@@ -1354,7 +1384,8 @@ namespace {
 struct QueryRequest {
     uint32_t mode = kQueryClosest;
     uint32_t width = 0, height = 0;      // the pick form (rays == null, kQueryClosest): ray i = pixel i of this frame, n = width * height;
-                                         // kQueryFeatures: entry i = local pixel i of the band below, n = n_rows * width
+                                         // kQueryFeatures: entry i = local pixel i of the band below, n = n_rows * width;
+                                         // kQueryPaths with rays == null (rtx_scene_trace_samples): the frame the ids' pixel indices count in
     uint32_t row_begin = 0, row_stride = 1, row_block = 1, n_rows = 0;   // the band of the frame, as render_band takes it (the pick form: every row)
     uint64_t n = 0;
     const RtxRay *rays = nullptr;
@@ -1474,6 +1505,24 @@ int32_t rtx_render_blocks(RtxSceneHandle h, uint32_t width, uint32_t height, uin
     if ((uint64_t)block_rows * n_parts > 0xFFFFFFF0ull) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_render_blocks: block_rows * n_parts overflows");
     const uint32_t n_rows = blocks_row_count(height, block_rows, part, n_parts);
     return render_band(h, width, height, part * block_rows, n_parts * block_rows, block_rows, n_rows, d_out_rgb, stream, stats);
+}
+
+int32_t rtx_render_blocks_accumulate(RtxSceneHandle h, uint32_t width, uint32_t height, uint32_t block_rows, uint32_t part, uint32_t n_parts,
+                                     uint64_t sample_begin, uint64_t n_samples, double *d_sum, double *d_sum_sq, void *stream, RtxStats *stats)
+{
+    if (!h) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_render_blocks_accumulate: null scene");
+    if (block_rows == 0 || n_parts == 0 || part >= n_parts) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_render_blocks_accumulate: bad partition");
+    if ((uint64_t)block_rows * n_parts > 0xFFFFFFF0ull)
+        return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_render_blocks_accumulate: block_rows * n_parts overflows");
+    if (sample_begin > 0xFFFFFFFFull || n_samples > 0xFFFFFFFFull || sample_begin + n_samples > 0xFFFFFFFFull)
+        return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_render_blocks_accumulate: sample_begin + n_samples exceeds 2^32-1");
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (n_samples == 0) return RTX_OK;                                          // nothing is touched
+    if (!d_sum) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_render_blocks_accumulate: null d_sum");
+    const uint32_t n_rows = blocks_row_count(height, block_rows, part, n_parts);
+    SampleRange sr;
+    sr.begin = sample_begin; sr.n = n_samples; sr.sum = d_sum; sr.sum_sq = d_sum_sq;
+    return render_band(h, width, height, part * block_rows, n_parts * block_rows, block_rows, n_rows, nullptr, stream, stats, &sr);
 }
 
 int32_t rtx_quantize_image_device(const double *d_rgb, uint32_t width, uint32_t height, uint8_t *d_rgb8, int32_t device,
@@ -1940,6 +1989,46 @@ int32_t rtx_debug_resolve(const double *records, const uint32_t *mask, uint32_t 
 #endif
 }
 
+int32_t rtx_debug_resolve_moments(const double *records, const uint32_t *mask, uint32_t width, uint32_t n_rows, uint32_t tiles_x,
+                                  uint32_t n_samples, double *sum, uint64_t sum_doubles, double *sum_sq, uint64_t sum_sq_doubles)
+{
+#ifndef RTX_LAB
+    (void)records; (void)mask; (void)width; (void)n_rows; (void)tiles_x; (void)n_samples; (void)sum; (void)sum_doubles; (void)sum_sq;
+    (void)sum_sq_doubles;
+    return fail(RTX_ERR_UNSUPPORTED, "rtx_debug_resolve_moments: a lab-library hook (librtx_hip_lab.so)");
+#else
+    const uint64_t npix = (uint64_t)width * n_rows;
+    if (npix == 0) return RTX_OK;
+    if (tiles_x != 0 && tiles_x != (width + 7u) / 8u) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_resolve_moments: tiles_x is 0 or ceil(width / 8)");
+    const uint64_t per_sample64 = tiles_x ? (uint64_t)tiles_x * ((n_rows + 7u) / 8u) * 64u : npix;     // as render_band sizes a sample
+    if (per_sample64 * ((uint64_t)n_samples + 1) > (1ull << 26)) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_resolve_moments: too large");
+    if (n_samples != 0 && (!records || !mask)) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_resolve_moments: null records or mask");
+    if (!sum || sum_doubles < 3 * npix) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_resolve_moments: sum holds 3 doubles per pixel");
+    if (sum_sq && sum_sq_doubles < 3 * npix) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_resolve_moments: sum_sq holds 3 doubles per pixel");
+    if (usable_device_count() == 0) return fail(RTX_ERR_NO_DEVICE, "no gfx950 device");
+    RTX_HIP_CHECK(hipSetDevice(0));
+    const uint64_t n_rays = per_sample64 * n_samples;
+    DebugBufs d;
+    void *d_rec, *d_mask, *d_sum, *d_sq;
+    // (as rtx_debug_resolve: one more sample's worth of NaN records under set bits behind the caller's records and bits)
+    const size_t rec_bytes = n_rays * 4 * sizeof(double), mask_bytes = (size_t)((n_rays + 31) / 32) * sizeof(uint32_t);
+    RTX_HIP_CHECK(d.up(records, rec_bytes, &d_rec, per_sample64 * 4 * sizeof(double)));
+    RTX_HIP_CHECK(d.up(mask, mask_bytes, &d_mask, nonzero_mask_bytes(per_sample64) + sizeof(uint32_t)));
+    RTX_HIP_CHECK(d.up(sum, sum_doubles * sizeof(double), &d_sum));
+    RTX_HIP_CHECK(d.up(sum_sq, sum_sq_doubles * sizeof(double), &d_sq));
+    RowsView rv{};                                     // the fields launch_resolve reads, as render_band fills them
+    rv.width = width; rv.n_rows = n_rows; rv.npix = (uint32_t)npix; rv.tiles_x = tiles_x;
+    rv.n_samples = n_samples; rv.n_rays = n_rays;
+    rv.nonzero = static_cast<uint32_t *>(d_mask); rv.nonzero_base = 0;
+    RTX_HIP_CHECK(launch_resolve(static_cast<const double *>(d_rec), static_cast<double *>(d_sum), nullptr, rv, (uint32_t)per_sample64,
+                                 n_samples, false, false, nullptr, static_cast<double *>(d_sq)));
+    RTX_HIP_CHECK(hipMemcpy(sum, d_sum, sum_doubles * sizeof(double), hipMemcpyDeviceToHost));
+    if (d_sq) RTX_HIP_CHECK(hipMemcpy(sum_sq, d_sq, sum_sq_doubles * sizeof(double), hipMemcpyDeviceToHost));
+    RTX_HIP_CHECK(hipDeviceSynchronize());
+    return RTX_OK;
+#endif
+}
+
 int32_t rtx_debug_gather(int32_t form, const void *parts, uint32_t width, uint32_t height, uint32_t n, uint32_t cap_rows,
                          uint32_t block, int32_t flip, void *full)
 {
@@ -2026,6 +2115,24 @@ int32_t rtx_scene_trace_paths(RtxSceneHandle h, const RtxRay *d_rays, const uint
     if (ranges_overlap(r, 4)) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_trace_paths: rays, ids, rgb and segments overlap");
     QueryRequest req;
     req.mode = kQueryPaths; req.n = n; req.rays = d_rays; req.rgb = d_rgb; req.ids = d_ids; req.segments = d_segments;
+    return query_run(h, req, stream, stats);
+}
+
+int32_t rtx_scene_trace_samples(RtxSceneHandle h, uint32_t width, uint32_t height, const uint64_t *d_ids, uint64_t n, double *d_rgb,
+                                uint32_t *d_segments, void *stream, RtxStats *stats)
+{
+    if (!h) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_trace_samples: null scene");
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (n == 0) return RTX_OK;
+    if (!d_ids || !d_rgb) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_trace_samples: null ids or rgb");
+    if (n >= 0xFFFFFFFFull) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_trace_samples: n must be below 2^32");
+    if (width == 0 || height == 0) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_trace_samples: an empty frame has no pixel to sample");
+    if ((uint64_t)width * height >= 0xFFFFFFF0ull) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_trace_samples: 2^32 - 16 pixels or more");
+    const Range r[3] = { { d_ids, n * 2 * sizeof(uint64_t) }, { d_rgb, n * 3 * sizeof(double) }, { d_segments, n * sizeof(uint32_t) } };
+    if (ranges_overlap(r, 3)) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_trace_samples: ids, rgb and segments overlap");
+    QueryRequest req;                                 // the path mode without rays: the kernel builds render_pixel's own (query_path_loop)
+    req.mode = kQueryPaths; req.width = width; req.height = height; req.n_rows = height; req.n = n;
+    req.ids = d_ids; req.rgb = d_rgb; req.segments = d_segments;
     return query_run(h, req, stream, stats);
 }
 
@@ -2148,6 +2255,22 @@ int32_t rtx_trace_paths(const RtxScene *scene, const RtxRay *rays, const uint64_
                                  { ids, nullptr, n * 2 * sizeof(uint64_t), (void **)&req.ids },
                                  { nullptr, segments, n * sizeof(uint32_t), (void **)&req.segments } };
     return query_once(scene, "rtx_trace_paths", req, arrays, 4);
+}
+
+int32_t rtx_trace_samples(const RtxScene *scene, uint32_t width, uint32_t height, const uint64_t *ids, uint64_t n, double *rgb,
+                          uint32_t *segments)
+{
+    if (int32_t rc = check_scene_args(scene, "rtx_trace_samples")) return rc;
+    if (n == 0) return RTX_OK;
+    if (!ids || !rgb) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_trace_samples: null ids or rgb");
+    if (n >= 0xFFFFFFFFull) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_trace_samples: n must be below 2^32");
+    if (width == 0 || height == 0) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_trace_samples: an empty frame has no pixel to sample");
+    if ((uint64_t)width * height >= 0xFFFFFFF0ull) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_trace_samples: 2^32 - 16 pixels or more");
+    QueryRequest req;
+    req.mode = kQueryPaths; req.width = width; req.height = height; req.n_rows = height; req.n = n;
+    const HostArray arrays[] = { { ids, nullptr, n * 2 * sizeof(uint64_t), (void **)&req.ids }, { nullptr, rgb, n * 3 * sizeof(double), (void **)&req.rgb },
+                                 { nullptr, segments, n * sizeof(uint32_t), (void **)&req.segments } };
+    return query_once(scene, "rtx_trace_samples", req, arrays, 3);
 }
 
 int32_t rtx_pixel_features(const RtxScene *scene, uint32_t width, uint32_t height, RtxPixelFeatures *features)

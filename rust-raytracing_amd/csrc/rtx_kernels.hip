@@ -523,12 +523,15 @@ __global__ __launch_bounds__(THREADS, WAVES_PER_EU) void trace_mixed_kernel(cons
 //   So s + 0.0 == s bit for bit for every addend of either sign.
 // (The running sum of an earlier batch, acc, is such a fold's value too.)  The bits of a sample's slots are read a word per
 // thread, eight samples ahead of the records, so that the records of those samples are in flight together.
+// sq (launch-uniform; null for every render): the second moments' accumulator of rtx_render_blocks_accumulate, in acc's layout --
+// where a record's bit is set, sq += c * c per component (a rounded multiply, then a rounded add: -ffp-contract=off).  The same
+// proof: c * c of a zero sample is +0.0, and a sum of squares from +0.0 is >= +0.0 or NaN, so the skipped samples change nothing.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void resolve_kernel(const double *__restrict__ samples, const uint32_t *__restrict__ nonzero,
                                                       double *__restrict__ acc,
                                                       double *__restrict__ out, uint32_t width, uint32_t n_rows, uint32_t tiles_x,
                                                       uint32_t per_sample, uint32_t n_samples,
-                                                      double divisor, int first, int last)
+                                                      double divisor, int first, int last, double *__restrict__ sq)
 {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= per_sample) return;
@@ -542,6 +545,8 @@ __global__ __launch_bounds__(256) void resolve_kernel(const double *__restrict__
     }
     double sx = 0.0, sy = 0.0, sz = 0.0;
     if (!first) { sx = acc[3 * (uint64_t)p]; sy = acc[3 * (uint64_t)p + 1]; sz = acc[3 * (uint64_t)p + 2]; }
+    double qx = 0.0, qy = 0.0, qz = 0.0;
+    if (sq) { qx = sq[3 * (uint64_t)p]; qy = sq[3 * (uint64_t)p + 1]; qz = sq[3 * (uint64_t)p + 2]; }
     constexpr uint32_t kAhead = 8;
     for (uint32_t s0 = 0; s0 < n_samples; s0 += kAhead) {
         const uint32_t n = n_samples - s0 < kAhead ? n_samples - s0 : kAhead;
@@ -563,7 +568,13 @@ __global__ __launch_bounds__(256) void resolve_kernel(const double *__restrict__
 #pragma unroll
         for (uint32_t j = 0; j < kAhead; ++j)
             if ((set >> j) & 1u) { sx = sx + c[j].x; sy = sy + c[j].y; sz = sz + c[j].z; }
+        if (sq) {
+#pragma unroll
+            for (uint32_t j = 0; j < kAhead; ++j)
+                if ((set >> j) & 1u) { qx = qx + c[j].x * c[j].x; qy = qy + c[j].y * c[j].y; qz = qz + c[j].z * c[j].z; }
+        }
     }
+    if (sq) { sq[3 * (uint64_t)p] = qx; sq[3 * (uint64_t)p + 1] = qy; sq[3 * (uint64_t)p + 2] = qz; }
     if (last) {
         double *o = out + 3 * (uint64_t)p;
         o[0] = sx / divisor; o[1] = sy / divisor; o[2] = sz / divisor;
@@ -772,11 +783,11 @@ hipError_t launch_trace_mixed(const SceneView *d_sv, const SceneView &sv, const 
 }
 
 hipError_t launch_resolve(const double *samples, double *acc, double *out, const RowsView &rv, uint32_t per_sample,
-                          uint64_t rays_per_pixel, bool first, bool last, hipStream_t stream)
+                          uint64_t rays_per_pixel, bool first, bool last, hipStream_t stream, double *sq)
 {
     if (per_sample == 0) return hipSuccess;
     hipLaunchKernelGGL(resolve_kernel, dim3((per_sample + 255) / 256), dim3(256), 0, stream, samples, rv.nonzero, acc, out, rv.width, rv.n_rows,
-                       rv.tiles_x, per_sample, rv.n_samples, (double)rays_per_pixel, first ? 1 : 0, last ? 1 : 0);
+                       rv.tiles_x, per_sample, rv.n_samples, (double)rays_per_pixel, first ? 1 : 0, last ? 1 : 0, sq);
     return hipGetLastError();
 }
 

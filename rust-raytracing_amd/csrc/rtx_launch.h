@@ -139,8 +139,10 @@ hipError_t launch_trace_wavefront_spheres(const SceneView *d_sv, const SceneView
 // of one sample (npix, or the padded 8x8-tile grid when rv.tiles_x != 0).  rv.nonzero (bit 0 = slot 0 of `samples`): the slots that
 // hold a record; the others count as zero and are not read.  first: acc starts from zero.
 // last: out[p] = acc / rays_per_pixel (rays_per_pixel == 0 with rv.n_samples == 0: 0/0 = NaN, as avg() of nothing).
+// sq (null for a render): the running sums of the samples' squares in acc's layout, read and written whatever first / last say
+// (rtx_render_blocks_accumulate: first = last = false, acc and sq are the caller's buffers).
 hipError_t launch_resolve(const double *samples, double *acc, double *out, const RowsView &rv, uint32_t per_sample,
-                          uint64_t rays_per_pixel, bool first, bool last, hipStream_t stream);
+                          uint64_t rays_per_pixel, bool first, bool last, hipStream_t stream, double *sq = nullptr);
 
 // render_to_image epilogue (scene.rs:175-178)
 hipError_t launch_quantize(const double *rgb, uint8_t *rgb8, uint32_t width, uint32_t height, hipStream_t stream);
@@ -163,9 +165,10 @@ struct QueryHit { double position[3], normal[3], distance; long long object; }; 
 struct QueryFeatures { double albedo[3], emission[3], normal[3], depth, coverage; long long object; };   // = RtxPixelFeatures
 static_assert(sizeof(QueryRay) == 48 && sizeof(QueryHit) == 64 && sizeof(QueryFeatures) == 96, "QueryRay / QueryHit / QueryFeatures");
 struct QueryArgs {
-    const QueryRay *rays;          // n rays (null in the pick form and the feature mode)
+    const QueryRay *rays;          // n rays (null in the pick form, the feature mode and the path mode's sample form)
     const RowsView *rv;            // the pick form: the frame's RowsView (one band of all rows), ray i = pixel i; the feature mode: the
-                                   // band's RowsView (row_begin, row_stride, row_block as render_band sets them), entry i = local pixel i; else null
+                                   // band's RowsView (row_begin, row_stride, row_block as render_band sets them), entry i = local pixel i; the
+                                   // path mode's sample form (rays == null): the frame's RowsView, as the pick form's; else null
     union {                        // the answers, by mode (the modes share the slots: one kernel argument layout for the three loops)
         QueryHit *hits;            // closest hits: n records
         uint8_t *occluded;         // any-hit: n bytes, 1 / 0
@@ -179,7 +182,8 @@ struct QueryArgs {
                                    // sv.rays_per_pixel gen_primary rays per pixel, folded (query_feature_loop)
     union {
         const double *t_max;       // any-hit: n limits, compared as given (null: +inf for every ray)
-        const unsigned long long *ids;   // paths: n (pixel index, sample index) pairs that key the RNG (null: (i, 0))
+        const unsigned long long *ids;   // paths: n (pixel index, sample index) pairs that key the RNG (null: (i, 0)); the sample form
+                                         // (rays == null; never null): the pair also names the ray -- gen_primary's of that pixel and sample
     };
     uint32_t *segments;            // paths: n closest_object counts, or null
 };

@@ -29,6 +29,9 @@
 // The path mode (QueryArgs.mode, rtx_scene_trace_paths; DESIGN.md "Path queries"): render_ray for the caller's rays -- the third
 // launch-uniform loop of the same two instances.  A lane owns a path and is refilled at the segment boundary; a segment is the
 // closest-hit loop's body (query_closest_ray) followed by advance_and_shade, with the render's draws 6 + 2b, 7 + 2b for bounce b.
+// Its sample form (QueryArgs.rays == null, rtx_scene_trace_samples; DESIGN.md "Progressive and adaptive sampling"): the lane builds
+// render_pixel's own ray for its (pixel, sample) pair with gen_primary on the full frame's RowsView where the path mode reads the
+// caller's ray -- a launch-uniform choice at the take, everything after it unchanged.
 //
 // The feature mode (QueryArgs.mode, rtx_scene_pixel_features; DESIGN.md "Pixel features"): the denoiser's guide buffers -- the fourth
 // launch-uniform loop of the same two instances.  A lane owns a PIXEL of the band: for every sample it builds render_pixel's own
@@ -414,7 +417,19 @@ __device__ __forceinline__ void query_path_loop(const SceneView &sv, const Query
             unsigned long long i2 = 0;
             if (wf_take(ch, head, grab, qa.n, !have && !got, i2)) { got = true; i = i2; }
         }
-        if (got) {
+        if (got && qa.rays == nullptr) {                                 // launch-uniform: the sample form -- render_pixel's own ray
+            const unsigned long long pix = qa.ids[2 * i], smp = qa.ids[2 * i + 1];
+            if (pix < (unsigned long long)qa.rv->npix && smp <= 0xFFFFFFFFull) {          // (before any table is indexed)
+                gen_primary(sv, *qa.rv, (uint32_t)pix, (uint32_t)smp, r);                // key (seed, pix, smp), draws 0..5; r.draw = 6
+                idx = (uint32_t)i;
+                have = true;
+            } else {                                                     // no such pixel or sample: NaN, nothing is traced
+                const double nan = __builtin_nan("");
+                double *out = qa.rgb + 3ull * i;
+                out[0] = nan; out[1] = nan; out[2] = nan;
+                if (qa.segments) qa.segments[i] = 0u;
+            }
+        } else if (got) {
             const QueryRay &qr = qa.rays[i];
             r.pos = mk(qr.position[0], qr.position[1], qr.position[2]);                      // Ray::new (ray.rs:14-21): no norm()
             r.dir = mk(qr.direction[0], qr.direction[1], qr.direction[2]);

@@ -134,6 +134,7 @@ extern "C" {
     pub fn rtx_render_rows(scene: RtxSceneHandle, width: u32, height: u32, row_begin: u32, row_stride: u32, n_rows: u32, d_out_rgb: *mut f64, stream: *mut c_void, stats: *mut RtxStats) -> i32;
     pub fn rtx_blocks_row_count(height: u32, block_rows: u32, part: u32, n_parts: u32) -> u32;
     pub fn rtx_render_blocks(scene: RtxSceneHandle, width: u32, height: u32, block_rows: u32, part: u32, n_parts: u32, d_out_rgb: *mut f64, stream: *mut c_void, stats: *mut RtxStats) -> i32;
+    pub fn rtx_render_blocks_accumulate(scene: RtxSceneHandle, width: u32, height: u32, block_rows: u32, part: u32, n_parts: u32, sample_begin: u64, n_samples: u64, d_sum: *mut f64, d_sum_sq: *mut f64, stream: *mut c_void, stats: *mut RtxStats) -> i32;
     pub fn rtx_scene_closest_hits(scene: RtxSceneHandle, d_rays: *const RtxRay, n: u64, d_hits: *mut RtxHit, stream: *mut c_void, stats: *mut RtxStats) -> i32;
     pub fn rtx_scene_primary_hits(scene: RtxSceneHandle, width: u32, height: u32, d_hits: *mut RtxHit, stream: *mut c_void, stats: *mut RtxStats) -> i32;
     pub fn rtx_closest_hits(scene: *const RtxScene, rays: *const RtxRay, n: u64, hits: *mut RtxHit) -> i32;
@@ -141,9 +142,12 @@ extern "C" {
     pub fn rtx_any_hits(scene: *const RtxScene, rays: *const RtxRay, t_max: *const f64, n: u64, occluded: *mut u8) -> i32;
     pub fn rtx_scene_trace_paths(scene: RtxSceneHandle, d_rays: *const RtxRay, d_ids: *const u64, n: u64, d_rgb: *mut f64, d_segments: *mut u32, stream: *mut c_void, stats: *mut RtxStats) -> i32;
     pub fn rtx_trace_paths(scene: *const RtxScene, rays: *const RtxRay, ids: *const u64, n: u64, rgb: *mut f64, segments: *mut u32) -> i32;
+    pub fn rtx_scene_trace_samples(scene: RtxSceneHandle, width: u32, height: u32, d_ids: *const u64, n: u64, d_rgb: *mut f64, d_segments: *mut u32, stream: *mut c_void, stats: *mut RtxStats) -> i32;
+    pub fn rtx_trace_samples(scene: *const RtxScene, width: u32, height: u32, ids: *const u64, n: u64, rgb: *mut f64, segments: *mut u32) -> i32;
     pub fn rtx_scene_pixel_features(scene: RtxSceneHandle, width: u32, height: u32, d_features: *mut RtxPixelFeatures, stream: *mut c_void, stats: *mut RtxStats) -> i32;
     pub fn rtx_scene_pixel_features_blocks(scene: RtxSceneHandle, width: u32, height: u32, block_rows: u32, part: u32, n_parts: u32, d_features: *mut RtxPixelFeatures, stream: *mut c_void, stats: *mut RtxStats) -> i32;
     pub fn rtx_pixel_features(scene: *const RtxScene, width: u32, height: u32, features: *mut RtxPixelFeatures) -> i32;
+    pub fn rtx_debug_resolve_moments(records: *const f64, mask: *const u32, width: u32, n_rows: u32, tiles_x: u32, n_samples: u32, sum: *mut f64, sum_doubles: u64, sum_sq: *mut f64, sum_sq_doubles: u64) -> i32;
     pub fn rtx_quantize_image_device(d_rgb: *const f64, width: u32, height: u32, d_rgb8: *mut u8, device: i32, stream: *mut c_void) -> i32;
 }
 

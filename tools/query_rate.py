@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Closest-hit, any-hit, path and feature query rates (rtx_scene_closest_hits / rtx_scene_primary_hits / rtx_scene_any_hits /
-rtx_scene_trace_paths / rtx_scene_pixel_features), in Mrays/s (the path legs: Msegments/s) from RtxStats.trace_ms, on the scenes of the
+"""Closest-hit, any-hit, path, feature and sample query rates (rtx_scene_closest_hits / rtx_scene_primary_hits / rtx_scene_any_hits /
+rtx_scene_trace_paths / rtx_scene_pixel_features / rtx_scene_trace_samples / rtx_render_blocks_accumulate), in Mrays/s (the path legs: Msegments/s) from RtxStats.trace_ms, on the scenes of the
 benchmark's C2 (10k spheres), C3 (100k triangles) and J1 (5k spheres + 50k triangles: a joint tree), built with scenes.py's
 generators and the same parameters:
 
@@ -18,6 +18,13 @@ generators and the same parameters:
                48-byte ray and writing 24 bytes per ray
   features     rtx_scene_pixel_features of the 1920x1080 frame with the bench camera and the default offsets, at 1 and at 16 samples
                per pixel (two lines): one segment per (pixel, sample), the ray built on the device, one 96-byte record per pixel
+  accumulate   the 1920x1080 frame at --spp samples (the benchmark's 64): rtx_render_blocks, then rtx_render_blocks_accumulate in one
+               call with and without d_sum_sq and in four calls of a quarter each (four lines; trace_ms and resolve_ms summed over the
+               calls) -- the same launches minus the division, and the price of splitting
+  samples_frame  rtx_scene_trace_samples, sample 0 of every pixel of the 1920x1080 frame with the default offsets, at max_bounces = 10
+               and at 0 (two lines; the second is what `features` at 1 spp and `paths_primary` trace), and rtx_render_rows of the frame
+               at 1 spp (the same samples through the render's tiles and packets)
+  samples_sparse  a random tenth of the frame's pixels, samples 0..7 of each, sample-major: per sample against samples_frame
 
     tools/query_rate.py [--rays 24] [--scenes C2,C3,J1] [--reps 3] [--exact-rays 20] [--legs incoherent,pick,...]
 
@@ -79,7 +86,7 @@ def primary_rays(rtx, cam, width, height):
 
 
 LEGS = ("incoherent", "pick", "exact", "any", "any_short", "any_aimed", "paths", "paths_1seg", "paths_pick", "render_pick", "paths_primary",
-        "features")
+        "features", "accumulate", "samples_frame", "samples_sparse")
 
 
 def main():
@@ -89,6 +96,7 @@ def main():
     ap.add_argument("--scenes", default="C2,C3,J1")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--legs", default=",".join(LEGS))
+    ap.add_argument("--spp", type=int, default=64, help="samples per pixel of the accumulate leg's frame")
     args = ap.parse_args()
     import torch
 
@@ -109,6 +117,11 @@ def main():
             legs = [l for l in legs if not l.startswith("paths")]
         if not hasattr(probe, "rtx_scene_pixel_features"):
             legs = [l for l in legs if l != "features"]
+        if not hasattr(probe, "rtx_scene_trace_samples"):
+            legs = [l for l in legs if not l.startswith("samples")]
+        have_accumulate = hasattr(probe, "rtx_render_blocks_accumulate")
+    else:
+        have_accumulate = True
     for name in args.scenes.split(","):
         objs = SCENES[name](scenes)
         o, d = incoherent(objs, n)
@@ -145,6 +158,66 @@ def main():
                                       "exact_tests_per_ray": round(st.exact_tests / st.segments, 2),
                                       "box_tests_per_ray": round(st.box_tests / st.segments, 2),
                                       "coverage": round(float(f["coverage"].mean()), 4)}), flush=True)
+                    hnd.close()
+                continue
+            if leg == "accumulate":
+                hnd = rtx.Scene.from_packed(cfg.with_rays_per_pixel(args.spp), rtx.Camera(*scenes.CAMERA), objs).upload(0)
+                d_sum = d_hits.view(torch.float64)[:3 * W * H]
+                d_sq = d_hits.view(torch.float64)[3 * W * H:6 * W * H]
+
+                def calls(parts, moments):
+                    """one frame's samples in `parts` calls: the stats of the calls added up"""
+                    d_sum.zero_()
+                    d_sq.zero_()
+                    torch.cuda.synchronize(dev)
+                    tot = None
+                    for q in range(parts):
+                        a, b = args.spp * q // parts, args.spp * (q + 1) // parts
+                        st = hnd.render_accumulate(W, H, a, b - a, d_sum.data_ptr(), d_sq.data_ptr() if moments else None)
+                        if tot is None:
+                            tot = st
+                        else:
+                            tot.trace_ms += st.trace_ms; tot.resolve_ms += st.resolve_ms; tot.trace_launches += st.trace_launches
+                            tot.segments += st.segments; tot.primary_rays += st.primary_rays
+                    return tot
+
+                forms = [("render_blocks", lambda: hnd.render_blocks(W, H, 8, 0, 1, d_sum.data_ptr()))]
+                if have_accumulate:
+                    forms += [("one call", lambda: calls(1, True)), ("one call, no d_sum_sq", lambda: calls(1, False)),
+                              ("four calls", lambda: calls(4, True))]
+                for form, fn in forms:
+                    fn()
+                    st = min((fn() for _ in range(args.reps)), key=lambda s: s.trace_ms + s.resolve_ms)
+                    print(json.dumps({"scene": name, "leg": leg, "form": form, "spp": args.spp, "rays": int(st.primary_rays),
+                                      "trace_ms": round(st.trace_ms, 3), "resolve_ms": round(st.resolve_ms, 3),
+                                      "mrays_per_s": round(st.primary_rays / ((st.trace_ms + st.resolve_ms) * 1e-3) / 1e6, 1),
+                                      "launches": int(st.trace_launches), "kernel": int(st.kernel)}), flush=True)
+                hnd.close()
+                continue
+            if leg.startswith("samples"):
+                d_rgb = d_hits.view(torch.float64)
+                if leg == "samples_frame":
+                    k = W * H
+                    d_ids = torch.stack([torch.arange(k, dtype=torch.int64, device=dev), torch.zeros(k, dtype=torch.int64, device=dev)], dim=1).contiguous()
+                else:
+                    pix = torch.from_numpy(np.sort(np.random.default_rng(9).permutation(W * H)[:W * H // 10])).to(dev)
+                    k = 8 * int(pix.numel())
+                    d_ids = torch.stack([pix.repeat(8), torch.arange(8, dtype=torch.int64, device=dev).repeat_interleave(pix.numel())], dim=1).contiguous()
+                torch.cuda.synchronize(dev)
+                for bounces in ((10, 0) if leg == "samples_frame" else (10,)):
+                    hnd = rtx.Scene.from_packed(cfg.with_max_bounces(bounces), rtx.Camera(*scenes.CAMERA), objs).upload(0)
+                    st = best(lambda: hnd.trace_samples(W, H, d_ids.data_ptr(), k, d_rgb.data_ptr()))
+                    print(json.dumps({"scene": name, "leg": leg, "max_bounces": bounces, "samples": k, "segments": int(st.segments),
+                                      "trace_ms": round(st.trace_ms, 3), "msamples_per_s": round(k / (st.trace_ms * 1e-3) / 1e6, 1),
+                                      "msegments_per_s": round(st.segments / (st.trace_ms * 1e-3) / 1e6, 1), "kernel": int(st.kernel),
+                                      "segments_per_sample": round(st.segments / k, 3),
+                                      "lit_fraction": round(float((d_rgb[:3 * k].view(-1, 3) != 0).any(dim=1).float().mean().item()), 4)}), flush=True)
+                    if leg == "samples_frame" and bounces == 10:
+                        st = best(lambda: hnd.render_rows(W, H, 0, 1, H, d_rgb.data_ptr()))
+                        print(json.dumps({"scene": name, "leg": leg, "form": "render_rows at 1 spp", "samples": k, "segments": int(st.segments),
+                                          "trace_ms": round(st.trace_ms, 3), "resolve_ms": round(st.resolve_ms, 3),
+                                          "msamples_per_s": round(k / (st.trace_ms * 1e-3) / 1e6, 1),
+                                          "msegments_per_s": round(st.segments / (st.trace_ms * 1e-3) / 1e6, 1), "kernel": int(st.kernel)}), flush=True)
                     hnd.close()
                 continue
             if leg == "render_pick":
