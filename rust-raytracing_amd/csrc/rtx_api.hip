@@ -1798,10 +1798,10 @@ int32_t rtx_debug_host_scene(const RtxScene *scene, uint64_t *stats)
             const uint32_t *lows[3] = { &q.lox, &q.loy, &q.loz }, *highs[3] = { &q.hix, &q.hiy, &q.hiz };
             const float org[3] = { q.ox, q.oy, q.oz }, stp[3] = { q.sx, q.sy, q.sz };
             for (int c = 0; c < 4; ++c) {
-                const uint32_t count = bits(w.b[c].w), type = q.link[c] >> kQNodeShift;
+                const uint32_t count = bits(w.b[c].w), type = q.link(c) >> kQNodeShift;
                 if ((count == 0xFFFFFFFFu) != (type == kQNodeEmpty)) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: 64-byte sphere node: empty slot differs");
                 if (type == kQNodeEmpty) continue;
-                if ((q.link[c] & kQNodeIndexMask) != bits(w.a[c].w) || (type == 0u) != (count == 0u) || (type != 0u && type != count))
+                if ((q.link(c) & kQNodeIndexMask) != bits(w.a[c].w) || (type == 0u) != (count == 0u) || (type != 0u && type != count))
                     return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: 64-byte sphere node: link / count differs");
                 const float l[3] = { w.a[c].x, w.a[c].y, w.a[c].z }, hh[3] = { w.b[c].x, w.b[c].y, w.b[c].z };
                 for (int a = 0; a < 3; ++a) {

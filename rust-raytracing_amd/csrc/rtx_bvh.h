@@ -30,6 +30,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <numeric>
 #include <vector>
@@ -522,19 +523,27 @@ inline bool build_qnodes(const Bvh4Build &b4, std::vector<BvhQNode> &out)
 // A per-lane walk fetches its node as address-divergent 16-byte requests, and the L1's request rate (about one per cycle per
 // CU) is what bounds the bounced rays of a sphere scene before the VALUs do (2.5e10 requests per C2 launch).
 // A 128-byte node costs 8 requests; this form costs 4: the child boxes as 8-bit offsets on the node's own grid,
-//     {ox, oy, oz, sx}   {sy, sz, lo.x[4], lo.y[4]}   {lo.z[4], hi.x[4], hi.y[4], hi.z[4]}   {link[4]}
-// (byte c of a packed word = child c).  plane = o + q * s with s a power of two and o a multiple of s, so the decoded plane
+//     {link0, ox, link1, oy}   {link2, oz, link3, sx}   {sy, sz, lo.x[4], lo.y[4]}   {lo.z[4], hi.x[4], hi.y[4], hi.z[4]}
+// (byte c of a packed word = child c).  The links are interleaved with the four words the visit consumes first (ox, oy, oz, sx are
+// dead once O and S are formed): the visit sorts (key, link) pairs as f64 values, and with a link in the even register of a loaded
+// pair the key is written into the odd one -- the pair is built in place, without copying the link.
+// plane = o + q * s with s a power of two and o a multiple of s, so the decoded plane
 // is exact in f32 (checked at build: |o / s| + 255 < 2^24); lo is rounded down and hi up AFTER another abs_pad was added, so
 // the decoded box contains the 128-byte node's box with the margin the extra roundings of the decode need.
 // link = type << 29 | index, type 0 interior, 1..6 sphere leaf with that many entries, 7 empty (as BvhQNode).
 struct BvhQ3Node {
-    float ox, oy, oz, sx;
+    uint32_t link0; float ox; uint32_t link1; float oy;
+    uint32_t link2; float oz; uint32_t link3; float sx;
     float sy, sz;
     uint32_t lox, loy;
     uint32_t loz, hix, hiy, hiz;
-    uint32_t link[4];
+    uint32_t link(int c) const { return c == 0 ? link0 : (c == 1 ? link1 : (c == 2 ? link2 : link3)); }
+    void set_link(int c, uint32_t v) { (c == 0 ? link0 : (c == 1 ? link1 : (c == 2 ? link2 : link3))) = v; }
 };
 static_assert(sizeof(BvhQ3Node) == 64, "BvhQ3Node must be 64 bytes");
+static_assert(offsetof(BvhQ3Node, link0) == 0 && offsetof(BvhQ3Node, ox) == 4 && offsetof(BvhQ3Node, link1) == 8 && offsetof(BvhQ3Node, oy) == 12 &&
+              offsetof(BvhQ3Node, link2) == 16 && offsetof(BvhQ3Node, oz) == 20 && offsetof(BvhQ3Node, link3) == 24 && offsetof(BvhQ3Node, sx) == 28 &&
+              offsetof(BvhQ3Node, sy) == 32 && offsetof(BvhQ3Node, lox) == 40 && offsetof(BvhQ3Node, loz) == 48, "BvhQ3Node layout (rtx_traverse.h reads it as four float4)");
 
 inline bool build_q3nodes(const Bvh4Build &b4, double abs_pad, std::vector<BvhQ3Node> &out)
 {
@@ -570,7 +579,7 @@ inline bool build_q3nodes(const Bvh4Build &b4, double abs_pad, std::vector<BvhQ3
         for (int c = 0; c < 4; ++c) {
             if (cnt[c] == 0xFFFFFFFFu) {                          // empty: an inverted box (lo 255, hi 0) is never entered
                 for (int a = 0; a < 3; ++a) *lows[a] |= 255u << (8 * c);
-                q.link[c] = kQNodeEmpty << kQNodeShift;
+                q.set_link(c, kQNodeEmpty << kQNodeShift);
                 continue;
             }
             const float l[3] = { w.a[c].x, w.a[c].y, w.a[c].z }, h[3] = { w.b[c].x, w.b[c].y, w.b[c].z };
@@ -585,7 +594,7 @@ inline bool build_q3nodes(const Bvh4Build &b4, double abs_pad, std::vector<BvhQ3
             else if ((cnt[c] & kBvhTriLeaf) == 0u && cnt[c] >= 1u && cnt[c] <= kQNodeLeafMax) type = cnt[c];
             else return false;                                    // a triangle leaf or a bigger leaf: no 64-byte form
             if (lnk[c] > kQNodeIndexMask || (lnk[c] & kBvhFlatNode)) return false;
-            q.link[c] = (type << kQNodeShift) | lnk[c];
+            q.set_link(c, (type << kQNodeShift) | lnk[c]);
         }
         out.push_back(q);
     }

@@ -168,6 +168,16 @@ __device__ __forceinline__ void rtx_minmax_f64_bits(double a, double b, double &
     asm("v_max_f64 %0, %1, %2" : "=v"(hi) : "v"(a), "v"(b));
 }
 
+// min(a, b) of two f32 that are never NaN, as the one instruction.  fminf() first canonicalises an operand the compiler cannot prove
+// quiet -- the walk's best_up, carried round the loop, costs a v_max_f32 x, x in every node visit -- and then issues this same v_min_f32:
+// for operands that are not NaN the result has the same bits.
+__device__ __forceinline__ float rtx_min_f32_bits(float a, float b)
+{
+    float m;
+    asm("v_min_f32 %0, %1, %2" : "=v"(m) : "v"(a), "v"(b));
+    return m;
+}
+
 constexpr int kBvhQueue = 8;                // candidate shapes a lane may hold between two exact passes
 constexpr uint32_t kQueueTri = 0x80000000u; // queue entry: a triangle filter record (else a local sphere index)
 
@@ -496,6 +506,9 @@ __device__ __forceinline__ void sphere_step(const float4 *__restrict__ nodes, co
 #ifndef RTX_Q3_SORT64
 #define RTX_Q3_SORT64 1
 #endif
+#ifndef RTX_Q3_MIN_BITS
+#define RTX_Q3_MIN_BITS 1                     // sphere_node_step_q3: 1 = the smaller limit by rtx_min_f32_bits; 0 = by fminf (one v_max x, x more per visit)
+#endif
 #ifndef RTX_Q3_PUSH_ALL
 #define RTX_Q3_PUSH_ALL 1                     // sphere_node_step_q3: 1 = all four links written, the nearest read back; 0 = the counted pushes
 #endif
@@ -509,11 +522,12 @@ __device__ __forceinline__ void sphere_step_q3(const float4 *__restrict__ qnodes
 {
     const float4 *np = qnodes + 4 * (size_t)node;
     const float4 h0 = np[0], h1 = np[1], h2 = np[2], h3 = np[3];
-    const float Sx = h0.w * q.ix, Sy = h1.x * q.iy, Sz = h1.y * q.iz;
-    const float Ox = __builtin_fmaf(h0.x, q.ix, q.nx), Oy = __builtin_fmaf(h0.y, q.iy, q.ny), Oz = __builtin_fmaf(h0.z, q.iz, q.nz);
-    const uint32_t lox = __float_as_uint(h1.z), loy = __float_as_uint(h1.w), loz = __float_as_uint(h2.x);
-    const uint32_t hix = __float_as_uint(h2.y), hiy = __float_as_uint(h2.z), hiz = __float_as_uint(h2.w);
-    const uint32_t lk[4] = { __float_as_uint(h3.x), __float_as_uint(h3.y), __float_as_uint(h3.z), __float_as_uint(h3.w) };
+    // {link0, ox, link1, oy} {link2, oz, link3, sx} {sy, sz, lox, loy} {loz, hix, hiy, hiz} (rtx_bvh.h BvhQ3Node)
+    const float Sx = h1.w * q.ix, Sy = h2.x * q.iy, Sz = h2.y * q.iz;
+    const float Ox = __builtin_fmaf(h0.y, q.ix, q.nx), Oy = __builtin_fmaf(h0.w, q.iy, q.ny), Oz = __builtin_fmaf(h1.y, q.iz, q.nz);
+    const uint32_t lox = __float_as_uint(h2.z), loy = __float_as_uint(h2.w), loz = __float_as_uint(h3.x);
+    const uint32_t hix = __float_as_uint(h3.y), hiy = __float_as_uint(h3.z), hiz = __float_as_uint(h3.w);
+    const uint32_t lk[4] = { __float_as_uint(h0.x), __float_as_uint(h0.z), __float_as_uint(h1.x), __float_as_uint(h1.z) };
     const float e = ray_slack(q);
     float tc[4];
     uint32_t lnk[4], typ[4];
@@ -682,11 +696,12 @@ __device__ __forceinline__ void sphere_node_step_q3(const float4 *__restrict__ q
         const float4 *np = qnodes + 4 * (size_t)node;
         h0 = np[0]; h1 = np[1]; h2 = np[2]; h3 = np[3];
     }
-    const float Sx = h0.w * q.ix, Sy = h1.x * q.iy, Sz = h1.y * q.iz;
-    const float Ox = __builtin_fmaf(h0.x, q.ix, q.nx), Oy = __builtin_fmaf(h0.y, q.iy, q.ny), Oz = __builtin_fmaf(h0.z, q.iz, q.nz);
-    const uint32_t lox = __float_as_uint(h1.z), loy = __float_as_uint(h1.w), loz = __float_as_uint(h2.x);
-    const uint32_t hix = __float_as_uint(h2.y), hiy = __float_as_uint(h2.z), hiz = __float_as_uint(h2.w);
-    const uint32_t lk[4] = { __float_as_uint(h3.x), __float_as_uint(h3.y), __float_as_uint(h3.z), __float_as_uint(h3.w) };
+    // {link0, ox, link1, oy} {link2, oz, link3, sx} {sy, sz, lox, loy} {loz, hix, hiy, hiz} (rtx_bvh.h BvhQ3Node)
+    const float Sx = h1.w * q.ix, Sy = h2.x * q.iy, Sz = h2.y * q.iz;
+    const float Ox = __builtin_fmaf(h0.y, q.ix, q.nx), Oy = __builtin_fmaf(h0.w, q.iy, q.ny), Oz = __builtin_fmaf(h1.y, q.iz, q.nz);
+    const uint32_t lox = __float_as_uint(h2.z), loy = __float_as_uint(h2.w), loz = __float_as_uint(h3.x);
+    const uint32_t hix = __float_as_uint(h3.y), hiy = __float_as_uint(h3.z), hiz = __float_as_uint(h3.w);
+    const uint32_t lk[4] = { __float_as_uint(h0.x), __float_as_uint(h0.z), __float_as_uint(h1.x), __float_as_uint(h1.z) };
     const float e = ray_slack(q);
     const bool gx = q.ix < 0.0f, gy = q.iy < 0.0f, gz = q.iz < 0.0f;                 // (sphere_step_q3: near / far plane by the sign)
     const uint32_t nxw = gx ? hix : lox, fxw = gx ? lox : hix;
@@ -706,7 +721,11 @@ __device__ __forceinline__ void sphere_node_step_q3(const float4 *__restrict__ q
         const float tn_lo = __builtin_fmaf(tn, 1.0f - 4.76837158e-7f, -e);
         const float tf_hi = __builtin_fmaf(tf, 1.0f + 4.76837158e-7f, e);
         // (one compare against the smaller of the two limits; type 7 is an empty slot: one select for both conditions)
+#if RTX_Q3_MIN_BITS
+        const bool enter = (tn_lo <= rtx_min_f32_bits(tf_hi, best_up)) & (lk[c] < 0xE0000000u);
+#else
         const bool enter = (tn_lo <= fminf(tf_hi, best_up)) & (lk[c] < 0xE0000000u);
+#endif
 #if RTX_Q3_PUSH_ALL
         n_enter += enter ? 1u : 0u;
         const float key = enter ? tn_lo : -__builtin_inff();
@@ -727,7 +746,8 @@ __device__ __forceinline__ void sphere_node_step_q3(const float4 *__restrict__ q
 #define RTX_CSWAP(i, j) { double lo_, hi_; rtx_minmax_f64_bits(kd[i], kd[j], lo_, hi_); kd[i] = hi_; kd[j] = lo_; }
     RTX_CSWAP(0, 1) RTX_CSWAP(2, 3) RTX_CSWAP(0, 2) RTX_CSWAP(1, 3) RTX_CSWAP(1, 2)
 #undef RTX_CSWAP
-    if (sp + 3u <= (uint32_t)STACK) {                    // (row STACK, the sink of the other form, is the fourth row of sp = STACK - 3)
+    static_assert(STACK >= 3, "the room test below is sp <= STACK - 3");
+    if (sp <= (uint32_t)(STACK - 3)) {                   // room for three rows, without the add (row STACK, the sink of the other form, is the fourth row of sp = STACK - 3)
         uint32_t *const row = lds_stack + ((size_t)sp * kBvhThreads + tid);
 #pragma unroll
         for (uint32_t i = 0; i < 4; ++i) row[i * kBvhThreads] = (uint32_t)__double2loint(kd[i]);
