@@ -395,6 +395,21 @@ public:
         check(rtx_render_blocks_accumulate(h_, (uint32_t)width, (uint32_t)height, (uint32_t)block_rows, (uint32_t)part, (uint32_t)n_parts,
                                            sample_begin, n_samples, d_sum, d_sum_sq, hip_stream, stats));
     }
+    // refinement to a noise threshold, decided on the device (rtx_render_blocks_refine): every pixel of render_blocks_accumulate's band
+    // whose summed variance of the mean exceeds (threshold * (mean + floor))^2 and that has fewer than max_samples samples gets n_more
+    // further samples per round, folded into d_sum / d_sum_sq; d_extra (one zeroed uint32 per pixel) counts each pixel's samples beyond
+    // sample_begin.  Returns {pixels that traced, samples traced, pixels still selected}: [2] == 0 is the stop signal
+    std::array<std::uint64_t, 3> refine(std::size_t width, std::size_t height, std::size_t block_rows, std::size_t part, std::size_t n_parts,
+                                        std::uint64_t sample_begin, std::uint32_t n_more, std::uint32_t max_samples, std::uint32_t rounds,
+                                        double threshold, double floor, double *d_sum, double *d_sum_sq, std::uint32_t *d_extra,
+                                        void *hip_stream = nullptr, RtxStats *stats = nullptr)
+    {
+        std::array<std::uint64_t, 3> result{};
+        check(rtx_render_blocks_refine(h_, (uint32_t)width, (uint32_t)height, (uint32_t)block_rows, (uint32_t)part, (uint32_t)n_parts,
+                                       sample_begin, n_more, max_samples, rounds, threshold, floor, d_sum, d_sum_sq, d_extra,
+                                       result.data(), hip_stream, stats));
+        return result;
+    }
     void set_scratch_limit(std::uint64_t bytes) { check(rtx_scene_set_scratch_limit(h_, bytes)); }
     // closest_object for n rays of DEVICE memory (d_rays[n] -> d_hits[n], not overlapping), on the HIP stream it names; with
     // stats = nullptr the call returns once the work is enqueued

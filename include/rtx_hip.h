@@ -459,6 +459,46 @@ int32_t rtx_trace_paths(const RtxScene *scene, const RtxRay *rays, const uint64_
 int32_t rtx_scene_trace_samples(RtxSceneHandle scene, uint32_t width, uint32_t height, const uint64_t *d_ids, uint64_t n,
                                 double *d_rgb, uint32_t *d_segments, void *stream, RtxStats *stats);
 
+/* Refinement to a noise threshold, decided on the device: every pixel of rtx_render_blocks_accumulate's band (the same partition, the
+ * same row order) that the rule below selects gets further samples of the render, folded into the caller's running sums, for up to
+ * `rounds` rounds -- no ids, no colours and no choice travel through the host.
+ *  - d_sum, d_sum_sq: that call's DEVICE buffers (both required).  d_extra: one uint32 per pixel of the band, in the same order: the
+ *    samples the pixel has had beyond sample_begin.  A caller accumulates [0, sample_begin), zeroes d_extra with a memset, then calls
+ *    this, again and again if it likes.  The three buffers must not overlap.
+ *  - The rule.  Pixel p has n = sample_begin + d_extra[p] samples, sums S[3] and sums of squares Q[3].  It is selected iff
+ *    n < max_samples && (n < 2 || e > b * b), with dn = (double)n and
+ *        v_k = Q_k - S_k * S_k / dn                      (k = 0, 1, 2)
+ *        e   = ((v_0 + v_1) + v_2) / (dn - 1.0) / dn     the summed per-channel variance of the mean
+ *        m   = ((S_0 + S_1) + S_2) / dn
+ *        b   = threshold * (m + floor)
+ *    every operation a separately rounded f64 operation in exactly this order (plain numpy reproduces the decision bit for bit); a
+ *    comparison with a NaN is false, so a NaN pixel is selected only while n < 2.
+ *  - A round.  A selected pixel traces min(n_more, max_samples - n) further samples, numbered n, n + 1, ...: each the render's own
+ *    (render_pixel's ray for the key rng_key(seed, y * width + x, s), then render_ray, as rtx_scene_trace_samples runs it), and after
+ *    each sample c: d_sum[3 p + k] += c_k, then d_sum_sq[3 p + k] += c_k * c_k (the multiply rounded, then the add; plain adds, which
+ *    on buffers that hold zero bytes or earlier outputs give the bits of rtx_render_blocks_accumulate's fold).  d_extra[p] advances by
+ *    the samples traced.  Then the rule is evaluated again; the pixel goes on for up to `rounds` rounds in this call.
+ *  - A pixel's sequence depends on nothing but its own samples: one call with rounds = k equals k calls with rounds = 1, for any
+ *    partition; and a pixel with n samples holds the render's samples 0 .. n - 1 folded in order, so d_sum / n is the render's pixel at
+ *    rays_per_pixel = n, bit for bit.
+ *  - result: a HOST array of 3 uint64, or NULL: [0] pixels that traced at least one sample, [1] samples traced, [2] pixels the rule
+ *    still selects after the call -- 0 means converged or capped everywhere: the caller's stop signal.
+ *  - max_samples <= sample_begin: nothing is selected, nothing is touched.  A scene without objects: nothing is touched, nothing is
+ *    launched, result is all zeros (as rtx_render_blocks_accumulate).
+ *  - RTX_ERR_INVALID_ARGUMENT: a NULL d_sum, d_sum_sq or d_extra; overlapping buffers; n_more == 0 or rounds == 0; threshold or floor
+ *    NaN or negative; sample_begin > 2^32 - 1; a bad partition; 2^32 - 16 pixels per call or more.
+ * RtxConfig.rays_per_pixel is not read.  No sample records, survivors' queue or tile lists are allocated: the scratch limit does not
+ * apply.  Streams, the watchdog word, RtxConfig.tuning bits of RTX_TUNE_LAB_MASK and RTX_KERNEL_EXACT (every segment swept): as
+ * rtx_scene_trace_samples.  With result == NULL && stats == NULL the call only enqueues; else it synchronises.  stats: primary_rays =
+ * samples traced; segments, exact_tests, filter_tests, box_tests, trace_ms, trace_launches = 1 and kernel as rtx_scene_trace_samples.
+ * (DESIGN.md "Refinement to a threshold".) */
+int32_t rtx_render_blocks_refine(RtxSceneHandle scene, uint32_t width, uint32_t height,
+                                 uint32_t block_rows, uint32_t part, uint32_t n_parts,
+                                 uint64_t sample_begin, uint32_t n_more, uint32_t max_samples, uint32_t rounds,
+                                 double threshold, double floor,
+                                 double *d_sum, double *d_sum_sq, uint32_t *d_extra,
+                                 uint64_t *result, void *stream, RtxStats *stats);
+
 /* One-shot host form (upload to device 0, trace, copy back), as rtx_closest_hits.  ids / rgb / segments (or NULL): HOST arrays. */
 int32_t rtx_trace_samples(const RtxScene *scene, uint32_t width, uint32_t height, const uint64_t *ids, uint64_t n, double *rgb,
                           uint32_t *segments);

@@ -528,6 +528,25 @@ class SceneHandle:
                                                            C.c_void_p(int(stream)) if stream else None, C.byref(stats) if want_stats else None))
         return stats if want_stats else None
 
+    def render_refine(self, width, height, sample_begin, n_more, max_samples, threshold, floor, d_sum_ptr, d_sum_sq_ptr, d_extra_ptr, rounds=1,
+                      block_rows=8, part=0, n_parts=1, stream=None, want_stats=True, want_result=True):
+        """Refinement to a noise threshold, decided on the device (rtx_render_blocks_refine): every pixel of render_accumulate's band with
+        n = sample_begin + extra < max_samples samples whose summed variance of the mean exceeds (threshold * (mean + floor))^2 (or with
+        n < 2) gets n_more further samples per round, for up to `rounds` rounds, folded into the sums at the device addresses d_sum_ptr /
+        d_sum_sq_ptr; d_extra_ptr: one uint32 per pixel, zero before the first call, the samples each pixel has had beyond sample_begin.
+        Returns (counts, stats): counts = (pixels that traced, samples traced, pixels the rule still selects) or None without
+        want_result; with neither result nor stats the call only enqueues."""
+        stats = abi.RtxStats()
+        result = (C.c_uint64 * 3)()
+        self._check(self._lib.rtx_render_blocks_refine(self._h, int(width), int(height), int(block_rows), int(part), int(n_parts),
+                                                       int(sample_begin), int(n_more), int(max_samples), int(rounds), float(threshold), float(floor),
+                                                       C.c_void_p(int(d_sum_ptr)) if d_sum_ptr else None,
+                                                       C.c_void_p(int(d_sum_sq_ptr)) if d_sum_sq_ptr else None,
+                                                       C.c_void_p(int(d_extra_ptr)) if d_extra_ptr else None,
+                                                       result if want_result else None,
+                                                       C.c_void_p(int(stream)) if stream else None, C.byref(stats) if want_stats else None))
+        return (tuple(int(v) for v in result) if want_result else None), (stats if want_stats else None)
+
     def trace_samples(self, width, height, d_ids_ptr, n, d_rgb_ptr, d_segments_ptr=None, stream=None, want_stats=True):
         """Sparse samples of the render (rtx_scene_trace_samples): entry i is sample ids[2 i + 1] of pixel ids[2 i] (= y * width + x) of
         the width x height frame, bit for bit the render's.  d_ids_ptr / d_rgb_ptr / d_segments_ptr are device addresses of n uint64
@@ -541,7 +560,7 @@ class SceneHandle:
 
     def progressive(self, width, height, moments=True):
         """A Progressive accumulator of a width x height frame on this handle: add(n) more samples everywhere, refine(pixels, n) more
-        on chosen pixels, mean() / variance() at any time."""
+        on chosen pixels, converge(threshold) more where the device finds the noise above a threshold, mean() / variance() at any time."""
         return Progressive(self, width, height, moments)
 
     def closest_hits(self, d_rays_ptr, n, d_hits_ptr, stream=None, want_stats=True):
@@ -749,6 +768,27 @@ class Progressive:
         self.count.view(-1)[pix] += n
         self.traced += n * m
         return st
+
+    def converge(self, threshold, floor=0.01, step=8, max_samples=1024, rounds=1):
+        """refinement to a noise threshold on the device (rtx_render_blocks_refine): every pixel with fewer than max_samples samples whose
+        summed variance of the mean exceeds (threshold * (mean + floor))^2 gets `step` more samples per round, `rounds` rounds in this
+        call, each continuing from its own count.  Only while every pixel has at least the add()ed samples (always, unless counts were
+        edited by hand) and with moments=True.  Returns (pixels that traced, samples traced, pixels still selected): call again until
+        the last is 0."""
+        import torch
+        if self.sum_sq is None:
+            raise ValueError("converge() needs moments=True")
+        dev = self.sum.device
+        extra = self.count - self._uniform
+        if int(extra.min()) < 0 or int(extra.max()) >= 1 << 31:
+            raise ValueError("converge(): a pixel's count is below the add()ed samples, or 2^31 samples beyond them")
+        d_extra = extra.to(torch.int32).contiguous()                         # the uint32 counts beyond _uniform (below 2^31: the same bits)
+        torch.cuda.synchronize(dev)
+        counts, _ = self._hnd.render_refine(self.width, self.height, self._uniform, int(step), int(max_samples), threshold, floor,
+                                            self.sum.data_ptr(), self.sum_sq.data_ptr(), d_extra.data_ptr(), rounds=int(rounds), want_stats=False)
+        self.count = self._uniform + d_extra.to(torch.int64)
+        self.traced += counts[1]
+        return counts
 
     def mean(self):
         """sum / count per pixel: the render's frame at each pixel's own sample count, bit for bit (0 samples: NaN) -> numpy (h, w, 3)"""

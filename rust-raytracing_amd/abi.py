@@ -127,6 +127,9 @@ SYMBOLS = [
     ("rtx_trace_paths", C.c_int32, [C.POINTER(RtxScene), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("rtx_scene_trace_samples", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.POINTER(RtxStats)]),
+    ("rtx_render_blocks_refine", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32,
+                                             C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(RtxStats)]),
     ("rtx_trace_samples", C.c_int32, [C.POINTER(RtxScene), C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("rtx_scene_pixel_features", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(RtxStats)]),
     ("rtx_scene_pixel_features_blocks", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

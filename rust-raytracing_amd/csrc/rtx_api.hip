@@ -91,6 +91,10 @@ bool debug_prints()
 // other half could take); RTX_TUNE_HALVES keeps the experiment one bit away.
 constexpr uint64_t kHalvesBelowRays = 0;
 
+// The handle's work_counter: the ray queue's head, then what rtx_render_blocks_refine's launch reads and writes (rtx_launch.h: its three
+// counts, its rule).
+constexpr size_t kWorkWords = kQueryRefineWords;
+
 struct RtxSceneHandle_ {
     int device = 0;
     int n_cus = 0;
@@ -560,7 +564,7 @@ int32_t create_handle(const RtxScene *scene, const PackedScene &p, int32_t devic
 
     hipError_t e = hipMalloc((void **)&h->counters, sizeof(Counters) * kCounterShards);
     if (e == hipSuccess) e = hipMalloc((void **)&h->counters_stage1, sizeof(Counters) * kCounterShards);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->work_counter, sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMalloc((void **)&h->work_counter, kWorkWords * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMalloc((void **)&h->d_sv, sizeof(SceneView));
     if (e == hipSuccess) e = hipMalloc((void **)&h->d_rv, sizeof(RowsView));
     if (e == hipSuccess) e = hipHostMalloc((void **)&h->h_watchdog, 2 * sizeof(unsigned long long), hipHostMallocDefault);   // [1]: the second half's
@@ -1394,6 +1398,11 @@ struct QueryRequest {
     double *rgb = nullptr;                                       // kQueryPaths (rtx_scene_trace_paths): render_ray's colour of the path each ray starts,
     const uint64_t *ids = nullptr; uint32_t *segments = nullptr; //   the (pixel, sample) pairs that key the RNG (null: (i, 0)), its closest_object calls (or null)
     RtxPixelFeatures *features = nullptr;                        // kQueryFeatures (rtx_scene_pixel_features_blocks): n records, the band's rows in order
+    // kQueryRefine (rtx_render_blocks_refine): entry i = local pixel i of the band, its sums, its count beyond sample_begin, the rule
+    double *sum = nullptr, *sum_sq = nullptr; uint32_t *extra = nullptr;
+    double threshold = 0.0, floor = 0.0;
+    uint32_t sample_begin = 0, n_more = 0, max_samples = 0, rounds = 0;
+    uint64_t *result = nullptr;                                  //   HOST: the three counts (or null)
 };
 
 }  // namespace
@@ -1404,7 +1413,9 @@ static int32_t query_run(RtxSceneHandle_ *h, const QueryRequest &req, void *stre
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const uint64_t n = req.n;
     const bool pick = req.width != 0;                 // a frame's pixels, not the caller's rays: the pick form, the feature mode
+    const bool refine = req.mode == kQueryRefine;
     if (stats) std::memset(stats, 0, sizeof *stats);
+    if (req.result) req.result[0] = req.result[1] = req.result[2] = 0;
     if (n == 0) return RTX_OK;
     RTX_HIP_CHECK(hipSetDevice(h->device));
     if (int32_t rc = check_watchdog(h, false)) return rc;
@@ -1432,6 +1443,11 @@ static int32_t query_run(RtxSceneHandle_ *h, const QueryRequest &req, void *stre
         }
         return RTX_OK;
     }
+    if (refine && h->sv.n_objects == 0) {                     // as rtx_render_blocks_accumulate: nothing is touched, nothing is launched
+        if (stats || req.result) RTX_HIP_CHECK(hipStreamSynchronize(stream));
+        if (stats) stats->kernel = RTX_KERNEL_EXACT;
+        return RTX_OK;
+    }
     if (pick) {                              // the pick buffer: one band of all rows, ray i = pixel i (row-major, row 0 = the reference's);
                                              // the feature buffers: the caller's band, entry i = its local pixel i
         if (int32_t rc = ensure_tables(h, req.width, req.height, req.row_begin, req.row_stride, req.row_block, req.n_rows, stream)) return rc;
@@ -1449,7 +1465,11 @@ static int32_t query_run(RtxSceneHandle_ *h, const QueryRequest &req, void *stre
         if (int32_t rc = grow((void **)&h->state, &h->state_bytes, query_spill_bytes(spill_entries, h->n_cus))) return rc;
     }
     if (int32_t rc = begin_launches(h, stream)) return rc;
-    RTX_HIP_CHECK(hipMemsetAsync(h->work_counter, 0, sizeof(unsigned long long), stream));
+    RTX_HIP_CHECK(hipMemsetAsync(h->work_counter, 0, (refine ? kQueryRefineRule : 1) * sizeof(unsigned long long), stream));
+    if (refine) {                                              // (pageable: staged before return)
+        const QueryRefineRule rule{ req.threshold, req.floor, req.sample_begin, req.n_more, req.max_samples, req.rounds };
+        RTX_HIP_CHECK(hipMemcpyAsync(h->work_counter + kQueryRefineRule, &rule, sizeof rule, hipMemcpyHostToDevice, stream));
+    }
     QueryArgs qa{};
     qa.rays = reinterpret_cast<const QueryRay *>(req.rays);
     qa.rv = pick ? h->d_rv : nullptr;
@@ -1457,18 +1477,29 @@ static int32_t query_run(RtxSceneHandle_ *h, const QueryRequest &req, void *stre
     if (req.mode == kQueryAnyHit) { qa.occluded = req.occluded; qa.t_max = req.t_max; }
     else if (req.mode == kQueryPaths) { qa.rgb = req.rgb; qa.ids = reinterpret_cast<const unsigned long long *>(req.ids); qa.segments = req.segments; }
     else if (req.mode == kQueryFeatures) qa.features = reinterpret_cast<QueryFeatures *>(req.features);
+    else if (refine) {
+        qa.sum = req.sum; qa.sum_sq = req.sum_sq; qa.extra = req.extra;
+    }
     else qa.hits = reinterpret_cast<QueryHit *>(req.hits);
     if (stats) RTX_HIP_CHECK(hipEventRecord(h->ev[0], stream));
     RTX_HIP_CHECK(launch_query_closest(h->d_sv, h->sv, qa, walk, spill_entries ? reinterpret_cast<uint32_t *>(h->state) : nullptr,
                                        spill_entries, h->n_cus, h->counters, h->work_counter, stream));
+    uint64_t counts[3] = { 0, 0, 0 };
+    if (refine && (stats || req.result)) {                     // the three counts: a blocking copy behind the launch
+        if (stats) RTX_HIP_CHECK(hipEventRecord(h->ev[1], stream));
+        RTX_HIP_CHECK(hipStreamSynchronize(stream));
+        RTX_HIP_CHECK(hipMemcpy(counts, h->work_counter + kQueryRefineCounts, sizeof counts, hipMemcpyDeviceToHost));
+        if (req.result) std::memcpy(req.result, counts, sizeof counts);
+    }
     if (stats) {
-        RTX_HIP_CHECK(hipEventRecord(h->ev[1], stream));
+        if (!refine) RTX_HIP_CHECK(hipEventRecord(h->ev[1], stream));
         RTX_HIP_CHECK(hipEventSynchronize(h->ev[1]));
         float ms = 0.f;
         RTX_HIP_CHECK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
         CounterSums c;
         if (int32_t rc = read_counters(h->counters, c)) return rc;
         stats->segments = c.segments; stats->exact_tests = c.exact; stats->filter_tests = c.filter; stats->box_tests = c.box;
+        if (refine) stats->primary_rays = counts[1];
         if (req.mode == kQueryPaths) stats->primary_rays = n;
         if (req.mode == kQueryFeatures) stats->primary_rays = n * h->cfg.rays_per_pixel;
         stats->trace_ms = ms;
@@ -2167,6 +2198,35 @@ static int32_t pixel_features_band(RtxSceneHandle h, const char *who, uint32_t w
     QueryRequest req;
     req.mode = kQueryFeatures; req.width = width; req.height = height; req.n = n; req.features = d_features;
     req.row_begin = part * block_rows; req.row_stride = n_parts * block_rows; req.row_block = block_rows; req.n_rows = n_rows;
+    return query_run(h, req, stream, stats);
+}
+
+int32_t rtx_render_blocks_refine(RtxSceneHandle h, uint32_t width, uint32_t height, uint32_t block_rows, uint32_t part, uint32_t n_parts,
+                                 uint64_t sample_begin, uint32_t n_more, uint32_t max_samples, uint32_t rounds, double threshold, double floor,
+                                 double *d_sum, double *d_sum_sq, uint32_t *d_extra, uint64_t *result, void *stream, RtxStats *stats)
+{
+    const char *w = "rtx_render_blocks_refine: ";
+    if (!h) return fail(RTX_ERR_INVALID_ARGUMENT, std::string(w) + "null scene");
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (result) result[0] = result[1] = result[2] = 0;
+    if (block_rows == 0 || n_parts == 0 || part >= n_parts) return fail(RTX_ERR_INVALID_ARGUMENT, std::string(w) + "bad partition");
+    if ((uint64_t)block_rows * n_parts > 0xFFFFFFF0ull) return fail(RTX_ERR_INVALID_ARGUMENT, std::string(w) + "block_rows * n_parts overflows");
+    if (sample_begin > 0xFFFFFFFFull) return fail(RTX_ERR_INVALID_ARGUMENT, std::string(w) + "sample_begin exceeds 2^32-1");
+    if (n_more == 0 || rounds == 0) return fail(RTX_ERR_INVALID_ARGUMENT, std::string(w) + "n_more and rounds must be at least 1");
+    if (!(threshold >= 0.0) || !(floor >= 0.0)) return fail(RTX_ERR_INVALID_ARGUMENT, std::string(w) + "threshold and floor must be numbers >= 0");
+    if (!d_sum || !d_sum_sq || !d_extra) return fail(RTX_ERR_INVALID_ARGUMENT, std::string(w) + "null d_sum, d_sum_sq or d_extra");
+    const uint32_t n_rows = blocks_row_count(height, block_rows, part, n_parts);
+    const uint64_t n = (uint64_t)n_rows * width;
+    if (n >= 0xFFFFFFF0ull) return fail(RTX_ERR_INVALID_ARGUMENT, std::string(w) + "2^32 - 16 pixels per call or more");
+    const Range r[3] = { { d_sum, n * 3 * sizeof(double) }, { d_sum_sq, n * 3 * sizeof(double) }, { d_extra, n * sizeof(uint32_t) } };
+    if (ranges_overlap(r, 3)) return fail(RTX_ERR_INVALID_ARGUMENT, std::string(w) + "d_sum, d_sum_sq and d_extra overlap");
+    if (n == 0 || max_samples <= sample_begin) return RTX_OK;                   // no pixel, or nothing can be selected: nothing is touched
+    QueryRequest req;                                 // entry i = local pixel i of the band (query_refine_loop)
+    req.mode = kQueryRefine; req.width = width; req.height = height; req.n = n;
+    req.row_begin = part * block_rows; req.row_stride = n_parts * block_rows; req.row_block = block_rows; req.n_rows = n_rows;
+    req.sum = d_sum; req.sum_sq = d_sum_sq; req.extra = d_extra; req.result = result;
+    req.threshold = threshold; req.floor = floor;
+    req.sample_begin = (uint32_t)sample_begin; req.n_more = n_more; req.max_samples = max_samples; req.rounds = rounds;
     return query_run(h, req, stream, stats);
 }
 

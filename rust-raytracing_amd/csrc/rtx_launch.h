@@ -173,26 +173,43 @@ struct QueryArgs {
         QueryHit *hits;            // closest hits: n records
         uint8_t *occluded;         // any-hit: n bytes, 1 / 0
         double *rgb;               // paths: 3 n doubles, rgb[3 i .. 3 i + 2] = resulting_color of the path that starts with ray i
+        double *sum;               // refine: the band's running sums, 3 n doubles (rtx_render_blocks_accumulate's d_sum)
         QueryFeatures *features;   // features: n records, one per local pixel of the band (the lane that owns the pixel parks its sums here)
     };
     unsigned long long n;
     uint32_t walk;                 // 0: every ray is swept (RTX_KERNEL_EXACT / no usable tree); set by the launcher
     uint32_t mode;                 // kQueryClosest; kQueryAnyHit: occluded[i] = some object's distance is normal, positive and < t_max[i];
                                    // kQueryPaths: render_ray (scene.rs:223-242) from ray i; kQueryFeatures: the first hits of
-                                   // sv.rays_per_pixel gen_primary rays per pixel, folded (query_feature_loop)
+                                   // sv.rays_per_pixel gen_primary rays per pixel, folded (query_feature_loop); kQueryRefine:
+                                   // entry i = local pixel i of the band, sampled while the rule selects it (query_refine_loop)
     union {
         const double *t_max;       // any-hit: n limits, compared as given (null: +inf for every ray)
         const unsigned long long *ids;   // paths: n (pixel index, sample index) pairs that key the RNG (null: (i, 0)); the sample form
                                          // (rays == null; never null): the pair also names the ray -- gen_primary's of that pixel and sample
+        double *sum_sq;            // refine: the running sums of the samples' squares, 3 n doubles
     };
-    uint32_t *segments;            // paths: n closest_object counts, or null
+    union {
+        uint32_t *segments;        // paths: n closest_object counts, or null
+        uint32_t *extra;           // refine: n counts, the samples pixel i has had beyond sample_begin
+    };
 };
-constexpr uint32_t kQueryClosest = 0u, kQueryAnyHit = 1u, kQueryPaths = 2u, kQueryFeatures = 3u;
+// The refine mode's rule (rtx_render_blocks_refine), read from device memory -- the four words behind the launch's counts, so that the
+// kernel's arguments are the other modes': pixel i has n = sample_begin + extra[i] samples and is selected iff n < max_samples and
+// (n < 2 or e > b * b) -- refine_selected; a selected pixel traces n_more samples (fewer at max_samples) per round, `rounds` rounds
+struct QueryRefineRule {
+    double threshold, floor;
+    uint32_t sample_begin, n_more, max_samples, rounds;
+};
+static_assert(sizeof(QueryRefineRule) == 32, "QueryRefineRule");
+constexpr int kQueryRefineCounts = 1, kQueryRefineRule = 4, kQueryRefineWords = 8;   // u64 words of `head` in the refine mode
+constexpr uint32_t kQueryClosest = 0u, kQueryAnyHit = 1u, kQueryPaths = 2u, kQueryFeatures = 3u, kQueryRefine = 4u;
 uint32_t query_tree_kind(const SceneView &sv);        // 0 no walk, 1 sphere tree, 2 a tree that holds triangles
 uint32_t query_spill_entries(const SceneView &sv);    // HBM stack entries per lane a walk may need beyond its LDS rows
 size_t query_spill_bytes(uint32_t entries, int n_cus);
-// head: a zeroed u64 (the ray queue's head); spill: query_spill_bytes(spill_entries, n_cus) bytes (fewer entries than
-// query_spill_entries: a deeper stack overflows, that ray is swept -- the same bits)
+// head: a zeroed u64 (the ray queue's head), in the refine mode followed by three more zeroed words -- the pixels that traced a sample,
+// the samples traced, the pixels the rule still selects (one atomic per wave and word at its end) -- and the QueryRefineRule; spill:
+// query_spill_bytes(spill_entries, n_cus) bytes (fewer entries than query_spill_entries: a deeper stack overflows, that ray is swept --
+// the same bits)
 hipError_t launch_query_closest(const SceneView *d_sv, const SceneView &sv, const QueryArgs &qa, bool walk, uint32_t *spill,
                                 uint32_t spill_entries, int n_cus, Counters *counters, unsigned long long *head, hipStream_t stream);
 

@@ -33,6 +33,11 @@
 // render_pixel's own ray for its (pixel, sample) pair with gen_primary on the full frame's RowsView where the path mode reads the
 // caller's ray -- a launch-uniform choice at the take, everything after it unchanged.
 //
+// The refine mode (QueryArgs.mode, rtx_render_blocks_refine; DESIGN.md "Refinement to a threshold"): adaptive sampling decided on the
+// device -- the fifth launch-uniform loop of the same two instances.  A lane owns a PIXEL of the band while the noise rule selects it:
+// the rule is evaluated on the pixel's running sums at the take, each path is the sample form's, and its colour is folded into the
+// sums in memory at the path's end (query_refine_loop).
+//
 // The feature mode (QueryArgs.mode, rtx_scene_pixel_features; DESIGN.md "Pixel features"): the denoiser's guide buffers -- the fourth
 // launch-uniform loop of the same two instances.  A lane owns a PIXEL of the band: for every sample it builds render_pixel's own
 // lens-jittered ray (gen_primary), asks query_closest_ray, and adds the winner's colours, normal and distance to the sums, which live in
@@ -526,6 +531,123 @@ __device__ __forceinline__ void query_feature_loop(const SceneView &sv, const Qu
     }
 }
 
+// ---- the refine mode -----------------------------------------------------------------------------------------------------------
+// The rule of rtx_render_blocks_refine for a pixel with n samples, sums s and sums of squares q: every operation one rounded f64
+// operation in the header's order (-ffp-contract=off), every comparison with a NaN false.
+__device__ __forceinline__ bool refine_selected(const QueryRefineRule &rule, uint32_t n, double s0, double s1, double s2, double q0, double q1,
+                                                double q2)
+{
+    if (n >= rule.max_samples) return false;
+    if (n < 2u) return true;
+    const double dn = (double)n;
+    const double v0 = q0 - s0 * s0 / dn, v1 = q1 - s1 * s1 / dn, v2 = q2 - s2 * s2 / dn;
+    const double e = ((v0 + v1) + v2) / (dn - 1.0) / dn;                 // the summed per-channel variance of the mean
+    const double m = ((s0 + s1) + s2) / dn;
+    const double b = rule.threshold * (m + rule.floor);
+    return e > b * b;
+}
+
+// Entry i is local pixel i of the band (qa.rv is the band's RowsView, as the feature mode's).  The lane that takes it reads the pixel's
+// count and sums, evaluates the rule and either starts the pixel's next sample or stays free -- and the wave keeps taking until no lane
+// is free or the queue is dry, BEFORE the walk: an iteration costs the other lanes a whole segment walk, and most entries are not
+// selected.  From there the loop is the path loop's: one closest_object call and advance_and_shade per iteration.  A lane owns its
+// pixel until the rule, the cap or the rounds stop it: at a path's end the colour is added to the pixel's sums in memory (plain adds;
+// the square is rounded before its add), and the lane either goes on with the next sample of the round or evaluates the rule at the
+// round's end.  What a lane carries across the walk is k, the samples it has traced for its pixel in this call: the sample index is
+// sample_begin + extra[pixel] + k (extra[pixel] is written when the lane lets go of the pixel), the round is k / n_more; the draw index
+// is derived from the bounce count.  The three counts of the call are wave-uniform: the lanes' events of an iteration are flags,
+// counted by ballot at the top of the next one, and added to the words behind the queue's head once per wave.  The rule is read from
+// device memory behind those words, so the kernel's arguments -- which every loop of the kernel holds in registers -- are the other
+// modes'.  A loop of its own, entered once per launch: with the take and the fold inside query_path_loop, the path legs of the joint
+// scene ran 23 % slower.
+template <bool TRIS>
+__device__ __forceinline__ void query_refine_loop(const SceneView &sv, const QueryArgs &qa, const float4 *__restrict__ nodes, const LeafArrays &la,
+                                                  const MeshArrays &ma, uint32_t *ls, uint32_t *lq, uint32_t tid, uint32_t *__restrict__ spill,
+                                                  uint32_t spill_entries, size_t spill_stride, size_t glane, unsigned long long *__restrict__ head,
+                                                  unsigned long long &segs, unsigned long long &exact, unsigned long long &box_tests,
+                                                  unsigned long long &leaf_filters)
+{
+    const unsigned long long grab = wf_grab_size(qa.n);
+    const uint32_t bounce_limit = sv.max_bounces >= 0xFFFFFFF0ull ? 0xFFFFFFF0u : (uint32_t)sv.max_bounces + 1u;     // scene.rs:227
+    const QueryRefineRule rule = *reinterpret_cast<const QueryRefineRule *>(head + kQueryRefineRule);
+    const RowsView &rv = *qa.rv;
+    WfChunk ch{0ull, 0ull, false};
+    RayState r;
+    uint32_t idx = 0;                                                    // the lane's pixel (n < 2^32)
+    uint32_t k = 0;                                                      // the samples traced for it in this call
+    bool have = false, fresh = false, ev_sample = false, ev_still = false;   // a sample to start; this iteration's events
+    uint32_t n_pixels = 0, n_samples = 0, n_still = 0;                   // the wave's counts (wave-uniform; pixels <= n < 2^32)
+    r.pos = r.dir = r.result = r.light = mk(0.0, 0.0, 0.0);
+    r.key = 0; r.draw = 6; r.bounce = 0;
+    for (;;) {
+        n_samples += (uint32_t)__popcll(__ballot(ev_sample));
+        n_still += (uint32_t)__popcll(__ballot(ev_still));
+        ev_sample = ev_still = false;
+        if (n_samples >= 0x80000000u) {                                  // (wave-uniform: the 32-bit count never wraps)
+            if ((tid & 63u) == 0u) atomicAdd(head + kQueryRefineCounts + 1, (unsigned long long)n_samples);
+            n_samples = 0;
+        }
+        while (!ch.drained && __ballot(!have) != 0ull) {                 // wave-uniform: every free lane takes, until none is free
+            unsigned long long i = 0;
+            const bool mine = wf_take(ch, head, grab, qa.n, !have, i);
+            bool start = false;
+            if (mine) {
+                const uint32_t n = rule.sample_begin + qa.extra[i];
+                if (n < rule.max_samples) {
+                    start = n < 2u;
+                    if (!start) {
+                        const double *S = qa.sum + 3ull * i, *Q = qa.sum_sq + 3ull * i;
+                        start = refine_selected(rule, n, S[0], S[1], S[2], Q[0], Q[1], Q[2]);
+                    }
+                }
+            }
+            if (start) { idx = (uint32_t)i; k = 0; have = true; fresh = true; }
+            n_pixels += (uint32_t)__popcll(__ballot(start));
+        }
+        if (have && fresh) gen_primary(sv, rv, idx, rule.sample_begin + qa.extra[idx] + k, r);   // key (seed, y * width + x, sample), draws 0..5
+        fresh = false;
+        if (ch.drained && __ballot(have) == 0ull) break;                 // wave-uniform
+        if (!have) continue;
+        const RayX rx = make_rayx(r.pos, r.dir);
+        Hit h;
+        ++segs;
+        query_closest_ray<TRIS>(sv, qa.walk, nodes, la, ma, r.pos, r.dir, rx, h, ls, lq, tid, spill, spill_entries, spill_stride, glane, exact,
+                                box_tests, leaf_filters);
+        bool done = true;                                                // scene.rs:232: None ends the path
+        if (h.id != kNone) {
+            r.draw = 6u + 2u * r.bounce;                                 // (the draws of bounce b: not carried across the walk)
+            advance_and_shade(sv, h, r);
+            done = (r.bounce >= bounce_limit) || light_is_zero(r);       // scene.rs:227-228
+        }
+        if (done) {
+            double *S = qa.sum + 3ull * idx, *Q = qa.sum_sq + 3ull * idx;
+            const double s0 = S[0] + r.result.x, s1 = S[1] + r.result.y, s2 = S[2] + r.result.z;
+            const double q0 = Q[0] + r.result.x * r.result.x, q1 = Q[1] + r.result.y * r.result.y, q2 = Q[2] + r.result.z * r.result.z;
+            S[0] = s0; S[1] = s1; S[2] = s2;
+            Q[0] = q0; Q[1] = q1; Q[2] = q2;
+            ++k;
+            ev_sample = true;
+            const uint32_t n = rule.sample_begin + qa.extra[idx] + k;
+            if (n < rule.max_samples) {
+                const uint32_t rounds_done = k / rule.n_more;
+                if (k - rounds_done * rule.n_more != 0u) fresh = true;   // inside a round
+                else {                                                   // a round's end: the rule again
+                    const bool sel = refine_selected(rule, n, s0, s1, s2, q0, q1, q2);
+                    fresh = sel && rounds_done < rule.rounds;
+                    ev_still = sel && !fresh;
+                }
+            }
+            if (!fresh) { qa.extra[idx] += k; have = false; }
+            __asm__ volatile("" ::: "memory");                           // the sums stay in memory: nothing of them is held across the walk
+        }
+    }
+    if ((tid & 63u) == 0u) {
+        if (n_pixels) atomicAdd(head + kQueryRefineCounts, (unsigned long long)n_pixels);
+        if (n_samples) atomicAdd(head + kQueryRefineCounts + 1, (unsigned long long)n_samples);
+        if (n_still) atomicAdd(head + kQueryRefineCounts + 2, (unsigned long long)n_still);
+    }
+}
+
 template <bool TRIS>
 __global__ __launch_bounds__(kBvhThreads, kQueryWaves) void query_closest_kernel(const SceneView *__restrict__ svp, const QueryArgs qa,
                                                                                  const float4 *__restrict__ nodes, const LeafArrays la,
@@ -556,6 +678,9 @@ __global__ __launch_bounds__(kBvhThreads, kQueryWaves) void query_closest_kernel
     else if (qa.mode == kQueryFeatures)                                  // launch-uniform: and the feature mode
         query_feature_loop<TRIS>(sv, qa, nodes, la, ma, ls, lq, tid, spill, spill_entries, spill_stride, glane, head, segs, exact, box_tests,
                                  leaf_filters);
+    else if (qa.mode == kQueryRefine)                                    // launch-uniform: and the refine mode
+        query_refine_loop<TRIS>(sv, qa, nodes, la, ma, ls, lq, tid, spill, spill_entries, spill_stride, glane, head, segs, exact, box_tests,
+                                leaf_filters);
     else for (;;) {
         unsigned long long i = 0;
         const bool mine = wf_take(ch, head, grab, qa.n, true, i);         // (every lane of the wave is here: lane 0 takes the chunk)

@@ -143,6 +143,7 @@ extern "C" {
     pub fn rtx_scene_trace_paths(scene: RtxSceneHandle, d_rays: *const RtxRay, d_ids: *const u64, n: u64, d_rgb: *mut f64, d_segments: *mut u32, stream: *mut c_void, stats: *mut RtxStats) -> i32;
     pub fn rtx_trace_paths(scene: *const RtxScene, rays: *const RtxRay, ids: *const u64, n: u64, rgb: *mut f64, segments: *mut u32) -> i32;
     pub fn rtx_scene_trace_samples(scene: RtxSceneHandle, width: u32, height: u32, d_ids: *const u64, n: u64, d_rgb: *mut f64, d_segments: *mut u32, stream: *mut c_void, stats: *mut RtxStats) -> i32;
+    pub fn rtx_render_blocks_refine(scene: RtxSceneHandle, width: u32, height: u32, block_rows: u32, part: u32, n_parts: u32, sample_begin: u64, n_more: u32, max_samples: u32, rounds: u32, threshold: f64, floor: f64, d_sum: *mut f64, d_sum_sq: *mut f64, d_extra: *mut u32, result: *mut u64, stream: *mut c_void, stats: *mut RtxStats) -> i32;
     pub fn rtx_trace_samples(scene: *const RtxScene, width: u32, height: u32, ids: *const u64, n: u64, rgb: *mut f64, segments: *mut u32) -> i32;
     pub fn rtx_scene_pixel_features(scene: RtxSceneHandle, width: u32, height: u32, d_features: *mut RtxPixelFeatures, stream: *mut c_void, stats: *mut RtxStats) -> i32;
     pub fn rtx_scene_pixel_features_blocks(scene: RtxSceneHandle, width: u32, height: u32, block_rows: u32, part: u32, n_parts: u32, d_features: *mut RtxPixelFeatures, stream: *mut c_void, stats: *mut RtxStats) -> i32;

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Closest-hit, any-hit, path, feature and sample query rates (rtx_scene_closest_hits / rtx_scene_primary_hits / rtx_scene_any_hits /
-rtx_scene_trace_paths / rtx_scene_pixel_features / rtx_scene_trace_samples / rtx_render_blocks_accumulate), in Mrays/s (the path legs: Msegments/s) from RtxStats.trace_ms, on the scenes of the
+"""Closest-hit, any-hit, path, feature, sample and refinement query rates (rtx_scene_closest_hits / rtx_scene_primary_hits / rtx_scene_any_hits /
+rtx_scene_trace_paths / rtx_scene_pixel_features / rtx_scene_trace_samples / rtx_render_blocks_accumulate / rtx_render_blocks_refine), in Mrays/s (the path legs: Msegments/s) from RtxStats.trace_ms, on the scenes of the
 benchmark's C2 (10k spheres), C3 (100k triangles) and J1 (5k spheres + 50k triangles: a joint tree), built with scenes.py's
 generators and the same parameters:
 
@@ -25,6 +25,12 @@ generators and the same parameters:
                and at 0 (two lines; the second is what `features` at 1 spp and `paths_primary` trace), and rtx_render_rows of the frame
                at 1 spp (the same samples through the render's tiles and packets)
   samples_sparse  a random tenth of the frame's pixels, samples 0..7 of each, sample-major: per sample against samples_frame
+  refine       the 1920x1080 frame with the bench camera: rtx_render_blocks_accumulate of 8 samples, then ONE rtx_render_blocks_refine
+               call to max_samples = 64 (8 samples per round, 7 rounds, threshold 0.5, floor 0.01: on C2 the oracle's samples of twelve
+               rows of the frame leave 14 % of the pixels selected after the base; 0.4 leaves 15 %, 0.6 6 %), against
+               the same refinement as 7 calls of one round each and
+               rtx_scene_trace_samples over the identical (pixel, sample) list, sample-major -- alternating, two runs each, each the best
+               of --reps after a warm-up: pixels refined, samples traced, ms and ns per sample
 
     tools/query_rate.py [--rays 24] [--scenes C2,C3,J1] [--reps 3] [--exact-rays 20] [--legs incoherent,pick,...]
 
@@ -86,7 +92,8 @@ def primary_rays(rtx, cam, width, height):
 
 
 LEGS = ("incoherent", "pick", "exact", "any", "any_short", "any_aimed", "paths", "paths_1seg", "paths_pick", "render_pick", "paths_primary",
-        "features", "accumulate", "samples_frame", "samples_sparse")
+        "features", "accumulate", "samples_frame", "samples_sparse", "refine")
+REFINE = dict(base=8, step=8, cap=64, threshold=0.5, floor=0.01)
 
 
 def main():
@@ -119,6 +126,8 @@ def main():
             legs = [l for l in legs if l != "features"]
         if not hasattr(probe, "rtx_scene_trace_samples"):
             legs = [l for l in legs if not l.startswith("samples")]
+        if not hasattr(probe, "rtx_render_blocks_refine"):
+            legs = [l for l in legs if l != "refine"]
         have_accumulate = hasattr(probe, "rtx_render_blocks_accumulate")
     else:
         have_accumulate = True
@@ -219,6 +228,65 @@ def main():
                                           "msamples_per_s": round(k / (st.trace_ms * 1e-3) / 1e6, 1),
                                           "msegments_per_s": round(st.segments / (st.trace_ms * 1e-3) / 1e6, 1), "kernel": int(st.kernel)}), flush=True)
                     hnd.close()
+                continue
+            if leg == "refine":
+                k, r = W * H, REFINE
+                hnd = rtx.Scene.from_packed(cfg, rtx.Camera(*scenes.CAMERA), objs).upload(0)
+                d_sums = d_hits.view(torch.float64)[:6 * k]                          # d_sum, then d_sum_sq
+                d_extra = torch.zeros(k, dtype=torch.int32, device=dev)
+                d_sums.zero_()
+                torch.cuda.synchronize(dev)
+                st_base = hnd.render_accumulate(W, H, 0, r["base"], d_sums.data_ptr(), d_sums[3 * k:].data_ptr())
+                d_base = d_sums.clone()
+                rounds = (r["cap"] - r["base"] + r["step"] - 1) // r["step"]
+                counts = [None]
+
+                def refine():
+                    d_sums.copy_(d_base)
+                    d_extra.zero_()
+                    torch.cuda.synchronize(dev)
+                    counts[0], st = hnd.render_refine(W, H, r["base"], r["step"], r["cap"], r["threshold"], r["floor"], d_sums.data_ptr(),
+                                                      d_sums[3 * k:].data_ptr(), d_extra.data_ptr(), rounds=rounds)
+                    return st
+
+                def refine_calls():
+                    """the same refinement as `rounds` calls of one round each: a launch per round"""
+                    d_sums.copy_(d_base)
+                    d_extra.zero_()
+                    torch.cuda.synchronize(dev)
+                    tot = None
+                    for _ in range(rounds):
+                        c, st = hnd.render_refine(W, H, r["base"], r["step"], r["cap"], r["threshold"], r["floor"], d_sums.data_ptr(),
+                                                  d_sums[3 * k:].data_ptr(), d_extra.data_ptr(), rounds=1)
+                        if tot is None:
+                            tot = st
+                        else:
+                            tot.trace_ms += st.trace_ms; tot.segments += st.segments; tot.primary_rays += st.primary_rays
+                            tot.trace_launches += st.trace_launches
+                    assert tot.primary_rays == counts[0][1] and c[2] == 0, (tot.primary_rays, c)
+                    return tot
+
+                refine()
+                extra = d_extra.cpu().numpy()
+                top = int(extra.max())
+                pix = [np.nonzero(extra > s)[0] for s in range(top)]                 # sample-major: the pixels that got sample base + s
+                ids = np.concatenate([np.stack([p_, np.full(len(p_), r["base"] + s)], axis=1) for s, p_ in enumerate(pix)]).astype(np.int64)
+                d_ids = torch.from_numpy(np.ascontiguousarray(ids)).to(dev)
+                d_rgb = torch.empty(3 * len(ids), dtype=torch.float64, device=dev)
+                torch.cuda.synchronize(dev)
+                assert len(ids) == counts[0][1], (len(ids), counts[0])
+                print(json.dumps({"scene": name, "leg": leg, "form": "base", "samples": int(st_base.primary_rays),
+                                  "trace_ms": round(st_base.trace_ms, 3), "resolve_ms": round(st_base.resolve_ms, 3),
+                                  "selected_after_base": round(float((extra > 0).mean()), 4), **r}), flush=True)
+                for run in (1, 2):
+                    for form, fn in (("rtx_render_blocks_refine", refine), ("rtx_render_blocks_refine, a call per round", refine_calls),
+                                     ("rtx_scene_trace_samples", lambda: hnd.trace_samples(W, H, d_ids.data_ptr(), len(ids), d_rgb.data_ptr()))):
+                        st = best(fn)
+                        print(json.dumps({"scene": name, "leg": leg, "form": form, "run": run, "pixels": counts[0][0], "samples": len(ids),
+                                          "still_selected": counts[0][2], "segments": int(st.segments), "trace_ms": round(st.trace_ms, 3),
+                                          "ns_per_sample": round(st.trace_ms * 1e6 / len(ids), 3),
+                                          "msegments_per_s": round(st.segments / (st.trace_ms * 1e-3) / 1e6, 1), "kernel": int(st.kernel)}), flush=True)
+                hnd.close()
                 continue
             if leg == "render_pick":
                 cfg = cfg.with_focal_offset(0.0).with_non_focal_offset(0.0)
