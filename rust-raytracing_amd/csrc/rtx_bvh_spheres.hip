@@ -236,7 +236,7 @@ __global__ __launch_bounds__(kBvhThreads, kSphWavesPerSimd) void trace_bvh_spher
                     q.ix = q0.ix; q.iy = q0.iy; q.iz = q0.iz; q.nx = q0.nx; q.ny = q0.ny; q.nz = q0.nz;
                     q.e = ray32_slack(q0.nx, q0.ny, q0.nz, in32);
                     if constexpr (Q3 == 2)            // node visits and leaf visits apart (the default)
-                        sphere_walk_phased<STACK, SPILL>(nodes, la.sphere_f32, la.sphere_prims, q, sr, w_node, w_sp, &lds_stack[0][0],
+                        sphere_walk_phased<STACK, SPILL, RTX_WALK_INNER != 0>(nodes, la.sphere_f32, la.sphere_prims, q, sr, w_node, w_sp, &lds_stack[0][0],
                                                          lq, tid, spill, spill_entries, spill_stride, glane, best_up, qcnt,
                                                          overflow, nbox, nleaf, cut_walkers, kSphCutDone, n_alive, kSphLeafLanes RTX_PROF_PASS);
                     else

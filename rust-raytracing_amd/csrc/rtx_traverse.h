@@ -512,6 +512,9 @@ __device__ __forceinline__ void sphere_step(const float4 *__restrict__ nodes, co
 #ifndef RTX_Q3_PUSH_ALL
 #define RTX_Q3_PUSH_ALL 1                     // sphere_node_step_q3: 1 = all four links written, the nearest read back; 0 = the counted pushes
 #endif
+#ifndef RTX_WALK_INNER
+#define RTX_WALK_INNER 1                      // sphere_walk_phased: 1 = consecutive node visits in an inner loop; 0 = one decision per iteration, two arms
+#endif
 template <int STACK, bool SPILL, class RAY>
 __device__ __forceinline__ void sphere_step_q3(const float4 *__restrict__ qnodes, const float4 *__restrict__ leaf_f32,
                                                const uint32_t *__restrict__ leaf_prims, const RAY &q, const SphereRay &sr,
@@ -892,7 +895,21 @@ __device__ __forceinline__ void sphere_leaf_step(const float4 *__restrict__ leaf
 // The resumable walk (below) in this form.  `node` is a link: type 0 = a node, 1..6 = a leaf; kNone = the walk has ended.
 // (Measured and dropped, LAB_NOTEBOOK R3.11: a lane that pops a leaf putting it aside in a register and going on with the next
 // entry instead of waiting for the wave's next leaf visit -- 54.8 against 54.6 ms, 1 % more box tests from the later best_up.)
-template <int STACK, bool SPILL, class RAY>
+// INNER (what the render kernels pass unless built with -DRTX_WALK_INNER=0; the queries keep the other form): the same iterations,
+// laid out as an outer loop that takes the decision and runs a leaf visit, and an inner loop of the node visits that follow one
+// another -- 82 % of the iterations, usually several in a row (LAB_NOTEBOOK R3.12, R8.1).  The lanes whose walk has ended, or that
+// hold a leaf, skip the node step but stay in the inner loop as masked lanes: every exit is a scalar branch, the walking lanes of
+// the next iteration (`am`) are the ballot the cut test has just taken (the other form takes a third ballot for them), and `node`,
+// `sp`, `nbox` and `best_up` are not merged from two arms after every visit.
+// Why this is the other form's sequence of (kind of iteration, participating lanes): both forms decide an iteration from
+// lm = the lanes holding a leaf and am = the lanes holding any entry, by the same rule, run the same step for the same lanes -- a
+// step touches only its own lane's node, sp, stack column, queue column and counts -- and apply the same cut test to the same ballot
+// after it.  am of the other form is the mask of the lanes still inside its `while (node != kNone)`, i.e. ballot(node != kNone)
+// after the previous visit, which is am here; a lane with node == kNone is in neither lm nor am and runs no step, whether it has
+// left the loop (there) or waits in it (here).  So by induction over the iterations the states are equal: the order of a lane's
+// visits cannot change, and best_up, which falls only in a leaf visit, falls at the same iterations -- it cannot fall later.  With
+// nobody left walking the other form leaves through its loop condition, this one through `am == 0`, whatever the cut test said.
+template <int STACK, bool SPILL, bool INNER = false, class RAY>
 __device__ __forceinline__ void sphere_walk_phased(const float4 *__restrict__ qnodes, const float4 *__restrict__ leaf_f32,
                                                    const uint32_t *__restrict__ leaf_prims, const RAY &q, const SphereRay &sr,
                                                    uint32_t &node, uint32_t &sp, uint32_t *lds_stack, uint32_t *lds_q,
@@ -901,6 +918,38 @@ __device__ __forceinline__ void sphere_walk_phased(const float4 *__restrict__ qn
                                                    uint32_t &nbox, uint32_t &nleaf, uint32_t cut_walkers, uint32_t cut_done, uint32_t n_alive,
                                                    uint32_t leaf_lanes RTX_PROF_ARG)
 {
+    if constexpr (INNER) {
+#if defined(RTX_LAB) && defined(RTX_SPH_PROFILE)
+        static_assert(!INNER || RTX_SPH_PROFILE < 3 || RTX_SPH_PROFILE == 8 || RTX_SPH_PROFILE > 9,
+                      "RTX_SPH_PROFILE 3-7 and 9 count in the two-arm walk loop: build them with -DRTX_WALK_INNER=0");
+#endif
+        // (type = node >> 29: 0 a node, 1..6 a leaf, 7 = kNone -- an empty slot's link, the other type 7, is never entered)
+        unsigned long long am = __ballot((node >> 29) != 7u);
+        while (am != 0ull) {
+            const bool at_leaf = (node >> 29) - 1u < 6u;
+            unsigned long long lm = __ballot(at_leaf);
+            if ((uint32_t)__popcll(lm) >= leaf_lanes || lm == am) {             // a leaf visit
+                if (at_leaf)
+                    sphere_leaf_step<STACK, SPILL>(leaf_f32, leaf_prims, sr, node, sp, lds_stack, lds_q, tid, spill, spill_stride, glane,
+                                                   best_up, qcnt, overflow, nleaf);
+                am = __ballot((node >> 29) != 7u);
+                const uint32_t still = (uint32_t)__popcll(am);
+                if (still < cut_walkers && n_alive - still >= cut_done) return;
+            } else {
+                do {                                                            // a run of node visits
+                    if ((node >> 29) == 0u)
+                        sphere_node_step_q3<STACK, SPILL>(qnodes, q, node, sp, lds_stack, tid, spill, spill_entries, spill_stride, glane,
+                                                          best_up, overflow, nbox);
+                    am = __ballot((node >> 29) != 7u);
+                    const uint32_t still = (uint32_t)__popcll(am);
+                    if (still < cut_walkers && n_alive - still >= cut_done) return;
+                    if (am == 0ull) return;
+                    lm = __ballot((node >> 29) - 1u < 6u);
+                } while (!((uint32_t)__popcll(lm) >= leaf_lanes || lm == am));
+            }
+        }
+        return;
+    }
     while (node != kNone) {
         const bool at_leaf = (node >> 29) != 0u;
         const unsigned long long lm = __ballot(at_leaf), am = __ballot(true);
