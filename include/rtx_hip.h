@@ -615,6 +615,46 @@ int32_t rtx_debug_resolve_moments(const double *records, const uint32_t *mask, u
 int32_t rtx_debug_gather(int32_t form, const void *parts, uint32_t width, uint32_t height, uint32_t n, uint32_t cap_rows,
                          uint32_t block, int32_t flip, void *full);
 
+/* rtx_debug_path_bounds (lab library; the product returns RTX_ERR_UNSUPPORTED): what the tree walks' f32 bounds decide for single
+ * (ray, object) pairs.  Every result is decided in f64; WHICH shapes reach the f64 test is decided by f32 slab tests and f32 distance
+ * bounds with hand-derived margins, and a margin that is too small shows only for rays within a few f32 ulps of a box
+ * face, a tangent or an edge.  For entry i < n the host finds the path root -> leaf of Scene.objects[objects[i]] in the scene's resident
+ * tree; one device thread then runs the walks' own device functions along that path with the bound best_up[i]: per step the slab test
+ * of the object's child, then the leaf bounds of the object's own record.  rays, objects, best_up and out are HOST arrays; the hook
+ * copies, launches once, copies back and synchronises.
+ * form: bit 0 -- an origin beyond origin_limit is walked with the f64 slab test (Ray64), else with the slack of Ray32S;
+ *       bit 1 -- the 64-byte nodes (a sphere tree: the sphere_node_step_q3 visit on an empty stack, the entered children read back from
+ *                its stack -- it has no f64 form; a pure (x, y)-footprint tree: qrect_entry), else the 128-byte nodes (box_entry32, or
+ *                rect_entry32 where the node is a footprint node); RTX_ERR_INVALID_ARGUMENT when the tree has no 64-byte nodes;
+ *       bits 8-9 -- the leaf test: 0 the phased walks' (sphere_leaf_step_at on a one-record leaf; tri_filter_sign + tri_bounds),
+ *                1 sphere_step's inline leaf and 2 mesh_step's inline leaf (sphere or triangle), each through a 128-byte node whose only
+ *                child is a one-record leaf of the object in an unbounded box; 3 sph_packet_leaf_test, the packet kernel's test of one
+ *                sphere record (a triangle: flag 64).
+ * out: 8 words per entry --
+ *   [0] flags: bits 0-1 the ray form the origin selects (0 Ray32: |o|_inf <= origin_limit, 1 Ray32S with its slack, 2 Ray64, 3 NO WALK:
+ *       beyond 2^27 origin_limit, a NaN origin or a direction that is not of unit length -- the kernels sweep, words 1..7 are 0);
+ *       4 the object is in the tree (else words 1..7 are 0: planes, shapes kept outside the tree); 8 the leaf test made it a CANDIDATE
+ *       under best_up[i]; 16 CERTAIN: the same leaf test started from best_up = +inf lowered the bound; 32 a triangle; 64 the form
+ *       does not exist for this element (words 1..7 are then not meaningful)
+ *   [1] the path's length in node visits   [2] how many of them entered the object's child under best_up[i]
+ *   [3] the largest entry distance those slab tests returned (f32 bits; -inf: none -- the 64-byte sphere visit returns none)
+ *   [4] t_lo (f32 bits; +inf: not a candidate under either bound)   [5] t_hi: the bound after the leaf test from +inf (+inf: not certain)
+ *   [6] best_up[i] after the leaf test   [7] the first step that did not enter (~0: none).
+ * Optional HOST outputs (null: not wanted) -- the resident data those functions read, so that a model of the f32 arithmetic can be
+ * run on the same bits:
+ *   scene_info[16]: the centre the f32 records are relative to (3), sphere_cmax, origin_limit, inv_max, tri_extent, the tree's flags
+ *       (rtx_debug_host_scene, stats[7]), depth, wide nodes, triangle records in the tree, spheres; written even when n is 0
+ *   records: 16 words per entry -- a sphere's leaf record {c - centre, |r| rounded up}; a triangle's A, B (the filter record) and g0, g1
+ *       (tri_bounds' record); zeros for an object outside the tree
+ *   path_data: 16 words per entry and step, path_steps steps per entry (further steps are not stored) -- word 0 the layout, word 15
+ *       the node's link: 0 a 128-byte child {lo.xyz, hi.xyz}; 1 a footprint child {lo.x, lo.y, hi.x, hi.y}; 2 a 64-byte sphere child
+ *       {o.xyz, s.xyz} and the child's six bytes {lo.xyz, hi.xyz} as integers; 3 a 64-byte footprint child {ox, oy, sx, sy} and the
+ *       words {lo.x | hi.x << 16, lo.y | hi.y << 16}.
+ * tests/test_walk_bounds.py holds these to the f64 text of the reference's distance functions on rays aimed at the margins. */
+int32_t rtx_debug_path_bounds(RtxSceneHandle scene, const RtxRay *rays, const uint32_t *objects, const float *best_up, uint64_t n,
+                              uint32_t form, uint32_t *out, double *scene_info, uint32_t *records, uint32_t *path_data,
+                              uint32_t path_steps);
+
 /* Test hook, needs no GPU: runs the host half of rtx_scene_upload (scene packing, filter records, the SAH build of
  * the flat BVH -- SURVEY 8f row N2; the reference's analogue is gpu_state.rs:53-77) and checks the tree's
  * invariants: every child box inside its parent's, every sphere / triangle-footprint inside its leaf's box, every

@@ -498,6 +498,26 @@ class SceneHandle:
         self._check(self._lib.rtx_debug_paths(self._h, int(width), int(height), int(row), int(max_steps), steps.ctypes.data, counts.ctypes.data))
         return steps, counts
 
+    def debug_path_bounds(self, origins, directions, objects, best_up, form=0, path_steps=0, want_records=False):
+        """What the tree walks' f32 bounds decide for the pairs (ray i, Scene.objects[objects[i]]) under the bound best_up[i]
+        (rtx_debug_path_bounds, include/rtx_hip.h: the form bits and the eight words; a lab-library hook: upload with lab=True).
+        best_up: a scalar or n float32 values.  Returns an (n, 8) uint32 array (words 3..6 are float32 bit patterns); with
+        want_records or path_steps > 0 a tuple (out, scene_info (16,) float64, records (n, 16) uint32, path_data (n, path_steps, 16)
+        uint32) -- the resident data the bound functions read."""
+        rays = make_rays(origins, directions)
+        n = len(rays)
+        obj = np.ascontiguousarray(np.broadcast_to(np.asarray(objects, dtype=np.uint32), (n,)))
+        bu = np.ascontiguousarray(np.broadcast_to(np.asarray(best_up, dtype=np.float32), (n,)))
+        out = np.zeros((n, 8), dtype=np.uint32)
+        extra = bool(want_records) or int(path_steps) > 0
+        info = np.zeros(16, dtype=np.float64)
+        rec = np.zeros((n, 16), dtype=np.uint32)
+        path = np.zeros((n, int(path_steps), 16), dtype=np.uint32)
+        self._check(self._lib.rtx_debug_path_bounds(self._h, rays.ctypes.data, obj.ctypes.data, bu.ctypes.data, n, int(form), out.ctypes.data,
+                                                    info.ctypes.data if extra else None, rec.ctypes.data if extra else None,
+                                                    path.ctypes.data if int(path_steps) > 0 else None, int(path_steps)))
+        return (out, info, rec, path) if extra else out
+
     def render_rows(self, width, height, row_begin, row_stride, n_rows, d_out_ptr, stream=None, want_stats=True):
         """d_out_ptr: device address of n_rows*width*3 doubles (e.g. a torch tensor's data_ptr())."""
         stats = abi.RtxStats()

@@ -141,6 +141,8 @@ SYMBOLS = [
     ("rtx_debug_store_samples", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
     ("rtx_debug_resolve", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int32,
                                       C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
+    ("rtx_debug_path_bounds", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_uint32]),
     ("rtx_debug_resolve_moments", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
                                               C.c_void_p, C.c_uint64]),
     ("rtx_debug_gather", C.c_int32, [C.c_int32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32,

@@ -2104,6 +2104,190 @@ int32_t rtx_debug_gather(int32_t form, const void *parts, uint32_t width, uint32
 #endif
 }
 
+int32_t rtx_debug_path_bounds(RtxSceneHandle h, const RtxRay *rays, const uint32_t *objects, const float *best_up, uint64_t n, uint32_t form,
+                              uint32_t *out, double *scene_info, uint32_t *records, uint32_t *path_data, uint32_t path_steps)
+{
+#ifndef RTX_LAB
+    (void)h; (void)rays; (void)objects; (void)best_up; (void)n; (void)form; (void)out; (void)scene_info; (void)records; (void)path_data;
+    (void)path_steps;
+    return fail(RTX_ERR_UNSUPPORTED, "rtx_debug_path_bounds: a lab-library hook (librtx_hip_lab.so)");
+#else
+    if (!h) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_path_bounds: null scene");
+    if (scene_info) {
+        const SceneView &v = h->sv;
+        const double info[16] = { v.sphere_center[0], v.sphere_center[1], v.sphere_center[2], v.sphere_cmax, (double)v.bvh_origin_limit,
+                                  (double)v.bvh_inv_max, v.tri_extent, (double)v.bvh_flags, (double)v.bvh_depth, (double)v.n_bvh_nodes,
+                                  (double)v.n_tri_tree, (double)v.n_spheres, 0.0, 0.0, 0.0, 0.0 };
+        std::memcpy(scene_info, info, sizeof info);
+    }
+    if (n == 0) return RTX_OK;
+    if (!rays || !objects || !best_up || !out) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_path_bounds: null argument");
+    if (n > (1ull << 22) || (path_data && n * (uint64_t)path_steps > (1ull << 24)))
+        return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_path_bounds: too large");
+    if ((form & ~0x303u) != 0u) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_path_bounds: unknown form");
+    const SceneView &sv = h->sv;
+    if ((form & 2u) && !((sv.bvh_flags & 16u) && sv.bvh_q3nodes) && !((sv.bvh_flags & 8u) && sv.bvh_qnodes))
+        return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_path_bounds: this scene's tree has no 64-byte nodes");
+    if (sv.n_bvh_nodes > (1u << 22)) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_path_bounds: the tree is too large");
+    RTX_HIP_CHECK(hipSetDevice(h->device));
+    RTX_HIP_CHECK(hipDeviceSynchronize());
+    // the resident tree and the maps from leaf entries to Scene.objects, as the device holds them
+    const bool s_tree = (sv.bvh_flags & 1u) != 0u, t_tree = (sv.bvh_flags & 2u) != 0u;
+    std::vector<Bvh4Node> nodes(sv.n_bvh_nodes);
+    std::vector<uint32_t> prims(s_tree ? sv.n_spheres : 0u), sphere_id(sv.n_spheres), tri_fidx(t_tree ? sv.n_tri_tree : 0u);
+    std::vector<TriX> tris(t_tree ? sv.n_tris : 0u);
+    auto down = [](void *dst, const void *src, size_t bytes) { return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess; };
+    RTX_HIP_CHECK(down(nodes.data(), sv.bvh_nodes, nodes.size() * sizeof(Bvh4Node)));
+    RTX_HIP_CHECK(down(prims.data(), sv.bvh_prims, prims.size() * sizeof(uint32_t)));
+    RTX_HIP_CHECK(down(sphere_id.data(), sv.sphere_id, sphere_id.size() * sizeof(uint32_t)));
+    RTX_HIP_CHECK(down(tri_fidx.data(), sv.tri_fidx, tri_fidx.size() * sizeof(uint32_t)));
+    RTX_HIP_CHECK(down(tris.data(), sv.tris, tris.size() * sizeof(TriX)));
+    // Scene.objects index -> leaf entry (kQueueTri: a triangle filter record of the tree)
+    constexpr uint32_t kTriEntry = 0x80000000u, kNoEntry = 0xFFFFFFFFu;
+    std::vector<uint32_t> entry_of(sv.n_objects, kNoEntry);
+    {
+        std::vector<uint32_t> prim_entry(sv.n_spheres, kNoEntry);
+        for (size_t k = 0; k < prims.size(); ++k) if (prims[k] < prim_entry.size()) prim_entry[prims[k]] = (uint32_t)k;
+        for (size_t s = 0; s < sphere_id.size(); ++s)
+            if (prim_entry[s] != kNoEntry && sphere_id[s] < sv.n_objects) entry_of[sphere_id[s]] = prim_entry[s];
+        for (size_t r = 0; r < tri_fidx.size(); ++r)
+            if (tri_fidx[r] < tris.size() && tris[tri_fidx[r]].id < sv.n_objects) entry_of[tris[tri_fidx[r]].id] = (uint32_t)r | kTriEntry;
+    }
+    // every leaf entry's path: one row of {link, child slot} per entry, found by one walk of the whole tree
+    const uint32_t stride = std::max(sv.bvh_depth, 1u);
+    const size_t n_rows = prims.size() + tri_fidx.size();
+    std::vector<uint32_t> steps(2 * n_rows * stride, 0u), lens(n_rows + 1, 0u);
+    auto bits = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
+    if (!nodes.empty()) {
+        struct Frame { uint32_t link; std::vector<uint32_t> path; };
+        std::vector<Frame> todo;
+        todo.push_back({sv.bvh_root, {}});
+        size_t visited = 0;
+        while (!todo.empty()) {
+            Frame f = std::move(todo.back());
+            todo.pop_back();
+            const uint32_t idx = f.link & ~kBvhFlatNode;
+            if (idx >= nodes.size() || ++visited > nodes.size() || f.path.size() / 2 >= stride)
+                return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_path_bounds: the resident tree is not a tree of the recorded depth");
+            const Bvh4Node &w = nodes[idx];
+            for (uint32_t c = 0; c < 4; ++c) {
+                uint32_t lnk, cnt;
+                if (f.link & kBvhFlatNode) {
+                    const float l4[4] = { w.b[0].x, w.b[0].y, w.b[0].z, w.b[0].w }, c4[4] = { w.b[1].x, w.b[1].y, w.b[1].z, w.b[1].w };
+                    lnk = bits(l4[c]); cnt = bits(c4[c]);
+                } else { lnk = bits(w.a[c].w); cnt = bits(w.b[c].w); }
+                if (cnt == 0xFFFFFFFFu) continue;
+                std::vector<uint32_t> path = f.path;
+                path.push_back(f.link); path.push_back(c);
+                if (cnt == 0u) { todo.push_back({lnk, std::move(path)}); continue; }
+                const bool tri = (cnt & kBvhTriLeaf) != 0u;
+                for (uint32_t k = 0; k < (cnt & 0xFFFFu); ++k) {
+                    const size_t e = (size_t)lnk + k;
+                    if (e >= (tri ? tri_fidx.size() : prims.size())) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_path_bounds: a leaf entry outside its array");
+                    const size_t row = tri ? prims.size() + e : e;
+                    lens[row] = (uint32_t)(path.size() / 2);
+                    std::copy(path.begin(), path.end(), steps.begin() + (ptrdiff_t)(2 * row * stride));
+                }
+            }
+        }
+    }
+    std::vector<uint32_t> entries(n), rows(n);
+    std::vector<Bvh4Node> leaf_nodes(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        if (objects[i] >= sv.n_objects) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_path_bounds: an object index outside Scene.objects");
+        uint32_t e = entry_of[objects[i]];
+        size_t row = n_rows;                                    // (the spare row: length 0)
+        if (e != kNoEntry) {
+            row = (e & kTriEntry) ? prims.size() + (e & ~kTriEntry) : e;
+            if (lens[row] == 0u) e = kNoEntry;                  // (in no leaf: cannot happen for a tree rtx_debug_host_scene accepts)
+        }
+        if (e == kNoEntry) row = n_rows;
+        entries[i] = e; rows[i] = (uint32_t)row;
+        Bvh4Node &w = leaf_nodes[i];
+        for (int c = 0; c < 4; ++c) {
+            w.a[c] = make_float4(INFINITY, INFINITY, INFINITY, u32_as_f32(0u));
+            w.b[c] = make_float4(-INFINITY, -INFINITY, -INFINITY, u32_as_f32(0xFFFFFFFFu));
+        }
+        if (e != kNoEntry) {
+            w.a[0] = make_float4(-INFINITY, -INFINITY, -INFINITY, u32_as_f32(e & ~kTriEntry));
+            w.b[0] = make_float4(INFINITY, INFINITY, INFINITY, u32_as_f32((e & kTriEntry) ? (kBvhTriLeaf | 1u) : 1u));
+        }
+    }
+    if (records) {                                              // the object's resident f32 records, as the leaf tests read them
+        std::vector<float4> cr(prims.size()), t32(2 * tri_fidx.size()), geo(2 * tri_fidx.size());
+        RTX_HIP_CHECK(down(cr.data(), sv.bvh_leaf_cr, cr.size() * sizeof(float4)));
+        RTX_HIP_CHECK(down(t32.data(), sv.tri_f32, t32.size() * sizeof(float4)));
+        RTX_HIP_CHECK(down(geo.data(), sv.tri_geo, geo.size() * sizeof(float4)));
+        std::memset(records, 0, n * 16 * sizeof(uint32_t));
+        for (uint64_t i = 0; i < n; ++i) {
+            const uint32_t e = entries[i];
+            if (e == kNoEntry) continue;
+            if (e & kTriEntry) {
+                const size_t r = e & ~kTriEntry;
+                const float4 four[4] = { t32[2 * r], t32[2 * r + 1], geo[2 * r], geo[2 * r + 1] };
+                std::memcpy(records + 16 * i, four, sizeof four);
+            } else std::memcpy(records + 16 * i, &cr[e], sizeof(float4));
+        }
+    }
+    if (path_data && path_steps) {                              // the object's child at every step, in the form the slab test reads
+        std::vector<BvhQ3Node> q3((form & 2u) && (sv.bvh_flags & 16u) && sv.bvh_q3nodes ? nodes.size() : 0u);
+        std::vector<BvhQNode> qn((form & 2u) && q3.empty() ? nodes.size() : 0u);
+        RTX_HIP_CHECK(down(q3.data(), sv.bvh_q3nodes, q3.size() * sizeof(BvhQ3Node)));
+        RTX_HIP_CHECK(down(qn.data(), sv.bvh_qnodes, qn.size() * sizeof(BvhQNode)));
+        std::memset(path_data, 0, n * (size_t)path_steps * 16 * sizeof(uint32_t));
+        for (uint64_t i = 0; i < n; ++i) {
+            const size_t row = rows[i];
+            for (uint32_t k = 0; k < lens[row] && k < path_steps; ++k) {
+                const uint32_t link = steps[2 * (row * stride + k)], c = steps[2 * (row * stride + k) + 1], idx = link & ~kBvhFlatNode;
+                uint32_t *w = path_data + 16 * ((size_t)i * path_steps + k);
+                auto putf = [&](int at, float f) { std::memcpy(w + at, &f, 4); };
+                if (!q3.empty()) {
+                    const BvhQ3Node &q = q3[idx];
+                    w[0] = 2u;
+                    putf(1, q.ox); putf(2, q.oy); putf(3, q.oz); putf(4, q.sx); putf(5, q.sy); putf(6, q.sz);
+                    w[7] = (q.lox >> (8 * c)) & 255u; w[8] = (q.loy >> (8 * c)) & 255u; w[9] = (q.loz >> (8 * c)) & 255u;
+                    w[10] = (q.hix >> (8 * c)) & 255u; w[11] = (q.hiy >> (8 * c)) & 255u; w[12] = (q.hiz >> (8 * c)) & 255u;
+                } else if (!qn.empty()) {
+                    const BvhQNode &q = qn[idx];
+                    w[0] = 3u;
+                    putf(1, q.ox); putf(2, q.oy); putf(3, q.sx); putf(4, q.sy); w[5] = q.qx[c]; w[6] = q.qy[c];
+                } else if (link & kBvhFlatNode) {
+                    w[0] = 1u;
+                    putf(1, nodes[idx].a[c].x); putf(2, nodes[idx].a[c].y); putf(3, nodes[idx].a[c].z); putf(4, nodes[idx].a[c].w);
+                } else {
+                    w[0] = 0u;
+                    putf(1, nodes[idx].a[c].x); putf(2, nodes[idx].a[c].y); putf(3, nodes[idx].a[c].z);
+                    putf(4, nodes[idx].b[c].x); putf(5, nodes[idx].b[c].y); putf(6, nodes[idx].b[c].z);
+                }
+                w[15] = link;
+            }
+        }
+    }
+    DebugBufs d;
+    void *d_sv, *d_rays, *d_entries, *d_rows, *d_lens, *d_steps, *d_best, *d_leaf, *d_out;
+    RTX_HIP_CHECK(d.up(&sv, sizeof(SceneView), &d_sv));
+    RTX_HIP_CHECK(d.up(rays, n * sizeof(RtxRay), &d_rays));
+    RTX_HIP_CHECK(d.up(entries.data(), n * sizeof(uint32_t), &d_entries));
+    RTX_HIP_CHECK(d.up(rows.data(), n * sizeof(uint32_t), &d_rows));
+    RTX_HIP_CHECK(d.up(lens.data(), lens.size() * sizeof(uint32_t), &d_lens));
+    steps.resize(steps.size() + 2, 0u);                         // (never empty)
+    RTX_HIP_CHECK(d.up(steps.data(), steps.size() * sizeof(uint32_t), &d_steps));
+    RTX_HIP_CHECK(d.up(best_up, n * sizeof(float), &d_best));
+    RTX_HIP_CHECK(d.up(leaf_nodes.data(), n * sizeof(Bvh4Node), &d_leaf));
+    RTX_HIP_CHECK(d.up(out, n * 8 * sizeof(uint32_t), &d_out));
+    static_assert(sizeof(RtxRay) == sizeof(QueryRay), "RtxRay layout");
+    PathBoundsArgs a;
+    a.rays = static_cast<const QueryRay *>(d_rays); a.entries = static_cast<const uint32_t *>(d_entries);
+    a.rows = static_cast<const uint32_t *>(d_rows); a.lens = static_cast<const uint32_t *>(d_lens);
+    a.steps = static_cast<const uint32_t *>(d_steps); a.best_up = static_cast<const float *>(d_best);
+    a.leaf_nodes = static_cast<const float4 *>(d_leaf); a.out = static_cast<uint32_t *>(d_out);
+    a.n = n; a.stride = stride; a.form = form;
+    RTX_HIP_CHECK(launch_debug_path_bounds(static_cast<const SceneView *>(d_sv), a, nullptr));
+    RTX_HIP_CHECK(hipMemcpy(out, d_out, n * 8 * sizeof(uint32_t), hipMemcpyDeviceToHost));   // (the null stream: after the kernel)
+    return RTX_OK;
+#endif
+}
+
 int32_t rtx_scene_closest_hits(RtxSceneHandle h, const RtxRay *d_rays, uint64_t n, RtxHit *d_hits, void *stream, RtxStats *stats)
 {
     if (!h) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_closest_hits: null scene");

@@ -234,7 +234,7 @@ __global__ __launch_bounds__(kBvhThreads, kSphWavesPerSimd) void trace_bvh_spher
                     make_ray32(r.pos, dirn, (double)sv.bvh_inv_max, q0);
                     Ray32S q;
                     q.ix = q0.ix; q.iy = q0.iy; q.iz = q0.iz; q.nx = q0.nx; q.ny = q0.ny; q.nz = q0.nz;
-                    q.e = ray32_slack(q0.nx, q0.ny, q0.nz, in32);
+                    q.e = ray32_slack(q0, in32);
                     if constexpr (Q3 == 2)            // node visits and leaf visits apart (the default)
                         sphere_walk_phased<STACK, SPILL, RTX_WALK_INNER != 0>(nodes, la.sphere_f32, la.sphere_prims, q, sr, w_node, w_sp, &lds_stack[0][0],
                                                          lq, tid, spill, spill_entries, spill_stride, glane, best_up, qcnt,
@@ -381,47 +381,8 @@ constexpr uint32_t kSphPool = 4u;            // stage 2 as the wave-local pool (
 constexpr uint32_t kSphSortSurvivors = 2u;   // stage 2 reads the survivors ordered by exit distance and octant
 #endif
 
-// One sphere of a leaf against one lane's ray, f32 only: the candidate test and bounds of sphere_step (rtx_traverse.h).  A sphere the
-// exact test cannot be excluded for joins the lane's candidate queue (LDS: {local index, t_lo}); a certain hit tightens best_up.
-__device__ __forceinline__ void sph_packet_leaf_test(const float4 rec, const uint32_t prim, const SphereRay &sr, uint32_t *lq, uint32_t tid,
-                                 float &best_up, uint32_t &qcnt, bool &overflow)
-{
-    const float ox = rec.x - sr.px, oy = rec.y - sr.py, oz = rec.z - sr.pz;
-    const float bq = __builtin_fmaf(ox, sr.dx, __builtin_fmaf(oy, sr.dy, oz * sr.dz));
-    const float lx = __builtin_fmaf(-bq, sr.dx, ox), ly = __builtin_fmaf(-bq, sr.dy, oy), lz = __builtin_fmaf(-bq, sr.dz, oz);
-    const float l2 = __builtin_fmaf(lx, lx, __builtin_fmaf(ly, ly, lz * lz));
-    const float Dl = __builtin_fmaf(rec.w, rec.w, -l2);
-    const float G = __builtin_fmaf(sr.Kg, rec.w, sr.c0);
-    const float Dp = Dl + G;
-    if (Dp >= 0.0f) {                                      // the exact test cannot be excluded (rtx_traverse.h, sphere_step)
-        const float tlo = bq - __builtin_amdgcn_sqrtf(Dp) * (1.0f + 4.76837158e-7f) - sr.K;
-        const float Dm = Dl - G;
-        const float thi = Dm > 0.0f ? bq - __builtin_amdgcn_sqrtf(Dm) * (1.0f - 4.76837158e-7f) + sr.K : __builtin_inff();
-        if (tlo <= best_up && !(thi < 0.0f)) {
-            if (tlo > sr.K) best_up = fminf(best_up, thi);
-            if (qcnt == (uint32_t)kSphQueue) {             // drop the entries a later certain hit has overtaken
-                uint32_t w = 0;
-#pragma unroll
-                for (int e = 0; e < kSphQueue; ++e) {
-                    const uint32_t ie = lq[(size_t)e * kBvhThreads + tid];
-                    const uint32_t te = lq[(size_t)(kSphQueue + e) * kBvhThreads + tid];
-                    if (__uint_as_float(te) <= best_up) {
-                        lq[(size_t)w * kBvhThreads + tid] = ie;
-                        lq[(size_t)(kSphQueue + w) * kBvhThreads + tid] = te;
-                        w += 1;
-                    }
-                }
-                qcnt = w;
-            }
-            if (qcnt == (uint32_t)kSphQueue) overflow = true;   // (the segment then tests every sphere exactly)
-            else {
-                lq[(size_t)qcnt * kBvhThreads + tid] = prim;
-                lq[(size_t)(kSphQueue + qcnt) * kBvhThreads + tid] = __float_as_uint(tlo);
-                qcnt += 1;
-            }
-        }
-    }
-}
+// (sph_packet_leaf_test, the packet kernel's leaf test of one sphere, lives in rtx_traverse.h next to sphere_leaf_step_at: the lab
+// library's rtx_debug_path_bounds calls it too)
 
 // The walk of one tile.  SGN < 8: every ray of the tile points into octant SGN (bit a set: direction component a is
 // negative), so the near / far plane of each slab is known at compile time; SGN == 8: mixed signs, min / max per slab.
@@ -658,7 +619,7 @@ __global__ __launch_bounds__(kBvhThreads, kSpkWaves) void trace_sph_packet_kerne
                 Ray32 q0;
                 make_ray32(r.pos, rx.dirn, (double)sv.bvh_inv_max, q0);
                 q.ix = q0.ix; q.iy = q0.iy; q.iz = q0.iz; q.nx = q0.nx; q.ny = q0.ny; q.nz = q0.nz;
-                q.e = ray32_slack(q0.nx, q0.ny, q0.nz, in32);           // 0 inside origin_limit: the bits of Ray32
+                q.e = ray32_slack(q0, in32);           // 0 inside origin_limit: the bits of Ray32
                 best_up = __builtin_inff();
                 walked = true;
             }

@@ -230,7 +230,7 @@ __global__ __launch_bounds__(kBvhThreads, kSphWavesPerSimd) void trace_sph_pool_
                     make_ray32(r.pos, rn.dirn, (double)sv.bvh_inv_max, q0);
                     pu[12 * ps + i] = __float_as_uint(q0.ix); pu[13 * ps + i] = __float_as_uint(q0.iy); pu[14 * ps + i] = __float_as_uint(q0.iz);
                     pu[15 * ps + i] = __float_as_uint(q0.nx); pu[16 * ps + i] = __float_as_uint(q0.ny); pu[17 * ps + i] = __float_as_uint(q0.nz);
-                    pu[18 * ps + i] = __float_as_uint(ray32_slack(q0.nx, q0.ny, q0.nz, in32));
+                    pu[18 * ps + i] = __float_as_uint(ray32_slack(q0, in32));
                     pu[19 * ps + i] = __float_as_uint(s2.px); pu[20 * ps + i] = __float_as_uint(s2.py); pu[21 * ps + i] = __float_as_uint(s2.pz);
                     pu[22 * ps + i] = __float_as_uint(s2.dx); pu[23 * ps + i] = __float_as_uint(s2.dy); pu[24 * ps + i] = __float_as_uint(s2.dz);
                     pu[25 * ps + i] = __float_as_uint(s2.Kg); pu[26 * ps + i] = __float_as_uint(s2.c0); pu[27 * ps + i] = __float_as_uint(s2.K);
@@ -587,7 +587,7 @@ __global__ __launch_bounds__(kBvhThreads, kPairWaves) void trace_sph_pair_kernel
                     Ray32 q0;
                     make_ray32(r.pos, rn.dirn, (double)sv.bvh_inv_max, q0);
                     pq.ix = q0.ix; pq.iy = q0.iy; pq.iz = q0.iz; pq.nx = q0.nx; pq.ny = q0.ny; pq.nz = q0.nz;
-                    pq.e = ray32_slack(q0.nx, q0.ny, q0.nz, in32);
+                    pq.e = ray32_slack(q0, in32);
                 }
                 pocket = true;
                 pslot = slot;
@@ -997,7 +997,7 @@ __global__ __launch_bounds__(kBvhThreads, kSphWavesPerSimd) void trace_sph_slots
                     make_ray32(r.pos, rn.dirn, (double)sv.bvh_inv_max, q0);
                     sl[0 * kSlotN + my] = __float_as_uint(q0.ix); sl[1 * kSlotN + my] = __float_as_uint(q0.iy); sl[2 * kSlotN + my] = __float_as_uint(q0.iz);
                     sl[3 * kSlotN + my] = __float_as_uint(q0.nx); sl[4 * kSlotN + my] = __float_as_uint(q0.ny); sl[5 * kSlotN + my] = __float_as_uint(q0.nz);
-                    sl[6 * kSlotN + my] = __float_as_uint(ray32_slack(q0.nx, q0.ny, q0.nz, in32));
+                    sl[6 * kSlotN + my] = __float_as_uint(ray32_slack(q0, in32));
                     sl[7 * kSlotN + my] = __float_as_uint(s2.px); sl[8 * kSlotN + my] = __float_as_uint(s2.py); sl[9 * kSlotN + my] = __float_as_uint(s2.pz);
                     sl[10 * kSlotN + my] = __float_as_uint(s2.dx); sl[11 * kSlotN + my] = __float_as_uint(s2.dy); sl[12 * kSlotN + my] = __float_as_uint(s2.dz);
                     sl[13 * kSlotN + my] = __float_as_uint(s2.Kg); sl[14 * kSlotN + my] = __float_as_uint(s2.c0); sl[15 * kSlotN + my] = __float_as_uint(s2.K);

@@ -225,6 +225,16 @@ bool debug_math_host(int op, const double *a, const double *b, double *out, uint
 // rtx_debug_store_samples: one thread per entry calls store_sample(samples, rv, slots[i], rgb[3 i .. 3 i + 2]) (rtx_device.h)
 hipError_t launch_debug_store_samples(const double *rgb, const uint64_t *slots, uint64_t n, double *samples, const RowsView &rv,
                                       hipStream_t stream);
+// rtx_debug_path_bounds (rtx_query.hip): one thread per (ray, object) pair runs the walks' bound functions along the object's path.
+// entries[i]: the object's leaf entry (a sphere's index in bvh_prims, or kQueueTri | its triangle filter record; ~0: not in the tree);
+// rows[i]: its row in the path table -- lens[row] steps of {the node's link as its parent holds it, the child slot}, `stride` steps per
+// row; leaf_nodes: per element a 128-byte node whose only child is a one-record leaf of the object (the inline-leaf forms); out: 8
+// words per element (include/rtx_hip.h)
+struct PathBoundsArgs {
+    const QueryRay *rays; const uint32_t *entries, *rows, *lens, *steps; const float *best_up; const float4 *leaf_nodes;
+    uint32_t *out; uint64_t n; uint32_t stride, form;
+};
+hipError_t launch_debug_path_bounds(const SceneView *d_sv, const PathBoundsArgs &a, hipStream_t stream);
 #endif
 
 }  // namespace rtx

@@ -111,16 +111,16 @@ __device__ __forceinline__ float qrect_entry(uint32_t qx, uint32_t qy, float Ax,
     const float tf_hi = __builtin_fmaf(tf, 1.0f + 4.76837158e-7f, e);
     return (tn_lo <= tf_hi && tn_lo <= best_up) ? tn_lo : __builtin_inff();
 }
-__device__ __forceinline__ double ray_slack(const Ray64 &) { return 0.0; }
+__device__ __forceinline__ double ray_slack(const Ray64 &r) { return r.e; }
 __device__ __forceinline__ float qnode_offset(float o, float inv, float noi) { return __builtin_fmaf(o, inv, noi); }
 __device__ __forceinline__ double qnode_offset(float o, double inv, double noi) { return __builtin_fma((double)o, inv, noi); }
-__device__ __forceinline__ float qrect_entry(uint32_t qx, uint32_t qy, double Ax, double Bx, double Ay, double By, float best_up, double)
+__device__ __forceinline__ float qrect_entry(uint32_t qx, uint32_t qy, double Ax, double Bx, double Ay, double By, float best_up, double e)
 {
     const double x0 = __builtin_fma((double)(qx & 0xFFFFu), Ax, Bx), x1 = __builtin_fma((double)(qx >> 16), Ax, Bx);
     const double y0 = __builtin_fma((double)(qy & 0xFFFFu), Ay, By), y1 = __builtin_fma((double)(qy >> 16), Ay, By);
     const double tn = fmax(fmax(fmin(x0, x1), fmin(y0, y1)), 0.0);
     const double tf = fmin(fmax(x0, x1), fmax(y0, y1));
-    const double tn_lo = tn * (1.0 - 4.76837158e-7), tf_hi = tf * (1.0 + 4.76837158e-7);
+    const double tn_lo = tn * (1.0 - 4.76837158e-7) - e, tf_hi = tf * (1.0 + 4.76837158e-7) + e;
     return (tn_lo <= tf_hi && tn_lo <= (double)best_up) ? __double2float_rd(tn_lo) : __builtin_inff();
 }
 

@@ -251,7 +251,7 @@ __device__ __forceinline__ uint32_t query_any_ray(const SceneView &sv, const flo
         make_ray32(pos, rx.dirn, (double)sv.bvh_inv_max, q0);
         Ray32S q;
         q.ix = q0.ix; q.iy = q0.iy; q.iz = q0.iz; q.nx = q0.nx; q.ny = q0.ny; q.nz = q0.nz;
-        q.e = ray32_slack(q0.nx, q0.ny, q0.nz, in32);
+        q.e = ray32_slack(q0, in32);
         float best_up = best0;
         uint32_t node = sv.bvh_root, sp = 0, qcnt = 0;
         // sphere_walk_phased's iteration -- node visits and leaf visits apart, chosen for the wave -- with the retirement check after
@@ -284,8 +284,12 @@ __device__ __forceinline__ uint32_t query_any_ray(const SceneView &sv, const flo
 __device__ __forceinline__ bool query_walkable(const SceneView &sv, uint32_t tree, V3 pos, V3 dir, bool &in32)
 {
     const float omax = fmaxf(fmaxf(__builtin_fabsf((float)pos.x), __builtin_fabsf((float)pos.y)), __builtin_fabsf((float)pos.z));
-    in32 = omax <= sv.bvh_origin_limit;                                                 // NaN origin -> exhaustive branch
-    return tree && query_dir_ok(dir) && (in32 || omax <= sv.bvh_origin_limit * kBvhRange64);
+    // (fmaxf drops a NaN operand: a NaN coordinate is asked for by name.  Such a ray has no reportable hit either way -- every distance is
+    // NaN -- but it does not belong in the walk: tests/test_walk_bounds.py.  The frame kernels' gates (rtx_bvh_spheres.hip, rtx_bvh_mesh.hip,
+    // rtx_wavefront.hip and the lab kernels) restate the fmaxf form and are left as they are: same results, and no hook looks at them)
+    const bool numbers = (pos.x == pos.x) & (pos.y == pos.y) & (pos.z == pos.z);
+    in32 = numbers && omax <= sv.bvh_origin_limit;                                      // NaN origin -> exhaustive branch
+    return tree && numbers && query_dir_ok(dir) && (in32 || omax <= sv.bvh_origin_limit * kBvhRange64);
 }
 
 // One closest_object call (scene.rs:243-251) for the ray (pos, dir): the origin-range gate, the walk, the flush, planes and the
@@ -333,7 +337,7 @@ __device__ __forceinline__ void query_closest_ray(const SceneView &sv, uint32_t 
             make_ray32(pos, rx.dirn, (double)sv.bvh_inv_max, q0);
             Ray32S q;                                 // (a far origin: Ray32's planes widened by the slack of noi's rounding)
             q.ix = q0.ix; q.iy = q0.iy; q.iz = q0.iz; q.nx = q0.nx; q.ny = q0.ny; q.nz = q0.nz;
-            q.e = ray32_slack(q0.nx, q0.ny, q0.nz, in32);
+            q.e = ray32_slack(q0, in32);
             float best_up = __builtin_inff();
             uint32_t node = sv.bvh_root, sp = 0, qcnt = 0;
             sphere_walk_phased<kQuerySphStack, true>(nodes, la.sphere_f32, la.sphere_prims, q, sr, node, sp, ls, lq, tid, spill,
@@ -791,5 +795,193 @@ hipError_t launch_query_closest(const SceneView *d_sv, const SceneView &sv, cons
                            counters, head);
     return hipGetLastError();
 }
+
+
+#ifdef RTX_LAB
+// ---- rtx_debug_path_bounds (librtx_hip_lab.so only) ----------------------------------------------------------------------------
+// What the walks' f32 bounds decide for ONE (ray, object) pair: a thread runs the walks' own device functions -- the slab tests of the
+// 128-byte, footprint and 64-byte nodes, the sphere and triangle leaf bounds -- along the root -> leaf path of its object, which the
+// host found in the flat tree, with the caller's best_up.  Nothing of their arithmetic is restated here: the kernel prepares the
+// ray as query_closest_ray does, calls, and reads the results back from the functions' own outputs (return value, node, stack, queue).
+constexpr int kPathStack = 8;                                    // LDS stack rows of the one-visit calls (they start on an empty stack)
+constexpr uint32_t kPbNoWalk = 3u;                             // word 0, bits 0-1: 0 Ray32, 1 Ray32S (slack != 0), 2 Ray64, 3 no walk
+constexpr uint32_t kPbInTree = 4u, kPbCandidate = 8u, kPbCertain = 16u, kPbTriangle = 32u, kPbNoForm = 64u;
+
+// the entered children of one visit that started on an empty stack: the next node and what lies below it
+__device__ __forceinline__ bool pb_entered(uint32_t target, uint32_t node, uint32_t sp, const uint32_t *ls, uint32_t tid)
+{
+    bool in = node == target;
+    for (uint32_t r = 0; r < sp; ++r) in = in || ls[(size_t)r * kBvhThreads + tid] == target;
+    return in;
+}
+
+// j's child at every step of the path; *entered counts the steps that enter it, *bound is the largest entry distance returned
+template <class RAY>
+__device__ __forceinline__ void pb_path(const SceneView &sv, const PathBoundsArgs &a, const RAY &q, uint32_t row, uint32_t len, float best_up,
+                                        uint32_t *ls, uint32_t tid, uint32_t &entered, float &bound, uint32_t &first_miss, bool &no_form)
+{
+    const bool small = (a.form & 2u) != 0u;                      // the 64-byte forms
+    const float4 *nodes128 = reinterpret_cast<const float4 *>(sv.bvh_nodes);
+    for (uint32_t s = 0; s < len; ++s) {
+        const uint32_t link = a.steps[2 * ((size_t)row * a.stride + s)], c = a.steps[2 * ((size_t)row * a.stride + s) + 1];
+        const uint32_t idx = link & ~kBvhFlatNode;
+        bool in = false;
+        if (!small) {
+            const float4 *np = nodes128 + 8 * (size_t)idx;
+            const float tc = (link & kBvhFlatNode) ? rect_entry32(np[c], q, best_up) : box_entry32(np[c], np[4 + c], q, best_up);
+            in = tc < __builtin_inff();
+            if (in) bound = fmaxf(bound, tc);
+        } else if ((sv.bvh_flags & 16u) != 0u && sv.bvh_q3nodes != nullptr) {
+            if constexpr (sizeof(q.ix) == sizeof(float)) {       // (sphere_node_step_q3 has no f64 form)
+                const float4 *qn = reinterpret_cast<const float4 *>(sv.bvh_q3nodes);
+                const uint32_t *words = reinterpret_cast<const uint32_t *>(sv.bvh_q3nodes + idx);
+                const uint32_t target = words[2 * c];            // {link0, ox, link1, oy} {link2, oz, link3, sx}
+                uint32_t node = idx, sp = 0, nbox = 0;
+                bool overflow = false;
+                sphere_node_step_q3<kPathStack, false>(qn, q, node, sp, ls, tid, nullptr, 0u, 0, 0, best_up, overflow, nbox);
+                in = pb_entered(target, node, sp, ls, tid);
+            } else no_form = true;
+        } else if ((sv.bvh_flags & 8u) != 0u && sv.bvh_qnodes != nullptr) {
+            const float4 *np = reinterpret_cast<const float4 *>(sv.bvh_qnodes) + 4 * (size_t)idx;
+            const float4 n0 = np[0], n1 = np[1], n2 = np[2];     // as mesh_step<2> opens the node (rtx_mesh_step.h, `if constexpr (PLAIN == 2)`
+                                                                 // under `resume == 0u`: Ax / Ay, qx / qy, qnode_offset) -- a copy: keep in step
+            const auto Ax = n0.z * q.ix, Ay = n0.w * q.iy;
+            const auto Bx = qnode_offset(n0.x, q.ix, q.nx), By = qnode_offset(n0.y, q.iy, q.ny);
+            const uint32_t qx = __float_as_uint(c == 0 ? n1.x : (c == 1 ? n1.y : (c == 2 ? n1.z : n1.w)));
+            const uint32_t qy = __float_as_uint(c == 0 ? n2.x : (c == 1 ? n2.y : (c == 2 ? n2.z : n2.w)));
+            const float tc = qrect_entry(qx, qy, Ax, Bx, Ay, By, best_up, ray_slack(q));
+            in = tc < __builtin_inff();
+            if (in) bound = fmaxf(bound, tc);
+        } else no_form = true;
+        if (in) entered += 1;
+        else if (first_miss == kNone) first_miss = s;
+    }
+}
+
+// the leaf test of j's record with the bound `bu`; returns whether j became a candidate, *tlo its lower bound; bu is updated
+template <class RAY>
+__device__ __forceinline__ bool pb_leaf(const SceneView &sv, const PathBoundsArgs &a, const RAY &q, const SphereRay &sr, const TriFilterParams &tpar,
+                                        bool tri, uint32_t rec, size_t i, float &bu, float &tlo, uint32_t *ls, uint32_t *lq, uint32_t tid,
+                                        bool &no_form)
+{
+    const uint32_t leaf = (a.form >> 8) & 3u;
+    uint32_t node = 0, sp = 0, qcnt = 0, nbox = 0, nleaf = 0;
+    bool overflow = false;
+    tlo = __builtin_inff();
+    if (leaf == 0u && !tri) {
+        node = (1u << 29) | rec;
+        sphere_leaf_step_at<kPathStack, false, kBvhThreads>(sv.bvh_leaf_cr, sv.bvh_prims, sr, node, sp, ls, lq, tid, tid, nullptr, 0, 0, bu, qcnt,
+                                                            overflow, nleaf);
+        if (qcnt == 1u) tlo = __uint_as_float(lq[(size_t)kSphQueue * kBvhThreads + tid]);
+        return qcnt == 1u;
+    }
+    if (leaf == 0u) {
+        const float4 A = sv.tri_f32[2 * (size_t)rec], B = sv.tri_f32[2 * (size_t)rec + 1];
+        if ((int)tri_filter_sign(A, B, tpar) < 0) return false;
+        float thi;
+        tlo = tri_bounds(A, sv.tri_geo[2 * (size_t)rec], sv.tri_geo[2 * (size_t)rec + 1], tpar, thi);
+        if (!(tlo <= bu && tlo < __builtin_inff())) return false;             // (a copy of mesh_step's candidate rule and bound update, its
+        bu = fminf(bu, thi);                                                  // triangle-leaf loop; leaf form 2 runs mesh_step's own)
+        return true;
+    }
+    if (leaf == 3u && !tri) {                                   // the packet kernel's test of one record of a leaf
+        sph_packet_leaf_test(sv.bvh_leaf_cr[rec], sv.bvh_prims[rec], sr, lq, tid, bu, qcnt, overflow);
+        if (qcnt == 1u) tlo = __uint_as_float(lq[(size_t)kSphQueue * kBvhThreads + tid]);
+        return qcnt == 1u;
+    }
+    if (leaf == 3u) { no_form = true; return false; }
+    // the leaf code inlined in a node visit: the host's one-child 128-byte node of j's record, its box unbounded
+    const float4 *one = a.leaf_nodes + 8 * i;
+    if (leaf == 1u && !tri) {
+        sphere_step<kPathStack, false>(one, sv.bvh_leaf_cr, sv.bvh_prims, q, sr, node, sp, ls, lq, tid, nullptr, 0u, 0, 0, bu, qcnt, overflow, nbox,
+                                       nleaf);
+        if (qcnt == 1u) tlo = __uint_as_float(lq[(size_t)kSphQueue * kBvhThreads + tid]);
+        return qcnt == 1u;
+    }
+    if (leaf == 2u) {
+        MeshArrays ma;
+        ma.sphere_cr = sv.bvh_leaf_cr; ma.sphere_prims = sv.bvh_prims; ma.tri_f32 = sv.tri_f32; ma.tri_geo = sv.tri_geo;
+        float4 nd[MeshNode<0>::n];
+        uint32_t resume = 0, resume_node = 0;
+        (void)mesh_step<false, 0, kPathStack>(one, ma, q, sr, tpar, nd, node, sp, qcnt, overflow, bu, resume, resume_node, ls, lq, tid, nullptr, 0u,
+                                              0, 0, nbox, nleaf);
+        if (qcnt == 1u) tlo = __uint_as_float(lq[(size_t)kMeshQueue * kBvhThreads + tid]);
+        return qcnt == 1u;
+    }
+    no_form = true;
+    return false;
+}
+
+template <class RAY>
+__device__ __forceinline__ void pb_element(const SceneView &sv, const PathBoundsArgs &a, const RAY &q, const SphereRay &sr, const TriFilterParams &tpar,
+                                           size_t i, uint32_t *ls, uint32_t *lq, uint32_t tid, uint32_t &flags, uint32_t *out)
+{
+    const uint32_t row = a.rows[i], entry = a.entries[i], len = a.lens[row];
+    const bool tri = (entry & kQueueTri) != 0u;
+    const float best_up = a.best_up[i];
+    uint32_t entered = 0, first_miss = kNone;
+    float bound = -__builtin_inff();
+    bool no_form = false;
+    pb_path(sv, a, q, row, len, best_up, ls, tid, entered, bound, first_miss, no_form);
+    float bu = best_up, tlo, tlo_inf, thi = __builtin_inff();
+    const bool cand = pb_leaf(sv, a, q, sr, tpar, tri, entry & ~kQueueTri, i, bu, tlo, ls, lq, tid, no_form);
+    (void)pb_leaf(sv, a, q, sr, tpar, tri, entry & ~kQueueTri, i, thi, tlo_inf, ls, lq, tid, no_form);   // best_up = +inf: falls iff certain
+    flags |= (cand ? kPbCandidate : 0u) | (thi < __builtin_inff() ? kPbCertain : 0u) | (tri ? kPbTriangle : 0u) | (no_form ? kPbNoForm : 0u);
+    out[1] = len; out[2] = entered; out[3] = __float_as_uint(bound); out[4] = __float_as_uint(cand ? tlo : tlo_inf);
+    out[5] = __float_as_uint(thi); out[6] = __float_as_uint(bu); out[7] = first_miss;
+}
+
+__global__ __launch_bounds__(kBvhThreads) void debug_path_bounds_kernel(const SceneView *__restrict__ svp, const PathBoundsArgs a)
+{
+    constexpr int QROWS = 2 * (kMeshQueue > kSphQueue ? kMeshQueue : kSphQueue);
+    __shared__ uint32_t lds_stack[kPathStack + 1][kBvhThreads];
+    __shared__ uint32_t lds_q[QROWS][kBvhThreads];
+    const SceneView &sv = *svp;
+    const uint32_t tid = threadIdx.x;
+    const size_t i = (size_t)blockIdx.x * kBvhThreads + tid;
+    if (i >= a.n) return;
+    uint32_t *const ls = &lds_stack[0][0], *const lq = &lds_q[0][0];
+    uint32_t *out = a.out + 8 * i;
+    for (int k = 0; k < 8; ++k) out[k] = 0u;
+    out[7] = kNone;
+    const QueryRay &qr = a.rays[i];
+    const V3 pos = mk(qr.position[0], qr.position[1], qr.position[2]);
+    const V3 dir = mk(qr.direction[0], qr.direction[1], qr.direction[2]);
+    const RayX rx = make_rayx(pos, dir);
+    bool in32;
+    const bool walk = query_walkable(sv, 1u, pos, dir, in32);
+    uint32_t flags = a.entries[i] != kNone ? kPbInTree : 0u;
+    if (!walk) { out[0] = flags | kPbNoWalk; return; }
+    if (!(flags & kPbInTree)) { out[0] = flags; return; }
+    // the ray as query_closest_ray prepares it
+    SphereRay sr;
+    sr.px = sr.py = sr.pz = sr.dx = sr.dy = sr.dz = sr.Kg = sr.K = 0.f; sr.c0 = __builtin_inff();
+    if (sv.bvh_flags & 1u) sphere_ray_from(sv, pos, dir, sr);
+    TriFilterParams tpar;
+    if (sv.bvh_flags & 2u) tri_filter_from_ray(sv, pos, dir, tpar); else tri_filter_idle(tpar);
+    if (in32 || (a.form & 1u) == 0u) {
+        Ray32 q0;
+        make_ray32(pos, rx.dirn, (double)sv.bvh_inv_max, q0);
+        Ray32S q;
+        q.ix = q0.ix; q.iy = q0.iy; q.iz = q0.iz; q.nx = q0.nx; q.ny = q0.ny; q.nz = q0.nz;
+        q.e = ray32_slack(q0, in32);             // 0 inside origin_limit: the bits of Ray32
+        flags |= in32 ? 0u : 1u;
+        pb_element(sv, a, q, sr, tpar, i, ls, lq, tid, flags, out);
+    } else {
+        Ray64 q;
+        make_ray64(pos, rx.dirn, (double)sv.bvh_inv_max, q);
+        flags |= 2u;
+        pb_element(sv, a, q, sr, tpar, i, ls, lq, tid, flags, out);
+    }
+    out[0] = flags;
+}
+
+hipError_t launch_debug_path_bounds(const SceneView *d_sv, const PathBoundsArgs &a, hipStream_t stream)
+{
+    if (a.n == 0) return hipSuccess;
+    hipLaunchKernelGGL(debug_path_bounds_kernel, dim3((unsigned)((a.n + kBvhThreads - 1) / kBvhThreads)), dim3(kBvhThreads), 0, stream, d_sv, a);
+    return hipGetLastError();
+}
+#endif  // RTX_LAB
 
 }  // namespace rtx

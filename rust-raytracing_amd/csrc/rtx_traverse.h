@@ -16,7 +16,7 @@ struct Ray32 { float ix, iy, iz, nx, ny, nz; };
 // reference's far phantom hits, a camera far from the scene): rounding noi in f64 moves the planes by 2^-53 |o|, which
 // the boxes' padding covers up to |o| <= 2^27 * origin_limit.  Without it such a ray would test every shape exactly --
 // 0.3 s for one segment over 500k triangles, while its wave and the launch wait.
-struct Ray64 { double ix, iy, iz, nx, ny, nz; };
+struct Ray64 { double ix, iy, iz, nx, ny, nz, e; };       // e: ray32_slack's second term (the reference's own roundings)
 // Ray32 with an absolute slack on every slab distance, for the same far origins where no f64 is wanted (the wavefront
 // walk kernels): what the boxes' padding no longer covers is the rounding of noi = fl(-o * inv), at most 2^-24 |o * inv|
 // per axis, so the interval [tn, tf] is widened by e = 2^-23 max_axis |noi| on both sides -- conservative for any finite
@@ -65,11 +65,30 @@ __device__ __forceinline__ float box_entry32(const float4 lo, const float4 hi, c
     return hit ? tn_lo : __builtin_inff();      // the widened (conservative) entry distance
 }
 
-// origin_limit < |o|_inf: the slack of Ray32S (rounded up); 0 inside the range the padding covers
-__device__ __forceinline__ float ray32_slack(float nx, float ny, float nz, bool in_range)
+// origin_limit < |o|_inf: the slack of Ray32S (rounded up); 0 inside the range the padding covers.  Two terms:
+//   * the rounding of noi, 2^-23 max_axis |noi|;
+//   * the REFERENCE's own roundings.  Sphere::distance forms b^2 - 4ac in f64, which cancels 4 |o - c|^2 against itself: its error,
+//     about 20 * 2^-53 * 4 |o - c|^2, lets the text report a sphere the ray misses by up to sqrt(20 * 2^-53) |o - c| = 2^-24.3 |o - c|
+//     (10 * 2^-53 |o - c|^2 / r for a large one) -- and the exhaustive kernel reports it with the text.  Inside origin_limit that is
+//     within the boxes' abs_pad; beyond it every slab is moved out by D = 2^-22 |o|_inf >= 2^-24.3 |o - c|_2 (|o - c|_2 <= 2.2 |o|_inf
+//     there), which on the axis with the largest |1 / d| is D * max|inv| of distance.  |o|_inf is read back from noi / inv (the
+//     walks' ray records hold nothing else); capped at 1e38, the whole stays +inf only where noi already is.
+// (tests/test_walk_bounds.py: found by rays aimed at tangents from 1000 x origin_limit, and by AUTO against the exhaustive kernel.  The
+// 2^-24.3 |o - c| is one more hand derivation; what tests it are that file's far10 and far26 cells, nothing else.  ONE slack for the
+// three slabs: with an axis-aligned or 1e-30 direction component max|inv| is inv_max, the slack reaches its cap and such a far ray
+// enters every box -- correct, and as slow as a sweep.  D * |inv_a| per axis would be tighter, at three more operands in every node
+// visit of every ray; far origins with such directions are too rare to pay that in the visit.)
+template <class R32>
+__device__ __forceinline__ float ray32_slack(const R32 &q, bool in_range)
 {
-    const float m = fmaxf(fmaxf(__builtin_fabsf(nx), __builtin_fabsf(ny)), __builtin_fabsf(nz));
-    return in_range ? 0.0f : m * (1.1920929e-7f * (1.0f + 9.5367432e-7f));
+    if (in_range) return 0.0f;
+    const float ax = __builtin_fabsf(q.nx), ay = __builtin_fabsf(q.ny), az = __builtin_fabsf(q.nz);
+    const float bx = __builtin_fabsf(q.ix), by = __builtin_fabsf(q.iy), bz = __builtin_fabsf(q.iz);
+    const float m = fmaxf(fmaxf(ax, ay), az);
+    const float om = fmaxf(fmaxf(ax / bx, ay / by), az / bz);
+    const float im = fmaxf(fmaxf(bx, by), bz);
+    const float c = 1.1920929e-7f * (1.0f + 9.5367432e-7f);              // 2^-23, rounded up
+    return m * c + fminf(om * im * (2.0f * c), 1.0e38f);
 }
 
 __device__ __forceinline__ void make_ray64(const V3 &pos, const V3 &dirn, double inv_max, Ray64 &r)
@@ -78,6 +97,8 @@ __device__ __forceinline__ void make_ray64(const V3 &pos, const V3 &dirn, double
     i = 1.0 / dirn.x; if (!(fabs(i) <= inv_max)) i = copysign(inv_max, dirn.x); r.ix = i; r.nx = -pos.x * i;
     i = 1.0 / dirn.y; if (!(fabs(i) <= inv_max)) i = copysign(inv_max, dirn.y); r.iy = i; r.ny = -pos.y * i;
     i = 1.0 / dirn.z; if (!(fabs(i) <= inv_max)) i = copysign(inv_max, dirn.z); r.iz = i; r.nz = -pos.z * i;
+    // (only origins beyond origin_limit come here: ray32_slack's second term, in f64)
+    r.e = fmin(fmax(fmax(fabs(pos.x), fabs(pos.y)), fabs(pos.z)) * fmax(fmax(fabs(r.ix), fabs(r.iy)), fabs(r.iz)) * (1.0 / 4194304.0), 1.0e300);
 }
 
 // f64 slab test on the same f32 boxes (same widening, far more than the f64 roundings need); the entry distance is
@@ -89,8 +110,8 @@ __device__ __forceinline__ float box_entry32(const float4 lo, const float4 hi, c
     const double z0 = __builtin_fma((double)lo.z, r.iz, r.nz), z1 = __builtin_fma((double)hi.z, r.iz, r.nz);
     const double tn = fmax(fmax(fmin(x0, x1), fmin(y0, y1)), fmax(fmin(z0, z1), 0.0));
     const double tf = fmin(fmin(fmax(x0, x1), fmax(y0, y1)), fmax(z0, z1));
-    const double tn_lo = tn * (1.0 - 4.76837158e-7);
-    const double tf_hi = tf * (1.0 + 4.76837158e-7);
+    const double tn_lo = tn * (1.0 - 4.76837158e-7) - r.e;
+    const double tf_hi = tf * (1.0 + 4.76837158e-7) + r.e;
     const bool hit = (tn_lo <= tf_hi) && (tn_lo <= (double)best_up);
     return hit ? __double2float_rd(tn_lo) : __builtin_inff();
 }
@@ -116,8 +137,8 @@ __device__ __forceinline__ float rect_entry32(const float4 r4, const Ray64 &r, f
     const double y0 = __builtin_fma((double)r4.y, r.iy, r.ny), y1 = __builtin_fma((double)r4.w, r.iy, r.ny);
     const double tn = fmax(fmax(fmin(x0, x1), fmin(y0, y1)), 0.0);
     const double tf = fmin(fmax(x0, x1), fmax(y0, y1));
-    const double tn_lo = tn * (1.0 - 4.76837158e-7);
-    const double tf_hi = tf * (1.0 + 4.76837158e-7);
+    const double tn_lo = tn * (1.0 - 4.76837158e-7) - r.e;
+    const double tf_hi = tf * (1.0 + 4.76837158e-7) + r.e;
     const bool hit = (tn_lo <= tf_hi) && (tn_lo <= (double)best_up);
     return hit ? __double2float_rd(tn_lo) : __builtin_inff();
 }
@@ -874,6 +895,48 @@ __device__ __forceinline__ void sphere_leaf_step_at(const float4 *__restrict__ l
         sp -= 1;
         node = (!SPILL || sp < (uint32_t)STACK) ? lds_stack[(size_t)sp * kBvhThreads + tid]
                                                 : spill[(size_t)(sp - (uint32_t)STACK) * spill_stride + glane];
+    }
+}
+
+// One sphere of a leaf against one lane's ray, f32 only: the candidate test and bounds of sphere_step (rtx_traverse.h).  A sphere the
+// exact test cannot be excluded for joins the lane's candidate queue (LDS: {local index, t_lo}); a certain hit tightens best_up.
+__device__ __forceinline__ void sph_packet_leaf_test(const float4 rec, const uint32_t prim, const SphereRay &sr, uint32_t *lq, uint32_t tid,
+                                 float &best_up, uint32_t &qcnt, bool &overflow)
+{
+    const float ox = rec.x - sr.px, oy = rec.y - sr.py, oz = rec.z - sr.pz;
+    const float bq = __builtin_fmaf(ox, sr.dx, __builtin_fmaf(oy, sr.dy, oz * sr.dz));
+    const float lx = __builtin_fmaf(-bq, sr.dx, ox), ly = __builtin_fmaf(-bq, sr.dy, oy), lz = __builtin_fmaf(-bq, sr.dz, oz);
+    const float l2 = __builtin_fmaf(lx, lx, __builtin_fmaf(ly, ly, lz * lz));
+    const float Dl = __builtin_fmaf(rec.w, rec.w, -l2);
+    const float G = __builtin_fmaf(sr.Kg, rec.w, sr.c0);
+    const float Dp = Dl + G;
+    if (Dp >= 0.0f) {                                      // the exact test cannot be excluded (rtx_traverse.h, sphere_step)
+        const float tlo = bq - __builtin_amdgcn_sqrtf(Dp) * (1.0f + 4.76837158e-7f) - sr.K;
+        const float Dm = Dl - G;
+        const float thi = Dm > 0.0f ? bq - __builtin_amdgcn_sqrtf(Dm) * (1.0f - 4.76837158e-7f) + sr.K : __builtin_inff();
+        if (tlo <= best_up && !(thi < 0.0f)) {
+            if (tlo > sr.K) best_up = fminf(best_up, thi);
+            if (qcnt == (uint32_t)kSphQueue) {             // drop the entries a later certain hit has overtaken
+                uint32_t w = 0;
+#pragma unroll
+                for (int e = 0; e < kSphQueue; ++e) {
+                    const uint32_t ie = lq[(size_t)e * kBvhThreads + tid];
+                    const uint32_t te = lq[(size_t)(kSphQueue + e) * kBvhThreads + tid];
+                    if (__uint_as_float(te) <= best_up) {
+                        lq[(size_t)w * kBvhThreads + tid] = ie;
+                        lq[(size_t)(kSphQueue + w) * kBvhThreads + tid] = te;
+                        w += 1;
+                    }
+                }
+                qcnt = w;
+            }
+            if (qcnt == (uint32_t)kSphQueue) overflow = true;   // (the segment then tests every sphere exactly)
+            else {
+                lq[(size_t)qcnt * kBvhThreads + tid] = prim;
+                lq[(size_t)(kSphQueue + qcnt) * kBvhThreads + tid] = __float_as_uint(tlo);
+                qcnt += 1;
+            }
+        }
     }
 }
 

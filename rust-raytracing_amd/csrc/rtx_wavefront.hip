@@ -60,7 +60,7 @@ __device__ __forceinline__ void wf_make_rec(const SceneView &sv, const V3 &pos, 
     // 2^27 times that, or NaN: no walk (the shade kernel tests every shape)
     const float omax = fmaxf(fmaxf(__builtin_fabsf((float)pos.x), __builtin_fabsf((float)pos.y)), __builtin_fabsf((float)pos.z));
     const bool in32 = omax <= sv.bvh_origin_limit;
-    w.slack = ray32_slack(q.nx, q.ny, q.nz, in32);
+    w.slack = ray32_slack(q, in32);
     w.best_up = (in32 || omax <= sv.bvh_origin_limit * kBvhRange64) ? best_up : __builtin_nanf("");
     w.ridx = ridx;
 }

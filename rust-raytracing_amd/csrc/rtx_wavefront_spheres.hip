@@ -52,7 +52,7 @@ __device__ __forceinline__ void wf_make_sph_rec(const SceneView &sv, const V3 &p
     // an origin outside origin_limit walks with Ray32S's slack; beyond 2^27 times that, or NaN: no walk (every sphere is tested)
     const float omax = fmaxf(fmaxf(__builtin_fabsf((float)pos.x), __builtin_fabsf((float)pos.y)), __builtin_fabsf((float)pos.z));
     const bool in32 = omax <= sv.bvh_origin_limit;
-    w.slack = ray32_slack(q.nx, q.ny, q.nz, in32);
+    w.slack = ray32_slack(q, in32);
     w.Kg = (in32 || omax <= sv.bvh_origin_limit * kBvhRange64) ? sr.Kg : __builtin_nanf("");
     w.ridx = ridx;
 }
