@@ -357,6 +357,22 @@ public:
         const std::vector<RtxObject> packed = one.pack();
         check(rtx_scene_append_objects(h_, packed.data(), packed.size()));
     }
+    // Scene.objects[indices[i]] = objects[i] on the resident scene (rtx_scene_update_objects): moved spheres are refitted into the
+    // resident tree on the device, materials and planes are rewritten in place; anything the tree cannot take (a kind change, a
+    // triangle's geometry, a sphere beyond the range the tree was built for) or rebuild = true rebuilds as add_object does.
+    // Returns RTX_UPDATED_NOTHING / RECORDS / REFIT / REBUILT.
+    uint32_t update_objects(const std::vector<std::uint64_t> &indices, const std::vector<object::Object> &objects, bool rebuild = false,
+                            void *hip_stream = nullptr)
+    {
+        if (indices.size() != objects.size()) throw std::invalid_argument("update_objects: indices and objects differ in length");
+        Scene list;
+        for (const object::Object &o : objects) list.add_object(o);
+        const std::vector<RtxObject> packed = list.pack();
+        uint32_t how = RTX_UPDATED_NOTHING;
+        check(rtx_scene_update_objects(h_, indices.data(), packed.data(), packed.size(), rebuild ? RTX_UPDATE_REBUILD : RTX_UPDATE_AUTO,
+                                       hip_stream, &how));
+        return how;
+    }
     // rows row_begin, row_begin + row_stride, ... (n_rows of them) of the width x height image -> d_out_rgb[n_rows][width][3]
     RtxStats render_rows(std::size_t width, std::size_t height, std::size_t row_begin, std::size_t row_stride, std::size_t n_rows,
                          double *d_out_rgb, void *hip_stream = nullptr)

@@ -311,6 +311,32 @@ int32_t rtx_scene_set_scratch_limit(RtxSceneHandle scene, uint64_t bytes);
  * device.  On failure (e.g. an unsupported kind) the resident scene is unchanged. */
 int32_t rtx_scene_append_objects(RtxSceneHandle scene, const RtxObject *objects, uint64_t n_objects);
 
+/* Scene.objects[indices[i]] = objects[i] for i = 0 .. n-1, in order, on an uploaded scene (the reference: shapes sit behind
+ * Arc<Mutex<..>> and `material` is a pub field, object.rs:9-15, so Scene.objects[i] is mutable between renders).  `indices` and
+ * `objects` are HOST arrays; when an index repeats, its last entry wins.  After a successful call every entry point of the handle
+ * returns, bit for bit, what a freshly uploaded handle would return for the updated list with the same config and camera (RtxStats
+ * counters may differ): every kernel decides hits in f64 and the tree only selects candidates, so a tree that keeps its topology and
+ * gets new boxes finds the same winners.
+ *   *how (may be NULL) reports the path:
+ *   RTX_UPDATED_REBUILT   rtx_scene_append_objects' path on the modified list (host build, every array replaced).  Taken when mode is
+ *                         RTX_UPDATE_REBUILD, an entry changes an object's kind or a triangle's geometry, a new sphere is not finite,
+ *                         its box leaves the range the resident tree was built for, its reach |c - centre| + |r| or the resident
+ *                         sphere_cmax is not below 1e14, or the refit finds a 64-byte node it cannot encode.
+ *   RTX_UPDATED_REFIT     a sphere of the tree gets new geometry: its records are rewritten and the boxes above it refitted, on the device,
+ *                         one small kernel launch per tree level.  The topology is the old one: after large moves the frame is the
+ *                         same but slower than after a rebuild ("Moving objects").
+ *   RTX_UPDATED_RECORDS   anything else (materials of any kind -- an entry that repeats a sphere's resident geometry bit for bit is a
+ *                         material update --, plane geometry, spheres of a scene without a sphere sub-tree): the records alone.
+ *   RTX_UPDATED_NOTHING   n == 0.
+ * Errors, found before the first device write (the resident scene is unchanged): RTX_ERR_INVALID_ARGUMENT -- a null argument, an
+ * index >= n_objects, an unknown mode; RTX_ERR_UNSUPPORTED -- an unknown kind, a non-zero `reserved`.
+ * "Streams" applies: the device work is enqueued on `stream` behind whatever earlier calls enqueued on the handle.  The call returns
+ * after its own device work has completed (it reads back a status word and the new sphere_cmax). */
+enum { RTX_UPDATE_AUTO = 0, RTX_UPDATE_REBUILD = 1 };                       /* mode */
+enum { RTX_UPDATED_NOTHING = 0, RTX_UPDATED_RECORDS = 1, RTX_UPDATED_REFIT = 2, RTX_UPDATED_REBUILT = 3 };   /* *how */
+int32_t rtx_scene_update_objects(RtxSceneHandle scene, const uint64_t *indices, const RtxObject *objects, uint64_t n,
+                                 uint32_t mode, void *stream, uint32_t *how);
+
 /* Replace the Camera of an uploaded scene without re-uploading the objects (the reference's analogue is
  * Scene.camera being a pub field, scene.rs:82, with Camera::set_direction camera.rs:35-40).  Only fov, position and
  * to_world_space are read by render. */
@@ -664,6 +690,19 @@ int32_t rtx_debug_path_bounds(RtxSceneHandle scene, const RtxRay *rays, const ui
  * 10 largest leaf, 11 flat (footprint) nodes, 12 stack entries bound (3*depth+2), 13 tree triangles whose footprint lies in
  * the (x, y) plane, 14 those with an (x, z) or (y, z) footprint (zero-pivot row swaps, triangle.rs:60-71,81-87), 15 nodes that also exist in the 64-byte quantised form (flag 8). */
 int32_t rtx_debug_host_scene(const RtxScene *scene, uint64_t *stats);
+
+/* Test hook of the lab library (the product returns RTX_ERR_UNSUPPORTED), needs no GPU: the host half of rtx_scene_update_objects.
+ * Packs `scene`, decides the update's path as the entry point does, applies it with the host reference of the device kernel
+ * (refit_packed: the same header text, csrc/rtx_refit.h) -- or re-packs, for REBUILT -- and runs rtx_debug_host_scene's walk over
+ * the result and the updated object list (same stats[16]).  *how: RTX_UPDATED_*.  digests[8]: FNV-1a-64 of the wide nodes, the
+ * 64-byte sphere nodes, the leaf records (bvh_leaf_f32 then bvh_leaf_cr), sphere_f32, the sphere, plane and material records, and
+ * the bits of sphere_cmax.  The high 16 bits of `mode`, when non-zero, are a split point s: entries [0, s) are applied as one
+ * update and [s, n) as a second one on its result (*how is then the larger of the two). */
+int32_t rtx_debug_host_refit(const RtxScene *scene, const uint64_t *indices, const RtxObject *objects, uint64_t n, uint32_t mode,
+                             uint64_t *stats, uint32_t *how, uint64_t *digests);
+
+/* Test hook of the lab library: downloads the resident arrays of `scene` and digests them in rtx_debug_host_refit's order. */
+int32_t rtx_debug_resident_digests(RtxSceneHandle scene, uint64_t *digests);
 
 #ifdef __cplusplus
 }

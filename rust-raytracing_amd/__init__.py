@@ -488,6 +488,26 @@ class SceneHandle:
         arr = np.ascontiguousarray(arr, dtype=OBJECT_DTYPE)
         self._check(self._lib.rtx_scene_append_objects(self._h, arr.ctypes.data, len(arr)))
 
+    def update_objects(self, indices, packed, mode="auto", stream=None):
+        """Scene.objects[indices[i]] = packed[i] on the resident scene (rtx_scene_update_objects; a repeated index: its last entry
+        wins).  `packed` is an OBJECT_DTYPE array (or a list of Objects); mode "auto" or "rebuild".  Returns how the update ran:
+        "nothing", "records", "refit" or "rebuilt"."""
+        arr = packed if isinstance(packed, np.ndarray) else pack_objects(packed)
+        arr = np.ascontiguousarray(arr, dtype=OBJECT_DTYPE)
+        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.uint64).reshape(-1))
+        if len(idx) != len(arr):
+            raise ValueError("update_objects: %d indices for %d objects" % (len(idx), len(arr)))
+        how = C.c_uint32(0)
+        self._check(self._lib.rtx_scene_update_objects(self._h, idx.ctypes.data, arr.ctypes.data, len(arr), _update_mode(mode),
+                                                       C.c_void_p(int(stream)) if stream else None, C.byref(how)))
+        return UPDATE_HOW[how.value]
+
+    def debug_resident_digests(self):
+        """FNV-1a-64 digests of the resident arrays, in debug_host_refit's order (rtx_debug_resident_digests; a lab-library hook)."""
+        digests = (C.c_uint64 * 8)()
+        self._check(self._lib.rtx_debug_resident_digests(self._h, digests))
+        return tuple(int(v) for v in digests)
+
     def debug_paths(self, width, height, row, max_steps):
         """(steps, counts) -- the transcript of every path of image row `row` as the exhaustive f64 kernel walks it (rtx_debug_paths;
         a lab-library hook: upload with lab=True).  steps: structured array [width][rays_per_pixel][max_steps] of PATH_STEP_DTYPE,
@@ -837,6 +857,33 @@ def debug_host_scene(scene):
     stats = (C.c_uint64 * 16)()
     abi.check(load_library().rtx_debug_host_scene(C.byref(sc), stats))
     return dict(zip(HOST_SCENE_STATS, (int(v) for v in stats)))
+
+
+UPDATE_HOW = ("nothing", "records", "refit", "rebuilt")        # RTX_UPDATED_*
+
+
+def _update_mode(mode):
+    if isinstance(mode, str):
+        return {"auto": abi.RTX_UPDATE_AUTO, "rebuild": abi.RTX_UPDATE_REBUILD}[mode]
+    return int(mode)
+
+
+def debug_host_refit(scene, indices, packed, mode="auto", split=0):
+    """The host half of SceneHandle.update_objects on `scene` (rtx_debug_host_refit of the lab library; needs no GPU): the path
+    decision, the host reference of the device kernel (or a re-pack) and debug_host_scene's invariant walk over the result.
+    split > 0: entries [0, split) are one update, the rest a second one on its result.  Returns (how, stats dict, digests (8,))."""
+    import ctypes as C
+    sc = _scene_c(scene.config, scene.camera, scene.packed())
+    arr = packed if isinstance(packed, np.ndarray) else pack_objects(packed)
+    arr = np.ascontiguousarray(arr, dtype=OBJECT_DTYPE)
+    idx = np.ascontiguousarray(np.asarray(indices, dtype=np.uint64).reshape(-1))
+    if len(idx) != len(arr):
+        raise ValueError("debug_host_refit: %d indices for %d objects" % (len(idx), len(arr)))
+    stats, digests, how = (C.c_uint64 * 16)(), (C.c_uint64 * 8)(), C.c_uint32(0)
+    lib = load_library(True)
+    abi.check(lib.rtx_debug_host_refit(C.byref(sc), idx.ctypes.data, arr.ctypes.data, len(arr), _update_mode(mode) | (int(split) << 16),
+                                       stats, C.byref(how), digests), lib)
+    return UPDATE_HOW[how.value], dict(zip(HOST_SCENE_STATS, (int(v) for v in stats))), tuple(int(v) for v in digests)
 
 
 # one segment of a path's transcript (RtxPathStep, include/rtx_hip.h)

@@ -37,6 +37,8 @@ RTX_TUNE_LAB_MASK = (RTX_TUNE_BVH_CLASSIC | RTX_TUNE_NO_QNODES | RTX_TUNE_NO_PAC
                      RTX_TUNE_STAGE2_SLOTS)
 RTX_TUNE_KNOWN_MASK = (RTX_TUNE_LAB_MASK | RTX_TUNE_NO_TILES | RTX_TUNE_ONE_STAGE | RTX_TUNE_TWO_STAGE | RTX_TUNE_BVH_MEDIAN |
                        (15 << RTX_TUNE_TRI_LEAF_SHIFT) | (127 << RTX_TUNE_THRESH_SHIFT) | RTX_TUNE_NO_CUT | RTX_TUNE_HALVES | RTX_TUNE_NO_HALVES | RTX_TUNE_NO_TILE_LISTS)
+RTX_UPDATE_AUTO, RTX_UPDATE_REBUILD = 0, 1
+RTX_UPDATED_NOTHING, RTX_UPDATED_RECORDS, RTX_UPDATED_REFIT, RTX_UPDATED_REBUILT = 0, 1, 2, 3
 RTX_OK, RTX_ERR_INVALID_ARGUMENT, RTX_ERR_NO_DEVICE, RTX_ERR_HIP, RTX_ERR_UNSUPPORTED, RTX_ERR_OUT_OF_MEMORY = range(6)
 
 # RtxObject, 136 bytes: one entry of Scene.objects (scene.rs:80; object.rs:9-15,78-86)
@@ -111,6 +113,7 @@ SYMBOLS = [
     ("rtx_scene_set_scratch_limit", C.c_int32, [C.c_void_p, C.c_uint64]),
     ("rtx_scene_set_camera", C.c_int32, [C.c_void_p, C.POINTER(RtxCamera)]),
     ("rtx_scene_append_objects", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    ("rtx_scene_update_objects", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]),
     ("rtx_render_rows", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                     C.c_void_p, C.c_void_p, C.POINTER(RtxStats)]),
     ("rtx_blocks_row_count", C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
@@ -148,6 +151,9 @@ SYMBOLS = [
     ("rtx_debug_gather", C.c_int32, [C.c_int32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32,
                                      C.c_void_p]),
     ("rtx_debug_host_scene", C.c_int32, [C.POINTER(RtxScene), C.POINTER(C.c_uint64)]),
+    ("rtx_debug_host_refit", C.c_int32, [C.POINTER(RtxScene), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    ("rtx_debug_resident_digests", C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64)]),
 ]
 
 

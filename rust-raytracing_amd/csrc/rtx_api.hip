@@ -95,6 +95,17 @@ constexpr uint64_t kHalvesBelowRays = 0;
 // counts, its rule).
 constexpr size_t kWorkWords = kQueryRefineWords;
 
+// What rtx_scene_update_objects needs to know about the resident tree, kept on the host from every pack (upload, append, rebuild).
+struct RefitTables {
+    double scale = -1.0;                                  // the build's largest finite box coordinate ((origin_limit - 1) / 4); < 0: no tree was built
+    double abs_pad = 0.0;
+    double centre[3] = { 0.0, 0.0, 0.0 };
+    bool sphere_tree = false;                             // the spheres are in the tree (bvh_flags bit 0)
+    std::vector<uint32_t> local;                          // object index -> index in spheres[] / planes[] / tris[] (the kind: h->objects)
+    std::vector<uint32_t> slot;                           // sphere -> its leaf entry (the inverse of bvh.prims); empty without a sphere tree
+    std::vector<uint32_t> level_nodes, level_begin;       // the non-flat wide nodes grouped by depth: level d = level_nodes[level_begin[d] .. level_begin[d + 1])
+};
+
 struct RtxSceneHandle_ {
     int device = 0;
     int n_cus = 0;
@@ -103,6 +114,16 @@ struct RtxSceneHandle_ {
     SceneView sv{};
     std::vector<RtxObject> objects;                       // Scene.objects as uploaded (rtx_scene_append_objects re-packs them)
     std::vector<void *> scene_allocs;
+    // rtx_scene_update_objects: the host tables of the resident pack, and their device side -- made at the first REFIT or RECORDS
+    // call, dropped by any rebuild (upload_packed)
+    RefitTables refit;
+    struct UpdateBufs {
+        bool valid = false;
+        uint32_t *levels = nullptr; float *box32 = nullptr; double *reach = nullptr;
+        UpdateEntry *h_entries = nullptr; size_t h_cap = 0;     // pinned staging of the update list
+        UpdateEntry *d_entries = nullptr; size_t d_cap = 0;
+        unsigned long long *d_status = nullptr, *h_status = nullptr;   // {status bits, the bits of the new sphere_cmax}; h_status pinned
+    } upd;
     // scratch, grown on demand
     double *samples = nullptr;  size_t samples_bytes = 0;
     double *acc = nullptr;      size_t acc_bytes = 0;
@@ -207,11 +228,23 @@ int32_t grow(void **p, size_t *have, size_t want)
     return RTX_OK;
 }
 
+void drop_update_tables(RtxSceneHandle_ *h)              // the device tables of one pack (the staging buffers stay)
+{
+    auto &b = h->upd;
+    for (void *q : { (void *)b.levels, (void *)b.box32, (void *)b.reach }) if (q) (void)hipFree(q);
+    b.levels = nullptr; b.box32 = nullptr; b.reach = nullptr; b.valid = false;
+}
+
 void free_handle(RtxSceneHandle_ *h)
 {
     if (!h) return;
     (void)hipSetDevice(h->device);
     for (void *p : h->scene_allocs) (void)hipFree(p);
+    drop_update_tables(h);
+    if (h->upd.h_entries) (void)hipHostFree(h->upd.h_entries);
+    if (h->upd.d_entries) (void)hipFree(h->upd.d_entries);
+    if (h->upd.d_status) (void)hipFree(h->upd.d_status);
+    if (h->upd.h_status) (void)hipHostFree(h->upd.h_status);
     if (h->samples) (void)hipFree(h->samples);
     if (h->acc) (void)hipFree(h->acc);
     if (h->tables) (void)hipFree(h->tables);
@@ -473,6 +506,38 @@ int32_t pack_scene(const RtxScene *scene, PackedScene &p)
     return RTX_OK;
 }
 
+RefitTables make_refit_tables(const PackedScene &p)
+{
+    RefitTables t;
+    t.abs_pad = p.bvh.abs_pad;
+    t.scale = p.bvh.origin_limit > 0.0 ? (p.bvh.origin_limit - 1.0) / 4.0 : -1.0;
+    for (int c = 0; c < 3; ++c) t.centre[c] = p.sv.sphere_center[c];
+    t.sphere_tree = (p.sv.bvh_flags & 1u) != 0u;
+    t.local.assign(p.mats.size(), 0u);
+    for (size_t k = 0; k < p.sphere_id.size(); ++k) t.local[p.sphere_id[k]] = (uint32_t)k;
+    for (size_t k = 0; k < p.planes.size(); ++k) t.local[p.planes[k].id] = (uint32_t)k;
+    for (size_t k = 0; k < p.tris.size(); ++k) t.local[p.tris[k].id] = (uint32_t)k;
+    if (!t.sphere_tree) return t;
+    t.slot.assign(p.spheres.size(), kNoSlot);
+    for (size_t k = 0; k < p.bvh.prims.size(); ++k) t.slot[p.bvh.prims[k]] = (uint32_t)k;
+    auto bits = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
+    std::vector<uint32_t> cur, next;
+    if (!(p.bvh4.root & kBvhFlatNode)) cur.push_back(0u);
+    t.level_begin.push_back(0u);
+    while (!cur.empty()) {
+        next.clear();
+        for (uint32_t idx : cur) {
+            t.level_nodes.push_back(idx);
+            const Bvh4Node &w = p.bvh4.nodes[idx];
+            for (int c = 0; c < 4; ++c)
+                if (bits(w.b[c].w) == 0u && !(bits(w.a[c].w) & kBvhFlatNode)) next.push_back(bits(w.a[c].w));
+        }
+        t.level_begin.push_back((uint32_t)t.level_nodes.size());
+        cur.swap(next);
+    }
+    return t;
+}
+
 // Puts a packed scene (shape arrays, filter records, BVH) on the handle's device, replacing what was there.  Config
 // and camera of the handle are kept.  The new arrays are uploaded first and swapped in on success, so a failure
 // leaves the resident scene as it was.
@@ -517,6 +582,8 @@ int32_t upload_packed(RtxSceneHandle_ *h, const PackedScene &p)
     }
     for (void *d : old_allocs) (void)hipFree(d);
     h->sv_dirty = true;
+    h->refit = make_refit_tables(p);
+    drop_update_tables(h);
     return RTX_OK;
 }
 
@@ -525,6 +592,135 @@ int32_t install_scene(RtxSceneHandle_ *h, const RtxScene *scene)
     PackedScene p;
     if (int32_t prc = pack_scene(scene, p)) return prc;
     return upload_packed(h, p);
+}
+
+// ---- rtx_scene_update_objects: what the host decides (no HIP call: rtx_debug_host_refit runs it without a GPU) -------------------
+
+// An update after validation: the de-duplicated entries (the last entry of an index wins) and the path they take.
+struct UpdatePlan {
+    std::vector<UpdateEntry> entries;
+    uint32_t how = RTX_UPDATED_NOTHING;
+    bool any_sphere = false;                              // a sphere's geometry changes: sphere_cmax is taken again
+};
+
+// Validates (nothing is written before every entry passed), removes duplicates and chooses the path (include/rtx_hip.h, "Which path
+// runs").  `cur` is the resident object list, `cmax` the resident sphere_cmax.  Every scene-wide constant of pack_scene either stays a
+// valid bound under REFIT / RECORDS or sends the update to REBUILT:
+//   sphere_center   kept: the f32 records are offsets from ANY fixed point; what depends on it is sphere_cmax, which mode C recomputes
+//                   against the kept centre, and the < 1e14 limit of pack_scene, which every new reach is held to here
+//   origin_limit, abs_pad, bvh_inv_max   functions of `scale`: a new box beyond it rebuilds
+//   tri_extent, the triangle records     triangle geometry never changes here (it rebuilds)
+//   bvh_depth, bvh_flags, the topology   the tree keeps its shape; a sphere that turns non-finite (it would leave the tree) rebuilds
+int32_t plan_update(const std::vector<RtxObject> &cur, const RefitTables &t, double cmax, const uint64_t *indices, const RtxObject *objects,
+                    uint64_t n, uint32_t mode, UpdatePlan &plan)
+{
+    plan = UpdatePlan();
+    if (mode != RTX_UPDATE_AUTO && mode != RTX_UPDATE_REBUILD) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_update_objects: unknown mode");
+    if (n == 0) return RTX_OK;
+    if (!indices || !objects) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_update_objects: null argument");
+    for (uint64_t i = 0; i < n; ++i) {
+        if (indices[i] >= cur.size())
+            return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_update_objects: index " + std::to_string(indices[i]) + " is not below n_objects");
+        if (objects[i].kind > RTX_TRIANGLE)
+            return fail(RTX_ERR_UNSUPPORTED, "rtx_scene_update_objects: entry " + std::to_string(i) + ": kind " + std::to_string(objects[i].kind) +
+                                                 " has no device primitive");
+        if (objects[i].reserved != 0u) return fail(RTX_ERR_UNSUPPORTED, "rtx_scene_update_objects: entry " + std::to_string(i) + ": reserved is not zero");
+    }
+    std::vector<uint8_t> seen(cur.size(), 0);
+    plan.entries.reserve((size_t)std::min<uint64_t>(n, cur.size()));
+    bool rebuild = mode == RTX_UPDATE_REBUILD || !(cmax < 1.0e14);
+    bool refit = false;
+    for (uint64_t i = n; i-- > 0;) {
+        const uint64_t idx = indices[i];
+        if (seen[idx]) continue;
+        seen[idx] = 1;
+        const RtxObject &o = objects[i];
+        UpdateEntry e;
+        std::memset(&e, 0, sizeof e);
+        e.object = (uint32_t)idx; e.local = t.local[idx]; e.slot = kNoSlot;
+        static_assert(sizeof(RtxObject) == 136 && offsetof(UpdateEntry, kind) == 16, "UpdateEntry carries an RtxObject");
+        std::memcpy(&e.kind, &o, sizeof o);
+        if (o.kind != cur[idx].kind) rebuild = true;
+        else if (o.kind == RTX_TRIANGLE) {
+            if (std::memcmp(o.geom, cur[idx].geom, sizeof o.geom) != 0) rebuild = true;
+        } else if (o.kind == RTX_SPHERE && std::memcmp(o.geom, cur[idx].geom, 4 * sizeof(double)) != 0) {      // (same geometry: a material update)
+            plan.any_sphere = true;
+            BvhBox b;
+            if (!sphere_box(o.geom, b)) rebuild = true;
+            else {
+                if (t.scale >= 0.0)
+                    for (int a = 0; a < 3; ++a) if (std::fabs(b.lo[a]) > t.scale || std::fabs(b.hi[a]) > t.scale) rebuild = true;
+                const double cx = o.geom[0] - t.centre[0], cy = o.geom[1] - t.centre[1], cz = o.geom[2] - t.centre[2];
+                if (!(std::sqrt(cx * cx + cy * cy + cz * cz) + std::fabs(o.geom[3]) < 1.0e14)) rebuild = true;
+            }
+            if (t.sphere_tree) { e.slot = t.slot[e.local]; refit = true; }
+        }
+        plan.entries.push_back(e);
+    }
+    plan.how = rebuild ? RTX_UPDATED_REBUILT : (refit ? RTX_UPDATED_REFIT : RTX_UPDATED_RECORDS);
+    return RTX_OK;
+}
+
+// box32 / reach of every sphere of `objects` (what mode B and mode C read for the spheres an update does not name).
+void derive_all_spheres(const PackedScene &p, const RtxObject *objects, const RefitTables &t, std::vector<float> &box32, std::vector<double> &reach)
+{
+    box32.assign(p.spheres.size() * 6, 0.f);
+    reach.assign(p.spheres.size(), 0.0);
+    for (size_t k = 0; k < p.spheres.size(); ++k) {
+        const SphereDerived d = derive_sphere(objects[p.sphere_id[k]].geom, t.centre, t.abs_pad);
+        for (int a = 0; a < 3; ++a) { box32[6 * k + a] = d.lo[a]; box32[6 * k + 3 + a] = d.hi[a]; }
+        reach[k] = d.reach;
+    }
+}
+
+// The host reference of the device path: rtx_refit.h's functions in the order the launches run them, on a packed scene.  Returns the
+// status word (kUpdateStatusNoQ3: a 64-byte node has no encoding -- the caller rebuilds).
+unsigned long long refit_packed(PackedScene &p, const RefitTables &t, const UpdatePlan &plan, std::vector<float> &box32, std::vector<double> &reach)
+{
+    unsigned long long status = 0ull;
+    UpdateArgs u{};
+    u.entries = plan.entries.data();
+    u.spheres = p.spheres.data(); u.planes = p.planes.data(); u.materials = p.mats.data();
+    u.sphere_f32 = reinterpret_cast<float *>(p.sph32.data());
+    u.leaf_f32 = p.leaf32.data(); u.leaf_cr = p.leaf_cr.data();
+    u.box32 = box32.data(); u.reach = reach.data();
+    u.nodes = p.bvh4.nodes.data(); u.q3nodes = (p.sv.bvh_flags & 16u) ? p.q3nodes.data() : nullptr;
+    u.prims = p.bvh.prims.data();
+    for (int c = 0; c < 3; ++c) u.centre[c] = t.centre[c];
+    u.abs_pad = t.abs_pad;
+    for (uint32_t i = 0; i < (uint32_t)plan.entries.size(); ++i) update_record(u, i);
+    if (plan.how == RTX_UPDATED_REFIT)
+        for (size_t d = t.level_begin.size() - 1; d-- > 0;)
+            for (uint32_t k = t.level_begin[d]; k < t.level_begin[d + 1]; ++k)
+                if (!refit_node(u, t.level_nodes[k])) status |= kUpdateStatusNoQ3;
+    if (plan.any_sphere) {
+        double m = 0.0;
+        for (double r : reach) m = r > m ? r : m;
+        p.sv.sphere_cmax = m;
+    }
+    return status;
+}
+
+// FNV-1a-64 digests of a scene's arrays, in the order of rtx_debug_host_refit: nodes, 64-byte sphere nodes, leaf records (bvh_leaf_f32
+// then bvh_leaf_cr), sphere_f32, spheres, planes, materials, the bits of sphere_cmax.
+uint64_t fnv1a(uint64_t h, const void *data, size_t bytes)
+{
+    const unsigned char *b = static_cast<const unsigned char *>(data);
+    for (size_t k = 0; k < bytes; ++k) { h ^= b[k]; h *= 0x100000001B3ull; }
+    return h;
+}
+constexpr uint64_t kFnvBasis = 0xCBF29CE484222325ull;
+
+void digest_packed(const PackedScene &p, uint64_t *digests)
+{
+    digests[0] = fnv1a(kFnvBasis, p.bvh4.nodes.data(), p.bvh4.nodes.size() * sizeof(Bvh4Node));
+    digests[1] = fnv1a(kFnvBasis, p.q3nodes.data(), p.q3nodes.size() * sizeof(BvhQ3Node));
+    digests[2] = fnv1a(fnv1a(kFnvBasis, p.leaf32.data(), p.leaf32.size() * sizeof(float4)), p.leaf_cr.data(), p.leaf_cr.size() * sizeof(float4));
+    digests[3] = fnv1a(kFnvBasis, p.sph32.data(), p.sph32.size() * sizeof(float4));
+    digests[4] = fnv1a(kFnvBasis, p.spheres.data(), p.spheres.size() * sizeof(SphereX));
+    digests[5] = fnv1a(kFnvBasis, p.planes.data(), p.planes.size() * sizeof(PlaneX));
+    digests[6] = fnv1a(kFnvBasis, p.mats.data(), p.mats.size() * sizeof(MaterialX));
+    digests[7] = fnv1a(kFnvBasis, &p.sv.sphere_cmax, sizeof(double));
 }
 
 int32_t check_scene_args(const RtxScene *scene, const char *who)
@@ -817,6 +1013,136 @@ int32_t rtx_scene_append_objects(RtxSceneHandle scene, const RtxObject *objects,
     sc.objects = all.data();
     if (int32_t rc = install_scene(scene, &sc)) return rc;      // (on failure the resident scene is as it was)
     scene->objects.swap(all);
+    return RTX_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The device side of the refit tables of the resident pack, made at the first REFIT or RECORDS call after it.
+int32_t ensure_update_tables(RtxSceneHandle_ *h)
+{
+    auto &b = h->upd;
+    if (!b.d_status) RTX_HIP_CHECK(hipMalloc((void **)&b.d_status, 2 * sizeof(unsigned long long)));
+    if (!b.h_status) RTX_HIP_CHECK(hipHostMalloc((void **)&b.h_status, 2 * sizeof(unsigned long long), hipHostMallocDefault));
+    if (b.valid) return RTX_OK;
+    drop_update_tables(h);
+    const RefitTables &t = h->refit;
+    const size_t ns = h->sv.n_spheres;
+    std::vector<float> box32(ns * 6, 0.f);
+    std::vector<double> reach(ns, 0.0);
+    for (size_t k = 0; k < h->objects.size(); ++k) {
+        if (h->objects[k].kind != RTX_SPHERE) continue;
+        const SphereDerived d = derive_sphere(h->objects[k].geom, t.centre, t.abs_pad);
+        const size_t q = t.local[k];
+        for (int a = 0; a < 3; ++a) { box32[6 * q + a] = d.lo[a]; box32[6 * q + 3 + a] = d.hi[a]; }
+        reach[q] = d.reach;
+    }
+    if (ns) {
+        RTX_HIP_CHECK(hipMalloc((void **)&b.box32, box32.size() * sizeof(float)));
+        RTX_HIP_CHECK(hipMalloc((void **)&b.reach, reach.size() * sizeof(double)));
+        RTX_HIP_CHECK(hipMemcpy(b.box32, box32.data(), box32.size() * sizeof(float), hipMemcpyHostToDevice));
+        RTX_HIP_CHECK(hipMemcpy(b.reach, reach.data(), reach.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (!t.level_nodes.empty()) {
+        RTX_HIP_CHECK(hipMalloc((void **)&b.levels, t.level_nodes.size() * sizeof(uint32_t)));
+        RTX_HIP_CHECK(hipMemcpy(b.levels, t.level_nodes.data(), t.level_nodes.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    b.valid = true;
+    return RTX_OK;
+}
+
+// The update as a rebuild: rtx_scene_append_objects' path on the modified list.
+int32_t update_by_rebuild(RtxSceneHandle_ *h, const UpdatePlan &plan)
+{
+    RTX_HIP_CHECK(hipDeviceSynchronize());                  // a render may still read the arrays about to be replaced
+    std::vector<RtxObject> all = h->objects;
+    for (const UpdateEntry &e : plan.entries) std::memcpy(&all[e.object], &e.kind, sizeof(RtxObject));
+    RtxScene sc{};
+    sc.config = h->cfg;
+    sc.camera = h->cam;
+    sc.n_objects = all.size();
+    sc.objects = all.data();
+    if (int32_t rc = install_scene(h, &sc)) return rc;
+    h->objects.swap(all);
+    return RTX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t rtx_scene_update_objects(RtxSceneHandle h, const uint64_t *indices, const RtxObject *objects, uint64_t n, uint32_t mode,
+                                 void *stream_, uint32_t *how)
+{
+    if (how) *how = RTX_UPDATED_NOTHING;
+    if (!h) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_update_objects: null scene");
+    UpdatePlan plan;
+    if (int32_t rc = plan_update(h->objects, h->refit, h->sv.sphere_cmax, indices, objects, n, mode, plan)) return rc;
+    if (plan.entries.empty()) return RTX_OK;
+    RTX_HIP_CHECK(hipSetDevice(h->device));
+    if (int32_t rc = check_watchdog(h, true)) return rc;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (plan.how != RTX_UPDATED_REBUILT) {
+        auto &b = h->upd;
+        if (int32_t rc = ensure_update_tables(h)) return rc;
+        const size_t ne = plan.entries.size(), bytes = ne * sizeof(UpdateEntry);
+        if (b.h_cap < ne) {
+            if (b.h_entries) { RTX_HIP_CHECK(hipHostFree(b.h_entries)); b.h_entries = nullptr; b.h_cap = 0; }
+            RTX_HIP_CHECK(hipHostMalloc((void **)&b.h_entries, bytes, hipHostMallocDefault));
+            b.h_cap = ne;
+        }
+        if (b.d_cap < ne) {
+            if (b.d_entries) { RTX_HIP_CHECK(hipFree(b.d_entries)); b.d_entries = nullptr; b.d_cap = 0; }
+            RTX_HIP_CHECK(hipMalloc((void **)&b.d_entries, bytes));
+            b.d_cap = ne;
+        }
+        std::memcpy(b.h_entries, plan.entries.data(), bytes);
+        {
+            if (int32_t rc = adopt_stream(h, stream)) return rc;      // the writes below wait for what earlier calls enqueued
+            DoneGuard done{h, stream};
+            const RefitTables &t = h->refit;
+            const SceneView &sv = h->sv;
+            RTX_HIP_CHECK(hipMemcpyAsync(b.d_entries, b.h_entries, bytes, hipMemcpyHostToDevice, stream));
+            RTX_HIP_CHECK(hipMemsetAsync(b.d_status, 0, 2 * sizeof(unsigned long long), stream));
+            UpdateArgs u{};
+            u.entries = b.d_entries;
+            u.spheres = const_cast<SphereX *>(sv.spheres); u.planes = const_cast<PlaneX *>(sv.planes);
+            u.materials = const_cast<MaterialX *>(sv.materials);
+            u.sphere_f32 = reinterpret_cast<float *>(const_cast<float4 *>(sv.sphere_f32));
+            u.leaf_f32 = const_cast<float4 *>(sv.bvh_leaf_f32); u.leaf_cr = const_cast<float4 *>(sv.bvh_leaf_cr);
+            u.box32 = b.box32; u.reach = b.reach;
+            u.nodes = const_cast<Bvh4Node *>(sv.bvh_nodes);
+            u.q3nodes = (sv.bvh_flags & 16u) ? const_cast<BvhQ3Node *>(sv.bvh_q3nodes) : nullptr;
+            u.prims = sv.bvh_prims;
+            u.status = b.d_status;
+            for (int c = 0; c < 3; ++c) u.centre[c] = t.centre[c];
+            u.abs_pad = t.abs_pad;
+            u.mode = 0u; u.n = (uint32_t)ne;
+            RTX_HIP_CHECK(launch_scene_update(u, stream));
+            if (plan.how == RTX_UPDATED_REFIT)
+                for (size_t d = t.level_begin.size() - 1; d-- > 0;) {       // deepest first: a node reads what its children's launch wrote
+                    u.mode = 1u; u.n = t.level_begin[d + 1] - t.level_begin[d];
+                    u.level = b.levels + t.level_begin[d];
+                    RTX_HIP_CHECK(launch_scene_update(u, stream));
+                }
+            if (plan.any_sphere) {
+                u.mode = 2u; u.n = sv.n_spheres;
+                RTX_HIP_CHECK(launch_scene_update(u, stream));
+            }
+            RTX_HIP_CHECK(hipMemcpyAsync(b.h_status, b.d_status, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+            RTX_HIP_CHECK(hipStreamSynchronize(stream));
+        }
+        if (h->upd.h_status[0] & kUpdateStatusNoQ3) plan.how = RTX_UPDATED_REBUILT;       // every array is replaced below
+        else {
+            for (const UpdateEntry &e : plan.entries) std::memcpy(&h->objects[e.object], &e.kind, sizeof(RtxObject));
+            if (plan.any_sphere) { std::memcpy(&h->sv.sphere_cmax, &h->upd.h_status[1], sizeof(double)); h->sv_dirty = true; }
+        }
+    }
+    if (plan.how == RTX_UPDATED_REBUILT)
+        if (int32_t rc = update_by_rebuild(h, plan)) return rc;
+    if (how) *how = plan.how;
     return RTX_OK;
 }
 
@@ -1647,7 +1973,7 @@ static int32_t render_common(const RtxScene *scene, uint32_t width, uint32_t hei
                 std::fprintf(stderr, "[rtx_hip] device %d band %u/%u: rays %llu segments %llu exact %llu filter %llu mismatches %llu trace %.3f ms resolve %.3f ms\n",
                              dev, k, n_dev, (unsigned long long)st.primary_rays, (unsigned long long)st.segments, (unsigned long long)st.exact_tests,
                              (unsigned long long)st.filter_tests, (unsigned long long)st.filter_mismatches, st.trace_ms, st.resolve_ms);
-            if (w.rc == RTX_OK && n_rows && as_u8) hip(launch_quantize_values(d_band, d_band8, width, n_rows, stream), "quantize_kernel");
+            if (w.rc == RTX_OK && n_rows && as_u8) hip(launch_quantize_values(d_band, d_band8, width, n_rows, stream), "epilogue_kernel");
             if (w.rc == RTX_OK && n_rows && !local)
                 hip(hipMemcpyPeerAsync(dst, dev0, as_u8 ? (const void *)d_band8 : (const void *)d_band, dev, n_vals * val_bytes, stream),
                     "hipMemcpyPeerAsync");
@@ -1714,12 +2040,13 @@ int32_t rtx_render_to_image_devices(const RtxScene *scene, uint32_t width, uint3
     return render_common(scene, width, height, devices, n_devices, nullptr, out_rgb8);
 }
 
-int32_t rtx_debug_host_scene(const RtxScene *scene, uint64_t *stats)
+}  // extern "C"
+
+// The invariant walk of rtx_debug_host_scene / rtx_debug_host_refit over a packed scene and the object list it stands for: every
+// shape's box inside its leaf child's box, every child inside its parent's, every 64-byte node's decoded child box around the
+// 128-byte child's.  `stats`: include/rtx_hip.h, rtx_debug_host_scene.
+static int32_t check_packed(const PackedScene &p, const RtxObject *objects, uint64_t *stats)
 {
-    if (!scene || !stats) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_host_scene: null argument");
-    if (scene->n_objects && !scene->objects) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_host_scene: objects is null");
-    PackedScene p;
-    if (int32_t rc = pack_scene(scene, p)) return rc;
     for (int k = 0; k < 16; ++k) stats[k] = 0;
     stats[0] = p.spheres.size(); stats[1] = p.tris.size(); stats[2] = p.sv.n_tri_filter; stats[3] = p.sv.n_tri_tree;
     stats[4] = p.bvh4.nodes.size(); stats[5] = (uint64_t)p.bvh4.depth; stats[6] = p.bvh.nodes.size(); stats[7] = p.sv.bvh_flags;
@@ -1772,7 +2099,7 @@ int32_t rtx_debug_host_scene(const RtxScene *scene, uint64_t *stats)
                     if (rec >= p.sv.n_tri_tree) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: triangle record out of range");
                     if (tri_seen[rec]++) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: triangle in two leaves");
                     const TriX &tx = p.tris[p.tri_fidx[rec]];
-                    const RtxObject &o = scene->objects[tx.id];
+                    const RtxObject &o = objects[tx.id];
                     const int free_axis = p.tri_rec_free_axis[rec];
                     if (free_axis != 3 - (int)tx.i - (int)tx.j) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: footprint plane differs from the elimination's rows");
                     if (flat && free_axis != 2) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: a flat node holds a triangle that is not solved in (x, y)");
@@ -1791,7 +2118,7 @@ int32_t rtx_debug_host_scene(const RtxScene *scene, uint64_t *stats)
                     const uint32_t sidx = p.bvh.prims[link + k];
                     if (sidx >= p.spheres.size() || sphere_seen[sidx]++) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: sphere in two leaves");
                     BvhBox sb;
-                    if (!sphere_box(scene->objects[p.sphere_id[sidx]].geom, sb)) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: non-finite sphere in the tree");
+                    if (!sphere_box(objects[p.sphere_id[sidx]].geom, sb)) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: non-finite sphere in the tree");
                     for (int a = 0; a < 3; ++a)
                         if (!((double)b.lo[a] <= sb.lo[a] && (double)b.hi[a] >= sb.hi[a]))
                             return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: sphere outside its leaf");
@@ -1851,6 +2178,91 @@ int32_t rtx_debug_host_scene(const RtxScene *scene, uint64_t *stats)
     if ((p.sv.bvh_flags & 1u) && stats[8] != p.spheres.size()) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: a sphere is in no leaf");
     if ((p.sv.bvh_flags & 2u) && stats[9] != p.sv.n_tri_tree) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: a triangle is in no leaf");
     return RTX_OK;
+}
+
+extern "C" {
+
+int32_t rtx_debug_host_scene(const RtxScene *scene, uint64_t *stats)
+{
+    if (!scene || !stats) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_host_scene: null argument");
+    if (scene->n_objects && !scene->objects) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_host_scene: objects is null");
+    PackedScene p;
+    if (int32_t rc = pack_scene(scene, p)) return rc;
+    return check_packed(p, scene->objects, stats);
+}
+
+int32_t rtx_debug_host_refit(const RtxScene *scene, const uint64_t *indices, const RtxObject *objects, uint64_t n, uint32_t mode,
+                             uint64_t *stats, uint32_t *how, uint64_t *digests)
+{
+#ifdef RTX_LAB
+    if (!scene || !stats || !how || !digests) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_host_refit: null argument");
+    if (scene->n_objects && !scene->objects) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_host_refit: objects is null");
+    *how = RTX_UPDATED_NOTHING;
+    const uint64_t split = mode >> 16;                       // (lab) entries [0, split) are one update, [split, n) the next
+    mode &= 0xFFFFu;
+    if (split > n) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_host_refit: the split point is beyond n");
+    std::vector<RtxObject> cur(scene->objects, scene->objects + scene->n_objects);
+    RtxScene sc = *scene;
+    PackedScene p;
+    if (int32_t rc = pack_scene(&sc, p)) return rc;
+    RefitTables t = make_refit_tables(p);
+    const uint64_t cut[3] = { 0, split, n };
+    for (int part = split ? 0 : 1; part < 2; ++part) {
+        const uint64_t first = cut[part], count = cut[part + 1] - cut[part];
+        UpdatePlan plan;
+        if (int32_t rc = plan_update(cur, t, p.sv.sphere_cmax, indices ? indices + first : nullptr, objects ? objects + first : nullptr, count, mode, plan))
+            return rc;
+        if (plan.how == RTX_UPDATED_REFIT || plan.how == RTX_UPDATED_RECORDS) {
+            std::vector<float> box32;
+            std::vector<double> reach;
+            derive_all_spheres(p, cur.data(), t, box32, reach);
+            if (refit_packed(p, t, plan, box32, reach) & kUpdateStatusNoQ3) plan.how = RTX_UPDATED_REBUILT;
+        }
+        for (const UpdateEntry &e : plan.entries) std::memcpy(&cur[e.object], &e.kind, sizeof(RtxObject));
+        if (plan.how == RTX_UPDATED_REBUILT) {
+            sc.objects = cur.data();
+            p = PackedScene();
+            if (int32_t rc = pack_scene(&sc, p)) return rc;
+            t = make_refit_tables(p);
+        }
+        if (plan.how > *how) *how = plan.how;
+    }
+    digest_packed(p, digests);
+    return check_packed(p, cur.data(), stats);
+#else
+    (void)scene; (void)indices; (void)objects; (void)n; (void)mode; (void)stats; (void)how; (void)digests;
+    return fail(RTX_ERR_UNSUPPORTED, "rtx_debug_host_refit is a hook of the lab library (librtx_hip_lab.so)");
+#endif
+}
+
+int32_t rtx_debug_resident_digests(RtxSceneHandle h, uint64_t *digests)
+{
+#ifdef RTX_LAB
+    if (!h || !digests) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_resident_digests: null argument");
+    RTX_HIP_CHECK(hipSetDevice(h->device));
+    RTX_HIP_CHECK(hipDeviceSynchronize());
+    const SceneView &sv = h->sv;
+    PackedScene p;                                            // the resident arrays, downloaded into the shape digest_packed reads
+    auto fetch = [](auto &vec, const void *src, size_t count) -> hipError_t {
+        vec.resize(count);
+        return count && src ? hipMemcpy(vec.data(), src, count * sizeof(vec[0]), hipMemcpyDeviceToHost) : hipSuccess;
+    };
+    const size_t n_leaf = h->refit.sphere_tree ? h->refit.slot.size() : 0;
+    RTX_HIP_CHECK(fetch(p.bvh4.nodes, sv.bvh_nodes, sv.n_bvh_nodes));
+    RTX_HIP_CHECK(fetch(p.q3nodes, sv.bvh_q3nodes, sv.bvh_q3nodes ? sv.n_bvh_nodes : 0));
+    RTX_HIP_CHECK(fetch(p.leaf32, sv.bvh_leaf_f32, n_leaf));
+    RTX_HIP_CHECK(fetch(p.leaf_cr, sv.bvh_leaf_cr, n_leaf));
+    RTX_HIP_CHECK(fetch(p.sph32, sv.sphere_f32, ((size_t)sv.n_spheres + 3) & ~(size_t)3));
+    RTX_HIP_CHECK(fetch(p.spheres, sv.spheres, sv.n_spheres));
+    RTX_HIP_CHECK(fetch(p.planes, sv.planes, sv.n_planes));
+    RTX_HIP_CHECK(fetch(p.mats, sv.materials, sv.n_objects));
+    p.sv.sphere_cmax = sv.sphere_cmax;
+    digest_packed(p, digests);
+    return RTX_OK;
+#else
+    (void)h; (void)digests;
+    return fail(RTX_ERR_UNSUPPORTED, "rtx_debug_resident_digests is a hook of the lab library (librtx_hip_lab.so)");
+#endif
 }
 
 int32_t rtx_debug_paths(RtxSceneHandle h, uint32_t width, uint32_t height, uint32_t row, uint32_t max_steps, RtxPathStep *steps,

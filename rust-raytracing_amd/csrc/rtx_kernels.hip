@@ -11,7 +11,7 @@
 //                       trace_exact_kernel.  Dead slots are refilled from a global ray queue with a
 //                       wave ballot + mbcnt prefix sum (one atomic per workgroup per round).
 //   resolve_kernel      left fold of a pixel's samples in sample order, then / rays_per_pixel.
-//   quantize_kernel     render_to_image epilogue.
+//   epilogue_kernel     render_to_image's quantize and the multi-device gather, by a launch-uniform form.
 //
 // Compiled with -ffp-contract=off; the f32 filter uses explicit fmaf.
 #include "rtx_launch.h"
@@ -594,34 +594,32 @@ __device__ __forceinline__ uint8_t rust_as_u8(double v)
     return (uint8_t)v;
 }
 
-// flip = 1: render_to_image's rows, output row y from row height - 1 - y (scene.rs:176) -- the whole-frame epilogue.
-// flip = 0: the rows of a band in place order (before it travels over xGMI: 3 bytes per pixel instead of 24; the gather
-// epilogue puts rows where they belong).
-__global__ __launch_bounds__(256) void quantize_kernel(const double *__restrict__ rgb, uint8_t *__restrict__ rgb8,
-                                                       uint32_t width, uint32_t height, uint32_t flip)
+// The epilogues: one kernel, a launch-uniform `form` (memory-bound movers of one value or one pixel per thread).
+//
+// form 0 -- quantize (render_to_image's `* 256`, Rust's saturating `as u8`), one pixel per thread.
+//   flip = 1: render_to_image's rows, output row y from row height - 1 - y (scene.rs:176) -- the whole-frame epilogue.
+//   flip = 0: the rows of a band in place order (before it travels over xGMI: 3 bytes per pixel instead of 24; the gather
+//   epilogue puts rows where they belong).
+// form 8 / 1 -- the multi-device gather epilogue on values of that many bytes (8: the f64 frame, 1: the quantised one), one value
+//   per thread, moved as one load and one store: parts[p] (cap_rows rows each) holds band p of n: the blocks of `block` image rows
+//   b = p, p + n, ... in order.  flip: output row height - 1 - y (render_to_image, scene.rs:176).
+__global__ __launch_bounds__(256) void epilogue_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
+                                                       uint32_t width, uint32_t height, uint32_t n, uint32_t cap_rows,
+                                                       uint32_t block, uint32_t flip, uint32_t form)
 {
-    uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t npix = (uint64_t)width * height;
-    if (p >= npix) return;
-    uint32_t y = (uint32_t)(p / width);
-    uint32_t x = (uint32_t)(p - (uint64_t)y * width);
-    const double *c = rgb + 3 * ((uint64_t)(flip ? height - y - 1 : y) * width + x);
-    uint8_t *o = rgb8 + 3 * p;
-    o[0] = rust_as_u8(c[0] * 256.0);
-    o[1] = rust_as_u8(c[1] * 256.0);
-    o[2] = rust_as_u8(c[2] * 256.0);
-}
-
-// ------------------------------------------------------------------------------------------
-// multi-device gather epilogue: parts[p] (cap_rows rows each) holds band p of n: the blocks of `block` image rows
-// b = p, p + n, ... in order.  flip: output row height - 1 - y (render_to_image, scene.rs:176).  A value is elem_bytes
-// bytes (8: the f64 frame, 1: the quantised one), moved as one load and one store.
-// ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void deinterleave_kernel(const uint8_t *__restrict__ parts, uint8_t *__restrict__ full,
-                                                           uint32_t width, uint32_t height, uint32_t n, uint32_t cap_rows,
-                                                           uint32_t block, uint32_t flip, uint32_t elem_bytes)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;       // one value of the frame
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (form == 0u) {
+        const uint64_t npix = (uint64_t)width * height;
+        if (i >= npix) return;
+        const uint32_t y = (uint32_t)(i / width);
+        const uint32_t x = (uint32_t)(i - (uint64_t)y * width);
+        const double *c = reinterpret_cast<const double *>(in) + 3 * ((uint64_t)(flip ? height - y - 1 : y) * width + x);
+        uint8_t *o = out + 3 * i;
+        o[0] = rust_as_u8(c[0] * 256.0);
+        o[1] = rust_as_u8(c[1] * 256.0);
+        o[2] = rust_as_u8(c[2] * 256.0);
+        return;
+    }
     const uint64_t row_vals = (uint64_t)width * 3;
     if (i >= row_vals * height) return;
     const uint32_t yo = (uint32_t)(i / row_vals);
@@ -629,8 +627,8 @@ __global__ __launch_bounds__(256) void deinterleave_kernel(const uint8_t *__rest
     const uint32_t y = flip ? height - 1u - yo : yo;
     const uint32_t b = y / block, p = b % n, k = (b / n) * block + (y - b * block);
     const uint64_t src = ((uint64_t)p * cap_rows + k) * row_vals + c;
-    if (elem_bytes == 8u) reinterpret_cast<unsigned long long *>(full)[i] = reinterpret_cast<const unsigned long long *>(parts)[src];
-    else full[i] = parts[src];
+    if (form == 8u) reinterpret_cast<unsigned long long *>(out)[i] = reinterpret_cast<const unsigned long long *>(in)[src];
+    else out[i] = in[src];
 }
 
 #ifdef RTX_LAB
@@ -795,8 +793,8 @@ hipError_t launch_quantize(const double *rgb, uint8_t *rgb8, uint32_t width, uin
 {
     uint64_t npix = (uint64_t)width * height;
     if (npix == 0) return hipSuccess;
-    hipLaunchKernelGGL(quantize_kernel, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, stream, rgb, rgb8, width,
-                       height, 1u);
+    hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, stream,
+                       reinterpret_cast<const uint8_t *>(rgb), rgb8, width, height, 1u, 0u, 1u, 1u, 0u);
     return hipGetLastError();
 }
 
@@ -804,8 +802,8 @@ hipError_t launch_quantize_values(const double *rgb, uint8_t *rgb8, uint32_t wid
 {
     uint64_t npix = (uint64_t)width * n_rows;
     if (npix == 0) return hipSuccess;
-    hipLaunchKernelGGL(quantize_kernel, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, stream, rgb, rgb8, width,
-                       n_rows, 0u);
+    hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, stream,
+                       reinterpret_cast<const uint8_t *>(rgb), rgb8, width, n_rows, 1u, 0u, 1u, 0u, 0u);
     return hipGetLastError();
 }
 
@@ -814,7 +812,7 @@ hipError_t launch_deinterleave(const double *parts, double *full, uint32_t width
 {
     const uint64_t total = (uint64_t)width * height * 3;
     if (total == 0) return hipSuccess;
-    hipLaunchKernelGGL(deinterleave_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, stream,
+    hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, stream,
                        reinterpret_cast<const uint8_t *>(parts), reinterpret_cast<uint8_t *>(full), width, height, n, cap_rows, block, 0u, 8u);
     return hipGetLastError();
 }
@@ -824,7 +822,7 @@ hipError_t launch_deinterleave_u8(const uint8_t *parts, uint8_t *full, uint32_t 
 {
     const uint64_t total = (uint64_t)width * height * 3;
     if (total == 0) return hipSuccess;
-    hipLaunchKernelGGL(deinterleave_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, stream, parts, full, width,
+    hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, stream, parts, full, width,
                        height, n, cap_rows, block, flip ? 1u : 0u, 1u);
     return hipGetLastError();
 }

@@ -3,6 +3,7 @@
 
 #include "../../include/rtx_hip.h"      // RTX_TUNE_* (SceneView::tuning)
 #include "rtx_device.h"
+#include "rtx_refit.h"
 
 namespace rtx {
 
@@ -145,6 +146,9 @@ hipError_t launch_resolve(const double *samples, double *acc, double *out, const
                           uint64_t rays_per_pixel, bool first, bool last, hipStream_t stream, double *sq = nullptr);
 
 // render_to_image epilogue (scene.rs:175-178)
+// rtx_scene_update_objects on the device (rtx_update.hip): one launch of scene_update_kernel in the mode u.mode names (rtx_refit.h).
+hipError_t launch_scene_update(const UpdateArgs &u, hipStream_t stream);
+
 hipError_t launch_quantize(const double *rgb, uint8_t *rgb8, uint32_t width, uint32_t height, hipStream_t stream);
 
 // rtx_render_devices' gather epilogue: parts = n bands of cap_rows rows each (band p = the blocks of `block` image rows

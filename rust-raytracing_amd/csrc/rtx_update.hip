@@ -1,0 +1,37 @@
+// rtx_update.hip -- scene_update_kernel: rtx_scene_update_objects on the device (include/rtx_hip.h, DESIGN.md "Moving objects").
+// One kernel, a launch-uniform mode (UpdateArgs, rtx_refit.h); the arithmetic is rtx_refit.h's, which the host reference
+// refit_packed (rtx_api.hip) compiles too.  No spin-waits, no dependence between the blocks of one launch; threads write
+// disjoint words (mode B reads the nodes the previous launch wrote: the host enqueues the levels deepest first on one stream).
+#include "rtx_launch.h"
+
+namespace rtx {
+
+__global__ __launch_bounds__(256) void scene_update_kernel(UpdateArgs u)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u.mode == 0u) {                                   // A: one entry's records
+        if (i < u.n) update_record(u, i);
+        return;
+    }
+    if (u.mode == 1u) {                                   // B: one wide node of this level
+        if (i < u.n && !refit_node(u, u.level[i])) atomicOr(u.status, kUpdateStatusNoQ3);
+        return;
+    }
+    // C: sphere_cmax = max of reach.  Grid-stride, then the 64-lane wave, then one atomicMax per wave on the bit pattern
+    // (non-negative doubles order like their bits; a launch of mode C only runs when every reach is finite).
+    double m = 0.0;
+    for (uint64_t k = i; k < u.n; k += (uint64_t)gridDim.x * blockDim.x) { const double r = u.reach[k]; m = r > m ? r : m; }
+    for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_down(m, off, 64); m = o > m ? o : m; }
+    if ((threadIdx.x & 63u) == 0u) atomicMax(u.status + 1, (unsigned long long)__double_as_longlong(m));
+}
+
+hipError_t launch_scene_update(const UpdateArgs &u, hipStream_t stream)
+{
+    if (u.n == 0) return hipSuccess;
+    uint32_t blocks = (uint32_t)(((uint64_t)u.n + 255u) / 256u);
+    if (u.mode == 2u && blocks > 1024u) blocks = 1024u;
+    hipLaunchKernelGGL(scene_update_kernel, dim3(blocks), dim3(256), 0, stream, u);
+    return hipGetLastError();
+}
+
+}  // namespace rtx

@@ -130,6 +130,8 @@ extern "C" {
     pub fn rtx_scene_set_config(scene: RtxSceneHandle, config: *const RtxConfig) -> i32;
     pub fn rtx_scene_set_scratch_limit(scene: RtxSceneHandle, bytes: u64) -> i32;
     pub fn rtx_scene_append_objects(scene: RtxSceneHandle, objects: *const RtxObject, n_objects: u64) -> i32;
+    pub fn rtx_scene_update_objects(scene: RtxSceneHandle, indices: *const u64, objects: *const RtxObject, n: u64, mode: u32,
+                                    stream: *mut c_void, how: *mut u32) -> i32;
     pub fn rtx_scene_set_camera(scene: RtxSceneHandle, camera: *const RtxCamera) -> i32;
     pub fn rtx_render_rows(scene: RtxSceneHandle, width: u32, height: u32, row_begin: u32, row_stride: u32, n_rows: u32, d_out_rgb: *mut f64, stream: *mut c_void, stats: *mut RtxStats) -> i32;
     pub fn rtx_blocks_row_count(height: u32, block_rows: u32, part: u32, n_parts: u32) -> u32;

@@ -1,0 +1,163 @@
+#!/usr/bin/env python3
+"""What moving objects costs on a resident scene: wall time of SceneHandle.update_objects (rtx_scene_update_objects) against the
+only way there was before it, rtx_scene_free + rtx_scene_upload of the modified list, and what a refitted tree costs per frame.
+
+  update   per scene (C2: scenes.random_spheres(10000, 1); M1: random_spheres(1000000, 1)) and share of the spheres (one sphere,
+           1 %, 100 %), the wall time of one call, host work and the final synchronisation included:
+             refit     every named sphere moved inside the box of the centres (RTX_UPDATED_REFIT)
+             records   the same spheres, materials only (RTX_UPDATED_RECORDS)
+             rebuild   the refit leg's list under RTX_UPDATE_REBUILD (host build + upload of every array)
+             reupload  close() + Scene.upload() of the modified list: the one leg a library without the entry point can run
+  frames   C2 at 1920x1080 and --spp samples, every sphere displaced by 1, 5 and 20 units in a random direction (centres clipped to
+           the box): the frame's device time (RtxStats trace_ms + resolve_ms) after a refit and after a fresh upload of the same
+           geometry -- the price of keeping the old topology
+
+    tools/update_rate.py [--scenes C2,M1] [--legs update,frames] [--reps 3] [--spp 4]
+
+The package is the one of the tree the tool lies in; in a checkout of the parent commit (copy the tool there) only the reupload leg runs.
+One JSON line per measurement: the best of --reps timed runs after one warm-up, with the slowest run and the spread between them.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+SCENES = {"C2": 10000, "M1": 1000000}
+
+
+def moved(objs, idx, rng, step=None):
+    """objs[idx] with new centres inside the box of all centres: uniform, or displaced by `step` in a random direction and clipped"""
+    g = objs["geom"]
+    rmax = float(np.abs(g[:, 3]).max())
+    lo, hi = g[:, :3].min(axis=0) + rmax, g[:, :3].max(axis=0) - rmax
+    new = objs[idx].copy()
+    if step is None:
+        new["geom"][:, :3] = lo + (hi - lo) * rng.random((len(idx), 3))
+    else:
+        d = rng.normal(size=(len(idx), 3))
+        d /= np.linalg.norm(d, axis=1)[:, None]
+        new["geom"][:, :3] = np.clip(new["geom"][:, :3] + step * d, lo, hi)
+    return new
+
+
+def timed(fn, reps, setup=None):
+    """wall ms of fn(): (best, worst) of `reps` runs after one warm-up; setup() runs before each, outside the clock"""
+    import torch
+    out = []
+    for k in range(reps + 1):
+        arg = setup() if setup else None
+        torch.cuda.synchronize(0)
+        t0 = time.perf_counter()
+        fn(arg)
+        torch.cuda.synchronize(0)
+        out.append((time.perf_counter() - t0) * 1e3)
+    out = out[1:]
+    return min(out), max(out)
+
+
+def emit(**kw):
+    print(json.dumps(kw), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scenes", default="C2,M1")
+    ap.add_argument("--legs", default="update,frames")
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--spp", type=int, default=4)
+    args = ap.parse_args()
+    import torch
+
+    import rust_raytracing_amd as rtx
+    from rust_raytracing_amd import scenes
+    cam = rtx.Camera(*scenes.CAMERA)
+    has_update = hasattr(rtx.SceneHandle, "update_objects")          # (a checkout of the parent commit: the reupload leg alone)
+    legs = args.legs.split(",")
+    for name in args.scenes.split(","):
+        objs = scenes.random_spheres(SCENES[name], 1)
+        cfg = rtx.Config(rays_per_pixel=args.spp, seed=scenes.RENDER_SEED)
+        n = len(objs)
+        if "update" in legs:
+            hnd = rtx.Scene.from_packed(cfg, cam, objs).upload(0)
+            current = objs.copy()                                # what the handle holds
+            for share, count in (("1", 1), ("1%", max(1, n // 100)), ("100%", n)):
+                rng = np.random.default_rng(7)
+                idx = np.sort(rng.permutation(n)[:count]).astype(np.uint64)
+
+                def fresh_move(_rng=rng, _idx=idx):
+                    return moved(objs, _idx, _rng)
+
+                def material(_rng=rng, _idx=idx):
+                    new = current[_idx.astype(np.int64)].copy()
+                    new["base_color"] = _rng.uniform(0.1, 0.9, (len(_idx), 3))
+                    return new
+
+                if has_update:
+                    for leg, setup, mode, want in (("refit", fresh_move, "auto", "refit"), ("records", material, "auto", "records"),
+                                                   ("rebuild", fresh_move, "rebuild", "rebuilt")):
+                        how = []
+
+                        def call(new, _mode=mode):
+                            how.append(hnd.update_objects(idx, new, mode=_mode))
+                            current[idx.astype(np.int64)] = new
+
+                        best, worst = timed(call, args.reps, setup)
+                        assert set(how) == {want}, (leg, how)
+                        emit(scene=name, leg="update", form=leg, spheres=n, updated=count, share=share, ms=round(best, 4), worst_ms=round(worst, 4),
+                             spread=round(worst / best - 1.0, 3), reps=args.reps)
+                state = {"hnd": hnd}
+
+                def reupload(new, _idx=idx):
+                    mod = objs.copy()
+                    mod[_idx.astype(np.int64)] = new
+                    state["hnd"].close()
+                    state["hnd"] = rtx.Scene.from_packed(cfg, cam, mod).upload(0)
+
+                best, worst = timed(reupload, args.reps, fresh_move)
+                hnd = state["hnd"]
+                emit(scene=name, leg="update", form="reupload", spheres=n, updated=count, share=share, ms=round(best, 4), worst_ms=round(worst, 4),
+                     spread=round(worst / best - 1.0, 3), reps=args.reps)
+            hnd.close()
+        if "frames" in legs and name == "C2" and has_update:
+            w, h = 1920, 1080
+            buf = torch.zeros((h, w, 3), dtype=torch.float64, device="cuda:0")
+
+            def frame_ms(handle):
+                out = []
+                for k in range(args.reps + 1):
+                    st = handle.render_rows(w, h, 0, 1, h, buf.data_ptr())
+                    out.append(st.trace_ms + st.resolve_ms)
+                return min(out[1:]), max(out[1:])
+
+            base = rtx.Scene.from_packed(cfg, cam, objs).upload(0)
+            b, wst = frame_ms(base)
+            emit(scene=name, leg="frames", form="as uploaded", step=0, spp=args.spp, ms=round(b, 4), worst_ms=round(wst, 4), spread=round(wst / b - 1.0, 3))
+            base.close()
+            for step in (1.0, 5.0, 20.0):
+                idx = np.arange(n, dtype=np.uint64)
+                new = moved(objs, idx, np.random.default_rng(11), step)
+                refit = rtx.Scene.from_packed(cfg, cam, objs).upload(0)
+                assert refit.update_objects(idx, new) == "refit"
+                fresh = rtx.Scene.from_packed(cfg, cam, new).upload(0)
+                for run in (1, 2):                               # alternating
+                    for form, handle in (("after refit", refit), ("fresh upload", fresh)):
+                        b, wst = frame_ms(handle)
+                        emit(scene=name, leg="frames", form=form, run=run, step=step, spp=args.spp, ms=round(b, 4), worst_ms=round(wst, 4),
+                             spread=round(wst / b - 1.0, 3))
+                refit.render_rows(w, h, 0, 1, h, buf.data_ptr())
+                img_refit = buf.cpu().numpy().copy()
+                fresh.render_rows(w, h, 0, 1, h, buf.data_ptr())
+                emit(scene=name, leg="frames", form="same bits", step=step, equal=bool(np.array_equal(img_refit, buf.cpu().numpy())))
+                refit.close()
+                fresh.close()
+
+
+if __name__ == "__main__":
+    main()
