@@ -670,7 +670,9 @@ int32_t rtx_debug_gather(int32_t form, const void *parts, uint32_t width, uint32
  * run on the same bits:
  *   scene_info[16]: the centre the f32 records are relative to (3), sphere_cmax, origin_limit, inv_max, tri_extent, the tree's flags
  *       (rtx_debug_host_scene, stats[7]), depth, wide nodes, triangle records in the tree, spheres; written even when n is 0
- *   records: 16 words per entry -- a sphere's leaf record {c - centre, |r| rounded up}; a triangle's A, B (the filter record) and g0, g1
+ *   records: 16 words per entry -- a sphere's leaf record {c - centre, |r| rounded up}, zeros behind it -- with form bit 11 (0x800,
+ *       which selects nothing else) words 4-7 and 8-11 are its filter record {c - centre, |c - centre|^2 - r^2} as the leaf holds it
+ *       (bvh_leaf_f32) and as the sweep holds it (sphere_f32, un-interleaved); a triangle's A, B (the filter record) and g0, g1
  *       (tri_bounds' record); zeros for an object outside the tree
  *   path_data: 16 words per entry and step, path_steps steps per entry (further steps are not stored) -- word 0 the layout, word 15
  *       the node's link: 0 a 128-byte child {lo.xyz, hi.xyz}; 1 a footprint child {lo.x, lo.y, hi.x, hi.y}; 2 a 64-byte sphere child

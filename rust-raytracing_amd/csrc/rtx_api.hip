@@ -2536,7 +2536,9 @@ int32_t rtx_debug_path_bounds(RtxSceneHandle h, const RtxRay *rays, const uint32
     if (!rays || !objects || !best_up || !out) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_path_bounds: null argument");
     if (n > (1ull << 22) || (path_data && n * (uint64_t)path_steps > (1ull << 24)))
         return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_path_bounds: too large");
-    if ((form & ~0x303u) != 0u) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_path_bounds: unknown form");
+    if ((form & ~0xB03u) != 0u) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_path_bounds: unknown form");
+    const bool filter_records = (form & 0x800u) != 0u;          // a host-side option of `records`: the device sees the other bits
+    form &= ~0x800u;
     const SceneView &sv = h->sv;
     if ((form & 2u) && !((sv.bvh_flags & 16u) && sv.bvh_q3nodes) && !((sv.bvh_flags & 8u) && sv.bvh_qnodes))
         return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_path_bounds: this scene's tree has no 64-byte nodes");
@@ -2626,8 +2628,13 @@ int32_t rtx_debug_path_bounds(RtxSceneHandle h, const RtxRay *rays, const uint32
         }
     }
     if (records) {                                              // the object's resident f32 records, as the leaf tests read them
-        std::vector<float4> cr(prims.size()), t32(2 * tri_fidx.size()), geo(2 * tri_fidx.size());
+        std::vector<float4> cr(prims.size()), l32(prims.size()), t32(2 * tri_fidx.size()), geo(2 * tri_fidx.size());
+        std::vector<float> s32(prims.empty() ? 0u : (((size_t)sv.n_spheres + 3) & ~(size_t)3) * 4);
         RTX_HIP_CHECK(down(cr.data(), sv.bvh_leaf_cr, cr.size() * sizeof(float4)));
+        if (filter_records) {
+            RTX_HIP_CHECK(down(l32.data(), sv.bvh_leaf_f32, l32.size() * sizeof(float4)));
+            RTX_HIP_CHECK(down(s32.data(), sv.sphere_f32, s32.size() * sizeof(float)));
+        }
         RTX_HIP_CHECK(down(t32.data(), sv.tri_f32, t32.size() * sizeof(float4)));
         RTX_HIP_CHECK(down(geo.data(), sv.tri_geo, geo.size() * sizeof(float4)));
         std::memset(records, 0, n * 16 * sizeof(uint32_t));
@@ -2638,7 +2645,17 @@ int32_t rtx_debug_path_bounds(RtxSceneHandle h, const RtxRay *rays, const uint32
                 const size_t r = e & ~kTriEntry;
                 const float4 four[4] = { t32[2 * r], t32[2 * r + 1], geo[2 * r], geo[2 * r + 1] };
                 std::memcpy(records + 16 * i, four, sizeof four);
-            } else std::memcpy(records + 16 * i, &cr[e], sizeof(float4));
+            } else {
+                std::memcpy(records + 16 * i, &cr[e], sizeof(float4));
+                if (!filter_records) continue;
+                std::memcpy(records + 16 * i + 4, &l32[e], sizeof(float4));
+                const uint32_t k = prims[e];                    // the pair-interleaved filter record of the same sphere, as scalars
+                if ((size_t)(k | 1u) * 4 + 3 < s32.size()) {
+                    const float *f = s32.data() + (size_t)(k & ~1u) * 4 + (k & 1u);
+                    const float four[4] = { f[0], f[2], f[4], f[6] };
+                    std::memcpy(records + 16 * i + 8, four, sizeof four);
+                }
+            }
         }
     }
     if (path_data && path_steps) {                              // the object's child at every step, in the form the slab test reads

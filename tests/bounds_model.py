@@ -569,6 +569,44 @@ def pack_for(objs, m=SHIPPED):
     return pk
 
 
+def refit(base_objs, indices, new, m=SHIPPED):
+    """What rtx_scene_update_objects' REFIT of the tree of `base_objs` by objects[indices[i]] = new[i] (in order: the last entry of a
+    repeated index wins) must leave, from its contract (include/rtx_hip.h) and not from the kernel's text: a dict as
+    pack_for() returns it.  KEPT from the base pack: centre, limit32 / limit (origin_limit), abs_pad, inv_max32, tri_extent, in_tree,
+    kind, free and every triangle's record and box.  NEW, for every sphere of the updated list against the KEPT centre: rec[:, :3] =
+    f32(c - centre), rec[:, 3] = |r| rounded up (the leaf record), fw = f32(|c - centre|^2 - r^2) (the filter record's fourth
+    scalar; `filt` is the whole filter record {f32(c - centre), fw}), lo / hi = sphere_box() widened by the base abs_pad and rounded
+    outward, and scene-wide cmax = max(sqrt(cc) + |r|).
+    A sphere the update does not name keeps the bits pack() gave it (the expressions are pack()'s).  numpy f64, one rounding per
+    operation, sums left to right."""
+    pk = pack_for(base_objs, m)
+    now = np.array(base_objs, copy=True)
+    for i, o in zip(np.asarray(indices).astype(np.int64), new):
+        now[int(i)] = o
+    assert np.array_equal(np.asarray(now["kind"]).astype(int), pk["kind"]), "a refit keeps every object's kind"
+    geom = np.asarray(now["geom"], dtype=np.float64)
+    sph = pk["kind"] == 0
+    out = dict(pk)
+    rec, lo, hi = pk["rec"].copy(), pk["lo"].copy(), pk["hi"].copy()
+    with np.errstate(all="ignore"):
+        s, r = geom[sph, :3], np.abs(geom[sph, 3])
+        c = s - pk["centre"][None, :]
+        cc = (c[:, 0] * c[:, 0] + c[:, 1] * c[:, 1]) + c[:, 2] * c[:, 2]
+        reach = np.sqrt(cc) + r
+        rec[sph, :3] = c.astype(F32)
+        rec[sph, 3] = ru32(r)
+        fw = np.zeros(len(now), dtype=F32)
+        fw[sph] = (cc - r * r).astype(F32)
+        filt = np.zeros((len(now), 4), dtype=F32)
+        filt[sph, :3] = c.astype(F32)
+        filt[sph, 3] = fw[sph]
+        pad = (np.abs(s) + r[:, None]) * (1.0 / 1048576.0) + 1e-300
+        lo[sph] = rd32(((s - r[:, None]) - pad) - pk["abs_pad"] * m.abs_pad)
+        hi[sph] = ru32(((s + r[:, None]) + pad) + pk["abs_pad"] * m.abs_pad)
+    out.update(rec=rec, lo=lo, hi=hi, lo128=lo, hi128=hi, fw=fw, filt=filt, cmax=float(reach.max()) if sph.any() else 0.0, objs=now)
+    return out
+
+
 def device_steps(path, lens):
     """the hook's path_data (n, steps, 16) uint32 -> steps as own_steps lists them; `lens` (n,): steps beyond a row's length are
     entered by definition"""

@@ -54,6 +54,70 @@ def test_fallbacks_rebuild(rtx, name):
         assert digests == fresh, (name, case)
 
 
+def test_the_edge_cases_are_what_their_names_say(rtx):
+    """on the inputs alone: grow enlarges the largest reach (a stale sphere_cmax would be too small) and keeps every box in the build's
+    range; neg_zero writes a -0.0 on y and z (x does not reach 0 in these scenes' move boxes); scale_in / scale_out put one padded
+    hi.x 0.1 % inside / outside the build's scale, everything else of the update inside it"""
+    for name in ("s9", "s65", "s300", "mixed"):
+        objs = uc.scene(name)
+        sph = objs["kind"] == 0
+        idx, new, _ = uc.update(objs, "grow")
+        assert uc.inside_build_range(objs, new), name
+        assert (np.abs(new["geom"][:, 3]) >= np.abs(objs["geom"][sph, 3])).all()
+        assert (np.abs(new["geom"][:, 3]) > 1.04 * np.abs(objs["geom"][sph, 3])).sum() * 2 > len(new), name
+        idx, new, _ = uc.update(objs, "neg_zero")
+        signed = [a for a in range(3) if (np.signbit(new["geom"][:, a]) & (new["geom"][:, a] == 0.0)).any()]
+        assert signed == [1, 2], (name, signed, "the move box excludes 0 on an axis other than x")
+        scale = uc.build_scale(objs)
+        for case, f in (("scale_in", 0.999), ("scale_out", 1.001)):
+            idx, new, _ = uc.update(objs, case)
+            g = new["geom"][0]
+            hi = g[0] + abs(g[3]) + (abs(g[0]) + abs(g[3])) / 1048576.0
+            assert abs(hi / scale - f) < 1e-9 and np.array_equal(g[1:4], objs["geom"][int(idx[0]), 1:4]), (name, case, hi / scale)
+
+
+@pytest.mark.parametrize("name", uc.ONEPOINT_SCENES)
+def test_the_fallback_only_the_refit_itself_can_find(rtx, name):
+    """collapse8 / onepoint_tiny: plan_update would refit them -- nothing leaves the range the tree was built for, and the same
+    indices at the same place with radius 1e-4 DO refit -- but mode B meets a 64-byte node without an encoding (kUpdateStatusNoQ3)
+    and the host rebuilds over the half-written arrays: the result is a fresh pack of the updated list.  That pack has lost the
+    64-byte form (flags & 16 == 0, no quantised node): a few co-located tiny spheres cost the whole tree its 64-byte nodes until
+    the next forced rebuild of a scene without them.  onepoint (every sphere at one point, r = 1e-4) still refits, 64-byte form kept."""
+    objs = uc.scene(name)
+    for case in uc.DEVICE_FALLBACK_CASES:
+        idx, new, want = uc.update(objs, case)
+        assert uc.inside_build_range(objs, new), (name, case)
+        how, stats, digests = rtx.debug_host_refit(_scene(rtx, objs), idx, new)
+        assert how == want == "rebuilt", (name, case, how)
+        milder = uc.collapse(objs, idx.astype(np.int64), 1.0e-4)
+        how_m, stats_m, _ = rtx.debug_host_refit(_scene(rtx, objs), idx, milder)
+        assert how_m == "refit" and stats_m["flags"] & 16 and stats_m["quantised_nodes"] == stats_m["wide_nodes"], (name, case, how_m)
+        _, _, fresh = rtx.debug_host_refit(_scene(rtx, uc.apply(objs, idx, new)), idx[:0], new[:0])
+        assert digests == fresh, (name, case)
+        assert stats["flags"] & 1 and stats["flags"] & 16 == 0 and stats["quantised_nodes"] == 0, (name, case, stats["flags"])
+    idx, new, want = uc.update(objs, "onepoint")
+    how, stats, _ = rtx.debug_host_refit(_scene(rtx, objs), idx, new)
+    assert how == want == "refit" and stats["flags"] & 16 and stats["quantised_nodes"] == stats["wide_nodes"], (name, how)
+
+
+@pytest.mark.parametrize("name", ["s9", "s300"])
+def test_a_refit_of_the_tree_without_64_byte_nodes_and_the_way_back(rtx, name):
+    """after collapse8 the resident tree is a sphere tree WITHOUT the 64-byte form (q3nodes == null in mode B): an ordinary move on it
+    refits and keeps the invariants; a forced rebuild of an update that spreads the eight spheres out again brings the form back"""
+    objs = uc.scene(name)
+    i1, n1, _ = uc.update(objs, "collapse8")
+    now = uc.apply(objs, i1, n1)
+    i2, n2, _ = uc.update(now, "third", seed=4)
+    how, stats, digests = rtx.debug_host_refit(_scene(rtx, objs), np.concatenate([i1, i2]), np.concatenate([n1, n2]), split=len(i1))
+    assert how == "rebuilt" and stats["flags"] & 16 == 0, (name, how, stats["flags"])         # (of a split call: the stronger of the two)
+    how, stats, direct = rtx.debug_host_refit(_scene(rtx, now), i2, n2)
+    assert how == "refit" and stats["flags"] == 1 and stats["quantised_nodes"] == 0, (name, how, stats["flags"])
+    assert digests == direct                                 # (the rebuilt tree is the fresh pack's: the same refit from either start)
+    back = objs[i1.astype(np.int64)].copy()
+    how, stats, _ = rtx.debug_host_refit(_scene(rtx, now), i1, back, mode="rebuild")
+    assert how == "rebuilt" and stats["flags"] & 16 and stats["quantised_nodes"] == stats["wide_nodes"], (name, stats["flags"])
+
+
 def test_a_rebuild_and_a_refit_agree_on_everything_but_the_tree(rtx):
     """the shape, plane and material records of a refit are those of a fresh pack; nodes, leaf order and the f32 records (offsets from
     the kept centre) may differ"""

@@ -10,8 +10,15 @@ from rust_raytracing_amd import scenes
 from rust_raytracing_amd.abi import OBJECT_DTYPE, RTX_PLANE, RTX_SPHERE, RTX_TRIANGLE
 
 MOVE_CASES = ("one", "third", "all", "repeat", "radius", "inbox")         # REFIT on every scene with a sphere tree
+EDGE_CASES = ("grow", "zero_radius", "neg_radius", "neg_zero", "scale_in")  # REFIT: the edges of the geometry and of the path decision
 RECORD_CASES = ("material", "plane")                                       # RECORDS
-FALLBACK_CASES = ("far", "nan_radius", "kind", "tri_vertex", "rebuild")    # REBUILT
+FALLBACK_CASES = ("far", "nan_radius", "kind", "tri_vertex", "rebuild", "scale_out")    # REBUILT, decided by plan_update
+# REBUILT although plan_update alone would refit: the device (mode B) finds a 64-byte node without an encoding -- co-located spheres of
+# radius 1e-9 make a node of extent 4 abs_pad, so small for its distance from the origin that |o / s| + 256 < 2^24 fails -- sets
+# kUpdateStatusNoQ3, and the host rebuilds over the half-written arrays.  Only on pure sphere scenes (a joint tree has no 64-byte form
+# to lose).
+DEVICE_FALLBACK_CASES = ("collapse8", "onepoint_tiny")
+ONEPOINT_SCENES = ("s9", "s65", "s300", "s3000")                           # where collapse8 / onepoint / onepoint_tiny are stated
 HOST_SPHERE_COUNTS = (5, 6, 9, 17, 65, 300)
 GPU_SPHERE_COUNTS = (5, 9, 65, 300, 3000)
 
@@ -35,7 +42,7 @@ def has(objs, kind):
 
 def cases_for(objs):
     """the update cases that exist on this scene (a plane update needs a plane, a vertex change a triangle)"""
-    out = list(MOVE_CASES) + ["material"]
+    out = list(MOVE_CASES) + list(EDGE_CASES) + ["material"]
     if has(objs, RTX_PLANE):
         out.append("plane")
     return out
@@ -51,6 +58,43 @@ def _move_box(objs):
     lo, hi = g[:, :3].min(axis=0) + rmax, g[:, :3].max(axis=0) - rmax
     mid = 0.5 * (lo + hi)
     return np.where(lo <= hi, lo, mid), np.where(lo <= hi, hi, mid)
+
+
+def scene_box(objs):
+    """the box of the spheres' own (unpadded) boxes: what the tree was built for"""
+    g = objs["geom"][objs["kind"] == RTX_SPHERE]
+    r = np.abs(g[:, 3:4])
+    return (g[:, :3] - r).min(axis=0), (g[:, :3] + r).max(axis=0)
+
+
+def inside_build_range(objs, new):
+    """no sphere of `new` has a box c +- |r| outside scene_box(objs): such an update cannot pass the build's `scale`"""
+    lo, hi = scene_box(objs)
+    g = new["geom"][new["kind"] == RTX_SPHERE]
+    r = np.abs(g[:, 3:4])
+    return bool(((g[:, :3] - r) >= lo).all() and ((g[:, :3] + r) <= hi).all())
+
+
+def build_scale(objs):
+    """the `scale` the resident tree was built for, (origin_limit - 1) / 4, from the restated builder's f32 origin_limit"""
+    import bounds_model as bm
+    return (float(bm.pack(objs)["limit32"]) - 1.0) / 4.0
+
+
+def collapse(objs, idx, radius):
+    """the spheres `idx` at the `hi` corner of the move box with one radius"""
+    _, hi = _move_box(objs)
+    new = objs[idx].copy()
+    new["geom"][:, :3] = hi
+    new["geom"][:, 3] = radius
+    return new
+
+
+def nearest8(objs):
+    """the 8 spheres nearest to the first sphere (itself included)"""
+    sph = np.nonzero(objs["kind"] == RTX_SPHERE)[0]
+    c = objs["geom"][sph, :3]
+    return sph[np.argsort(np.linalg.norm(c - c[0], axis=1), kind="stable")[:8]]
 
 
 def update(objs, case, seed=0):
@@ -86,6 +130,43 @@ def update(objs, case, seed=0):
         new = objs[sph].copy()
         new["geom"][:, :3] = lo + (hi - lo) * rng.random((len(sph), 3))
         return sph.astype(np.uint64), new, "refit"
+    # ---- edges of the geometry and of the path decision
+    if case == "grow":                              # radii x U(1.05, 1.6), clipped so that no box leaves the box the tree was built for
+        blo, bhi = scene_box(objs)
+        new = objs[sph].copy()
+        c, r = new["geom"][:, :3], np.abs(new["geom"][:, 3])
+        room = 0.99 * np.minimum(c - blo, bhi - c).min(axis=1)
+        new["geom"][:, 3] = np.maximum(r, np.minimum(r * rng.uniform(1.05, 1.6, len(sph)), room))
+        return sph.astype(np.uint64), new, "refit"
+    if case in ("zero_radius", "neg_radius"):
+        idx = rng.permutation(sph)[:max(1, len(sph) // 3)]
+        new = objs[idx].copy()
+        new["geom"][:, 3] = 0.0 if case == "zero_radius" else -0.9 * np.abs(new["geom"][:, 3])
+        return idx.astype(np.uint64), new, "refit"
+    if case == "neg_zero":                          # one sphere per axis gets a coordinate of -0.0, where the move box reaches 0
+        axes = [a for a in range(3) if lo[a] <= 0.0 <= hi[a]]
+        assert axes, "neg_zero: the move box excludes 0 on every axis of this scene"
+        idx = rng.permutation(sph)[:len(axes)]
+        new = objs[idx].copy()
+        for k, a in enumerate(axes):
+            new["geom"][k, a] = -0.0
+        return idx.astype(np.uint64), new, "refit"
+    if case in ("scale_in", "scale_out"):           # one sphere along +x: its padded hi.x at 0.999 / 1.001 of the build's scale
+        idx = sph[[0]]
+        new = objs[idx].copy()
+        r = abs(float(new["geom"][0, 3]))
+        want = (0.999 if case == "scale_in" else 1.001) * build_scale(objs)
+        k = 1.0 / 1048576.0
+        new["geom"][0, 0] = (want - r * (1.0 + k)) / (1.0 + k)           # x + r + (|x| + r) 2^-20 = want, x > 0
+        return idx.astype(np.uint64), new, "refit" if case == "scale_in" else "rebuilt"
+    # ---- co-located spheres: every box of their sub-tree (onepoint: of the tree) coincides
+    if case == "collapse8":
+        idx = nearest8(objs)
+        return idx.astype(np.uint64), collapse(objs, idx, 1.0e-9), "rebuilt"
+    if case == "onepoint":
+        return sph.astype(np.uint64), collapse(objs, sph, 1.0e-4), "refit"
+    if case == "onepoint_tiny":
+        return sph.astype(np.uint64), collapse(objs, sph, 1.0e-9), "rebuilt"
     if case == "material":                          # of every kind the scene has; the geometry stays
         idx = rng.permutation(len(objs))[:max(3, len(objs) // 5)]
         new = objs[idx].copy()

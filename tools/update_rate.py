@@ -12,7 +12,13 @@ only way there was before it, rtx_scene_free + rtx_scene_upload of the modified 
            the box): the frame's device time (RtxStats trace_ms + resolve_ms) after a refit and after a fresh upload of the same
            geometry -- the price of keeping the old topology
 
-    tools/update_rate.py [--scenes C2,M1] [--legs update,frames] [--reps 3] [--spp 4]
+  q3loss   C2 at 1920x1080: the 8 spheres nearest to the first go to one point with radius 1e-9 -- the refit finds a 64-byte node it
+           cannot encode, the update falls back to a rebuild, and that rebuild has no 64-byte form for ANY node:
+           the frame's device time on it against the scene as uploaded, alternating; then after an ordinary move (a refit, still
+           without the form) and after RTX_UPDATE_REBUILD of the first list (the form is back) -- what a few co-located tiny
+           spheres cost every later frame
+
+    tools/update_rate.py [--scenes C2,M1] [--legs update,frames,q3loss] [--reps 3] [--spp 4]
 
 The package is the one of the tree the tool lies in; in a checkout of the parent commit (copy the tool there) only the reupload leg runs.
 One JSON line per measurement: the best of --reps timed runs after one warm-up, with the slowest run and the spread between them.
@@ -158,6 +164,47 @@ def main():
                 refit.close()
                 fresh.close()
 
+        if "q3loss" in legs and name == "C2" and has_update:
+            w, h = 1920, 1080
+            buf = torch.zeros((h, w, 3), dtype=torch.float64, device="cuda:0")
+
+            def frame_ms(handle):
+                out = []
+                for k in range(args.reps + 1):
+                    st = handle.render_rows(w, h, 0, 1, h, buf.data_ptr())
+                    out.append(st.trace_ms + st.resolve_ms)
+                return min(out[1:]), max(out[1:])
+
+            def flags_of(o):
+                return rtx.debug_host_scene(rtx.Scene.from_packed(cfg, cam, o))["flags"]      # (host only; & 16: the 64-byte form exists)
+
+            c = objs["geom"][:, :3]
+            idx = np.argsort(np.linalg.norm(c - c[0], axis=1), kind="stable")[:8].astype(np.uint64)
+            tiny = objs[idx.astype(np.int64)].copy()
+            tiny["geom"][:, :3] = c[0]
+            tiny["geom"][:, 3] = 1.0e-9
+            collapsed = objs.copy()
+            collapsed[idx.astype(np.int64)] = tiny
+            plain = rtx.Scene.from_packed(cfg, cam, objs).upload(0)
+            hnd = rtx.Scene.from_packed(cfg, cam, objs).upload(0)
+            how = hnd.update_objects(idx, tiny)
+            assert how == "rebuilt", how
+            for run in (1, 2):                                   # alternating
+                for form, handle, o in (("as uploaded", plain, objs), ("8 spheres collapsed: rebuilt by the fallback", hnd, collapsed)):
+                    b, wst = frame_ms(handle)
+                    emit(scene=name, leg="q3loss", form=form, run=run, spp=args.spp, flags=flags_of(o), ms=round(b, 4), worst_ms=round(wst, 4),
+                         spread=round(wst / b - 1.0, 3))
+            # a later ordinary move is a refit of the tree without the form; spreading the eight out again under RTX_UPDATE_REBUILD ends it
+            moved_idx = np.arange(100, 200, dtype=np.uint64)
+            how = hnd.update_objects(moved_idx, moved(objs, moved_idx, np.random.default_rng(3), 1.0))
+            b, wst = frame_ms(hnd)
+            emit(scene=name, leg="q3loss", form="then 100 spheres moved: " + how, spp=args.spp, ms=round(b, 4), worst_ms=round(wst, 4), spread=round(wst / b - 1.0, 3))
+            how = hnd.update_objects(np.concatenate([idx, moved_idx]), objs[np.concatenate([idx, moved_idx]).astype(np.int64)].copy(), mode="rebuild")
+            b, wst = frame_ms(hnd)
+            emit(scene=name, leg="q3loss", form="then the first list again under RTX_UPDATE_REBUILD: " + how, spp=args.spp, flags=flags_of(objs),
+                 ms=round(b, 4), worst_ms=round(wst, 4), spread=round(wst / b - 1.0, 3))
+            plain.close()
+            hnd.close()
 
 if __name__ == "__main__":
     main()
