@@ -42,7 +42,7 @@ struct SphSurvivor {
     double px, py, pz, dx, dy, dz;
     uint32_t ridx;                            // kNone: a slot its wave reserved and did not use
     uint32_t first_id;                        // scene index of the object of the first hit
-    uint32_t pad_[2];
+    uint64_t key;                             // the path's RNG key (RTX_ROUND_CARRY_KEY; without it 0.0, and stage 2 makes the key again from ridx)
 };
 static_assert(sizeof(SphSurvivor) == 64, "SphSurvivor must be one 64-byte line");
 struct SphQueue {
@@ -62,6 +62,17 @@ constexpr uint32_t kSphQueueChunk = 512;
 #ifndef RTX_SPH_LEAF_LANES
 #define RTX_SPH_LEAF_LANES 8
 #endif
+// The round code around the walk (LAB_NOTEBOOK round 9, counted by tools/isa_round_count.py); 0 builds the former form of each for A/B runs
+#ifndef RTX_ROUND_GLOBAL
+#define RTX_ROUND_GLOBAL 1                   // the scene's records (material, sphere, plane, triangle, the nonzero bits) read as global memory
+#endif
+#ifndef RTX_ROUND_CARRY_KEY
+#define RTX_ROUND_CARRY_KEY 1                // the RNG key travels in the survivor record's last 8 bytes: stage 2's refill does no pixel arithmetic
+#endif
+#ifndef RTX_ROUND_DRAW
+#define RTX_ROUND_DRAW 1                     // the RNG cursor made from the bounce count where it is used: one register less across the walk,
+#endif                                       // the one that keeps stage 2 at 2 spilled VGPRs and 12 B of scratch (6 and 20 B without it)
+constexpr bool kRoundGlobal = RTX_ROUND_GLOBAL != 0;
 constexpr uint32_t kSphLeafLanes = RTX_SPH_LEAF_LANES;   // a leaf visit runs when this many lanes of the wave hold a leaf (or all that walk do)
 constexpr uint32_t kSphCutWalkers = RTX_SPH_CUT;     // a round's walk is left when fewer lanes than this still walk ...
 constexpr uint32_t kSphCutDone = RTX_SPH_CUT_DONE;   // ... and at least this many of the wave's rays wait for their f64 phase
@@ -92,7 +103,12 @@ __device__ __forceinline__ void sph_queue_append(const SphQueue &sq, Counters *_
             p[0] = make_double4(r.pos.x, r.pos.y, r.pos.z, r.dir.x);
             uint2 tail;
             tail.x = ridx; tail.y = first_id;
+#if RTX_ROUND_CARRY_KEY
+            p[1] = make_double4(r.dir.y, r.dir.z, __longlong_as_double(((long long)tail.y << 32) | (long long)tail.x),
+                                __longlong_as_double((long long)r.key));
+#else
             p[1] = make_double4(r.dir.y, r.dir.z, __longlong_as_double(((long long)tail.y << 32) | (long long)tail.x), 0.0);
+#endif
         } else {
             atomicAdd(&ctr[1].pad_, 1ull);
         }
@@ -174,17 +190,21 @@ __global__ __launch_bounds__(kBvhThreads, kSphWavesPerSimd) void trace_bvh_spher
                         valid = ridx != kNone;
                     }
                     if (valid) {
+#if RTX_ROUND_CARRY_KEY
+                        r.key = (uint64_t)__double_as_longlong(s1.w);                 // as stage 1 keyed the path (sph_queue_append)
+#else
                         if (rv.tiles_x != 0u) (void)ray_index_to_pixel_tiled(rv, ridx, pl, smp);
                         else ray_index_to_pixel(rv, ridx, pl, smp);
                         const uint32_t k = fastdiv(pl, rv.div_width), x = pl - k * rv.width;
                         const uint64_t pix = (uint64_t)image_row(rv, k) * rv.width + x;
                         r.key = rng_key(sv.seed, pix, rv.sample_begin + smp);
+#endif
                         r.bounce = 1u;
                         r.draw = 8u;
                         r.pos = mk(s0.x, s0.y, s0.z);
                         r.dir = mk(s0.w, s1.x, s1.y);
                         // ray_hit's two folds of the first hit (scene.rs:276-277) from resulting_color = 0, light_color = 1 (ray.rs:18-19)
-                        const MaterialX m = sv.materials[(uint32_t)((unsigned long long)__double_as_longlong(s1.z) >> 32)];
+                        const MaterialX m = load_record<kRoundGlobal>(sv.materials + (uint32_t)((unsigned long long)__double_as_longlong(s1.z) >> 32));
                         r.result = vadd(mk(0.0, 0.0, 0.0), vmulv(mk(1.0, 1.0, 1.0), m.emission_color));
                         r.light = vmulv(mk(1.0, 1.0, 1.0), m.base_color);
                         alive = true;
@@ -318,12 +338,15 @@ __global__ __launch_bounds__(kBvhThreads, kSphWavesPerSimd) void trace_bvh_spher
             // ---- render_ray's match arm + ray_hit (scene.rs:232-239, 260-278)
             bool done = true;
             if (h.id != kNone) {
-                advance_and_shade(sv, h, r);
+#if RTX_ROUND_DRAW
+                r.draw = 6u + 2u * r.bounce;          // six draws for the primary ray, two per bounce: not a value to carry through the walk
+#endif
+                advance_and_shade<kRoundGlobal>(sv, h, r);
                 first_id = h.id;
                 done = (r.bounce >= bounce_limit) || light_is_zero(r);            // scene.rs:227-228
             }
             if (done) {
-                store_sample(samples, rv, ridx, r.result);
+                store_sample<kRoundGlobal>(samples, rv, ridx, r.result);
                 alive = false;
             }
         }
@@ -699,12 +722,12 @@ __global__ __launch_bounds__(kBvhThreads, kSpkWaves) void trace_sph_packet_kerne
             // ---- render_ray's match arm + ray_hit (scene.rs:232-239, 260-278)
             bool done = true;
             if (h.id != kNone) {
-                advance_and_shade(sv, h, r);
+                advance_and_shade<kRoundGlobal>(sv, h, r);
                 first_id = h.id;
                 done = (r.bounce >= bounce_limit) || light_is_zero(r);            // scene.rs:227-228
             }
             if (done) {
-                store_sample(samples, rv, ridx, r.result);
+                store_sample<kRoundGlobal>(samples, rv, ridx, r.result);
                 alive = false;
             }
         }

@@ -157,6 +157,39 @@ __device__ __forceinline__ void hit_consider(Hit &h, double t, uint32_t id, uint
     if (h.id == 0xFFFFFFFFu || t < h.t || (t == h.t && id < h.id)) { h.t = t; h.id = id; h.kind = kind; h.local = local; }
 }
 
+// A record read through a pointer that came out of a view in memory (sv.materials, sv.spheres, rv.nonzero ...): the compiler cannot
+// know its address space and emits flat_load, whose s_waitcnt also waits for every LDS access in flight.  The scene's arrays are
+// device allocations, so the callers that ask for it (GLOBAL) read them as global memory: the same words, global_load, vmcnt only.
+template <bool GLOBAL, class T>
+__device__ __forceinline__ T load_record(const T *p)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (GLOBAL) {
+        static_assert(sizeof(T) % 8 == 0 && alignof(T) == 8, "load_record: records of 8-byte words");
+        const unsigned long long __attribute__((address_space(1))) *g = (const unsigned long long __attribute__((address_space(1))) *)p;
+        unsigned long long w[sizeof(T) / 8];
+#pragma unroll
+        for (unsigned i = 0; i < sizeof(T) / 8; ++i) w[i] = g[i];
+        T out;
+        __builtin_memcpy(&out, w, sizeof(T));
+        return out;
+    }
+#endif
+    return *p;
+}
+
+template <bool GLOBAL>
+__device__ __forceinline__ void atomic_or_u32(uint32_t *p, uint32_t v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (GLOBAL) {
+        (void)__hip_atomic_fetch_or((uint32_t __attribute__((address_space(1))) *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+#endif
+    atomicOr(p, v);
+}
+
 // map a ray index of the launch to (local pixel, sample), pixel-fastest so that a wave's 64 rays
 // are 64 neighbouring pixels of one sample (coalesced sample-plane writes).
 __device__ __forceinline__ void ray_index_to_pixel(const RowsView &rv, uint64_t i, uint32_t &pl, uint32_t &s_local)
@@ -188,13 +221,14 @@ __device__ __forceinline__ bool ray_index_to_pixel_tiled(const RowsView &rv, uin
 // samples are zero (a path that never reaches a light: ~95 % of C2's).  Every other sample is written as before and sets its
 // slot's bit in rv.nonzero, which the host clears before each launch; resolve_kernel reads a record only where the bit is
 // set, so whatever an earlier launch left under a clear bit is never read.
+template <bool GLOBAL = false>
 __device__ __forceinline__ void store_sample(double *__restrict__ samples, const RowsView &rv, uint64_t ridx, V3 c)
 {
     if (c.x == 0.0 && c.y == 0.0 && c.z == 0.0) return;
     double4 *rec = reinterpret_cast<double4 *>(samples) + ridx;
     *rec = make_double4(c.x, c.y, c.z, 0.0);
     const uint64_t bit = rv.nonzero_base + ridx;
-    atomicOr(rv.nonzero + (bit >> 5), 1u << (uint32_t)(bit & 31u));
+    atomic_or_u32<GLOBAL>(rv.nonzero + (bit >> 5), 1u << (uint32_t)(bit & 31u));
 }
 
 // focal_point of a local pixel: get_ray_dir (scene.rs:213-222, with the host-computed trig values) and scene.rs:203
@@ -266,22 +300,24 @@ __device__ __forceinline__ V3 random_bounce_dir(V3 ray_dir, V3 surface_normal, d
 }
 
 // Object::normal_at of the winning object (object.rs:37-39)
+template <bool GLOBAL = false>
 __device__ __forceinline__ V3 normal_at(const SceneView &sv, const Hit &h, V3 world_pos)
 {
-    if (h.kind == 0) return sphere_normal_at(sv.spheres[h.local], world_pos);
-    if (h.kind == 1) return sv.planes[h.local].nhat;
-    return sv.tris[h.local].nn;
+    if (h.kind == 0) return sphere_normal_at(load_record<GLOBAL>(sv.spheres + h.local), world_pos);
+    if (h.kind == 1) return load_record<GLOBAL>(&sv.planes[h.local].nhat);
+    return load_record<GLOBAL>(&sv.tris[h.local].nn);
 }
 
 // render_ray's Some((dst, obj)) arm (scene.rs:233-236) + ray_hit (scene.rs:260-278)
+template <bool GLOBAL = false>
 __device__ __forceinline__ void advance_and_shade(const SceneView &sv, const Hit &h, RayState &r)
 {
     r.pos = vadd(r.pos, vmuls(r.dir, h.t));                                    // scene.rs:234
-    const MaterialX m = sv.materials[h.id];
+    const MaterialX m = load_record<GLOBAL>(sv.materials + h.id);
     double u_z = rng_u01(r.key, r.draw);                                       // vector.rs:37
     double u_theta = rng_u01(r.key, r.draw + 1);                               // vector.rs:38
     r.draw += 2;
-    r.dir = random_bounce_dir(r.dir, normal_at(sv, h, r.pos), m.roughness, u_z, u_theta);  // scene.rs:275
+    r.dir = random_bounce_dir(r.dir, normal_at<GLOBAL>(sv, h, r.pos), m.roughness, u_z, u_theta);  // scene.rs:275
     r.result = vadd(r.result, vmulv(r.light, m.emission_color));               // scene.rs:276
     r.light = vmulv(r.light, m.base_color);                                    // scene.rs:277
     r.bounce += 1;

@@ -340,9 +340,16 @@ __device__ __forceinline__ void query_closest_ray(const SceneView &sv, uint32_t 
             q.e = ray32_slack(q0, in32);
             float best_up = __builtin_inff();
             uint32_t node = sv.bvh_root, sp = 0, qcnt = 0;
+#if defined(RTX_LAB) && defined(RTX_SPH_PROFILE)      // the lab profile builds count in stage 2 of the renders only: the walk's count goes nowhere here
+            unsigned long long rtx_prof = 0;
+#define RTX_QUERY_PROF_PASS , rtx_prof
+#else
+#define RTX_QUERY_PROF_PASS
+#endif
             sphere_walk_phased<kQuerySphStack, true>(nodes, la.sphere_f32, la.sphere_prims, q, sr, node, sp, ls, lq, tid, spill,
                                                      spill_entries, spill_stride, glane, best_up, qcnt, overflow, nbox, nleaf,
-                                                     0u, 0u, 0u, kQueryLeafLanes);
+                                                     0u, 0u, 0u, kQueryLeafLanes RTX_QUERY_PROF_PASS);
+#undef RTX_QUERY_PROF_PASS
             if (!overflow) query_flush(la, rx, lq, tid, kSphQueue, qcnt, best_up, h, exact);
         }
         box_tests += nbox;
