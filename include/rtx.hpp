@@ -364,13 +364,19 @@ public:
     uint32_t update_objects(const std::vector<std::uint64_t> &indices, const std::vector<object::Object> &objects, bool rebuild = false,
                             void *hip_stream = nullptr)
     {
+        return update_objects_mode(indices, objects, rebuild ? RTX_UPDATE_REBUILD : RTX_UPDATE_AUTO, hip_stream);
+    }
+    // The same with the mode spelled out: RTX_UPDATE_AUTO, RTX_UPDATE_REBUILD, or RTX_UPDATE_DEFORM -- AUTO, and a triangle that gets
+    // new vertices and keeps its class (include/rtx_hip.h) is rewritten and refitted in place too (a deforming mesh, a moving part).
+    uint32_t update_objects_mode(const std::vector<std::uint64_t> &indices, const std::vector<object::Object> &objects, uint32_t mode,
+                                 void *hip_stream = nullptr)
+    {
         if (indices.size() != objects.size()) throw std::invalid_argument("update_objects: indices and objects differ in length");
         Scene list;
         for (const object::Object &o : objects) list.add_object(o);
         const std::vector<RtxObject> packed = list.pack();
         uint32_t how = RTX_UPDATED_NOTHING;
-        check(rtx_scene_update_objects(h_, indices.data(), packed.data(), packed.size(), rebuild ? RTX_UPDATE_REBUILD : RTX_UPDATE_AUTO,
-                                       hip_stream, &how));
+        check(rtx_scene_update_objects(h_, indices.data(), packed.data(), packed.size(), mode, hip_stream, &how));
         return how;
     }
     // rows row_begin, row_begin + row_stride, ... (n_rows of them) of the width x height image -> d_out_rgb[n_rows][width][3]

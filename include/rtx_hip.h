@@ -319,7 +319,7 @@ int32_t rtx_scene_append_objects(RtxSceneHandle scene, const RtxObject *objects,
  * gets new boxes finds the same winners.
  *   *how (may be NULL) reports the path:
  *   RTX_UPDATED_REBUILT   rtx_scene_append_objects' path on the modified list (host build, every array replaced).  Taken when mode is
- *                         RTX_UPDATE_REBUILD, an entry changes an object's kind or a triangle's geometry, a new sphere is not finite,
+ *                         RTX_UPDATE_REBUILD, an entry changes an object's kind or a triangle's geometry (but see "Triangles"), a new sphere is not finite,
  *                         its box leaves the range the resident tree was built for, its reach |c - centre| + |r| or the resident
  *                         sphere_cmax is not below 1e14, or the refit finds a 64-byte node it cannot encode.
  *   RTX_UPDATED_REFIT     a sphere of the tree gets new geometry: its records are rewritten and the boxes above it refitted, on the device,
@@ -331,8 +331,21 @@ int32_t rtx_scene_append_objects(RtxSceneHandle scene, const RtxObject *objects,
  * Errors, found before the first device write (the resident scene is unchanged): RTX_ERR_INVALID_ARGUMENT -- a null argument, an
  * index >= n_objects, an unknown mode; RTX_ERR_UNSUPPORTED -- an unknown kind, a non-zero `reserved`.
  * "Streams" applies: the device work is enqueued on `stream` behind whatever earlier calls enqueued on the handle.  The call returns
- * after its own device work has completed (it reads back a status word and the new sphere_cmax). */
-enum { RTX_UPDATE_AUTO = 0, RTX_UPDATE_REBUILD = 1 };                       /* mode */
+ * after its own device work has completed (it reads back a status word and the new sphere_cmax).
+ *   Triangles.  Under RTX_UPDATE_AUTO a triangle entry with new vertices ALWAYS rebuilds, and keeps doing so: callers written against
+ * that mode see the path (*how) and the cost they saw before -- compatibility, nothing else.  RTX_UPDATE_DEFORM is AUTO plus the
+ * in-place update of such triangles (a deforming mesh, a rigid part that moves between frames).  A triangle has a class, decided by
+ * the host exactly as the upload decides it: NONE -- it can never be hit (degenerate, a non-finite normal or n.v0, or n.v0 <
+ * -(1 + 1e-9)) and has no filter record; ALWAYS -- it has a record and is tested for every segment (a non-finite vertex, or a
+ * projection with |det| <= 1e-6 |r| |s|); QUALIFIED(f) -- it may enter the tree with its footprint in the plane that leaves out axis f
+ * (the rows Triangle::contains' elimination reads).  A triangle with new vertices is updated in place when its class and f are the
+ * resident ones and, where it is qualified, every finite face of its new footprint lies within the range the resident tree was built
+ * for.  *how is then RTX_UPDATED_REFIT when at least one such triangle has its record in the tree (its records and f32 footprint are
+ * rewritten, the rectangles / boxes above it and their 64-byte forms refitted level by level, tri_extent taken again), and
+ * RTX_UPDATED_RECORDS when all of them lie outside the tree.  Any other triangle with new vertices (a class or f change either way, a
+ * non-finite vertex, a footprint beyond the range), a footprint node whose 64-byte form cannot be encoded, and everything that
+ * rebuilds under AUTO give RTX_UPDATED_REBUILT.  The contract above holds for every path. */
+enum { RTX_UPDATE_AUTO = 0, RTX_UPDATE_REBUILD = 1, RTX_UPDATE_DEFORM = 2 };   /* mode */
 enum { RTX_UPDATED_NOTHING = 0, RTX_UPDATED_RECORDS = 1, RTX_UPDATED_REFIT = 2, RTX_UPDATED_REBUILT = 3 };   /* *how */
 int32_t rtx_scene_update_objects(RtxSceneHandle scene, const uint64_t *indices, const RtxObject *objects, uint64_t n,
                                  uint32_t mode, void *stream, uint32_t *how);
@@ -705,6 +718,16 @@ int32_t rtx_debug_host_refit(const RtxScene *scene, const uint64_t *indices, con
 
 /* Test hook of the lab library: downloads the resident arrays of `scene` and digests them in rtx_debug_host_refit's order. */
 int32_t rtx_debug_resident_digests(RtxSceneHandle scene, uint64_t *digests);
+
+/* rtx_debug_host_refit with the arrays a triangle update writes (lab library; no GPU; the split point in the high 16 bits of `mode`
+ * too).  digests[16]: [0..7] as rtx_debug_host_refit; [8] the triangle records (tris), [9] tri_f32, [10] tri_geo, [11] the 64-byte
+ * footprint nodes, [12] the bits of tri_extent; [13..15] 0.  info[8]: the centre the f32 records are offsets from (3 values),
+ * tri_extent, sphere_cmax, abs_pad, the range (scale) the tree was built for (< 0: no tree), 0. */
+int32_t rtx_debug_host_refit_mesh(const RtxScene *scene, const uint64_t *indices, const RtxObject *objects, uint64_t n, uint32_t mode,
+                                  uint64_t *stats, uint32_t *how, uint64_t *digests, double *info);
+
+/* Test hook of the lab library: the 16 digests of rtx_debug_host_refit_mesh, from the downloaded resident arrays of `scene`. */
+int32_t rtx_debug_resident_mesh_digests(RtxSceneHandle scene, uint64_t *digests);
 
 #ifdef __cplusplus
 }

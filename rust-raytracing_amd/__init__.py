@@ -490,8 +490,9 @@ class SceneHandle:
 
     def update_objects(self, indices, packed, mode="auto", stream=None):
         """Scene.objects[indices[i]] = packed[i] on the resident scene (rtx_scene_update_objects; a repeated index: its last entry
-        wins).  `packed` is an OBJECT_DTYPE array (or a list of Objects); mode "auto" or "rebuild".  Returns how the update ran:
-        "nothing", "records", "refit" or "rebuilt"."""
+        wins).  `packed` is an OBJECT_DTYPE array (or a list of Objects); mode "auto", "rebuild" or "deform" ("auto", and a triangle
+        that gets new vertices and keeps its class is rewritten and refitted in place too: RTX_UPDATE_DEFORM).  Returns how the update
+        ran: "nothing", "records", "refit" or "rebuilt"."""
         arr = packed if isinstance(packed, np.ndarray) else pack_objects(packed)
         arr = np.ascontiguousarray(arr, dtype=OBJECT_DTYPE)
         idx = np.ascontiguousarray(np.asarray(indices, dtype=np.uint64).reshape(-1))
@@ -506,6 +507,12 @@ class SceneHandle:
         """FNV-1a-64 digests of the resident arrays, in debug_host_refit's order (rtx_debug_resident_digests; a lab-library hook)."""
         digests = (C.c_uint64 * 8)()
         self._check(self._lib.rtx_debug_resident_digests(self._h, digests))
+        return tuple(int(v) for v in digests)
+
+    def debug_resident_mesh_digests(self):
+        """The 16 digests of debug_host_refit_mesh from the resident arrays (rtx_debug_resident_mesh_digests; a lab-library hook)."""
+        digests = (C.c_uint64 * 16)()
+        self._check(self._lib.rtx_debug_resident_mesh_digests(self._h, digests))
         return tuple(int(v) for v in digests)
 
     def debug_paths(self, width, height, row, max_steps):
@@ -864,7 +871,7 @@ UPDATE_HOW = ("nothing", "records", "refit", "rebuilt")        # RTX_UPDATED_*
 
 def _update_mode(mode):
     if isinstance(mode, str):
-        return {"auto": abi.RTX_UPDATE_AUTO, "rebuild": abi.RTX_UPDATE_REBUILD}[mode]
+        return {"auto": abi.RTX_UPDATE_AUTO, "rebuild": abi.RTX_UPDATE_REBUILD, "deform": abi.RTX_UPDATE_DEFORM}[mode]
     return int(mode)
 
 
@@ -884,6 +891,28 @@ def debug_host_refit(scene, indices, packed, mode="auto", split=0):
     abi.check(lib.rtx_debug_host_refit(C.byref(sc), idx.ctypes.data, arr.ctypes.data, len(arr), _update_mode(mode) | (int(split) << 16),
                                        stats, C.byref(how), digests), lib)
     return UPDATE_HOW[how.value], dict(zip(HOST_SCENE_STATS, (int(v) for v in stats))), tuple(int(v) for v in digests)
+
+
+MESH_REFIT_INFO = ("centre_x", "centre_y", "centre_z", "tri_extent", "sphere_cmax", "abs_pad", "scale", "reserved")
+
+
+def debug_host_refit_mesh(scene, indices, packed, mode="deform", split=0):
+    """debug_host_refit with the arrays a triangle update writes (rtx_debug_host_refit_mesh of the lab library; needs no GPU).
+    Returns (how, stats dict, digests (16,), info dict): digests[8..12] = tris, tri_f32, tri_geo, the 64-byte footprint nodes, the
+    bits of tri_extent; info: MESH_REFIT_INFO."""
+    import ctypes as C
+    sc = _scene_c(scene.config, scene.camera, scene.packed())
+    arr = packed if isinstance(packed, np.ndarray) else pack_objects(packed)
+    arr = np.ascontiguousarray(arr, dtype=OBJECT_DTYPE)
+    idx = np.ascontiguousarray(np.asarray(indices, dtype=np.uint64).reshape(-1))
+    if len(idx) != len(arr):
+        raise ValueError("debug_host_refit_mesh: %d indices for %d objects" % (len(idx), len(arr)))
+    stats, digests, how, info = (C.c_uint64 * 16)(), (C.c_uint64 * 16)(), C.c_uint32(0), (C.c_double * 8)()
+    lib = load_library(True)
+    abi.check(lib.rtx_debug_host_refit_mesh(C.byref(sc), idx.ctypes.data, arr.ctypes.data, len(arr), _update_mode(mode) | (int(split) << 16),
+                                            stats, C.byref(how), digests, info), lib)
+    return (UPDATE_HOW[how.value], dict(zip(HOST_SCENE_STATS, (int(v) for v in stats))), tuple(int(v) for v in digests),
+            dict(zip(MESH_REFIT_INFO, (float(v) for v in info))))
 
 
 # one segment of a path's transcript (RtxPathStep, include/rtx_hip.h)

@@ -37,7 +37,7 @@ RTX_TUNE_LAB_MASK = (RTX_TUNE_BVH_CLASSIC | RTX_TUNE_NO_QNODES | RTX_TUNE_NO_PAC
                      RTX_TUNE_STAGE2_SLOTS)
 RTX_TUNE_KNOWN_MASK = (RTX_TUNE_LAB_MASK | RTX_TUNE_NO_TILES | RTX_TUNE_ONE_STAGE | RTX_TUNE_TWO_STAGE | RTX_TUNE_BVH_MEDIAN |
                        (15 << RTX_TUNE_TRI_LEAF_SHIFT) | (127 << RTX_TUNE_THRESH_SHIFT) | RTX_TUNE_NO_CUT | RTX_TUNE_HALVES | RTX_TUNE_NO_HALVES | RTX_TUNE_NO_TILE_LISTS)
-RTX_UPDATE_AUTO, RTX_UPDATE_REBUILD = 0, 1
+RTX_UPDATE_AUTO, RTX_UPDATE_REBUILD, RTX_UPDATE_DEFORM = 0, 1, 2
 RTX_UPDATED_NOTHING, RTX_UPDATED_RECORDS, RTX_UPDATED_REFIT, RTX_UPDATED_REBUILT = 0, 1, 2, 3
 RTX_OK, RTX_ERR_INVALID_ARGUMENT, RTX_ERR_NO_DEVICE, RTX_ERR_HIP, RTX_ERR_UNSUPPORTED, RTX_ERR_OUT_OF_MEMORY = range(6)
 
@@ -154,6 +154,9 @@ SYMBOLS = [
     ("rtx_debug_host_refit", C.c_int32, [C.POINTER(RtxScene), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64),
                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     ("rtx_debug_resident_digests", C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    ("rtx_debug_host_refit_mesh", C.c_int32, [C.POINTER(RtxScene), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64),
+                                              C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    ("rtx_debug_resident_mesh_digests", C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64)]),
 ]
 
 

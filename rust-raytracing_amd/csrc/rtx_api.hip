@@ -104,6 +104,12 @@ struct RefitTables {
     std::vector<uint32_t> local;                          // object index -> index in spheres[] / planes[] / tris[] (the kind: h->objects)
     std::vector<uint32_t> slot;                           // sphere -> its leaf entry (the inverse of bvh.prims); empty without a sphere tree
     std::vector<uint32_t> level_nodes, level_begin;       // the non-flat wide nodes grouped by depth: level d = level_nodes[level_begin[d] .. level_begin[d + 1])
+    // the triangle half (RTX_UPDATE_DEFORM): per triangle its class and free axis as pack_scene decided them (classify_triangle) and its
+    // record in tri_f32 (tri_fidx inverted; kNoSlot: class "none"; < n_tri_tree: a tree record, the index in tri_geo too)
+    std::vector<uint8_t> tri_class, tri_axis;
+    std::vector<uint32_t> tri_rec;
+    uint32_t n_tri_tree = 0;
+    std::vector<uint32_t> all_level_nodes, all_level_begin;   // EVERY wide node by depth, a footprint node with kBvhFlatNode set
 };
 
 struct RtxSceneHandle_ {
@@ -120,9 +126,11 @@ struct RtxSceneHandle_ {
     struct UpdateBufs {
         bool valid = false;
         uint32_t *levels = nullptr; float *box32 = nullptr; double *reach = nullptr;
+        bool mesh_valid = false;                                // the triangle half: made at the first DEFORM call that moves a triangle
+        uint32_t *all_levels = nullptr; float *tribox32 = nullptr; double *tri_reach = nullptr;
         UpdateEntry *h_entries = nullptr; size_t h_cap = 0;     // pinned staging of the update list
         UpdateEntry *d_entries = nullptr; size_t d_cap = 0;
-        unsigned long long *d_status = nullptr, *h_status = nullptr;   // {status bits, the bits of the new sphere_cmax}; h_status pinned
+        unsigned long long *d_status = nullptr, *h_status = nullptr;   // {status bits, the bits of the new sphere_cmax, of the new tri_extent}; h_status pinned
     } upd;
     // scratch, grown on demand
     double *samples = nullptr;  size_t samples_bytes = 0;
@@ -231,8 +239,10 @@ int32_t grow(void **p, size_t *have, size_t want)
 void drop_update_tables(RtxSceneHandle_ *h)              // the device tables of one pack (the staging buffers stay)
 {
     auto &b = h->upd;
-    for (void *q : { (void *)b.levels, (void *)b.box32, (void *)b.reach }) if (q) (void)hipFree(q);
+    for (void *q : { (void *)b.levels, (void *)b.box32, (void *)b.reach, (void *)b.all_levels, (void *)b.tribox32, (void *)b.tri_reach })
+        if (q) (void)hipFree(q);
     b.levels = nullptr; b.box32 = nullptr; b.reach = nullptr; b.valid = false;
+    b.all_levels = nullptr; b.tribox32 = nullptr; b.tri_reach = nullptr; b.mesh_valid = false;
 }
 
 void free_handle(RtxSceneHandle_ *h)
@@ -287,11 +297,40 @@ struct PackedScene {
     std::vector<float4> sph32, tri32, leaf32, leaf_cr, tri_geo;
     std::vector<uint32_t> tri_fidx;
     std::vector<uint8_t> tri_rec_free_axis;          // per tree record (leaf order): the axis its footprint is unbounded along
+    std::vector<uint8_t> tri_class, tri_axis;        // per triangle: classify_triangle's answer
     BvhBuild bvh;
     Bvh4Build bvh4;
     std::vector<BvhQNode> qnodes;                    // the 64-byte form of bvh4's nodes, when the tree allows it
     std::vector<BvhQ3Node> q3nodes;                  // the 64-byte form of a sphere tree's nodes
 };
+
+// The class of a triangle before any demotion, decided in ONE place for pack_scene (which record it gets, whether it may enter the
+// tree) and plan_update (whether new vertices can be written in place):
+//   kTriNone       no filter record: it can never be hit
+//   kTriAlways     a record, tested for every segment: the projection the elimination reads is not usable for a footprint
+//   kTriQualified  may enter the tree with its footprint in the plane that leaves out `free_axis`
+enum : uint8_t { kTriNone = 0, kTriAlways = 1, kTriQualified = 2 };
+struct TriClass { uint8_t cls; uint8_t free_axis; };
+
+TriClass classify_triangle(const TriX &t, const double geom[9], const double centre[3])
+{
+    TriClass c{kTriNone, 2};
+    if (t.degenerate) return c;                                       // Triangle::contains is always false (triangle.rs:64,83)
+    const double kabs = dot(t.n, t.v0);
+    if (!std::isfinite(kabs) || !std::isfinite(t.n.x) || !std::isfinite(t.n.y) || !std::isfinite(t.n.z))
+        return c;                                                     // NaN normal: every comparison of the exact test fails
+    if (kabs < -(1.0 + 1e-9)) return c;                               // n.(v0 - dir) < 0 for every unit dir (triangle.rs:115)
+    c.cls = kTriAlways;
+    double v[3][3];
+    bool finite = true;
+    for (int k = 0; k < 9; ++k) { v[k / 3][k % 3] = geom[k] - centre[k % 3]; finite = finite && std::isfinite(geom[k]); }
+    const int free_axis = 3 - (int)t.i - (int)t.j;                    // t.i != t.j: the two rows the elimination reads
+    const int a0 = free_axis == 0 ? 1 : 0, a1 = free_axis == 2 ? 1 : 2;
+    const double r0 = v[1][a0] - v[0][a0], r1 = v[1][a1] - v[0][a1], s0 = v[2][a0] - v[0][a0], s1 = v[2][a1] - v[0][a1];
+    const double det = r0 * s1 - r1 * s0;
+    if (finite && t.i != t.j && std::fabs(det) > 1e-6 * std::hypot(r0, r1) * std::hypot(s0, s1)) { c.cls = kTriQualified; c.free_axis = (uint8_t)free_axis; }
+    return c;
+}
 
 int32_t pack_scene(const RtxScene *scene, PackedScene &p)
 {
@@ -363,24 +402,23 @@ int32_t pack_scene(const RtxScene *scene, PackedScene &p)
     std::vector<TriRec> tree_recs[3], always_recs;                     // tree_recs[f]: the elimination does not read axis f
     std::vector<BvhBox> tri_boxes[3];
     double tri_extent = 0.0;
+    p.tri_class.assign(tris.size(), (uint8_t)kTriNone);
+    p.tri_axis.assign(tris.size(), (uint8_t)2);
     for (size_t k = 0; k < tris.size(); ++k) {
         const TriX &t = tris[k];
         const RtxObject &o = scene->objects[t.id];
-        if (t.degenerate) continue;                                   // Triangle::contains is always false (triangle.rs:64,83)
+        const TriClass tc = classify_triangle(t, o.geom, centre);
+        p.tri_class[k] = tc.cls; p.tri_axis[k] = tc.free_axis;
+        if (tc.cls == kTriNone) continue;
         const double kabs = dot(t.n, t.v0);
-        if (!std::isfinite(kabs) || !std::isfinite(t.n.x) || !std::isfinite(t.n.y) || !std::isfinite(t.n.z))
-            continue;                                                 // NaN normal: every comparison of the exact test fails
-        if (kabs < -(1.0 + 1e-9)) continue;                           // n.(v0 - dir) < 0 for every unit dir (triangle.rs:115)
         double v[3][3];
-        bool finite = true;
-        for (int c = 0; c < 9; ++c) { v[c / 3][c % 3] = o.geom[c] - centre[c % 3]; finite = finite && std::isfinite(o.geom[c]); }
+        for (int c = 0; c < 9; ++c) v[c / 3][c % 3] = o.geom[c] - centre[c % 3];
         const int free_axis = 3 - (int)t.i - (int)t.j;                // t.i != t.j: the two rows the elimination reads
         const int a0 = free_axis == 0 ? 1 : 0, a1 = free_axis == 2 ? 1 : 2;
         const double r0 = v[1][a0] - v[0][a0], r1 = v[1][a1] - v[0][a1], s0 = v[2][a0] - v[0][a0], s1 = v[2][a1] - v[0][a1];
         const double det = r0 * s1 - r1 * s0;
         BvhBox fp;
-        const bool in_tree = finite && t.i != t.j && std::fabs(det) > 1e-6 * std::hypot(r0, r1) * std::hypot(s0, s1) &&
-                             triangle_footprint(o.geom, fp, free_axis);
+        const bool in_tree = tc.cls == kTriQualified && triangle_footprint(o.geom, fp, free_axis);
         TriRec rec;
         rec.A = make_float4(0.f, 0.f, 0.f, 0.f);                       // "always a candidate"
         rec.B = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -517,10 +555,34 @@ RefitTables make_refit_tables(const PackedScene &p)
     for (size_t k = 0; k < p.sphere_id.size(); ++k) t.local[p.sphere_id[k]] = (uint32_t)k;
     for (size_t k = 0; k < p.planes.size(); ++k) t.local[p.planes[k].id] = (uint32_t)k;
     for (size_t k = 0; k < p.tris.size(); ++k) t.local[p.tris[k].id] = (uint32_t)k;
+    auto bits = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
+    t.tri_class = p.tri_class; t.tri_axis = p.tri_axis;
+    t.tri_rec.assign(p.tris.size(), kNoSlot);
+    for (size_t r = 0; r < p.tri_fidx.size(); ++r) t.tri_rec[p.tri_fidx[r]] = (uint32_t)r;
+    t.n_tri_tree = p.sv.n_tri_tree;
+    if (t.n_tri_tree) {                                       // every wide node by depth (the sphere-only list below stops at footprint links)
+        std::vector<uint32_t> cur, next;
+        cur.push_back(p.bvh4.root);
+        t.all_level_begin.push_back(0u);
+        while (!cur.empty()) {
+            next.clear();
+            for (uint32_t entry : cur) {
+                t.all_level_nodes.push_back(entry);
+                const Bvh4Node &w = p.bvh4.nodes[entry & ~kBvhFlatNode];
+                const float lk[4] = { w.b[0].x, w.b[0].y, w.b[0].z, w.b[0].w }, ct[4] = { w.b[1].x, w.b[1].y, w.b[1].z, w.b[1].w };
+                for (int c = 0; c < 4; ++c) {
+                    const bool flat = (entry & kBvhFlatNode) != 0u;
+                    const uint32_t link = bits(flat ? lk[c] : w.a[c].w), count = bits(flat ? ct[c] : w.b[c].w);
+                    if (count == 0u) next.push_back(flat ? (link | kBvhFlatNode) : link);
+                }
+            }
+            t.all_level_begin.push_back((uint32_t)t.all_level_nodes.size());
+            cur.swap(next);
+        }
+    }
     if (!t.sphere_tree) return t;
     t.slot.assign(p.spheres.size(), kNoSlot);
     for (size_t k = 0; k < p.bvh.prims.size(); ++k) t.slot[p.bvh.prims[k]] = (uint32_t)k;
-    auto bits = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
     std::vector<uint32_t> cur, next;
     if (!(p.bvh4.root & kBvhFlatNode)) cur.push_back(0u);
     t.level_begin.push_back(0u);
@@ -601,6 +663,9 @@ struct UpdatePlan {
     std::vector<UpdateEntry> entries;
     uint32_t how = RTX_UPDATED_NOTHING;
     bool any_sphere = false;                              // a sphere's geometry changes: sphere_cmax is taken again
+    bool tri_geom = false;                                // a triangle's geometry changes in place (RTX_UPDATE_DEFORM): the triangle tables are needed
+    bool tri_refit = false;                               // ... and it has a tree record: every level is refitted, footprint nodes included
+    bool any_tri = false;                                 // ... and it is qualified: tri_extent is taken again
 };
 
 // Validates (nothing is written before every entry passed), removes duplicates and chooses the path (include/rtx_hip.h, "Which path
@@ -609,13 +674,15 @@ struct UpdatePlan {
 //   sphere_center   kept: the f32 records are offsets from ANY fixed point; what depends on it is sphere_cmax, which mode C recomputes
 //                   against the kept centre, and the < 1e14 limit of pack_scene, which every new reach is held to here
 //   origin_limit, abs_pad, bvh_inv_max   functions of `scale`: a new box beyond it rebuilds
-//   tri_extent, the triangle records     triangle geometry never changes here (it rebuilds)
+//   tri_extent, the triangle records     under AUTO triangle geometry never changes here (it rebuilds).  Under RTX_UPDATE_DEFORM a triangle
+//                   that keeps its class and free axis (classify_triangle: the decision pack_scene takes) is rewritten against the kept
+//                   centre and mode D takes tri_extent again; the class rule keeps tri_fidx, the leaf order and which records are real
 //   bvh_depth, bvh_flags, the topology   the tree keeps its shape; a sphere that turns non-finite (it would leave the tree) rebuilds
 int32_t plan_update(const std::vector<RtxObject> &cur, const RefitTables &t, double cmax, const uint64_t *indices, const RtxObject *objects,
                     uint64_t n, uint32_t mode, UpdatePlan &plan)
 {
     plan = UpdatePlan();
-    if (mode != RTX_UPDATE_AUTO && mode != RTX_UPDATE_REBUILD) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_update_objects: unknown mode");
+    if (mode != RTX_UPDATE_AUTO && mode != RTX_UPDATE_REBUILD && mode != RTX_UPDATE_DEFORM) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_update_objects: unknown mode");
     if (n == 0) return RTX_OK;
     if (!indices || !objects) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_update_objects: null argument");
     for (uint64_t i = 0; i < n; ++i) {
@@ -642,7 +709,29 @@ int32_t plan_update(const std::vector<RtxObject> &cur, const RefitTables &t, dou
         std::memcpy(&e.kind, &o, sizeof o);
         if (o.kind != cur[idx].kind) rebuild = true;
         else if (o.kind == RTX_TRIANGLE) {
-            if (std::memcmp(o.geom, cur[idx].geom, sizeof o.geom) != 0) rebuild = true;
+            if (std::memcmp(o.geom, cur[idx].geom, sizeof o.geom) != 0) {          // (same geometry: a material update)
+                bool finite = true;
+                for (int c = 0; c < 9; ++c) finite = finite && std::isfinite(o.geom[c]);
+                const uint32_t k = e.local;
+                TriClass tc{kTriNone, 2};
+                if (mode == RTX_UPDATE_DEFORM && finite) tc = classify_triangle(make_triangle(o.geom, (uint32_t)idx), o.geom, t.centre);
+                if (mode != RTX_UPDATE_DEFORM || !finite || tc.cls != t.tri_class[k] || (tc.cls == kTriQualified && tc.free_axis != t.tri_axis[k]))
+                    rebuild = true;                                   // AUTO: always, as ever; DEFORM: the class or the free axis changes
+                else {
+                    plan.tri_geom = true;
+                    e.tri = kTriEntryGeom; e.slot = t.tri_rec[k];
+                    if (tc.cls == kTriQualified) {
+                        e.tri |= kTriEntryQualified | ((uint32_t)tc.free_axis << kTriEntryAxisShift);
+                        plan.any_tri = true;
+                        BvhBox fp;
+                        if (!triangle_footprint(o.geom, fp, tc.free_axis)) rebuild = true;
+                        else if (t.scale >= 0.0)
+                            for (int a = 0; a < 3; ++a)
+                                if (a != tc.free_axis && (std::fabs(fp.lo[a]) > t.scale || std::fabs(fp.hi[a]) > t.scale)) rebuild = true;
+                        if (e.slot < t.n_tri_tree) { e.tri |= kTriEntryTree; plan.tri_refit = true; refit = true; }
+                    }
+                }
+            }
         } else if (o.kind == RTX_SPHERE && std::memcmp(o.geom, cur[idx].geom, 4 * sizeof(double)) != 0) {      // (same geometry: a material update)
             plan.any_sphere = true;
             BvhBox b;
@@ -673,9 +762,27 @@ void derive_all_spheres(const PackedScene &p, const RtxObject *objects, const Re
     }
 }
 
+// tribox32 (per tree record) / tri_reach (per triangle) of every triangle of `objects`: what modes B and D read for the triangles an
+// update does not name.
+void derive_all_triangles(const RtxObject *objects, size_t n_objects, const RefitTables &t, std::vector<float> &tribox32, std::vector<double> &tri_reach)
+{
+    tribox32.assign((size_t)t.n_tri_tree * 6, 0.f);
+    tri_reach.assign(t.tri_class.size(), 0.0);
+    for (size_t k = 0; k < n_objects; ++k) {
+        if (objects[k].kind != RTX_TRIANGLE) continue;
+        const uint32_t q = t.local[k];
+        if (t.tri_class[q] != kTriQualified) continue;
+        const TriDerived d = derive_triangle(objects[k].geom, (uint32_t)k, true, (int)t.tri_axis[q], t.centre, t.abs_pad);
+        tri_reach[q] = d.reach;
+        if (t.tri_rec[q] < t.n_tri_tree) for (int a = 0; a < 6; ++a) tribox32[(size_t)t.tri_rec[q] * 6 + a] = d.box[a];
+    }
+}
+
 // The host reference of the device path: rtx_refit.h's functions in the order the launches run them, on a packed scene.  Returns the
-// status word (kUpdateStatusNoQ3: a 64-byte node has no encoding -- the caller rebuilds).
-unsigned long long refit_packed(PackedScene &p, const RefitTables &t, const UpdatePlan &plan, std::vector<float> &box32, std::vector<double> &reach)
+// status word (kUpdateStatusNoQ3 / kUpdateStatusNoQ: a 64-byte node has no encoding -- the caller rebuilds).  tribox32 / tri_reach are
+// read only when the plan moves a triangle.
+unsigned long long refit_packed(PackedScene &p, const RefitTables &t, const UpdatePlan &plan, std::vector<float> &box32, std::vector<double> &reach,
+                                std::vector<float> &tribox32, std::vector<double> &tri_reach)
 {
     unsigned long long status = 0ull;
     UpdateArgs u{};
@@ -688,15 +795,26 @@ unsigned long long refit_packed(PackedScene &p, const RefitTables &t, const Upda
     u.prims = p.bvh.prims.data();
     for (int c = 0; c < 3; ++c) u.centre[c] = t.centre[c];
     u.abs_pad = t.abs_pad;
+    if (plan.tri_geom) {
+        u.tris = p.tris.data(); u.tri_f32 = p.tri32.data(); u.tri_geo = p.tri_geo.data();
+        u.tribox32 = tribox32.data(); u.tri_reach = tri_reach.data();
+        u.qnodes = (p.sv.bvh_flags & 8u) ? p.qnodes.data() : nullptr;
+    }
     for (uint32_t i = 0; i < (uint32_t)plan.entries.size(); ++i) update_record(u, i);
-    if (plan.how == RTX_UPDATED_REFIT)
-        for (size_t d = t.level_begin.size() - 1; d-- > 0;)
-            for (uint32_t k = t.level_begin[d]; k < t.level_begin[d + 1]; ++k)
-                if (!refit_node(u, t.level_nodes[k])) status |= kUpdateStatusNoQ3;
+    if (plan.how == RTX_UPDATED_REFIT) {
+        const std::vector<uint32_t> &nodes = plan.tri_refit ? t.all_level_nodes : t.level_nodes, &begin = plan.tri_refit ? t.all_level_begin : t.level_begin;
+        for (size_t d = begin.empty() ? 0 : begin.size() - 1; d-- > 0;)
+            for (uint32_t k = begin[d]; k < begin[d + 1]; ++k) status |= refit_level_entry(u, nodes[k]);
+    }
     if (plan.any_sphere) {
         double m = 0.0;
         for (double r : reach) m = r > m ? r : m;
         p.sv.sphere_cmax = m;
+    }
+    if (plan.any_tri) {
+        double m = 0.0;
+        for (double r : tri_reach) m = r > m ? r : m;
+        p.sv.tri_extent = m;
     }
     return status;
 }
@@ -721,6 +839,18 @@ void digest_packed(const PackedScene &p, uint64_t *digests)
     digests[5] = fnv1a(kFnvBasis, p.planes.data(), p.planes.size() * sizeof(PlaneX));
     digests[6] = fnv1a(kFnvBasis, p.mats.data(), p.mats.size() * sizeof(MaterialX));
     digests[7] = fnv1a(kFnvBasis, &p.sv.sphere_cmax, sizeof(double));
+}
+
+// digest_packed, then (rtx_debug_host_refit_mesh) the triangle records, tri_f32, tri_geo, the 64-byte footprint nodes, the bits of tri_extent.
+void digest_packed_mesh(const PackedScene &p, uint64_t *digests)
+{
+    digest_packed(p, digests);
+    digests[8] = fnv1a(kFnvBasis, p.tris.data(), p.tris.size() * sizeof(TriX));
+    digests[9] = fnv1a(kFnvBasis, p.tri32.data(), p.tri32.size() * sizeof(float4));
+    digests[10] = fnv1a(kFnvBasis, p.tri_geo.data(), p.tri_geo.size() * sizeof(float4));
+    digests[11] = fnv1a(kFnvBasis, p.qnodes.data(), p.qnodes.size() * sizeof(BvhQNode));
+    digests[12] = fnv1a(kFnvBasis, &p.sv.tri_extent, sizeof(double));
+    digests[13] = digests[14] = digests[15] = 0;
 }
 
 int32_t check_scene_args(const RtxScene *scene, const char *who)
@@ -1024,8 +1154,8 @@ namespace {
 int32_t ensure_update_tables(RtxSceneHandle_ *h)
 {
     auto &b = h->upd;
-    if (!b.d_status) RTX_HIP_CHECK(hipMalloc((void **)&b.d_status, 2 * sizeof(unsigned long long)));
-    if (!b.h_status) RTX_HIP_CHECK(hipHostMalloc((void **)&b.h_status, 2 * sizeof(unsigned long long), hipHostMallocDefault));
+    if (!b.d_status) RTX_HIP_CHECK(hipMalloc((void **)&b.d_status, 3 * sizeof(unsigned long long)));
+    if (!b.h_status) RTX_HIP_CHECK(hipHostMalloc((void **)&b.h_status, 3 * sizeof(unsigned long long), hipHostMallocDefault));
     if (b.valid) return RTX_OK;
     drop_update_tables(h);
     const RefitTables &t = h->refit;
@@ -1050,6 +1180,27 @@ int32_t ensure_update_tables(RtxSceneHandle_ *h)
         RTX_HIP_CHECK(hipMemcpy(b.levels, t.level_nodes.data(), t.level_nodes.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     b.valid = true;
+    return RTX_OK;
+}
+
+// The triangle half of the device tables (derive_all_spheres' analogue), made at the first DEFORM call that moves a triangle.
+int32_t ensure_mesh_tables(RtxSceneHandle_ *h)
+{
+    auto &b = h->upd;
+    if (b.mesh_valid) return RTX_OK;
+    const RefitTables &t = h->refit;
+    std::vector<float> tribox32;
+    std::vector<double> tri_reach;
+    derive_all_triangles(h->objects.data(), h->objects.size(), t, tribox32, tri_reach);
+    auto put = [](auto **dst, const auto &v) -> hipError_t {
+        if (v.empty()) return hipSuccess;
+        const hipError_t e = hipMalloc((void **)dst, v.size() * sizeof(v[0]));
+        return e != hipSuccess ? e : hipMemcpy(*dst, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice);
+    };
+    RTX_HIP_CHECK(put(&b.tribox32, tribox32));
+    RTX_HIP_CHECK(put(&b.tri_reach, tri_reach));
+    RTX_HIP_CHECK(put(&b.all_levels, t.all_level_nodes));
+    b.mesh_valid = true;
     return RTX_OK;
 }
 
@@ -1087,6 +1238,7 @@ int32_t rtx_scene_update_objects(RtxSceneHandle h, const uint64_t *indices, cons
     if (plan.how != RTX_UPDATED_REBUILT) {
         auto &b = h->upd;
         if (int32_t rc = ensure_update_tables(h)) return rc;
+        if (plan.tri_geom) if (int32_t rc = ensure_mesh_tables(h)) return rc;
         const size_t ne = plan.entries.size(), bytes = ne * sizeof(UpdateEntry);
         if (b.h_cap < ne) {
             if (b.h_entries) { RTX_HIP_CHECK(hipHostFree(b.h_entries)); b.h_entries = nullptr; b.h_cap = 0; }
@@ -1105,7 +1257,8 @@ int32_t rtx_scene_update_objects(RtxSceneHandle h, const uint64_t *indices, cons
             const RefitTables &t = h->refit;
             const SceneView &sv = h->sv;
             RTX_HIP_CHECK(hipMemcpyAsync(b.d_entries, b.h_entries, bytes, hipMemcpyHostToDevice, stream));
-            RTX_HIP_CHECK(hipMemsetAsync(b.d_status, 0, 2 * sizeof(unsigned long long), stream));
+            const size_t status_bytes = (plan.any_tri ? 3 : 2) * sizeof(unsigned long long);      // (the third word: mode D's)
+            RTX_HIP_CHECK(hipMemsetAsync(b.d_status, 0, status_bytes, stream));
             UpdateArgs u{};
             u.entries = b.d_entries;
             u.spheres = const_cast<SphereX *>(sv.spheres); u.planes = const_cast<PlaneX *>(sv.planes);
@@ -1119,25 +1272,39 @@ int32_t rtx_scene_update_objects(RtxSceneHandle h, const uint64_t *indices, cons
             u.status = b.d_status;
             for (int c = 0; c < 3; ++c) u.centre[c] = t.centre[c];
             u.abs_pad = t.abs_pad;
+            if (plan.tri_geom) {
+                u.tris = const_cast<TriX *>(sv.tris); u.tri_f32 = const_cast<float4 *>(sv.tri_f32); u.tri_geo = const_cast<float4 *>(sv.tri_geo);
+                u.tribox32 = b.tribox32; u.tri_reach = b.tri_reach;
+                u.qnodes = (sv.bvh_flags & 8u) ? const_cast<BvhQNode *>(sv.bvh_qnodes) : nullptr;
+            }
             u.mode = 0u; u.n = (uint32_t)ne;
             RTX_HIP_CHECK(launch_scene_update(u, stream));
-            if (plan.how == RTX_UPDATED_REFIT)
-                for (size_t d = t.level_begin.size() - 1; d-- > 0;) {       // deepest first: a node reads what its children's launch wrote
-                    u.mode = 1u; u.n = t.level_begin[d + 1] - t.level_begin[d];
-                    u.level = b.levels + t.level_begin[d];
+            if (plan.how == RTX_UPDATED_REFIT) {
+                // a moved triangle of the tree: every level, footprint nodes included; spheres alone: the non-flat levels, as ever
+                const std::vector<uint32_t> &begin = plan.tri_refit ? t.all_level_begin : t.level_begin;
+                const uint32_t *levels = plan.tri_refit ? b.all_levels : b.levels;
+                for (size_t d = begin.empty() ? 0 : begin.size() - 1; d-- > 0;) {       // deepest first: a node reads what its children's launch wrote
+                    u.mode = 1u; u.n = begin[d + 1] - begin[d];
+                    u.level = levels + begin[d];
                     RTX_HIP_CHECK(launch_scene_update(u, stream));
                 }
+            }
             if (plan.any_sphere) {
                 u.mode = 2u; u.n = sv.n_spheres;
                 RTX_HIP_CHECK(launch_scene_update(u, stream));
             }
-            RTX_HIP_CHECK(hipMemcpyAsync(b.h_status, b.d_status, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+            if (plan.any_tri) {
+                u.mode = 3u; u.n = sv.n_tris;
+                RTX_HIP_CHECK(launch_scene_update(u, stream));
+            }
+            RTX_HIP_CHECK(hipMemcpyAsync(b.h_status, b.d_status, status_bytes, hipMemcpyDeviceToHost, stream));
             RTX_HIP_CHECK(hipStreamSynchronize(stream));
         }
-        if (h->upd.h_status[0] & kUpdateStatusNoQ3) plan.how = RTX_UPDATED_REBUILT;       // every array is replaced below
+        if (h->upd.h_status[0] & (kUpdateStatusNoQ3 | kUpdateStatusNoQ)) plan.how = RTX_UPDATED_REBUILT;       // every array is replaced below
         else {
             for (const UpdateEntry &e : plan.entries) std::memcpy(&h->objects[e.object], &e.kind, sizeof(RtxObject));
             if (plan.any_sphere) { std::memcpy(&h->sv.sphere_cmax, &h->upd.h_status[1], sizeof(double)); h->sv_dirty = true; }
+            if (plan.any_tri) { std::memcpy(&h->sv.tri_extent, &h->upd.h_status[2], sizeof(double)); h->sv_dirty = true; }
         }
     }
     if (plan.how == RTX_UPDATED_REBUILT)
@@ -2191,16 +2358,17 @@ int32_t rtx_debug_host_scene(const RtxScene *scene, uint64_t *stats)
     return check_packed(p, scene->objects, stats);
 }
 
-int32_t rtx_debug_host_refit(const RtxScene *scene, const uint64_t *indices, const RtxObject *objects, uint64_t n, uint32_t mode,
-                             uint64_t *stats, uint32_t *how, uint64_t *digests)
-{
 #ifdef RTX_LAB
-    if (!scene || !stats || !how || !digests) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_host_refit: null argument");
-    if (scene->n_objects && !scene->objects) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_host_refit: objects is null");
+// rtx_debug_host_refit / rtx_debug_host_refit_mesh: `who` names the hook in messages; digests: 8 values, or 16 when `info` is given.
+static int32_t host_refit(const char *who, const RtxScene *scene, const uint64_t *indices, const RtxObject *objects, uint64_t n, uint32_t mode,
+                          uint64_t *stats, uint32_t *how, uint64_t *digests, double *info)
+{
+    if (!scene || !stats || !how || !digests) return fail(RTX_ERR_INVALID_ARGUMENT, std::string(who) + ": null argument");
+    if (scene->n_objects && !scene->objects) return fail(RTX_ERR_INVALID_ARGUMENT, std::string(who) + ": objects is null");
     *how = RTX_UPDATED_NOTHING;
     const uint64_t split = mode >> 16;                       // (lab) entries [0, split) are one update, [split, n) the next
     mode &= 0xFFFFu;
-    if (split > n) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_host_refit: the split point is beyond n");
+    if (split > n) return fail(RTX_ERR_INVALID_ARGUMENT, std::string(who) + ": the split point is beyond n");
     std::vector<RtxObject> cur(scene->objects, scene->objects + scene->n_objects);
     RtxScene sc = *scene;
     PackedScene p;
@@ -2213,10 +2381,11 @@ int32_t rtx_debug_host_refit(const RtxScene *scene, const uint64_t *indices, con
         if (int32_t rc = plan_update(cur, t, p.sv.sphere_cmax, indices ? indices + first : nullptr, objects ? objects + first : nullptr, count, mode, plan))
             return rc;
         if (plan.how == RTX_UPDATED_REFIT || plan.how == RTX_UPDATED_RECORDS) {
-            std::vector<float> box32;
-            std::vector<double> reach;
+            std::vector<float> box32, tribox32;
+            std::vector<double> reach, tri_reach;
             derive_all_spheres(p, cur.data(), t, box32, reach);
-            if (refit_packed(p, t, plan, box32, reach) & kUpdateStatusNoQ3) plan.how = RTX_UPDATED_REBUILT;
+            if (plan.tri_geom) derive_all_triangles(cur.data(), cur.size(), t, tribox32, tri_reach);
+            if (refit_packed(p, t, plan, box32, reach, tribox32, tri_reach) & (kUpdateStatusNoQ3 | kUpdateStatusNoQ)) plan.how = RTX_UPDATED_REBUILT;
         }
         for (const UpdateEntry &e : plan.entries) std::memcpy(&cur[e.object], &e.kind, sizeof(RtxObject));
         if (plan.how == RTX_UPDATED_REBUILT) {
@@ -2227,22 +2396,20 @@ int32_t rtx_debug_host_refit(const RtxScene *scene, const uint64_t *indices, con
         }
         if (plan.how > *how) *how = plan.how;
     }
-    digest_packed(p, digests);
+    if (info) {
+        digest_packed_mesh(p, digests);
+        for (int c = 0; c < 3; ++c) info[c] = t.centre[c];
+        info[3] = p.sv.tri_extent; info[4] = p.sv.sphere_cmax; info[5] = t.abs_pad; info[6] = t.scale; info[7] = 0.0;
+    } else digest_packed(p, digests);
     return check_packed(p, cur.data(), stats);
-#else
-    (void)scene; (void)indices; (void)objects; (void)n; (void)mode; (void)stats; (void)how; (void)digests;
-    return fail(RTX_ERR_UNSUPPORTED, "rtx_debug_host_refit is a hook of the lab library (librtx_hip_lab.so)");
-#endif
 }
 
-int32_t rtx_debug_resident_digests(RtxSceneHandle h, uint64_t *digests)
+// The resident arrays, downloaded into the shape digest_packed / digest_packed_mesh read.
+static int32_t fetch_resident(RtxSceneHandle_ *h, bool mesh, PackedScene &p)
 {
-#ifdef RTX_LAB
-    if (!h || !digests) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_resident_digests: null argument");
     RTX_HIP_CHECK(hipSetDevice(h->device));
     RTX_HIP_CHECK(hipDeviceSynchronize());
     const SceneView &sv = h->sv;
-    PackedScene p;                                            // the resident arrays, downloaded into the shape digest_packed reads
     auto fetch = [](auto &vec, const void *src, size_t count) -> hipError_t {
         vec.resize(count);
         return count && src ? hipMemcpy(vec.data(), src, count * sizeof(vec[0]), hipMemcpyDeviceToHost) : hipSuccess;
@@ -2257,11 +2424,64 @@ int32_t rtx_debug_resident_digests(RtxSceneHandle h, uint64_t *digests)
     RTX_HIP_CHECK(fetch(p.planes, sv.planes, sv.n_planes));
     RTX_HIP_CHECK(fetch(p.mats, sv.materials, sv.n_objects));
     p.sv.sphere_cmax = sv.sphere_cmax;
+    if (!mesh) return RTX_OK;
+    RTX_HIP_CHECK(fetch(p.tris, sv.tris, sv.n_tris));
+    RTX_HIP_CHECK(fetch(p.tri32, sv.tri_f32, sv.n_tri_filter ? 2 * ((size_t)sv.n_tri_filter + 1) : 0));      // (+ the pad record)
+    RTX_HIP_CHECK(fetch(p.tri_geo, sv.tri_geo, 2 * (size_t)sv.n_tri_tree));
+    RTX_HIP_CHECK(fetch(p.qnodes, sv.bvh_qnodes, sv.bvh_qnodes ? sv.n_bvh_nodes : 0));
+    p.sv.tri_extent = sv.tri_extent;
+    return RTX_OK;
+}
+#endif
+
+int32_t rtx_debug_host_refit(const RtxScene *scene, const uint64_t *indices, const RtxObject *objects, uint64_t n, uint32_t mode,
+                             uint64_t *stats, uint32_t *how, uint64_t *digests)
+{
+#ifdef RTX_LAB
+    return host_refit("rtx_debug_host_refit", scene, indices, objects, n, mode, stats, how, digests, nullptr);
+#else
+    (void)scene; (void)indices; (void)objects; (void)n; (void)mode; (void)stats; (void)how; (void)digests;
+    return fail(RTX_ERR_UNSUPPORTED, "rtx_debug_host_refit is a hook of the lab library (librtx_hip_lab.so)");
+#endif
+}
+
+int32_t rtx_debug_host_refit_mesh(const RtxScene *scene, const uint64_t *indices, const RtxObject *objects, uint64_t n, uint32_t mode,
+                                  uint64_t *stats, uint32_t *how, uint64_t *digests, double *info)
+{
+#ifdef RTX_LAB
+    if (!info) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_host_refit_mesh: null argument");
+    return host_refit("rtx_debug_host_refit_mesh", scene, indices, objects, n, mode, stats, how, digests, info);
+#else
+    (void)scene; (void)indices; (void)objects; (void)n; (void)mode; (void)stats; (void)how; (void)digests; (void)info;
+    return fail(RTX_ERR_UNSUPPORTED, "rtx_debug_host_refit_mesh is a hook of the lab library (librtx_hip_lab.so)");
+#endif
+}
+
+int32_t rtx_debug_resident_digests(RtxSceneHandle h, uint64_t *digests)
+{
+#ifdef RTX_LAB
+    if (!h || !digests) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_resident_digests: null argument");
+    PackedScene p;
+    if (int32_t rc = fetch_resident(h, false, p)) return rc;
     digest_packed(p, digests);
     return RTX_OK;
 #else
     (void)h; (void)digests;
     return fail(RTX_ERR_UNSUPPORTED, "rtx_debug_resident_digests is a hook of the lab library (librtx_hip_lab.so)");
+#endif
+}
+
+int32_t rtx_debug_resident_mesh_digests(RtxSceneHandle h, uint64_t *digests)
+{
+#ifdef RTX_LAB
+    if (!h || !digests) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_resident_mesh_digests: null argument");
+    PackedScene p;
+    if (int32_t rc = fetch_resident(h, true, p)) return rc;
+    digest_packed_mesh(p, digests);
+    return RTX_OK;
+#else
+    (void)h; (void)digests;
+    return fail(RTX_ERR_UNSUPPORTED, "rtx_debug_resident_mesh_digests is a hook of the lab library (librtx_hip_lab.so)");
 #endif
 }
 

@@ -17,17 +17,23 @@ namespace rtx {
 struct UpdateEntry {
     uint32_t object;                       // index in Scene.objects
     uint32_t local;                        // index in spheres[] / planes[] / tris[]
-    uint32_t slot;                         // sphere in the tree: its leaf entry (the inverse of bvh_prims), else kNoSlot
-    uint32_t pad_;
+    uint32_t slot;                         // sphere in the tree: its leaf entry (the inverse of bvh_prims), else kNoSlot;
+                                           // triangle with new geometry: its record in tri_f32 (the inverse of tri_fidx), else kNoSlot
+    uint32_t tri;                          // triangle: kTriEntry* bits (0: its geometry is the resident one)
     uint32_t kind, reserved;               // RtxObject, field by field (the C struct is not visible to every includer)
     double geom[9];
     double base_color[3], emission_color[3], roughness;
 };
 static_assert(sizeof(UpdateEntry) == 16 + 136, "UpdateEntry = 4 words + RtxObject");
 constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
+// UpdateEntry.tri: the geometry changed (RTX_UPDATE_DEFORM); the class is "qualified"; the record is a tree record (it has tri_geo and
+// tribox32 rows); the free axis of a qualified triangle in bits 4..5.  The host decides all of it (plan_update).
+constexpr uint32_t kTriEntryGeom = 1u, kTriEntryQualified = 2u, kTriEntryTree = 4u, kTriEntryAxisShift = 4u;
 
 // What one launch of scene_update_kernel works on.  `mode` is launch-uniform:
-//   0 (A) records: one thread per entry;  1 (B) one level of wide nodes: one thread per node of `level`;  2 (C) sphere_cmax.
+//   0 (A) records: one thread per entry;  1 (B) one level of wide nodes: one thread per node of `level`;  2 (C) sphere_cmax;
+//   3 (D) tri_extent.  The triangle arrays are null in a launch of an update that moves no triangle: mode B then leaves triangle
+//   leaves and footprint nodes as they are.
 struct UpdateArgs {
     uint32_t mode, n;
     const UpdateEntry *entries;
@@ -38,12 +44,17 @@ struct UpdateArgs {
     double *reach;                         // per sphere: |c - centre| + |r|
     Bvh4Node *nodes; BvhQ3Node *q3nodes;   // q3nodes: null when the tree has no 64-byte form
     const uint32_t *prims;
-    const uint32_t *level;                 // mode B: the node indices of this level
-    unsigned long long *status;            // [0]: bit 0 = a 64-byte node could not be encoded;  [1]: the bits of the new sphere_cmax
+    const uint32_t *level;                 // mode B: the node indices of this level (kBvhFlatNode set: a footprint node)
+    unsigned long long *status;            // [0]: kUpdateStatus* bits;  [1]: the bits of the new sphere_cmax;  [2]: of the new tri_extent
+    TriX *tris;                            // the triangle half (null: no triangle moves)
+    float4 *tri_f32, *tri_geo;
+    float *tribox32;                       // per tree record: lo.xyz, hi.xyz of its padded f32 footprint (-inf / +inf along its free axis)
+    double *tri_reach;                     // per triangle: max |v - centre| over its nine coordinates (0: not qualified)
+    BvhQNode *qnodes;                      // null when the tree has no 64-byte footprint form
     double centre[3];
     double abs_pad;
 };
-constexpr unsigned long long kUpdateStatusNoQ3 = 1ull;
+constexpr unsigned long long kUpdateStatusNoQ3 = 1ull, kUpdateStatusNoQ = 2ull;     // a BvhQ3Node / a BvhQNode has no encoding
 
 RTX_HD uint32_t refit_f32_bits(float f) { union { float f; uint32_t u; } v; v.f = f; return v.u; }
 RTX_HD float refit_bits_f32(uint32_t u) { union { float f; uint32_t u; } v; v.u = u; return v.f; }
@@ -102,6 +113,62 @@ RTX_HD SphereDerived derive_sphere(const double g[4], const double centre[3], do
     return d;
 }
 
+// Everything of one triangle that is derived from its vertices, the scene's `centre` and the tree's abs_pad: pack_scene's expressions
+// in pack_scene's order (min / max as comparisons: the values of fmin / fmax for finite operands, and one answer for -0 against +0
+// on host and device).  `qualified` and `f` (the free axis) are the host's classification (classify_triangle, rtx_api.hip); a
+// triangle that is not qualified has the "always a candidate" record and no footprint.
+struct TriDerived {
+    TriX exact;
+    float4 A, B, g0, g1;                   // tri_f32[2 rec], [2 rec + 1]; tri_geo[2 rec], [2 rec + 1]
+    double reach;
+    float box[6];                          // triangle_footprint() widened by abs_pad, rounded outward (bvh_append_tree's leaf box)
+};
+
+RTX_HD double refit_min3(double x0, double x1, double x2) { const double m = x2 < x1 ? x2 : x1; return m < x0 ? m : x0; }
+RTX_HD double refit_max3(double x0, double x1, double x2) { const double m = x2 > x1 ? x2 : x1; return m > x0 ? m : x0; }
+
+RTX_HD TriDerived derive_triangle(const double g[9], uint32_t object, bool qualified, int f, const double centre[3], double abs_pad)
+{
+    TriDerived d;
+    d.exact = make_triangle(g, object);
+    d.A = make_float4(0.f, 0.f, 0.f, 0.f); d.B = make_float4(0.f, 0.f, 0.f, 0.f);
+    d.g0 = make_float4(0.f, 0.f, 0.f, 0.f); d.g1 = make_float4(0.f, 0.f, 0.f, 0.f);
+    d.reach = 0.0;
+    for (int a = 0; a < 3; ++a) { d.box[a] = -INFINITY; d.box[3 + a] = INFINITY; }
+    if (!qualified) return d;
+    const TriX &t = d.exact;
+    const double kabs = dot(t.n, t.v0);
+    double v[3][3];
+    for (int c = 0; c < 9; ++c) v[c / 3][c % 3] = g[c] - centre[c % 3];
+    const int a0 = f == 0 ? 1 : 0, a1 = f == 2 ? 1 : 2;
+    const double r0 = v[1][a0] - v[0][a0], r1 = v[1][a1] - v[0][a1], s0 = v[2][a0] - v[0][a0], s1 = v[2][a1] - v[0][a1];
+    const double det = r0 * s1 - r1 * s0;
+    const double m00 = s1 / det, m01 = -s0 / det, m10 = -r1 / det, m11 = r0 / det;
+    const double kc = t.n.x * v[0][0] + t.n.y * v[0][1] + t.n.z * v[0][2];
+    d.g0 = make_float4((float)v[0][a0], (float)v[0][a1], (float)m00, (float)m01);
+    d.g1 = make_float4((float)m10, (float)m11, (float)kabs, (float)(2 - f));
+    d.A = make_float4((float)t.n.x, (float)t.n.y, (float)t.n.z, (float)kc);
+    d.B = make_float4(0.f, 0.f, 1.0e30f, 1.0e30f);
+    for (int c = 0; c < 9; ++c) { const double m = fabs(v[c / 3][c % 3]); d.reach = m > d.reach ? m : d.reach; }
+    if (f == 2) {
+        const double xlo = refit_min3(v[0][0], v[1][0], v[2][0]), xhi = refit_max3(v[0][0], v[1][0], v[2][0]);
+        const double ylo = refit_min3(v[0][1], v[1][1], v[2][1]), yhi = refit_max3(v[0][1], v[1][1], v[2][1]);
+        const double grow = 1.0 + 1.0 / 1048576.0;
+        d.B = make_float4((float)(0.5 * (xlo + xhi)), (float)(0.5 * (ylo + yhi)),
+                          refit_round_up_f32(0.5 * (xhi - xlo) * grow + 1e-30), refit_round_up_f32(0.5 * (yhi - ylo) * grow + 1e-30));
+    }
+    for (int a = 0; a < 3; ++a) {          // triangle_footprint (rtx_bvh.h), then bvh_append_tree's padding and rounding
+        if (a == f) continue;
+        const double lo = refit_min3(g[a], g[3 + a], g[6 + a]), hi = refit_max3(g[a], g[3 + a], g[6 + a]);
+        const double al = fabs(lo), ah = fabs(hi);
+        const double pad = (al > ah ? al : ah) * (1.0 / 1048576.0) + 1e-300;
+        const double blo = lo - pad, bhi = hi + pad;
+        d.box[a] = refit_round_down_f32(blo - abs_pad);
+        d.box[3 + a] = refit_round_up_f32(bhi + abs_pad);
+    }
+    return d;
+}
+
 // ---- mode A ---------------------------------------------------------------------------------------------------------------------
 RTX_HD void update_record(const UpdateArgs &u, uint32_t i)
 {
@@ -112,6 +179,20 @@ RTX_HD void update_record(const UpdateArgs &u, uint32_t i)
     m.roughness = e.roughness;
     u.materials[e.object] = m;
     if (e.kind == 1u) { u.planes[e.local] = make_plane(e.geom, e.object); return; }
+    if (e.kind == 2u && (e.tri & kTriEntryGeom)) {                   // a triangle that keeps its class and gets new vertices (DEFORM)
+        const uint32_t k = e.local;
+        const TriDerived d = derive_triangle(e.geom, e.object, (e.tri & kTriEntryQualified) != 0u, (int)((e.tri >> kTriEntryAxisShift) & 3u),
+                                             u.centre, u.abs_pad);
+        u.tris[k] = d.exact;
+        u.tri_reach[k] = d.reach;
+        if (e.slot == kNoSlot) return;                               // class "none": no filter record
+        u.tri_f32[2 * (size_t)e.slot] = d.A; u.tri_f32[2 * (size_t)e.slot + 1] = d.B;
+        if (!(e.tri & kTriEntryTree)) return;
+        u.tri_geo[2 * (size_t)e.slot] = d.g0; u.tri_geo[2 * (size_t)e.slot + 1] = d.g1;
+        float *b = u.tribox32 + (size_t)e.slot * 6;
+        for (int a = 0; a < 6; ++a) b[a] = d.box[a];
+        return;
+    }
     if (e.kind != 0u) return;                                        // a triangle: its geometry did not change (the host checked)
     const uint32_t k = e.local;
     const SphereDerived d = derive_sphere(e.geom, u.centre, u.abs_pad);
@@ -199,18 +280,119 @@ RTX_HD bool q3_encode(const Bvh4Node &w, double abs_pad, BvhQ3Node &q)
     return true;
 }
 
+// The 64-byte form of one footprint node from its (refitted) 128-byte form, under build_qnodes' invariants: o = the smallest lo of
+// the non-empty children (an f32 value: exact), s = the smallest power of two with ext / s <= 65535 -- which is build_qnodes' step,
+// found on the exponent field -- a normal f32 and <= 1e30; lo floored (>= 0), hi ceiled (<= 65535); an empty child reads
+// 0x0000FFFF; the link words as they were.  False: no such encoding.
+RTX_HD bool qnode_encode(const Bvh4Node &w, BvhQNode &q)
+{
+    const uint32_t ct[4] = { refit_f32_bits(w.b[1].x), refit_f32_bits(w.b[1].y), refit_f32_bits(w.b[1].z), refit_f32_bits(w.b[1].w) };
+    double lo[2] = { (double)INFINITY, (double)INFINITY }, hi[2] = { -(double)INFINITY, -(double)INFINITY };
+    bool any = false;
+    for (int c = 0; c < 4; ++c) {
+        if (ct[c] == 0xFFFFFFFFu) continue;
+        const float r[4] = { w.a[c].x, w.a[c].y, w.a[c].z, w.a[c].w };
+        for (int k = 0; k < 4; ++k) if ((refit_f32_bits(r[k]) & 0x7F800000u) == 0x7F800000u) return false;       // not finite
+        any = true;
+        for (int a = 0; a < 2; ++a) {
+            const double l = (double)r[a], h = (double)r[2 + a];
+            lo[a] = l < lo[a] ? l : lo[a];
+            hi[a] = h > hi[a] ? h : hi[a];
+        }
+    }
+    double o[2], sc[2];
+    for (int a = 0; a < 2; ++a) {
+        o[a] = any ? lo[a] : 0.0;
+        sc[a] = 1.0;
+        const double ext = any ? hi[a] - lo[a] : 0.0;
+        if (ext > 0.0) {
+            // ext = m * 2^e, 1 <= m < 2: ext / 2^(e - 15) = 32768 m in [32768, 65536); one more doubling when that is above 65535
+            const int e = (int)((refit_f64_bits(ext) >> 52) & 0x7FFu) - 1023;
+            if (e < -900) return false;
+            int k = e - 15;
+            if (ext / refit_pow2(k) > 65535.0) k += 1;
+            if (k < -126 || k > 99) return false;                                         // the step must stay a normal f32 (and <= 1e30)
+            sc[a] = refit_pow2(k);
+        }
+    }
+    BvhQNode r = q;                                                                       // (the links)
+    r.ox = (float)o[0]; r.oy = (float)o[1]; r.sx = (float)sc[0]; r.sy = (float)sc[1];
+    for (int c = 0; c < 4; ++c) {
+        if (ct[c] == 0xFFFFFFFFu) { r.qx[c] = 0x0000FFFFu; r.qy[c] = 0x0000FFFFu; continue; }
+        const double l0 = floor(((double)w.a[c].x - o[0]) / sc[0]), h0 = ceil(((double)w.a[c].z - o[0]) / sc[0]);
+        const double l1 = floor(((double)w.a[c].y - o[1]) / sc[1]), h1 = ceil(((double)w.a[c].w - o[1]) / sc[1]);
+        if (!(l0 >= 0.0 && l1 >= 0.0 && h0 <= 65535.0 && h1 <= 65535.0)) return false;
+        r.qx[c] = (uint32_t)l0 | ((uint32_t)h0 << 16);
+        r.qy[c] = (uint32_t)l1 | ((uint32_t)h1 << 16);
+    }
+    q = r;
+    return true;
+}
+
+// One footprint node (the flat layout: a[c] = {lo.x, lo.y, hi.x, hi.y}, the links in b[0], the counts in b[1]): the rectangle of a
+// triangle leaf is the min / max of tribox32 over its records, that of an interior child -- a footprint node too, refitted by the
+// previous launch -- the min / max of its four rectangles (an empty slot's {inf, inf, -inf, -inf} never wins).  This is the builder's
+// rectangle for the same topology: the builder rounds the union of the padded f64 footprints, x -> round_down_f32(x - abs_pad) is
+// monotone (round_up likewise), so the rounded union is the union of the rounded rectangles, at every level.  Empty slots, links and
+// counts are not touched.  False when the node's 64-byte form (u.qnodes != null) cannot be encoded.
+RTX_HD bool refit_flat_node(const UpdateArgs &u, uint32_t idx)
+{
+    Bvh4Node &w = u.nodes[idx];
+    const uint32_t lk[4] = { refit_f32_bits(w.b[0].x), refit_f32_bits(w.b[0].y), refit_f32_bits(w.b[0].z), refit_f32_bits(w.b[0].w) };
+    const uint32_t ct[4] = { refit_f32_bits(w.b[1].x), refit_f32_bits(w.b[1].y), refit_f32_bits(w.b[1].z), refit_f32_bits(w.b[1].w) };
+    for (int c = 0; c < 4; ++c) {
+        if (ct[c] == 0xFFFFFFFFu) continue;
+        float lo[2] = { INFINITY, INFINITY }, hi[2] = { -INFINITY, -INFINITY };
+        if (ct[c] == 0u) {
+            const Bvh4Node &ch = u.nodes[lk[c] & ~kBvhFlatNode];
+            for (int k = 0; k < 4; ++k) {
+                const float l[2] = { ch.a[k].x, ch.a[k].y }, h[2] = { ch.a[k].z, ch.a[k].w };
+                for (int a = 0; a < 2; ++a) { lo[a] = l[a] < lo[a] ? l[a] : lo[a]; hi[a] = h[a] > hi[a] ? h[a] : hi[a]; }
+            }
+        } else {
+            const uint32_t n = ct[c] & 0xFFFFu;
+            for (uint32_t k = 0; k < n; ++k) {
+                const float *b = u.tribox32 + (size_t)(lk[c] + k) * 6;
+                for (int a = 0; a < 2; ++a) { lo[a] = b[a] < lo[a] ? b[a] : lo[a]; hi[a] = b[3 + a] > hi[a] ? b[3 + a] : hi[a]; }
+            }
+        }
+        w.a[c] = make_float4(lo[0], lo[1], hi[0], hi[1]);
+    }
+    if (!u.qnodes) return true;
+    BvhQNode q = u.qnodes[idx];
+    if (!qnode_encode(w, q)) return false;
+    u.qnodes[idx] = q;
+    return true;
+}
+
 // One non-flat wide node: the boxes of its sphere leaves from box32, of its non-flat interior children from those children's four
-// boxes (refitted by the previous launch: the levels run deepest first); triangle leaves, footprint children and empty slots stay.
+// boxes (refitted by the previous launch: the levels run deepest first).  When triangles move (u.tribox32 != null) a triangle leaf
+// gets the min / max of tribox32 over its records -- unbounded along their free axis -- and a footprint child the (x, y) union of that
+// node's four rectangles, unbounded in z; otherwise triangle leaves and footprint children stay.  Empty slots stay.
 // Link and count words are not touched.  (min / max as comparisons: one answer for -0 against +0 on host and device.)  Returns false when the node's 64-byte form (u.q3nodes != null) cannot be encoded.
 RTX_HD bool refit_node(const UpdateArgs &u, uint32_t idx)
 {
     Bvh4Node &w = u.nodes[idx];
     for (int c = 0; c < 4; ++c) {
         const uint32_t link = refit_f32_bits(w.a[c].w), count = refit_f32_bits(w.b[c].w);
-        if (count == 0xFFFFFFFFu || (count & kBvhTriLeaf)) continue;
+        if (count == 0xFFFFFFFFu) continue;
         float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
-        if (count == 0u) {
-            if (link & kBvhFlatNode) continue;
+        if (count & kBvhTriLeaf) {
+            if (!u.tribox32) continue;
+            const uint32_t n = count & 0xFFFFu;
+            for (uint32_t k = 0; k < n; ++k) {
+                const float *b = u.tribox32 + (size_t)(link + k) * 6;
+                for (int a = 0; a < 3; ++a) { lo[a] = b[a] < lo[a] ? b[a] : lo[a]; hi[a] = b[3 + a] > hi[a] ? b[3 + a] : hi[a]; }
+            }
+        } else if (count == 0u && (link & kBvhFlatNode)) {
+            if (!u.tribox32) continue;
+            const Bvh4Node &ch = u.nodes[link & ~kBvhFlatNode];
+            for (int k = 0; k < 4; ++k) {
+                const float l[2] = { ch.a[k].x, ch.a[k].y }, h[2] = { ch.a[k].z, ch.a[k].w };
+                for (int a = 0; a < 2; ++a) { lo[a] = l[a] < lo[a] ? l[a] : lo[a]; hi[a] = h[a] > hi[a] ? h[a] : hi[a]; }
+            }
+            lo[2] = -INFINITY; hi[2] = INFINITY;
+        } else if (count == 0u) {
             const Bvh4Node &ch = u.nodes[link];
             for (int k = 0; k < 4; ++k) {
                 const float l[3] = { ch.a[k].x, ch.a[k].y, ch.a[k].z }, h[3] = { ch.b[k].x, ch.b[k].y, ch.b[k].z };
@@ -231,6 +413,13 @@ RTX_HD bool refit_node(const UpdateArgs &u, uint32_t idx)
     if (!q3_encode(w, u.abs_pad, q)) return false;
     u.q3nodes[idx] = q;
     return true;
+}
+
+// One entry of a level list: the status bits its node raises.
+RTX_HD unsigned long long refit_level_entry(const UpdateArgs &u, uint32_t entry)
+{
+    if (entry & kBvhFlatNode) return refit_flat_node(u, entry & ~kBvhFlatNode) ? 0ull : kUpdateStatusNoQ;
+    return refit_node(u, entry) ? 0ull : kUpdateStatusNoQ3;
 }
 
 }  // namespace rtx

@@ -14,22 +14,23 @@ __global__ __launch_bounds__(256) void scene_update_kernel(UpdateArgs u)
         return;
     }
     if (u.mode == 1u) {                                   // B: one wide node of this level
-        if (i < u.n && !refit_node(u, u.level[i])) atomicOr(u.status, kUpdateStatusNoQ3);
+        if (i < u.n) { const unsigned long long bad = refit_level_entry(u, u.level[i]); if (bad) atomicOr(u.status, bad); }
         return;
     }
-    // C: sphere_cmax = max of reach.  Grid-stride, then the 64-lane wave, then one atomicMax per wave on the bit pattern
+    // C: sphere_cmax = max of reach;  D: tri_extent = max of tri_reach.  Grid-stride, then the 64-lane wave, then one atomicMax per wave on the bit pattern
     // (non-negative doubles order like their bits; a launch of mode C only runs when every reach is finite).
+    const double *src = u.mode == 2u ? u.reach : u.tri_reach;
     double m = 0.0;
-    for (uint64_t k = i; k < u.n; k += (uint64_t)gridDim.x * blockDim.x) { const double r = u.reach[k]; m = r > m ? r : m; }
+    for (uint64_t k = i; k < u.n; k += (uint64_t)gridDim.x * blockDim.x) { const double r = src[k]; m = r > m ? r : m; }
     for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_down(m, off, 64); m = o > m ? o : m; }
-    if ((threadIdx.x & 63u) == 0u) atomicMax(u.status + 1, (unsigned long long)__double_as_longlong(m));
+    if ((threadIdx.x & 63u) == 0u) atomicMax(u.status + (u.mode == 2u ? 1 : 2), (unsigned long long)__double_as_longlong(m));
 }
 
 hipError_t launch_scene_update(const UpdateArgs &u, hipStream_t stream)
 {
     if (u.n == 0) return hipSuccess;
     uint32_t blocks = (uint32_t)(((uint64_t)u.n + 255u) / 256u);
-    if (u.mode == 2u && blocks > 1024u) blocks = 1024u;
+    if (u.mode >= 2u && blocks > 1024u) blocks = 1024u;
     hipLaunchKernelGGL(scene_update_kernel, dim3(blocks), dim3(256), 0, stream, u);
     return hipGetLastError();
 }

@@ -18,9 +18,19 @@ only way there was before it, rtx_scene_free + rtx_scene_upload of the modified 
            without the form) and after RTX_UPDATE_REBUILD of the first list (the form is back) -- what a few co-located tiny
            spheres cost every later frame
 
-    tools/update_rate.py [--scenes C2,M1] [--legs update,frames,q3loss] [--reps 3] [--spp 4]
+  mesh     triangles that move under RTX_UPDATE_DEFORM (include/rtx_hip.h, "Triangles"): C3 (scenes.random_triangles(100000)) and T1M
+           (random_triangles(1000000)); every named triangle is translated as a whole and clipped into the vertices' box, and only
+           triangles that keep their class are named (a translation keeps the elimination's rows and the projection; n.v0 is checked):
+             deform    one triangle, 1 %, all of them under RTX_UPDATE_DEFORM (RTX_UPDATED_REFIT)
+             auto      the same entries under RTX_UPDATE_AUTO: the rebuild every triangle move was before the mode existed
+             reupload  close() + Scene.upload() of the modified list
+           and C3 at 1920x1080, --spp samples, every triangle translated by 0.1, 0.5 and 2 triangle sizes (the median edge): the
+           frame's device time after the refit and after a fresh upload of the same geometry, alternating
 
-The package is the one of the tree the tool lies in; in a checkout of the parent commit (copy the tool there) only the reupload leg runs.
+    tools/update_rate.py [--scenes C2,M1] [--legs update,frames,q3loss,mesh] [--reps 3] [--spp 4]
+
+The package is the one of the tree the tool lies in; in a checkout of the parent commit (copy the tool there) only the reupload leg runs
+(of the mesh leg: its auto and reupload forms).
 One JSON line per measurement: the best of --reps timed runs after one warm-up, with the slowest run and the spread between them.
 """
 import argparse
@@ -51,6 +61,112 @@ def moved(objs, idx, rng, step=None):
         d /= np.linalg.norm(d, axis=1)[:, None]
         new["geom"][:, :3] = np.clip(new["geom"][:, :3] + step * d, lo, hi)
     return new
+
+
+def tri_cull_side(g):
+    """n.v0 < -(1 + 1e-9) per triangle (9 doubles each), with make_triangle's operations: such a triangle has no filter record"""
+    v0, r, s = g[:, 0:3], g[:, 3:6] - g[:, 0:3], g[:, 6:9] - g[:, 0:3]
+    n = np.stack([r[:, 1] * s[:, 2] - r[:, 2] * s[:, 1], r[:, 2] * s[:, 0] - r[:, 0] * s[:, 2], r[:, 0] * s[:, 1] - r[:, 1] * s[:, 0]], axis=1)
+    with np.errstate(all="ignore"):
+        n = n / np.sqrt(n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1] + n[:, 2] * n[:, 2])[:, None]
+        return (n[:, 0] * v0[:, 0] + n[:, 1] * v0[:, 1] + n[:, 2] * v0[:, 2]) < -(1.0 + 1e-9)
+
+
+def translated(objs, idx, rng, step):
+    """objs[idx], each triangle moved as a whole by `step` in a random direction, the move cut so that it stays inside the box of all
+    vertices shrunk by 1 % (no footprint can then leave the range the tree was built for) -> (the entries, mask: the class is kept)"""
+    v = objs["geom"].reshape(-1, 3, 3)
+    lo, hi = v.min(axis=(0, 1)), v.max(axis=(0, 1))
+    lo, hi = lo + 0.01 * (hi - lo), hi - 0.01 * (hi - lo)
+    new = objs[idx].copy()
+    w = new["geom"].reshape(len(idx), 3, 3)
+    d = rng.normal(size=(len(idx), 3))
+    d *= step / np.linalg.norm(d, axis=1)[:, None]
+    room_lo, room_hi = np.minimum(lo - w.min(axis=1), 0.0), np.maximum(hi - w.max(axis=1), 0.0)
+    d = np.clip(d, room_lo, room_hi)
+    new["geom"] = (w + d[:, None, :]).reshape(len(idx), 9)
+    return new, tri_cull_side(new["geom"]) == tri_cull_side(objs["geom"][idx])
+
+
+def mesh_legs(rtx, scenes, cam, args, emit_):
+    import torch
+    has_deform = hasattr(rtx.abi, "RTX_UPDATE_DEFORM")           # (a checkout of the parent commit: the auto and reupload forms alone)
+    for name, n in (("C3", 100000), ("T1M", 1000000)):
+        objs = scenes.random_triangles(n)
+        cfg = rtx.Config(rays_per_pixel=args.spp, seed=scenes.RENDER_SEED)
+        e = objs["geom"].reshape(-1, 3, 3)
+        size = float(np.median(np.linalg.norm(e - np.roll(e, 1, axis=1), axis=2)))
+        hnd = rtx.Scene.from_packed(cfg, cam, objs).upload(0)
+        for share, count in (("1", 1), ("1%", n // 100), ("100%", n)):
+            rng = np.random.default_rng(7)
+            cand = np.sort(rng.permutation(n)[:count])
+            new, keep = translated(objs, cand, rng, 0.5 * size)
+            idx, new = cand[keep].astype(np.uint64), new[keep]
+            if len(idx) == 0:                                    # (the one triangle drawn changes its class: take the next that does not)
+                new, keep = translated(objs, np.arange(n), rng, 0.5 * size)
+                idx, new = np.arange(n)[keep][:1].astype(np.uint64), new[keep][:1]
+            back = objs[idx.astype(np.int64)].copy()
+            state = {"k": 0}
+
+            def there_or_back():                                 # alternate, so that every timed call really moves the triangles
+                state["k"] += 1
+                return new if state["k"] % 2 else back
+
+            for form, mode, want in ((("deform", "deform", "refit"),) if has_deform else ()) + (("auto", "auto", "rebuilt"),):
+                how = []
+                best, worst = timed(lambda a, _m=mode: how.append(hnd.update_objects(idx, a, mode=_m)), args.reps, there_or_back)
+                emit_(scene=name, leg="mesh", form=form, triangles=n, updated=len(idx), share=share, how=sorted(set(how)), expected=want,
+                      ms=round(best, 4), worst_ms=round(worst, 4), spread=round(worst / best - 1.0, 3), reps=args.reps)
+            box = {"hnd": hnd}
+
+            def reupload(a):
+                mod = objs.copy()
+                mod[idx.astype(np.int64)] = a
+                box["hnd"].close()
+                box["hnd"] = rtx.Scene.from_packed(cfg, cam, mod).upload(0)
+
+            best, worst = timed(reupload, args.reps, there_or_back)
+            hnd = box["hnd"]
+            hnd.close()
+            hnd = rtx.Scene.from_packed(cfg, cam, objs).upload(0)
+            emit_(scene=name, leg="mesh", form="reupload", triangles=n, updated=len(idx), share=share, ms=round(best, 4), worst_ms=round(worst, 4),
+                  spread=round(worst / best - 1.0, 3), reps=args.reps)
+        hnd.close()
+        if name != "C3" or not has_deform:
+            continue
+        w, h = 1920, 1080
+        buf = torch.zeros((h, w, 3), dtype=torch.float64, device="cuda:0")
+
+        def frame_ms(handle):
+            out = []
+            for k in range(args.reps + 1):
+                st = handle.render_rows(w, h, 0, 1, h, buf.data_ptr())
+                out.append(st.trace_ms + st.resolve_ms)
+            return min(out[1:]), max(out[1:])
+
+        base = rtx.Scene.from_packed(cfg, cam, objs).upload(0)
+        b, wst = frame_ms(base)
+        emit_(scene=name, leg="mesh-frames", form="as uploaded", step=0, spp=args.spp, ms=round(b, 4), worst_ms=round(wst, 4), spread=round(wst / b - 1.0, 3))
+        base.close()
+        for sizes in (0.1, 0.5, 2.0):
+            new, keep = translated(objs, np.arange(n), np.random.default_rng(11), sizes * size)
+            idx, new = np.arange(n)[keep].astype(np.uint64), new[keep]
+            mod = objs.copy()
+            mod[idx.astype(np.int64)] = new
+            refit = rtx.Scene.from_packed(cfg, cam, objs).upload(0)
+            how = refit.update_objects(idx, new, mode="deform")
+            fresh = rtx.Scene.from_packed(cfg, cam, mod).upload(0)
+            for run in (1, 2):                                   # alternating
+                for form, handle in (("after " + how, refit), ("fresh upload", fresh)):
+                    b, wst = frame_ms(handle)
+                    emit_(scene=name, leg="mesh-frames", form=form, run=run, step_in_triangle_sizes=sizes, updated=len(idx), spp=args.spp,
+                          ms=round(b, 4), worst_ms=round(wst, 4), spread=round(wst / b - 1.0, 3))
+            refit.render_rows(w, h, 0, 1, h, buf.data_ptr())
+            img = buf.cpu().numpy().copy()
+            fresh.render_rows(w, h, 0, 1, h, buf.data_ptr())
+            emit_(scene=name, leg="mesh-frames", form="same bits", step_in_triangle_sizes=sizes, equal=bool(np.array_equal(img, buf.cpu().numpy())))
+            refit.close()
+            fresh.close()
 
 
 def timed(fn, reps, setup=None):
@@ -86,6 +202,11 @@ def main():
     cam = rtx.Camera(*scenes.CAMERA)
     has_update = hasattr(rtx.SceneHandle, "update_objects")          # (a checkout of the parent commit: the reupload leg alone)
     legs = args.legs.split(",")
+    if "mesh" in legs:
+        mesh_legs(rtx, scenes, cam, args, emit)
+        legs = [k for k in legs if k != "mesh"]
+        if not legs:
+            return
     for name in args.scenes.split(","):
         objs = scenes.random_spheres(SCENES[name], 1)
         cfg = rtx.Config(rays_per_pixel=args.spp, seed=scenes.RENDER_SEED)
