@@ -1,13 +1,12 @@
 // rtx_api.hip -- host side of librtx_hip.so: the extern "C" entry points of include/rtx_hip.h.
-// Scene packing (Scene.objects -> per-type device arrays with scene-order ids), the
-// ray-independent precompute, scratch management, kernel launches, timing.
+// The handle and its resources, scratch management, kernel launches, timing.  Its siblings: rtx_pack.hip (scene packing and update
+// planning: no HIP call), rtx_api_update.hip (rtx_scene_update_objects, rtx_scene_append_objects), rtx_api_debug.hip (rtx_debug_*).
 // There is no CPU fallback in this file: every render path ends in a gfx950 kernel launch.
 // The two launch paths: render_band (a band of a frame over a SampleRange -- a render's [0, rays_per_pixel) into the mean, or
 // rtx_render_blocks_accumulate's range into the caller's sums: choose_kernel, plan_batch, plan_forms, grow_scratch, launch_halves or
 // launch_batches, finish_stats over a BandPlan) and query_run (one QueryRequest: the mode, the rays or the pick frame, that mode's
 // pointers); both start with DoneGuard, scratch_cap, rows_view and begin_launches and read their counters through sum_counters.
-#include "../../include/rtx_hip.h"
-#include "rtx_launch.h"
+#include "rtx_host.h"
 
 #include <cmath>
 #include <cstdio>
@@ -17,25 +16,7 @@
 #include <thread>
 #include <vector>
 
-using namespace rtx;
-
 namespace {
-
-thread_local std::string g_last_error;
-
-int32_t fail(RtxStatus st, const std::string &msg)
-{
-    g_last_error = msg;
-    return (int32_t)st;
-}
-
-#define RTX_HIP_CHECK(expr)                                                                              \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess)                                                                            \
-            return fail(e_ == hipErrorOutOfMemory ? RTX_ERR_OUT_OF_MEMORY : RTX_ERR_HIP,                 \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                              \
-    } while (0)
 
 bool device_is_gfx950(int dev)
 {
@@ -44,41 +25,9 @@ bool device_is_gfx950(int dev)
     return std::strncmp(prop.gcnArchName, "gfx950", 6) == 0;
 }
 
-int usable_device_count()
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    int ok = 0;
-    for (int d = 0; d < n; ++d) ok += device_is_gfx950(d) ? 1 : 0;
-    return ok;
-}
-
 // per-render scratch of one handle: sized for a 288 GB part (24 GiB: a C2 frame of 64 spp -- 12.7 GB of sample records and
 // queue -- and 59 M rays of the wavefront form run as one launch; fewer, larger launches measured 3-10 % faster)
 constexpr size_t kDefaultScratchBytes = (size_t)24576 << 20;
-
-// the non-zero mask of a launch's sample records (store_sample, rtx_device.h): one bit per ray-queue slot, in whole 32-bit words
-static size_t nonzero_mask_bytes(uint64_t n_rays) { return (size_t)((n_rays + 31) / 32) * sizeof(uint32_t); }
-
-// Triangles per BVH leaf (RTX_TUNE_TRI_LEAF_SHIFT bits of RtxConfig.tuning: 1..6 -- a leaf must fit the walk's 6-entry
-// candidate queue, or every visit of it ends in the exhaustive sweep).  A tree of (x, y) footprints alone (`plain`: C3, C5)
-// gets 5: a packet tests a leaf's records for 64 rays at once and the regrouping kernel's leaf half reads one leaf per lane
-// per iteration (rtx_mesh_step.h), so fewer, fuller leaves pay.  Measured, C3 1080p x 8 / C5 band x 4 in ms, the wavefront
-// form | the regrouping kernel alone:  3: 41.7 / 59.5 | 79.8 / 75.2,  4: 39.5 / 56.4 | 76.5 / 72.3,  5: 38.0 / 55.2 | 77.4 / 72.1,
-// 6: 38.6 / 56.6 | 78.9 / 74.0  (2, before the step was split: 53.2 / 72.6 | 99.2 / 94.7).  A joint tree keeps 2 (240k axis-aligned
-// faces: 222 ms at 2, 242 at 4).
-uint32_t tri_leaf_size(bool plain, uint32_t tuning)
-{
-    const uint32_t t = (tuning >> RTX_TUNE_TRI_LEAF_SHIFT) & 15u;
-    const uint32_t v = t ? t : (plain ? 5u : 2u);
-    return v > kQNodeLeafMax ? kQNodeLeafMax : v;
-}
-
-bool debug_prints()
-{
-    static const bool on = std::getenv("RTX_HIP_DEBUG") != nullptr;      // diagnostics on stderr only; changes no result
-    return on;
-}
 
 }  // namespace
 
@@ -94,89 +43,6 @@ constexpr uint64_t kHalvesBelowRays = 0;
 // The handle's work_counter: the ray queue's head, then what rtx_render_blocks_refine's launch reads and writes (rtx_launch.h: its three
 // counts, its rule).
 constexpr size_t kWorkWords = kQueryRefineWords;
-
-// What rtx_scene_update_objects needs to know about the resident tree, kept on the host from every pack (upload, append, rebuild).
-struct RefitTables {
-    double scale = -1.0;                                  // the build's largest finite box coordinate ((origin_limit - 1) / 4); < 0: no tree was built
-    double abs_pad = 0.0;
-    double centre[3] = { 0.0, 0.0, 0.0 };
-    bool sphere_tree = false;                             // the spheres are in the tree (bvh_flags bit 0)
-    std::vector<uint32_t> local;                          // object index -> index in spheres[] / planes[] / tris[] (the kind: h->objects)
-    std::vector<uint32_t> slot;                           // sphere -> its leaf entry (the inverse of bvh.prims); empty without a sphere tree
-    std::vector<uint32_t> level_nodes, level_begin;       // the non-flat wide nodes grouped by depth: level d = level_nodes[level_begin[d] .. level_begin[d + 1])
-    // the triangle half (RTX_UPDATE_DEFORM): per triangle its class and free axis as pack_scene decided them (classify_triangle) and its
-    // record in tri_f32 (tri_fidx inverted; kNoSlot: class "none"; < n_tri_tree: a tree record, the index in tri_geo too)
-    std::vector<uint8_t> tri_class, tri_axis;
-    std::vector<uint32_t> tri_rec;
-    uint32_t n_tri_tree = 0;
-    std::vector<uint32_t> all_level_nodes, all_level_begin;   // EVERY wide node by depth, a footprint node with kBvhFlatNode set
-};
-
-struct RtxSceneHandle_ {
-    int device = 0;
-    int n_cus = 0;
-    RtxConfig cfg{};
-    RtxCamera cam{};
-    SceneView sv{};
-    std::vector<RtxObject> objects;                       // Scene.objects as uploaded (rtx_scene_append_objects re-packs them)
-    std::vector<void *> scene_allocs;
-    // rtx_scene_update_objects: the host tables of the resident pack, and their device side -- made at the first REFIT or RECORDS
-    // call, dropped by any rebuild (upload_packed)
-    RefitTables refit;
-    struct UpdateBufs {
-        bool valid = false;
-        uint32_t *levels = nullptr; float *box32 = nullptr; double *reach = nullptr;
-        bool mesh_valid = false;                                // the triangle half: made at the first DEFORM call that moves a triangle
-        uint32_t *all_levels = nullptr; float *tribox32 = nullptr; double *tri_reach = nullptr;
-        UpdateEntry *h_entries = nullptr; size_t h_cap = 0;     // pinned staging of the update list
-        UpdateEntry *d_entries = nullptr; size_t d_cap = 0;
-        unsigned long long *d_status = nullptr, *h_status = nullptr;   // {status bits, the bits of the new sphere_cmax, of the new tri_extent}; h_status pinned
-    } upd;
-    // scratch, grown on demand
-    double *samples = nullptr;  size_t samples_bytes = 0;
-    double *acc = nullptr;      size_t acc_bytes = 0;
-    double *tables = nullptr;   size_t tables_doubles = 0;
-    double *h_tables = nullptr; size_t h_tables_doubles = 0;
-    double *state = nullptr;    size_t state_bytes = 0;
-    void *wf_state = nullptr;   size_t wf_bytes = 0;       // the wavefront kernels' ray state
-    void *pool = nullptr;       size_t pool_bytes = 0;     // (lab) the pool / pair forms of the sphere kernel's stage 2
-    void *slots = nullptr;      size_t slots_bytes = 0;    // the slot records of the sphere kernel's stage 2 (trace_sph_slots_kernel)
-    void *tile_lists = nullptr; size_t tile_lists_bytes = 0;   // what each tile's primary rays can reach (build_tile_lists_kernel)
-    PathStep *transcript = nullptr; uint32_t *transcript_counts = nullptr; uint32_t transcript_steps = 0;   // (lab) rtx_debug_paths, set for one call
-    Counters *counters = nullptr;
-    unsigned long long *work_counter = nullptr;
-    SceneView *d_sv = nullptr;  bool sv_dirty = true;     // device copy of sv (kernels take it by pointer)
-    RowsView *d_rv = nullptr;
-    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };      // [3]: the end of the sphere kernel's stage 1 (stats only)
-    // The second half's own stream and buffers when a launch runs as two halves in flight (render_band, "halves"): created on first use.
-    struct SecondHalf {
-        hipStream_t stream = nullptr;
-        hipEvent_t fork = nullptr, join = nullptr, stage1_done = nullptr;
-        Counters *counters = nullptr, *counters_stage1 = nullptr;
-        unsigned long long *work_counter = nullptr;
-        RowsView *d_rv = nullptr;
-        double *state = nullptr;    size_t state_bytes = 0;
-        void *queue = nullptr;      size_t queue_bytes = 0;
-    } half2;
-    Counters *counters_stage1 = nullptr;                   // the counters as stage 1 left them (stats only)
-    // The handle's device buffers (descriptors, tables, counters, scratch) are shared by all of its renders, so they
-    // are ordered on ONE stream at a time: when a call brings a different stream the previous one is drained first.
-    size_t scratch_limit = 0;                             // rtx_scene_set_scratch_limit (0 = default)
-    hipStream_t last_stream = nullptr;                    // compared, never used: the caller may have destroyed it since
-    bool have_last_stream = false;
-    hipEvent_t ev_done = nullptr;                         // recorded at the end of every render, on the stream it ran on
-    bool have_done = false;
-    // Round-bound watchdog of the sweep kernel (ctr[1].pad_): copied to this pinned word after every launch and looked
-    // at by the next entry point that finds the copy complete (and by rtx_scene_free), so that the asynchronous
-    // stats == NULL path reports it too.
-    unsigned long long *h_watchdog = nullptr;
-    hipEvent_t ev_watchdog = nullptr;
-    bool watchdog_pending = false;
-    // what the trig tables currently hold
-    uint32_t t_w = 0, t_h = 0, t_rb = 0, t_rs = 0, t_blk = 0, t_nr = 0;
-    double t_fov = 0.0;
-    bool t_valid = false;
-};
 
 namespace {
 
@@ -236,6 +102,19 @@ int32_t grow(void **p, size_t *have, size_t want)
     return RTX_OK;
 }
 
+}  // namespace
+
+RTX_HOST_BEGIN
+
+int usable_device_count()
+{
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    int ok = 0;
+    for (int d = 0; d < n; ++d) ok += device_is_gfx950(d) ? 1 : 0;
+    return ok;
+}
+
 void drop_update_tables(RtxSceneHandle_ *h)              // the device tables of one pack (the staging buffers stay)
 {
     auto &b = h->upd;
@@ -243,361 +122,6 @@ void drop_update_tables(RtxSceneHandle_ *h)              // the device tables of
         if (q) (void)hipFree(q);
     b.levels = nullptr; b.box32 = nullptr; b.reach = nullptr; b.valid = false;
     b.all_levels = nullptr; b.tribox32 = nullptr; b.tri_reach = nullptr; b.mesh_valid = false;
-}
-
-void free_handle(RtxSceneHandle_ *h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    for (void *p : h->scene_allocs) (void)hipFree(p);
-    drop_update_tables(h);
-    if (h->upd.h_entries) (void)hipHostFree(h->upd.h_entries);
-    if (h->upd.d_entries) (void)hipFree(h->upd.d_entries);
-    if (h->upd.d_status) (void)hipFree(h->upd.d_status);
-    if (h->upd.h_status) (void)hipHostFree(h->upd.h_status);
-    if (h->samples) (void)hipFree(h->samples);
-    if (h->acc) (void)hipFree(h->acc);
-    if (h->tables) (void)hipFree(h->tables);
-    if (h->h_tables) (void)hipHostFree(h->h_tables);
-    if (h->state) (void)hipFree(h->state);
-    if (h->wf_state) (void)hipFree(h->wf_state);
-    if (h->pool) (void)hipFree(h->pool);
-    if (h->slots) (void)hipFree(h->slots);
-    if (h->tile_lists) (void)hipFree(h->tile_lists);
-    if (h->counters) (void)hipFree(h->counters);
-    if (h->counters_stage1) (void)hipFree(h->counters_stage1);
-    if (h->work_counter) (void)hipFree(h->work_counter);
-    if (h->d_sv) (void)hipFree(h->d_sv);
-    if (h->d_rv) (void)hipFree(h->d_rv);
-    {
-        auto &b = h->half2;
-        if (b.stream) { (void)hipStreamSynchronize(b.stream); (void)hipStreamDestroy(b.stream); }
-        for (hipEvent_t e : { b.fork, b.join, b.stage1_done }) if (e) (void)hipEventDestroy(e);
-        for (void *q : { (void *)b.counters, (void *)b.counters_stage1, (void *)b.work_counter, (void *)b.d_rv, (void *)b.state, b.queue })
-            if (q) (void)hipFree(q);
-    }
-    if (h->h_watchdog) (void)hipHostFree(h->h_watchdog);
-    if (h->ev_watchdog) (void)hipEventDestroy(h->ev_watchdog);
-    if (h->ev_done) (void)hipEventDestroy(h->ev_done);
-    for (auto &e : h->ev) if (e) (void)hipEventDestroy(e);
-    delete h;
-}
-
-}  // namespace
-
-// Everything rtx_scene_upload prepares on the host: per-type shape arrays with scene-order ids, the ray-independent
-// precompute, the f32 filter records and the BVH.  No HIP call in here (rtx_debug_host_scene runs it without a GPU).
-namespace {
-
-struct PackedScene {
-    SceneView sv{};
-    std::vector<SphereX> spheres; std::vector<uint32_t> sphere_id;
-    std::vector<PlaneX> planes; std::vector<TriX> tris;
-    std::vector<MaterialX> mats;
-    std::vector<float4> sph32, tri32, leaf32, leaf_cr, tri_geo;
-    std::vector<uint32_t> tri_fidx;
-    std::vector<uint8_t> tri_rec_free_axis;          // per tree record (leaf order): the axis its footprint is unbounded along
-    std::vector<uint8_t> tri_class, tri_axis;        // per triangle: classify_triangle's answer
-    BvhBuild bvh;
-    Bvh4Build bvh4;
-    std::vector<BvhQNode> qnodes;                    // the 64-byte form of bvh4's nodes, when the tree allows it
-    std::vector<BvhQ3Node> q3nodes;                  // the 64-byte form of a sphere tree's nodes
-};
-
-// The class of a triangle before any demotion, decided in ONE place for pack_scene (which record it gets, whether it may enter the
-// tree) and plan_update (whether new vertices can be written in place):
-//   kTriNone       no filter record: it can never be hit
-//   kTriAlways     a record, tested for every segment: the projection the elimination reads is not usable for a footprint
-//   kTriQualified  may enter the tree with its footprint in the plane that leaves out `free_axis`
-enum : uint8_t { kTriNone = 0, kTriAlways = 1, kTriQualified = 2 };
-struct TriClass { uint8_t cls; uint8_t free_axis; };
-
-TriClass classify_triangle(const TriX &t, const double geom[9], const double centre[3])
-{
-    TriClass c{kTriNone, 2};
-    if (t.degenerate) return c;                                       // Triangle::contains is always false (triangle.rs:64,83)
-    const double kabs = dot(t.n, t.v0);
-    if (!std::isfinite(kabs) || !std::isfinite(t.n.x) || !std::isfinite(t.n.y) || !std::isfinite(t.n.z))
-        return c;                                                     // NaN normal: every comparison of the exact test fails
-    if (kabs < -(1.0 + 1e-9)) return c;                               // n.(v0 - dir) < 0 for every unit dir (triangle.rs:115)
-    c.cls = kTriAlways;
-    double v[3][3];
-    bool finite = true;
-    for (int k = 0; k < 9; ++k) { v[k / 3][k % 3] = geom[k] - centre[k % 3]; finite = finite && std::isfinite(geom[k]); }
-    const int free_axis = 3 - (int)t.i - (int)t.j;                    // t.i != t.j: the two rows the elimination reads
-    const int a0 = free_axis == 0 ? 1 : 0, a1 = free_axis == 2 ? 1 : 2;
-    const double r0 = v[1][a0] - v[0][a0], r1 = v[1][a1] - v[0][a1], s0 = v[2][a0] - v[0][a0], s1 = v[2][a1] - v[0][a1];
-    const double det = r0 * s1 - r1 * s0;
-    if (finite && t.i != t.j && std::fabs(det) > 1e-6 * std::hypot(r0, r1) * std::hypot(s0, s1)) { c.cls = kTriQualified; c.free_axis = (uint8_t)free_axis; }
-    return c;
-}
-
-int32_t pack_scene(const RtxScene *scene, PackedScene &p)
-{
-    const uint64_t n = scene->n_objects;
-    std::vector<SphereX> &spheres = p.spheres; std::vector<uint32_t> &sphere_id = p.sphere_id;
-    std::vector<PlaneX> &planes = p.planes; std::vector<TriX> &tris = p.tris;
-    std::vector<MaterialX> &mats = p.mats;
-    mats.assign(n, MaterialX());
-    double lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
-    for (uint64_t k = 0; k < n; ++k) {
-        const RtxObject &o = scene->objects[k];
-        mats[k].base_color = mk(o.base_color[0], o.base_color[1], o.base_color[2]);
-        mats[k].emission_color = mk(o.emission_color[0], o.emission_color[1], o.emission_color[2]);
-        mats[k].roughness = o.roughness;
-        switch (o.kind) {
-            case RTX_SPHERE:
-                spheres.push_back(make_sphere(o.geom));
-                sphere_id.push_back((uint32_t)k);
-                for (int c = 0; c < 3; ++c) {
-                    if (std::isfinite(o.geom[c])) { lo[c] = std::fmin(lo[c], o.geom[c]); hi[c] = std::fmax(hi[c], o.geom[c]); }
-                }
-                break;
-            case RTX_PLANE: planes.push_back(make_plane(o.geom, (uint32_t)k)); break;
-            case RTX_TRIANGLE:
-                tris.push_back(make_triangle(o.geom, (uint32_t)k));
-                for (int c = 0; c < 9; ++c)
-                    if (std::isfinite(o.geom[c])) { lo[c % 3] = std::fmin(lo[c % 3], o.geom[c]); hi[c % 3] = std::fmax(hi[c % 3], o.geom[c]); }
-                break;
-            default:
-                return fail(RTX_ERR_UNSUPPORTED, "object " + std::to_string(k) + ": kind " + std::to_string(o.kind) +
-                                                     " has no device primitive (user CustomShape impls cannot run on the GPU)");
-        }
-    }
-    // f32 filter records, relative to the centre of the spheres' bounding box, pair-interleaved for
-    // v_pk_fma_f32: record 2k = {x[2k], x[2k+1], y[2k], y[2k+1]}, record 2k+1 = {z.., w..}, w = |c|^2 - r^2;
-    // padded to a multiple of 4 spheres with a sentinel that never passes (w = 1e30)
-    const size_t ns4 = (spheres.size() + 3) & ~(size_t)3;
-    std::vector<float4> &sph32 = p.sph32;
-    sph32.assign(ns4, make_float4(0.f, 0.f, 0.f, 0.f));
-    std::vector<float> fx(ns4, 0.f), fy(ns4, 0.f), fz(ns4, 0.f), fw(ns4, 1.0e30f);
-    double centre[3] = { 0, 0, 0 };
-    for (int c = 0; c < 3; ++c) if (lo[c] <= hi[c]) centre[c] = 0.5 * (lo[c] + hi[c]);
-    double cmax = 0.0;
-    for (size_t k = 0; k < spheres.size(); ++k) {
-        const RtxObject &o = scene->objects[sphere_id[k]];
-        double cx = o.geom[0] - centre[0], cy = o.geom[1] - centre[1], cz = o.geom[2] - centre[2];
-        double cc = cx * cx + cy * cy + cz * cz;
-        double reach = std::sqrt(cc) + std::fabs(o.geom[3]);
-        if (!(reach <= cmax)) cmax = reach;                   // NaN/inf propagate: every ray then takes the exact sweep
-        fx[k] = (float)cx; fy[k] = (float)cy; fz[k] = (float)cz; fw[k] = (float)(cc - spheres[k].rr);
-    }
-    if (!(cmax < 1.0e14)) {
-        // non-finite or enormous sphere data: the f32 records cannot represent it.  Every record becomes
-        // "always a candidate" (w = -1e30), so every ray overflows its queue and takes the exact f64 sweep.
-        for (size_t k = 0; k < ns4; ++k) { fx[k] = fy[k] = fz[k] = 0.f; fw[k] = -1.0e30f; }
-    }
-    for (size_t k = 0; k < ns4; k += 2) {
-        sph32[k] = make_float4(fx[k], fx[k + 1], fy[k], fy[k + 1]);
-        sph32[k + 1] = make_float4(fz[k], fz[k + 1], fw[k], fw[k + 1]);
-    }
-    // triangle filter records (rtx_device.h "triangle filter"): only triangles that can be hit at all.  Triangle::contains
-    // decides a hit from two coordinates of the hit point -- rows (i, j) of its elimination: (x, y) unless a zero pivot
-    // swaps another row in (triangle.rs:60-71,81-87; e.g. every face in a plane x = const is solved in (y, z)) -- so the
-    // triangle enters the tree with its footprint in THAT coordinate plane, unbounded along the third axis (rtx_bvh.h).
-    // Triangles solved in (x, y) also get a real filter record; the others a pass-all record (their leaf box already
-    // says "the ray passes over the footprint").  An ill-conditioned projection (the rounding of a, b could report a
-    // hit outside the footprint) keeps a triangle outside the tree: tested for every segment.
-    struct TriRec { float4 A, B, g0, g1; uint32_t tri; };
-    std::vector<TriRec> tree_recs[3], always_recs;                     // tree_recs[f]: the elimination does not read axis f
-    std::vector<BvhBox> tri_boxes[3];
-    double tri_extent = 0.0;
-    p.tri_class.assign(tris.size(), (uint8_t)kTriNone);
-    p.tri_axis.assign(tris.size(), (uint8_t)2);
-    for (size_t k = 0; k < tris.size(); ++k) {
-        const TriX &t = tris[k];
-        const RtxObject &o = scene->objects[t.id];
-        const TriClass tc = classify_triangle(t, o.geom, centre);
-        p.tri_class[k] = tc.cls; p.tri_axis[k] = tc.free_axis;
-        if (tc.cls == kTriNone) continue;
-        const double kabs = dot(t.n, t.v0);
-        double v[3][3];
-        for (int c = 0; c < 9; ++c) v[c / 3][c % 3] = o.geom[c] - centre[c % 3];
-        const int free_axis = 3 - (int)t.i - (int)t.j;                // t.i != t.j: the two rows the elimination reads
-        const int a0 = free_axis == 0 ? 1 : 0, a1 = free_axis == 2 ? 1 : 2;
-        const double r0 = v[1][a0] - v[0][a0], r1 = v[1][a1] - v[0][a1], s0 = v[2][a0] - v[0][a0], s1 = v[2][a1] - v[0][a1];
-        const double det = r0 * s1 - r1 * s0;
-        BvhBox fp;
-        const bool in_tree = tc.cls == kTriQualified && triangle_footprint(o.geom, fp, free_axis);
-        TriRec rec;
-        rec.A = make_float4(0.f, 0.f, 0.f, 0.f);                       // "always a candidate"
-        rec.B = make_float4(0.f, 0.f, 0.f, 0.f);
-        rec.g0 = make_float4(0.f, 0.f, 0.f, 0.f);
-        rec.g1 = make_float4(0.f, 0.f, NAN, 0.f);                      // n.v0 = NaN: no f32 bounds for this record (outside the tree)
-        rec.tri = (uint32_t)k;
-        if (in_tree) {
-            // (a, b) = M (q - v0)_uv with M the inverse of [r s] in the two rows Triangle::contains' elimination reads
-            // (triangle.rs:55-100; (u, v) = (x, y), (x, z) or (y, z)); n.v0 in absolute coordinates for the cull test
-            // (triangle.rs:115); the plane's code for tri_bounds (rtx_mesh_step.h)
-            const double m00 = s1 / det, m01 = -s0 / det, m10 = -r1 / det, m11 = r0 / det;
-            const double kc = t.n.x * v[0][0] + t.n.y * v[0][1] + t.n.z * v[0][2];
-            rec.g0 = make_float4((float)v[0][a0], (float)v[0][a1], (float)m00, (float)m01);
-            rec.g1 = make_float4((float)m10, (float)m11, (float)kabs, (float)(2 - free_axis));
-            rec.A = make_float4((float)t.n.x, (float)t.n.y, (float)t.n.z, (float)kc);
-            rec.B = make_float4(0.f, 0.f, 1.0e30f, 1.0e30f);           // no (x, y) rectangle to test: every ray passes the footprint filter
-            for (int c = 0; c < 9; ++c) tri_extent = std::fmax(tri_extent, std::fabs(v[c / 3][c % 3]));
-        }
-        if (in_tree && free_axis == 2) {
-            const double xlo = std::fmin(v[0][0], std::fmin(v[1][0], v[2][0])), xhi = std::fmax(v[0][0], std::fmax(v[1][0], v[2][0]));
-            const double ylo = std::fmin(v[0][1], std::fmin(v[1][1], v[2][1])), yhi = std::fmax(v[0][1], std::fmax(v[1][1], v[2][1]));
-            const double grow = 1.0 + 1.0 / 1048576.0;
-            rec.B = make_float4((float)(0.5 * (xlo + xhi)), (float)(0.5 * (ylo + yhi)),
-                                round_up_f32(0.5 * (xhi - xlo) * grow + 1e-30), round_up_f32(0.5 * (yhi - ylo) * grow + 1e-30));
-        }
-        if (in_tree) { tree_recs[free_axis].push_back(rec); tri_boxes[free_axis].push_back(fp); }
-        else always_recs.push_back(rec);
-    }
-    // a plane with fewer than 5 triangles gets no sub-tree: those are tested for every segment ((x, y) ones keep their
-    // filter record, which is valid outside the tree too)
-    std::vector<TriRec> demoted;
-    for (int f = 0; f < 3; ++f)
-        if (tree_recs[f].size() <= 4) {
-            for (const TriRec &r : tree_recs[f]) (f == 2 ? demoted : always_recs).push_back(r);
-            tree_recs[f].clear(); tri_boxes[f].clear();
-        }
-
-    // flat BVH over the sphere boxes and the triangle footprints (rtx_bvh.h); fewer than 5 spheres, or non-finite
-    // spheres, get no sub-tree (the BVH kernel then tests those shapes for every segment)
-    std::vector<BvhBox> sphere_boxes(spheres.size());
-    bool spheres_finite = true;
-    for (size_t k = 0; k < spheres.size() && spheres_finite; ++k)
-        spheres_finite = sphere_box(scene->objects[sphere_id[k]].geom, sphere_boxes[k]);
-    if (!spheres_finite || sphere_boxes.size() <= 4) sphere_boxes.clear();
-    const bool use_sah = (scene->config.tuning & RTX_TUNE_BVH_MEDIAN) == 0u;
-    BvhBuild &bvh = p.bvh;
-    const bool plain_tree = sphere_boxes.empty() && tri_boxes[0].empty() && tri_boxes[1].empty();   // (x, y) footprints alone (free axis 2)
-    bvh = build_bvh(sphere_boxes, tri_boxes, tri_leaf_size(plain_tree, scene->config.tuning), use_sah);
-    Bvh4Build &bvh4 = p.bvh4;
-    bvh4 = collapse_to_bvh4(bvh);
-
-    // records in leaf order first (a triangle leaf's link indexes them; tri_order indexes [plane xy][xz][yz]), then the
-    // ones outside the tree
-    std::vector<float4> &tri32 = p.tri32;
-    std::vector<uint32_t> &tri_fidx = p.tri_fidx;
-    std::vector<TriRec> all_tree;
-    std::vector<uint8_t> all_free;
-    for (int f = 2; f >= 0; --f)
-        for (const TriRec &r : tree_recs[f]) { all_tree.push_back(r); all_free.push_back((uint8_t)f); }
-    tri32.reserve(2 * (all_tree.size() + demoted.size() + always_recs.size()) + 2);
-    p.tri_rec_free_axis.clear();
-    size_t n_in_tree = 0;
-    if (bvh.has_tris) {
-        for (uint32_t idx : bvh.tri_order) {
-            const TriRec &r = all_tree[idx];
-            tri32.push_back(r.A); tri32.push_back(r.B); tri_fidx.push_back(r.tri); p.tri_rec_free_axis.push_back(all_free[idx]);
-            p.tri_geo.push_back(r.g0); p.tri_geo.push_back(r.g1);
-        }
-        n_in_tree = bvh.tri_order.size();
-    } else {                                    // (the build was refused: coordinates too large for the f32 slab test)
-        for (size_t k = 0; k < all_tree.size(); ++k) (all_free[k] == 2 ? demoted : always_recs).push_back(all_tree[k]);
-    }
-    p.sv.n_tri_tree = (uint32_t)n_in_tree;
-    for (const TriRec &r : demoted) { tri32.push_back(r.A); tri32.push_back(r.B); tri_fidx.push_back(r.tri); }
-    for (const TriRec &r : always_recs) { tri32.push_back(r.A); tri32.push_back(r.B); tri_fidx.push_back(r.tri); }
-    if (!tri32.empty()) {                       // one pad record: bvh_step reads records in pairs
-        tri32.push_back(make_float4(0.f, 0.f, 0.f, 0.f));
-        tri32.push_back(make_float4(0.f, 0.f, 0.f, 0.f));
-    }
-    p.sv.n_tri_filter = (uint32_t)tri_fidx.size();
-    p.sv.tri_extent = tri_extent;
-    p.sv.n_objects = (uint32_t)n;
-    p.sv.n_spheres = (uint32_t)spheres.size();
-    p.sv.n_planes = (uint32_t)planes.size();
-    p.sv.n_tris = (uint32_t)tris.size();
-    for (int c = 0; c < 3; ++c) p.sv.sphere_center[c] = centre[c];
-    p.sv.sphere_cmax = cmax;
-
-    p.sv.n_bvh_nodes = (uint32_t)bvh4.nodes.size();
-    p.sv.bvh_depth = (uint32_t)bvh4.depth;
-    p.sv.bvh_root = bvh4.root;
-    p.sv.bvh_origin_limit = (float)bvh.origin_limit;
-    p.sv.bvh_inv_max = (float)std::fmin(1.0e30, 1.0e37 / std::fmax(bvh.origin_limit, 1.0));     // |o * inv|, |b * inv| stay finite in f32
-    p.sv.bvh_flags = (bvh.has_spheres ? 1u : 0u) | (bvh.has_tris ? 2u : 0u) |
-                     (bvh.has_tris && !bvh.has_spheres && tree_recs[1].empty() && tree_recs[0].empty() ? 4u : 0u);
-    if ((p.sv.bvh_flags & 4u) && build_qnodes(bvh4, p.qnodes)) p.sv.bvh_flags |= 8u;
-    else p.qnodes.clear();
-#ifndef RTX_LAB
-    // the product library holds the pure-footprint kernels in their 64-byte-node instances only: a tree whose nodes have no such
-    // form (coordinates beyond the quantisation's range) walks as a joint tree, which takes any node
-    if ((p.sv.bvh_flags & 12u) == 4u) p.sv.bvh_flags &= ~4u;
-#endif
-    if ((p.sv.bvh_flags & 3u) == 1u && build_q3nodes(bvh4, bvh.abs_pad, p.q3nodes)) p.sv.bvh_flags |= 16u;     // spheres only
-    else p.q3nodes.clear();
-    if (debug_prints())
-        std::fprintf(stderr, "[rtx_hip] upload: %zu spheres, %zu triangles (%zu in the tree: %zu xy / %zu xz / %zu yz footprints, %zu tested per segment), bvh: %zu binary nodes, %zu wide nodes, depth %d\n",
-                     spheres.size(), tris.size(), n_in_tree, tree_recs[2].size(), tree_recs[1].size(), tree_recs[0].size(),
-                     demoted.size() + always_recs.size(), bvh.nodes.size(), bvh4.nodes.size(), bvh4.depth);
-    std::vector<float4> &leaf32 = p.leaf32;
-    leaf32.assign(bvh.prims.size(), make_float4(0.f, 0.f, 0.f, 0.f));
-    for (size_t k = 0; k < bvh.prims.size(); ++k) {
-        const uint32_t p = bvh.prims[k];
-        leaf32[k] = make_float4(fx[p], fy[p], fz[p], fw[p]);
-    }
-    // the spheres kernel's leaf record {c - centre, |r|} (sphere.rs:24 squares the radius: its sign does not matter);
-    // |r| rounded up, which only adds candidates
-    p.leaf_cr.assign(bvh.prims.size(), make_float4(0.f, 0.f, 0.f, 0.f));
-    for (size_t k = 0; k < bvh.prims.size(); ++k) {
-        const uint32_t q = bvh.prims[k];
-        p.leaf_cr[k] = make_float4(fx[q], fy[q], fz[q], round_up_f32(std::fabs(scene->objects[sphere_id[q]].geom[3])));
-    }
-
-    return RTX_OK;
-}
-
-RefitTables make_refit_tables(const PackedScene &p)
-{
-    RefitTables t;
-    t.abs_pad = p.bvh.abs_pad;
-    t.scale = p.bvh.origin_limit > 0.0 ? (p.bvh.origin_limit - 1.0) / 4.0 : -1.0;
-    for (int c = 0; c < 3; ++c) t.centre[c] = p.sv.sphere_center[c];
-    t.sphere_tree = (p.sv.bvh_flags & 1u) != 0u;
-    t.local.assign(p.mats.size(), 0u);
-    for (size_t k = 0; k < p.sphere_id.size(); ++k) t.local[p.sphere_id[k]] = (uint32_t)k;
-    for (size_t k = 0; k < p.planes.size(); ++k) t.local[p.planes[k].id] = (uint32_t)k;
-    for (size_t k = 0; k < p.tris.size(); ++k) t.local[p.tris[k].id] = (uint32_t)k;
-    auto bits = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
-    t.tri_class = p.tri_class; t.tri_axis = p.tri_axis;
-    t.tri_rec.assign(p.tris.size(), kNoSlot);
-    for (size_t r = 0; r < p.tri_fidx.size(); ++r) t.tri_rec[p.tri_fidx[r]] = (uint32_t)r;
-    t.n_tri_tree = p.sv.n_tri_tree;
-    if (t.n_tri_tree) {                                       // every wide node by depth (the sphere-only list below stops at footprint links)
-        std::vector<uint32_t> cur, next;
-        cur.push_back(p.bvh4.root);
-        t.all_level_begin.push_back(0u);
-        while (!cur.empty()) {
-            next.clear();
-            for (uint32_t entry : cur) {
-                t.all_level_nodes.push_back(entry);
-                const Bvh4Node &w = p.bvh4.nodes[entry & ~kBvhFlatNode];
-                const float lk[4] = { w.b[0].x, w.b[0].y, w.b[0].z, w.b[0].w }, ct[4] = { w.b[1].x, w.b[1].y, w.b[1].z, w.b[1].w };
-                for (int c = 0; c < 4; ++c) {
-                    const bool flat = (entry & kBvhFlatNode) != 0u;
-                    const uint32_t link = bits(flat ? lk[c] : w.a[c].w), count = bits(flat ? ct[c] : w.b[c].w);
-                    if (count == 0u) next.push_back(flat ? (link | kBvhFlatNode) : link);
-                }
-            }
-            t.all_level_begin.push_back((uint32_t)t.all_level_nodes.size());
-            cur.swap(next);
-        }
-    }
-    if (!t.sphere_tree) return t;
-    t.slot.assign(p.spheres.size(), kNoSlot);
-    for (size_t k = 0; k < p.bvh.prims.size(); ++k) t.slot[p.bvh.prims[k]] = (uint32_t)k;
-    std::vector<uint32_t> cur, next;
-    if (!(p.bvh4.root & kBvhFlatNode)) cur.push_back(0u);
-    t.level_begin.push_back(0u);
-    while (!cur.empty()) {
-        next.clear();
-        for (uint32_t idx : cur) {
-            t.level_nodes.push_back(idx);
-            const Bvh4Node &w = p.bvh4.nodes[idx];
-            for (int c = 0; c < 4; ++c)
-                if (bits(w.b[c].w) == 0u && !(bits(w.a[c].w) & kBvhFlatNode)) next.push_back(bits(w.a[c].w));
-        }
-        t.level_begin.push_back((uint32_t)t.level_nodes.size());
-        cur.swap(next);
-    }
-    return t;
 }
 
 // Puts a packed scene (shape arrays, filter records, BVH) on the handle's device, replacing what was there.  Config
@@ -649,208 +173,77 @@ int32_t upload_packed(RtxSceneHandle_ *h, const PackedScene &p)
     return RTX_OK;
 }
 
-int32_t install_scene(RtxSceneHandle_ *h, const RtxScene *scene)
+// The watchdog word of the last launch, if its copy has arrived (wait = true: drain the stream first).
+int32_t check_watchdog(RtxSceneHandle_ *h, bool wait)
 {
-    PackedScene p;
-    if (int32_t prc = pack_scene(scene, p)) return prc;
-    return upload_packed(h, p);
-}
-
-// ---- rtx_scene_update_objects: what the host decides (no HIP call: rtx_debug_host_refit runs it without a GPU) -------------------
-
-// An update after validation: the de-duplicated entries (the last entry of an index wins) and the path they take.
-struct UpdatePlan {
-    std::vector<UpdateEntry> entries;
-    uint32_t how = RTX_UPDATED_NOTHING;
-    bool any_sphere = false;                              // a sphere's geometry changes: sphere_cmax is taken again
-    bool tri_geom = false;                                // a triangle's geometry changes in place (RTX_UPDATE_DEFORM): the triangle tables are needed
-    bool tri_refit = false;                               // ... and it has a tree record: every level is refitted, footprint nodes included
-    bool any_tri = false;                                 // ... and it is qualified: tri_extent is taken again
-};
-
-// Validates (nothing is written before every entry passed), removes duplicates and chooses the path (include/rtx_hip.h, "Which path
-// runs").  `cur` is the resident object list, `cmax` the resident sphere_cmax.  Every scene-wide constant of pack_scene either stays a
-// valid bound under REFIT / RECORDS or sends the update to REBUILT:
-//   sphere_center   kept: the f32 records are offsets from ANY fixed point; what depends on it is sphere_cmax, which mode C recomputes
-//                   against the kept centre, and the < 1e14 limit of pack_scene, which every new reach is held to here
-//   origin_limit, abs_pad, bvh_inv_max   functions of `scale`: a new box beyond it rebuilds
-//   tri_extent, the triangle records     under AUTO triangle geometry never changes here (it rebuilds).  Under RTX_UPDATE_DEFORM a triangle
-//                   that keeps its class and free axis (classify_triangle: the decision pack_scene takes) is rewritten against the kept
-//                   centre and mode D takes tri_extent again; the class rule keeps tri_fidx, the leaf order and which records are real
-//   bvh_depth, bvh_flags, the topology   the tree keeps its shape; a sphere that turns non-finite (it would leave the tree) rebuilds
-int32_t plan_update(const std::vector<RtxObject> &cur, const RefitTables &t, double cmax, const uint64_t *indices, const RtxObject *objects,
-                    uint64_t n, uint32_t mode, UpdatePlan &plan)
-{
-    plan = UpdatePlan();
-    if (mode != RTX_UPDATE_AUTO && mode != RTX_UPDATE_REBUILD && mode != RTX_UPDATE_DEFORM) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_update_objects: unknown mode");
-    if (n == 0) return RTX_OK;
-    if (!indices || !objects) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_update_objects: null argument");
-    for (uint64_t i = 0; i < n; ++i) {
-        if (indices[i] >= cur.size())
-            return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_update_objects: index " + std::to_string(indices[i]) + " is not below n_objects");
-        if (objects[i].kind > RTX_TRIANGLE)
-            return fail(RTX_ERR_UNSUPPORTED, "rtx_scene_update_objects: entry " + std::to_string(i) + ": kind " + std::to_string(objects[i].kind) +
-                                                 " has no device primitive");
-        if (objects[i].reserved != 0u) return fail(RTX_ERR_UNSUPPORTED, "rtx_scene_update_objects: entry " + std::to_string(i) + ": reserved is not zero");
+    if (!h->watchdog_pending) return RTX_OK;
+    if (wait) RTX_HIP_CHECK(hipEventSynchronize(h->ev_watchdog));
+    else {
+        const hipError_t q = hipEventQuery(h->ev_watchdog);
+        if (q == hipErrorNotReady) return RTX_OK;            // still running: looked at by a later call
+        RTX_HIP_CHECK(q);
     }
-    std::vector<uint8_t> seen(cur.size(), 0);
-    plan.entries.reserve((size_t)std::min<uint64_t>(n, cur.size()));
-    bool rebuild = mode == RTX_UPDATE_REBUILD || !(cmax < 1.0e14);
-    bool refit = false;
-    for (uint64_t i = n; i-- > 0;) {
-        const uint64_t idx = indices[i];
-        if (seen[idx]) continue;
-        seen[idx] = 1;
-        const RtxObject &o = objects[i];
-        UpdateEntry e;
-        std::memset(&e, 0, sizeof e);
-        e.object = (uint32_t)idx; e.local = t.local[idx]; e.slot = kNoSlot;
-        static_assert(sizeof(RtxObject) == 136 && offsetof(UpdateEntry, kind) == 16, "UpdateEntry carries an RtxObject");
-        std::memcpy(&e.kind, &o, sizeof o);
-        if (o.kind != cur[idx].kind) rebuild = true;
-        else if (o.kind == RTX_TRIANGLE) {
-            if (std::memcmp(o.geom, cur[idx].geom, sizeof o.geom) != 0) {          // (same geometry: a material update)
-                bool finite = true;
-                for (int c = 0; c < 9; ++c) finite = finite && std::isfinite(o.geom[c]);
-                const uint32_t k = e.local;
-                TriClass tc{kTriNone, 2};
-                if (mode == RTX_UPDATE_DEFORM && finite) tc = classify_triangle(make_triangle(o.geom, (uint32_t)idx), o.geom, t.centre);
-                if (mode != RTX_UPDATE_DEFORM || !finite || tc.cls != t.tri_class[k] || (tc.cls == kTriQualified && tc.free_axis != t.tri_axis[k]))
-                    rebuild = true;                                   // AUTO: always, as ever; DEFORM: the class or the free axis changes
-                else {
-                    plan.tri_geom = true;
-                    e.tri = kTriEntryGeom; e.slot = t.tri_rec[k];
-                    if (tc.cls == kTriQualified) {
-                        e.tri |= kTriEntryQualified | ((uint32_t)tc.free_axis << kTriEntryAxisShift);
-                        plan.any_tri = true;
-                        BvhBox fp;
-                        if (!triangle_footprint(o.geom, fp, tc.free_axis)) rebuild = true;
-                        else if (t.scale >= 0.0)
-                            for (int a = 0; a < 3; ++a)
-                                if (a != tc.free_axis && (std::fabs(fp.lo[a]) > t.scale || std::fabs(fp.hi[a]) > t.scale)) rebuild = true;
-                        if (e.slot < t.n_tri_tree) { e.tri |= kTriEntryTree; plan.tri_refit = true; refit = true; }
-                    }
-                }
-            }
-        } else if (o.kind == RTX_SPHERE && std::memcmp(o.geom, cur[idx].geom, 4 * sizeof(double)) != 0) {      // (same geometry: a material update)
-            plan.any_sphere = true;
-            BvhBox b;
-            if (!sphere_box(o.geom, b)) rebuild = true;
-            else {
-                if (t.scale >= 0.0)
-                    for (int a = 0; a < 3; ++a) if (std::fabs(b.lo[a]) > t.scale || std::fabs(b.hi[a]) > t.scale) rebuild = true;
-                const double cx = o.geom[0] - t.centre[0], cy = o.geom[1] - t.centre[1], cz = o.geom[2] - t.centre[2];
-                if (!(std::sqrt(cx * cx + cy * cy + cz * cz) + std::fabs(o.geom[3]) < 1.0e14)) rebuild = true;
-            }
-            if (t.sphere_tree) { e.slot = t.slot[e.local]; refit = true; }
-        }
-        plan.entries.push_back(e);
+    h->watchdog_pending = false;
+    if ((h->h_watchdog[0] | h->h_watchdog[1]) != 0ull) {
+        const unsigned long long n = h->h_watchdog[0] + h->h_watchdog[1];
+        h->h_watchdog[0] = h->h_watchdog[1] = 0ull;
+        return fail(RTX_ERR_HIP, "an earlier render on this scene raised its watchdog word (internal error: the sweep kernel's round "
+                                 "bound, or a full survivors' queue): " + std::to_string(n) + " event(s); its image is incomplete");
     }
-    plan.how = rebuild ? RTX_UPDATED_REBUILT : (refit ? RTX_UPDATED_REFIT : RTX_UPDATED_RECORDS);
     return RTX_OK;
 }
 
-// box32 / reach of every sphere of `objects` (what mode B and mode C read for the spheres an update does not name).
-void derive_all_spheres(const PackedScene &p, const RtxObject *objects, const RefitTables &t, std::vector<float> &box32, std::vector<double> &reach)
+// Orders a call on `stream` after everything the handle enqueued on the stream it used before: the new stream waits, on
+// the device, for the event the previous render recorded at its end.  The previous stream handle itself is not touched (a
+// caller that rotates streams may have destroyed it) and the host does not block.
+int32_t adopt_stream(RtxSceneHandle_ *h, hipStream_t stream)
 {
-    box32.assign(p.spheres.size() * 6, 0.f);
-    reach.assign(p.spheres.size(), 0.0);
-    for (size_t k = 0; k < p.spheres.size(); ++k) {
-        const SphereDerived d = derive_sphere(objects[p.sphere_id[k]].geom, t.centre, t.abs_pad);
-        for (int a = 0; a < 3; ++a) { box32[6 * k + a] = d.lo[a]; box32[6 * k + 3 + a] = d.hi[a]; }
-        reach[k] = d.reach;
-    }
+    if (h->have_last_stream && h->last_stream != stream && h->have_done) RTX_HIP_CHECK(hipStreamWaitEvent(stream, h->ev_done, 0));
+    h->last_stream = stream;
+    h->have_last_stream = true;
+    return RTX_OK;
 }
 
-// tribox32 (per tree record) / tri_reach (per triangle) of every triangle of `objects`: what modes B and D read for the triangles an
-// update does not name.
-void derive_all_triangles(const RtxObject *objects, size_t n_objects, const RefitTables &t, std::vector<float> &tribox32, std::vector<double> &tri_reach)
-{
-    tribox32.assign((size_t)t.n_tri_tree * 6, 0.f);
-    tri_reach.assign(t.tri_class.size(), 0.0);
-    for (size_t k = 0; k < n_objects; ++k) {
-        if (objects[k].kind != RTX_TRIANGLE) continue;
-        const uint32_t q = t.local[k];
-        if (t.tri_class[q] != kTriQualified) continue;
-        const TriDerived d = derive_triangle(objects[k].geom, (uint32_t)k, true, (int)t.tri_axis[q], t.centre, t.abs_pad);
-        tri_reach[q] = d.reach;
-        if (t.tri_rec[q] < t.n_tri_tree) for (int a = 0; a < 6; ++a) tribox32[(size_t)t.tri_rec[q] * 6 + a] = d.box[a];
-    }
-}
+RTX_HOST_END
 
-// The host reference of the device path: rtx_refit.h's functions in the order the launches run them, on a packed scene.  Returns the
-// status word (kUpdateStatusNoQ3 / kUpdateStatusNoQ: a 64-byte node has no encoding -- the caller rebuilds).  tribox32 / tri_reach are
-// read only when the plan moves a triangle.
-unsigned long long refit_packed(PackedScene &p, const RefitTables &t, const UpdatePlan &plan, std::vector<float> &box32, std::vector<double> &reach,
-                                std::vector<float> &tribox32, std::vector<double> &tri_reach)
-{
-    unsigned long long status = 0ull;
-    UpdateArgs u{};
-    u.entries = plan.entries.data();
-    u.spheres = p.spheres.data(); u.planes = p.planes.data(); u.materials = p.mats.data();
-    u.sphere_f32 = reinterpret_cast<float *>(p.sph32.data());
-    u.leaf_f32 = p.leaf32.data(); u.leaf_cr = p.leaf_cr.data();
-    u.box32 = box32.data(); u.reach = reach.data();
-    u.nodes = p.bvh4.nodes.data(); u.q3nodes = (p.sv.bvh_flags & 16u) ? p.q3nodes.data() : nullptr;
-    u.prims = p.bvh.prims.data();
-    for (int c = 0; c < 3; ++c) u.centre[c] = t.centre[c];
-    u.abs_pad = t.abs_pad;
-    if (plan.tri_geom) {
-        u.tris = p.tris.data(); u.tri_f32 = p.tri32.data(); u.tri_geo = p.tri_geo.data();
-        u.tribox32 = tribox32.data(); u.tri_reach = tri_reach.data();
-        u.qnodes = (p.sv.bvh_flags & 8u) ? p.qnodes.data() : nullptr;
-    }
-    for (uint32_t i = 0; i < (uint32_t)plan.entries.size(); ++i) update_record(u, i);
-    if (plan.how == RTX_UPDATED_REFIT) {
-        const std::vector<uint32_t> &nodes = plan.tri_refit ? t.all_level_nodes : t.level_nodes, &begin = plan.tri_refit ? t.all_level_begin : t.level_begin;
-        for (size_t d = begin.empty() ? 0 : begin.size() - 1; d-- > 0;)
-            for (uint32_t k = begin[d]; k < begin[d + 1]; ++k) status |= refit_level_entry(u, nodes[k]);
-    }
-    if (plan.any_sphere) {
-        double m = 0.0;
-        for (double r : reach) m = r > m ? r : m;
-        p.sv.sphere_cmax = m;
-    }
-    if (plan.any_tri) {
-        double m = 0.0;
-        for (double r : tri_reach) m = r > m ? r : m;
-        p.sv.tri_extent = m;
-    }
-    return status;
-}
+namespace {
 
-// FNV-1a-64 digests of a scene's arrays, in the order of rtx_debug_host_refit: nodes, 64-byte sphere nodes, leaf records (bvh_leaf_f32
-// then bvh_leaf_cr), sphere_f32, spheres, planes, materials, the bits of sphere_cmax.
-uint64_t fnv1a(uint64_t h, const void *data, size_t bytes)
+void free_handle(RtxSceneHandle_ *h)
 {
-    const unsigned char *b = static_cast<const unsigned char *>(data);
-    for (size_t k = 0; k < bytes; ++k) { h ^= b[k]; h *= 0x100000001B3ull; }
-    return h;
-}
-constexpr uint64_t kFnvBasis = 0xCBF29CE484222325ull;
-
-void digest_packed(const PackedScene &p, uint64_t *digests)
-{
-    digests[0] = fnv1a(kFnvBasis, p.bvh4.nodes.data(), p.bvh4.nodes.size() * sizeof(Bvh4Node));
-    digests[1] = fnv1a(kFnvBasis, p.q3nodes.data(), p.q3nodes.size() * sizeof(BvhQ3Node));
-    digests[2] = fnv1a(fnv1a(kFnvBasis, p.leaf32.data(), p.leaf32.size() * sizeof(float4)), p.leaf_cr.data(), p.leaf_cr.size() * sizeof(float4));
-    digests[3] = fnv1a(kFnvBasis, p.sph32.data(), p.sph32.size() * sizeof(float4));
-    digests[4] = fnv1a(kFnvBasis, p.spheres.data(), p.spheres.size() * sizeof(SphereX));
-    digests[5] = fnv1a(kFnvBasis, p.planes.data(), p.planes.size() * sizeof(PlaneX));
-    digests[6] = fnv1a(kFnvBasis, p.mats.data(), p.mats.size() * sizeof(MaterialX));
-    digests[7] = fnv1a(kFnvBasis, &p.sv.sphere_cmax, sizeof(double));
-}
-
-// digest_packed, then (rtx_debug_host_refit_mesh) the triangle records, tri_f32, tri_geo, the 64-byte footprint nodes, the bits of tri_extent.
-void digest_packed_mesh(const PackedScene &p, uint64_t *digests)
-{
-    digest_packed(p, digests);
-    digests[8] = fnv1a(kFnvBasis, p.tris.data(), p.tris.size() * sizeof(TriX));
-    digests[9] = fnv1a(kFnvBasis, p.tri32.data(), p.tri32.size() * sizeof(float4));
-    digests[10] = fnv1a(kFnvBasis, p.tri_geo.data(), p.tri_geo.size() * sizeof(float4));
-    digests[11] = fnv1a(kFnvBasis, p.qnodes.data(), p.qnodes.size() * sizeof(BvhQNode));
-    digests[12] = fnv1a(kFnvBasis, &p.sv.tri_extent, sizeof(double));
-    digests[13] = digests[14] = digests[15] = 0;
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    for (void *p : h->scene_allocs) (void)hipFree(p);
+    drop_update_tables(h);
+    if (h->upd.h_entries) (void)hipHostFree(h->upd.h_entries);
+    if (h->upd.d_entries) (void)hipFree(h->upd.d_entries);
+    if (h->upd.d_status) (void)hipFree(h->upd.d_status);
+    if (h->upd.h_status) (void)hipHostFree(h->upd.h_status);
+    if (h->samples) (void)hipFree(h->samples);
+    if (h->acc) (void)hipFree(h->acc);
+    if (h->tables) (void)hipFree(h->tables);
+    if (h->h_tables) (void)hipHostFree(h->h_tables);
+    if (h->state) (void)hipFree(h->state);
+    if (h->wf_state) (void)hipFree(h->wf_state);
+    if (h->pool) (void)hipFree(h->pool);
+    if (h->slots) (void)hipFree(h->slots);
+    if (h->tile_lists) (void)hipFree(h->tile_lists);
+    if (h->counters) (void)hipFree(h->counters);
+    if (h->counters_stage1) (void)hipFree(h->counters_stage1);
+    if (h->work_counter) (void)hipFree(h->work_counter);
+    if (h->d_sv) (void)hipFree(h->d_sv);
+    if (h->d_rv) (void)hipFree(h->d_rv);
+    {
+        auto &b = h->half2;
+        if (b.stream) { (void)hipStreamSynchronize(b.stream); (void)hipStreamDestroy(b.stream); }
+        for (hipEvent_t e : { b.fork, b.join, b.stage1_done }) if (e) (void)hipEventDestroy(e);
+        for (void *q : { (void *)b.counters, (void *)b.counters_stage1, (void *)b.work_counter, (void *)b.d_rv, (void *)b.state, b.queue })
+            if (q) (void)hipFree(q);
+    }
+    if (h->h_watchdog) (void)hipHostFree(h->h_watchdog);
+    if (h->ev_watchdog) (void)hipEventDestroy(h->ev_watchdog);
+    if (h->ev_done) (void)hipEventDestroy(h->ev_done);
+    for (auto &e : h->ev) if (e) (void)hipEventDestroy(e);
+    delete h;
 }
 
 int32_t check_scene_args(const RtxScene *scene, const char *who)
@@ -901,48 +294,6 @@ int32_t create_handle(const RtxScene *scene, const PackedScene &p, int32_t devic
     *out = h;
     return RTX_OK;
 }
-
-// The watchdog word of the last launch, if its copy has arrived (wait = true: drain the stream first).
-int32_t check_watchdog(RtxSceneHandle_ *h, bool wait)
-{
-    if (!h->watchdog_pending) return RTX_OK;
-    if (wait) RTX_HIP_CHECK(hipEventSynchronize(h->ev_watchdog));
-    else {
-        const hipError_t q = hipEventQuery(h->ev_watchdog);
-        if (q == hipErrorNotReady) return RTX_OK;            // still running: looked at by a later call
-        RTX_HIP_CHECK(q);
-    }
-    h->watchdog_pending = false;
-    if ((h->h_watchdog[0] | h->h_watchdog[1]) != 0ull) {
-        const unsigned long long n = h->h_watchdog[0] + h->h_watchdog[1];
-        h->h_watchdog[0] = h->h_watchdog[1] = 0ull;
-        return fail(RTX_ERR_HIP, "an earlier render on this scene raised its watchdog word (internal error: the sweep kernel's round "
-                                 "bound, or a full survivors' queue): " + std::to_string(n) + " event(s); its image is incomplete");
-    }
-    return RTX_OK;
-}
-
-// Orders a call on `stream` after everything the handle enqueued on the stream it used before: the new stream waits, on
-// the device, for the event the previous render recorded at its end.  The previous stream handle itself is not touched (a
-// caller that rotates streams may have destroyed it) and the host does not block.
-int32_t adopt_stream(RtxSceneHandle_ *h, hipStream_t stream)
-{
-    if (h->have_last_stream && h->last_stream != stream && h->have_done) RTX_HIP_CHECK(hipStreamWaitEvent(stream, h->ev_done, 0));
-    h->last_stream = stream;
-    h->have_last_stream = true;
-    return RTX_OK;
-}
-
-// From adopt_stream on, work may be enqueued on `stream`, and last_stream already names it: whatever way the call leaves -- a failed
-// HIP call after some launches, the watchdog return, the empty-scene answer -- the event a later call on ANOTHER stream waits
-// for (adopt_stream) is recorded behind everything enqueued so far, so that call never reuses the handle's scratch early.
-struct DoneGuard {
-    RtxSceneHandle_ *h; hipStream_t stream;
-    ~DoneGuard() {
-        if (hipEventRecord(h->ev_done, stream) == hipSuccess) h->have_done = true;
-        else { (void)hipGetLastError(); (void)hipDeviceSynchronize(); h->have_done = false; }   // (no event: drain instead)
-    }
-};
 
 // The scratch cap of a call: the handle's limit, never more than 3/4 of what is free on the device now (other handles, ranks or
 // frameworks may share it; `mine_bytes`, what this handle already holds of the buffers the cap is for, counts as free for it)
@@ -1041,7 +392,7 @@ extern "C" {
 
 int32_t rtx_version(void) { return RTX_HIP_VERSION; }
 
-const char *rtx_last_error(void) { return g_last_error.c_str(); }
+const char *rtx_last_error(void) { return last_error().c_str(); }
 
 int32_t rtx_device_count(void) { return usable_device_count(); }
 
@@ -1126,193 +477,6 @@ int32_t rtx_scene_set_camera(RtxSceneHandle scene, const RtxCamera *camera)
     return RTX_OK;
 }
 
-int32_t rtx_scene_append_objects(RtxSceneHandle scene, const RtxObject *objects, uint64_t n_objects)
-{
-    if (!scene || (n_objects && !objects)) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_append_objects: null argument");
-    if (n_objects == 0) return RTX_OK;
-    if (scene->objects.size() + n_objects > 0xFFFFFFF0ull) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_append_objects: too many objects");
-    RTX_HIP_CHECK(hipSetDevice(scene->device));
-    RTX_HIP_CHECK(hipDeviceSynchronize());                  // a render may still read the arrays about to be replaced
-    if (int32_t rc = check_watchdog(scene, true)) return rc;
-    std::vector<RtxObject> all = scene->objects;
-    all.insert(all.end(), objects, objects + n_objects);
-    RtxScene sc{};
-    sc.config = scene->cfg;
-    sc.camera = scene->cam;
-    sc.n_objects = all.size();
-    sc.objects = all.data();
-    if (int32_t rc = install_scene(scene, &sc)) return rc;      // (on failure the resident scene is as it was)
-    scene->objects.swap(all);
-    return RTX_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// The device side of the refit tables of the resident pack, made at the first REFIT or RECORDS call after it.
-int32_t ensure_update_tables(RtxSceneHandle_ *h)
-{
-    auto &b = h->upd;
-    if (!b.d_status) RTX_HIP_CHECK(hipMalloc((void **)&b.d_status, 3 * sizeof(unsigned long long)));
-    if (!b.h_status) RTX_HIP_CHECK(hipHostMalloc((void **)&b.h_status, 3 * sizeof(unsigned long long), hipHostMallocDefault));
-    if (b.valid) return RTX_OK;
-    drop_update_tables(h);
-    const RefitTables &t = h->refit;
-    const size_t ns = h->sv.n_spheres;
-    std::vector<float> box32(ns * 6, 0.f);
-    std::vector<double> reach(ns, 0.0);
-    for (size_t k = 0; k < h->objects.size(); ++k) {
-        if (h->objects[k].kind != RTX_SPHERE) continue;
-        const SphereDerived d = derive_sphere(h->objects[k].geom, t.centre, t.abs_pad);
-        const size_t q = t.local[k];
-        for (int a = 0; a < 3; ++a) { box32[6 * q + a] = d.lo[a]; box32[6 * q + 3 + a] = d.hi[a]; }
-        reach[q] = d.reach;
-    }
-    if (ns) {
-        RTX_HIP_CHECK(hipMalloc((void **)&b.box32, box32.size() * sizeof(float)));
-        RTX_HIP_CHECK(hipMalloc((void **)&b.reach, reach.size() * sizeof(double)));
-        RTX_HIP_CHECK(hipMemcpy(b.box32, box32.data(), box32.size() * sizeof(float), hipMemcpyHostToDevice));
-        RTX_HIP_CHECK(hipMemcpy(b.reach, reach.data(), reach.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
-    if (!t.level_nodes.empty()) {
-        RTX_HIP_CHECK(hipMalloc((void **)&b.levels, t.level_nodes.size() * sizeof(uint32_t)));
-        RTX_HIP_CHECK(hipMemcpy(b.levels, t.level_nodes.data(), t.level_nodes.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    b.valid = true;
-    return RTX_OK;
-}
-
-// The triangle half of the device tables (derive_all_spheres' analogue), made at the first DEFORM call that moves a triangle.
-int32_t ensure_mesh_tables(RtxSceneHandle_ *h)
-{
-    auto &b = h->upd;
-    if (b.mesh_valid) return RTX_OK;
-    const RefitTables &t = h->refit;
-    std::vector<float> tribox32;
-    std::vector<double> tri_reach;
-    derive_all_triangles(h->objects.data(), h->objects.size(), t, tribox32, tri_reach);
-    auto put = [](auto **dst, const auto &v) -> hipError_t {
-        if (v.empty()) return hipSuccess;
-        const hipError_t e = hipMalloc((void **)dst, v.size() * sizeof(v[0]));
-        return e != hipSuccess ? e : hipMemcpy(*dst, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice);
-    };
-    RTX_HIP_CHECK(put(&b.tribox32, tribox32));
-    RTX_HIP_CHECK(put(&b.tri_reach, tri_reach));
-    RTX_HIP_CHECK(put(&b.all_levels, t.all_level_nodes));
-    b.mesh_valid = true;
-    return RTX_OK;
-}
-
-// The update as a rebuild: rtx_scene_append_objects' path on the modified list.
-int32_t update_by_rebuild(RtxSceneHandle_ *h, const UpdatePlan &plan)
-{
-    RTX_HIP_CHECK(hipDeviceSynchronize());                  // a render may still read the arrays about to be replaced
-    std::vector<RtxObject> all = h->objects;
-    for (const UpdateEntry &e : plan.entries) std::memcpy(&all[e.object], &e.kind, sizeof(RtxObject));
-    RtxScene sc{};
-    sc.config = h->cfg;
-    sc.camera = h->cam;
-    sc.n_objects = all.size();
-    sc.objects = all.data();
-    if (int32_t rc = install_scene(h, &sc)) return rc;
-    h->objects.swap(all);
-    return RTX_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int32_t rtx_scene_update_objects(RtxSceneHandle h, const uint64_t *indices, const RtxObject *objects, uint64_t n, uint32_t mode,
-                                 void *stream_, uint32_t *how)
-{
-    if (how) *how = RTX_UPDATED_NOTHING;
-    if (!h) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_update_objects: null scene");
-    UpdatePlan plan;
-    if (int32_t rc = plan_update(h->objects, h->refit, h->sv.sphere_cmax, indices, objects, n, mode, plan)) return rc;
-    if (plan.entries.empty()) return RTX_OK;
-    RTX_HIP_CHECK(hipSetDevice(h->device));
-    if (int32_t rc = check_watchdog(h, true)) return rc;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (plan.how != RTX_UPDATED_REBUILT) {
-        auto &b = h->upd;
-        if (int32_t rc = ensure_update_tables(h)) return rc;
-        if (plan.tri_geom) if (int32_t rc = ensure_mesh_tables(h)) return rc;
-        const size_t ne = plan.entries.size(), bytes = ne * sizeof(UpdateEntry);
-        if (b.h_cap < ne) {
-            if (b.h_entries) { RTX_HIP_CHECK(hipHostFree(b.h_entries)); b.h_entries = nullptr; b.h_cap = 0; }
-            RTX_HIP_CHECK(hipHostMalloc((void **)&b.h_entries, bytes, hipHostMallocDefault));
-            b.h_cap = ne;
-        }
-        if (b.d_cap < ne) {
-            if (b.d_entries) { RTX_HIP_CHECK(hipFree(b.d_entries)); b.d_entries = nullptr; b.d_cap = 0; }
-            RTX_HIP_CHECK(hipMalloc((void **)&b.d_entries, bytes));
-            b.d_cap = ne;
-        }
-        std::memcpy(b.h_entries, plan.entries.data(), bytes);
-        {
-            if (int32_t rc = adopt_stream(h, stream)) return rc;      // the writes below wait for what earlier calls enqueued
-            DoneGuard done{h, stream};
-            const RefitTables &t = h->refit;
-            const SceneView &sv = h->sv;
-            RTX_HIP_CHECK(hipMemcpyAsync(b.d_entries, b.h_entries, bytes, hipMemcpyHostToDevice, stream));
-            const size_t status_bytes = (plan.any_tri ? 3 : 2) * sizeof(unsigned long long);      // (the third word: mode D's)
-            RTX_HIP_CHECK(hipMemsetAsync(b.d_status, 0, status_bytes, stream));
-            UpdateArgs u{};
-            u.entries = b.d_entries;
-            u.spheres = const_cast<SphereX *>(sv.spheres); u.planes = const_cast<PlaneX *>(sv.planes);
-            u.materials = const_cast<MaterialX *>(sv.materials);
-            u.sphere_f32 = reinterpret_cast<float *>(const_cast<float4 *>(sv.sphere_f32));
-            u.leaf_f32 = const_cast<float4 *>(sv.bvh_leaf_f32); u.leaf_cr = const_cast<float4 *>(sv.bvh_leaf_cr);
-            u.box32 = b.box32; u.reach = b.reach;
-            u.nodes = const_cast<Bvh4Node *>(sv.bvh_nodes);
-            u.q3nodes = (sv.bvh_flags & 16u) ? const_cast<BvhQ3Node *>(sv.bvh_q3nodes) : nullptr;
-            u.prims = sv.bvh_prims;
-            u.status = b.d_status;
-            for (int c = 0; c < 3; ++c) u.centre[c] = t.centre[c];
-            u.abs_pad = t.abs_pad;
-            if (plan.tri_geom) {
-                u.tris = const_cast<TriX *>(sv.tris); u.tri_f32 = const_cast<float4 *>(sv.tri_f32); u.tri_geo = const_cast<float4 *>(sv.tri_geo);
-                u.tribox32 = b.tribox32; u.tri_reach = b.tri_reach;
-                u.qnodes = (sv.bvh_flags & 8u) ? const_cast<BvhQNode *>(sv.bvh_qnodes) : nullptr;
-            }
-            u.mode = 0u; u.n = (uint32_t)ne;
-            RTX_HIP_CHECK(launch_scene_update(u, stream));
-            if (plan.how == RTX_UPDATED_REFIT) {
-                // a moved triangle of the tree: every level, footprint nodes included; spheres alone: the non-flat levels, as ever
-                const std::vector<uint32_t> &begin = plan.tri_refit ? t.all_level_begin : t.level_begin;
-                const uint32_t *levels = plan.tri_refit ? b.all_levels : b.levels;
-                for (size_t d = begin.empty() ? 0 : begin.size() - 1; d-- > 0;) {       // deepest first: a node reads what its children's launch wrote
-                    u.mode = 1u; u.n = begin[d + 1] - begin[d];
-                    u.level = levels + begin[d];
-                    RTX_HIP_CHECK(launch_scene_update(u, stream));
-                }
-            }
-            if (plan.any_sphere) {
-                u.mode = 2u; u.n = sv.n_spheres;
-                RTX_HIP_CHECK(launch_scene_update(u, stream));
-            }
-            if (plan.any_tri) {
-                u.mode = 3u; u.n = sv.n_tris;
-                RTX_HIP_CHECK(launch_scene_update(u, stream));
-            }
-            RTX_HIP_CHECK(hipMemcpyAsync(b.h_status, b.d_status, status_bytes, hipMemcpyDeviceToHost, stream));
-            RTX_HIP_CHECK(hipStreamSynchronize(stream));
-        }
-        if (h->upd.h_status[0] & (kUpdateStatusNoQ3 | kUpdateStatusNoQ)) plan.how = RTX_UPDATED_REBUILT;       // every array is replaced below
-        else {
-            for (const UpdateEntry &e : plan.entries) std::memcpy(&h->objects[e.object], &e.kind, sizeof(RtxObject));
-            if (plan.any_sphere) { std::memcpy(&h->sv.sphere_cmax, &h->upd.h_status[1], sizeof(double)); h->sv_dirty = true; }
-            if (plan.any_tri) { std::memcpy(&h->sv.tri_extent, &h->upd.h_status[2], sizeof(double)); h->sv_dirty = true; }
-        }
-    }
-    if (plan.how == RTX_UPDATED_REBUILT)
-        if (int32_t rc = update_by_rebuild(h, plan)) return rc;
-    if (how) *how = plan.how;
-    return RTX_OK;
-}
-
 }  // extern "C"
 
 // Rows of part `part` of `n_parts` when the frame is cut into blocks of `block` rows dealt out round-robin.
@@ -1387,10 +551,6 @@ struct BandPlan {                                         // what the call decid
     bool spheres_kernel = false, mesh_kernel = false, pool_kernel = false, spheres_two_stage = false, stage2_slots = false;
     bool wf_mesh = false, halves = false;                 // the wavefront form can take this tree; two halves in flight
 };
-// The samples a call traces and where their fold goes.  A render: [0, rays_per_pixel) from zero into out = sum / rays_per_pixel.
-// rtx_render_blocks_accumulate (sum != null): [begin, begin + n) on top of what the caller's sum (and sum_sq, or null) hold; nothing
-// is divided and no accumulator of the handle's is used -- the caller's buffers have its layout.
-struct SampleRange { uint64_t begin = 0, n = 0; double *sum = nullptr, *sum_sq = nullptr; };
 struct BandRun { float trace_ms = 0.f, resolve_ms = 0.f, stage1_ms = 0.f; CounterSums stage1; uint32_t launches = 0; };   // what its launches measured (RtxStats)
 
 // The kernel a band of npix pixels x spp samples runs: RtxConfig.kernel, resolved.  No HIP call in here.
@@ -1801,12 +961,14 @@ int32_t finish_stats(RtxSceneHandle_ *h, const BandPlan &plan, const BandRun &ru
 
 }  // namespace
 
+RTX_HOST_BEGIN
+
 // Renders the band of n_rows rows -- local row k -> image row row_begin + (k / row_block) * row_stride + k % row_block (rtx_device.h,
 // image_row) -- on `stream`; stats == NULL: asynchronous.  accumulate == null: the handle's rays_per_pixel samples, their mean into
 // d_out_rgb (a render); else that range of samples on top of its sums (rtx_render_blocks_accumulate; d_out_rgb is not read).
-static int32_t render_band(RtxSceneHandle h, uint32_t width, uint32_t height, uint32_t row_begin, uint32_t row_stride,
-                           uint32_t row_block, uint32_t n_rows, double *d_out_rgb, void *stream_, RtxStats *stats,
-                           const SampleRange *accumulate = nullptr)
+int32_t render_band(RtxSceneHandle h, uint32_t width, uint32_t height, uint32_t row_begin, uint32_t row_stride,
+                    uint32_t row_block, uint32_t n_rows, double *d_out_rgb, void *stream_, RtxStats *stats,
+                    const SampleRange *accumulate)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (stats) std::memset(stats, 0, sizeof *stats);
@@ -1872,6 +1034,8 @@ static int32_t render_band(RtxSceneHandle h, uint32_t width, uint32_t height, ui
     }
     return finish_stats(h, plan, run, (uint64_t)npix * spp, stream, stats);
 }
+
+RTX_HOST_END
 
 // ---- ray queries: closest_object (scene.rs:243-251) for the caller's rays or for the zero-offset primary ray of every pixel of a
 // width x height frame (the pick buffer), in one of three modes -- or, the fourth, the folded first hits of render_pixel's own rays for
@@ -2115,7 +1279,7 @@ static int32_t render_common(const RtxScene *scene, uint32_t width, uint32_t hei
         uint8_t *d_band8 = nullptr;                                     // its u8 form (render_to_image)
         const uint32_t n_rows = blocks_row_count(height, kRowBlock, k, n_dev);
         const size_t n_vals = (size_t)n_rows * width * 3;
-        auto step = [&](int32_t r) { if (r && !w.rc) { w.rc = r; w.msg = g_last_error; } return w.rc == RTX_OK; };
+        auto step = [&](int32_t r) { if (r && !w.rc) { w.rc = r; w.msg = last_error(); } return w.rc == RTX_OK; };
         auto hip = [&](hipError_t he, const char *what) {
             if (he != hipSuccess && !w.rc) { w.rc = he == hipErrorOutOfMemory ? RTX_ERR_OUT_OF_MEMORY : RTX_ERR_HIP; w.msg = std::string(what) + ": " + hipGetErrorString(he); }
             return w.rc == RTX_OK;
@@ -2209,733 +1373,7 @@ int32_t rtx_render_to_image_devices(const RtxScene *scene, uint32_t width, uint3
 
 }  // extern "C"
 
-// The invariant walk of rtx_debug_host_scene / rtx_debug_host_refit over a packed scene and the object list it stands for: every
-// shape's box inside its leaf child's box, every child inside its parent's, every 64-byte node's decoded child box around the
-// 128-byte child's.  `stats`: include/rtx_hip.h, rtx_debug_host_scene.
-static int32_t check_packed(const PackedScene &p, const RtxObject *objects, uint64_t *stats)
-{
-    for (int k = 0; k < 16; ++k) stats[k] = 0;
-    stats[0] = p.spheres.size(); stats[1] = p.tris.size(); stats[2] = p.sv.n_tri_filter; stats[3] = p.sv.n_tri_tree;
-    stats[4] = p.bvh4.nodes.size(); stats[5] = (uint64_t)p.bvh4.depth; stats[6] = p.bvh.nodes.size(); stats[7] = p.sv.bvh_flags;
-    stats[12] = 3ull * (uint64_t)p.bvh4.depth + 2ull;
-    if (p.bvh4.nodes.empty()) return RTX_OK;
-
-    struct Box { float lo[3], hi[3]; };
-    auto inside = [](const Box &c, const Box &o) {
-        for (int a = 0; a < 3; ++a) if (!(c.lo[a] >= o.lo[a] && c.hi[a] <= o.hi[a])) return false;
-        return true;
-    };
-    auto bits = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
-    const size_t n_nodes = p.bvh4.nodes.size();
-    std::vector<uint8_t> node_seen(n_nodes, 0), sphere_seen(p.spheres.size(), 0), tri_seen(p.sv.n_tri_tree, 0);
-    struct Item { uint32_t link; Box box; int depth; };
-    std::vector<Item> todo;
-    Box all;
-    for (int a = 0; a < 3; ++a) { all.lo[a] = -INFINITY; all.hi[a] = INFINITY; }
-    todo.push_back({p.bvh4.root, all, 1});
-    int depth = 0;
-    while (!todo.empty()) {
-        const Item it = todo.back();
-        todo.pop_back();
-        const uint32_t idx = it.link & ~kBvhFlatNode;
-        const bool flat = (it.link & kBvhFlatNode) != 0u;
-        if (idx >= n_nodes) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: link out of range");
-        if (node_seen[idx]++) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: node reached twice");
-        depth = std::max(depth, it.depth);
-        if (flat) stats[11] += 1;
-        const Bvh4Node &w = p.bvh4.nodes[idx];
-        for (int c = 0; c < 4; ++c) {
-            Box b;
-            uint32_t link, count;
-            if (flat) {
-                const float lk[4] = { w.b[0].x, w.b[0].y, w.b[0].z, w.b[0].w }, ct[4] = { w.b[1].x, w.b[1].y, w.b[1].z, w.b[1].w };
-                b.lo[0] = w.a[c].x; b.lo[1] = w.a[c].y; b.hi[0] = w.a[c].z; b.hi[1] = w.a[c].w; b.lo[2] = -INFINITY; b.hi[2] = INFINITY;
-                link = bits(lk[c]); count = bits(ct[c]);
-            } else {
-                b.lo[0] = w.a[c].x; b.lo[1] = w.a[c].y; b.lo[2] = w.a[c].z; b.hi[0] = w.b[c].x; b.hi[1] = w.b[c].y; b.hi[2] = w.b[c].z;
-                link = bits(w.a[c].w); count = bits(w.b[c].w);
-            }
-            if (count == 0xFFFFFFFFu) continue;                                   // empty slot
-            if (!inside(b, it.box)) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: child box outside its parent's");
-            if (count == 0u) { todo.push_back({link, b, it.depth + 1}); continue; }
-            const uint32_t n = count & 0xFFFFu;
-            stats[10] = std::max<uint64_t>(stats[10], n);
-            if (count & kBvhTriLeaf) {
-                for (uint32_t k = 0; k < n; ++k) {
-                    const uint32_t rec = link + k;
-                    if (rec >= p.sv.n_tri_tree) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: triangle record out of range");
-                    if (tri_seen[rec]++) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: triangle in two leaves");
-                    const TriX &tx = p.tris[p.tri_fidx[rec]];
-                    const RtxObject &o = objects[tx.id];
-                    const int free_axis = p.tri_rec_free_axis[rec];
-                    if (free_axis != 3 - (int)tx.i - (int)tx.j) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: footprint plane differs from the elimination's rows");
-                    if (flat && free_axis != 2) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: a flat node holds a triangle that is not solved in (x, y)");
-                    if (!(std::isinf(b.lo[free_axis]) && std::isinf(b.hi[free_axis]))) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: triangle leaf bounded along the axis its test does not read");
-                    BvhBox fp;
-                    if (!triangle_footprint(o.geom, fp, free_axis)) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: non-finite triangle in the tree");
-                    for (int a = 0; a < 3; ++a)
-                        if (a != free_axis && !((double)b.lo[a] <= fp.lo[a] && (double)b.hi[a] >= fp.hi[a]))
-                            return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: footprint outside its leaf");
-                    stats[9] += 1;
-                    stats[13 + (free_axis == 2 ? 0 : 1)] += 1;          // 13: (x, y) footprints, 14: (x, z) and (y, z)
-                }
-            } else {
-                for (uint32_t k = 0; k < n; ++k) {
-                    if (link + k >= p.bvh.prims.size()) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: sphere entry out of range");
-                    const uint32_t sidx = p.bvh.prims[link + k];
-                    if (sidx >= p.spheres.size() || sphere_seen[sidx]++) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: sphere in two leaves");
-                    BvhBox sb;
-                    if (!sphere_box(objects[p.sphere_id[sidx]].geom, sb)) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: non-finite sphere in the tree");
-                    for (int a = 0; a < 3; ++a)
-                        if (!((double)b.lo[a] <= sb.lo[a] && (double)b.hi[a] >= sb.hi[a]))
-                            return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: sphere outside its leaf");
-                    stats[8] += 1;
-                }
-            }
-        }
-    }
-    if (p.sv.bvh_flags & 8u) {                     // the 64-byte form: every decoded child rectangle contains the 128-byte node's
-        if (p.qnodes.size() != n_nodes) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: quantised node count differs");
-        for (size_t k = 0; k < n_nodes; ++k) {
-            const Bvh4Node &w = p.bvh4.nodes[k];
-            const BvhQNode &q = p.qnodes[k];
-            const float lk[4] = { w.b[0].x, w.b[0].y, w.b[0].z, w.b[0].w }, ct[4] = { w.b[1].x, w.b[1].y, w.b[1].z, w.b[1].w };
-            for (int c = 0; c < 4; ++c) {
-                const uint32_t count = bits(ct[c]), type = q.link[c] >> kQNodeShift;
-                if ((count == 0xFFFFFFFFu) != (type == kQNodeEmpty)) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: quantised node: empty slot differs");
-                if (type == kQNodeEmpty) continue;
-                if ((q.link[c] & kQNodeIndexMask) != (bits(lk[c]) & ~kBvhFlatNode) || (type == 0u) != (count == 0u) ||
-                    (type != 0u && type != (count & 0xFFFFu)))
-                    return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: quantised node: link / count differs");
-                const double lx = (double)q.ox + (double)(q.qx[c] & 0xFFFFu) * q.sx, hx = (double)q.ox + (double)(q.qx[c] >> 16) * q.sx;
-                const double ly = (double)q.oy + (double)(q.qy[c] & 0xFFFFu) * q.sy, hy = (double)q.oy + (double)(q.qy[c] >> 16) * q.sy;
-                if (!(lx <= (double)w.a[c].x && ly <= (double)w.a[c].y && hx >= (double)w.a[c].z && hy >= (double)w.a[c].w))
-                    return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: quantised rectangle does not contain the child's");
-            }
-        }
-        stats[15] = p.qnodes.size();
-    }
-    if (p.sv.bvh_flags & 16u) {                    // a sphere tree's 64-byte form: every decoded child box contains the 128-byte node's
-        if (p.q3nodes.size() != n_nodes) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: 64-byte sphere node count differs");
-        for (size_t k = 0; k < n_nodes; ++k) {
-            const Bvh4Node &w = p.bvh4.nodes[k];
-            const BvhQ3Node &q = p.q3nodes[k];
-            const uint32_t *lows[3] = { &q.lox, &q.loy, &q.loz }, *highs[3] = { &q.hix, &q.hiy, &q.hiz };
-            const float org[3] = { q.ox, q.oy, q.oz }, stp[3] = { q.sx, q.sy, q.sz };
-            for (int c = 0; c < 4; ++c) {
-                const uint32_t count = bits(w.b[c].w), type = q.link(c) >> kQNodeShift;
-                if ((count == 0xFFFFFFFFu) != (type == kQNodeEmpty)) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: 64-byte sphere node: empty slot differs");
-                if (type == kQNodeEmpty) continue;
-                if ((q.link(c) & kQNodeIndexMask) != bits(w.a[c].w) || (type == 0u) != (count == 0u) || (type != 0u && type != count))
-                    return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: 64-byte sphere node: link / count differs");
-                const float l[3] = { w.a[c].x, w.a[c].y, w.a[c].z }, hh[3] = { w.b[c].x, w.b[c].y, w.b[c].z };
-                for (int a = 0; a < 3; ++a) {
-                    // decoded exactly as the device does: one f32 FMA of an exact product
-                    const float dl = std::fmaf((float)((*lows[a] >> (8 * c)) & 255u), stp[a], org[a]);
-                    const float dh = std::fmaf((float)((*highs[a] >> (8 * c)) & 255u), stp[a], org[a]);
-                    if (!((double)dl <= (double)l[a] - p.bvh.abs_pad * 0.999 && (double)dh >= (double)hh[a] + p.bvh.abs_pad * 0.999))
-                        return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: decoded 64-byte box does not contain the child's (+ pad)");
-                }
-            }
-        }
-        stats[15] = p.q3nodes.size();
-    }
-    if (depth != p.bvh4.depth) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: recorded depth differs");
-    for (size_t k = 0; k < n_nodes; ++k) if (!node_seen[k]) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: unreachable node");
-    if ((p.sv.bvh_flags & 1u) && stats[8] != p.spheres.size()) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: a sphere is in no leaf");
-    if ((p.sv.bvh_flags & 2u) && stats[9] != p.sv.n_tri_tree) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: a triangle is in no leaf");
-    return RTX_OK;
-}
-
 extern "C" {
-
-int32_t rtx_debug_host_scene(const RtxScene *scene, uint64_t *stats)
-{
-    if (!scene || !stats) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_host_scene: null argument");
-    if (scene->n_objects && !scene->objects) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_host_scene: objects is null");
-    PackedScene p;
-    if (int32_t rc = pack_scene(scene, p)) return rc;
-    return check_packed(p, scene->objects, stats);
-}
-
-#ifdef RTX_LAB
-// rtx_debug_host_refit / rtx_debug_host_refit_mesh: `who` names the hook in messages; digests: 8 values, or 16 when `info` is given.
-static int32_t host_refit(const char *who, const RtxScene *scene, const uint64_t *indices, const RtxObject *objects, uint64_t n, uint32_t mode,
-                          uint64_t *stats, uint32_t *how, uint64_t *digests, double *info)
-{
-    if (!scene || !stats || !how || !digests) return fail(RTX_ERR_INVALID_ARGUMENT, std::string(who) + ": null argument");
-    if (scene->n_objects && !scene->objects) return fail(RTX_ERR_INVALID_ARGUMENT, std::string(who) + ": objects is null");
-    *how = RTX_UPDATED_NOTHING;
-    const uint64_t split = mode >> 16;                       // (lab) entries [0, split) are one update, [split, n) the next
-    mode &= 0xFFFFu;
-    if (split > n) return fail(RTX_ERR_INVALID_ARGUMENT, std::string(who) + ": the split point is beyond n");
-    std::vector<RtxObject> cur(scene->objects, scene->objects + scene->n_objects);
-    RtxScene sc = *scene;
-    PackedScene p;
-    if (int32_t rc = pack_scene(&sc, p)) return rc;
-    RefitTables t = make_refit_tables(p);
-    const uint64_t cut[3] = { 0, split, n };
-    for (int part = split ? 0 : 1; part < 2; ++part) {
-        const uint64_t first = cut[part], count = cut[part + 1] - cut[part];
-        UpdatePlan plan;
-        if (int32_t rc = plan_update(cur, t, p.sv.sphere_cmax, indices ? indices + first : nullptr, objects ? objects + first : nullptr, count, mode, plan))
-            return rc;
-        if (plan.how == RTX_UPDATED_REFIT || plan.how == RTX_UPDATED_RECORDS) {
-            std::vector<float> box32, tribox32;
-            std::vector<double> reach, tri_reach;
-            derive_all_spheres(p, cur.data(), t, box32, reach);
-            if (plan.tri_geom) derive_all_triangles(cur.data(), cur.size(), t, tribox32, tri_reach);
-            if (refit_packed(p, t, plan, box32, reach, tribox32, tri_reach) & (kUpdateStatusNoQ3 | kUpdateStatusNoQ)) plan.how = RTX_UPDATED_REBUILT;
-        }
-        for (const UpdateEntry &e : plan.entries) std::memcpy(&cur[e.object], &e.kind, sizeof(RtxObject));
-        if (plan.how == RTX_UPDATED_REBUILT) {
-            sc.objects = cur.data();
-            p = PackedScene();
-            if (int32_t rc = pack_scene(&sc, p)) return rc;
-            t = make_refit_tables(p);
-        }
-        if (plan.how > *how) *how = plan.how;
-    }
-    if (info) {
-        digest_packed_mesh(p, digests);
-        for (int c = 0; c < 3; ++c) info[c] = t.centre[c];
-        info[3] = p.sv.tri_extent; info[4] = p.sv.sphere_cmax; info[5] = t.abs_pad; info[6] = t.scale; info[7] = 0.0;
-    } else digest_packed(p, digests);
-    return check_packed(p, cur.data(), stats);
-}
-
-// The resident arrays, downloaded into the shape digest_packed / digest_packed_mesh read.
-static int32_t fetch_resident(RtxSceneHandle_ *h, bool mesh, PackedScene &p)
-{
-    RTX_HIP_CHECK(hipSetDevice(h->device));
-    RTX_HIP_CHECK(hipDeviceSynchronize());
-    const SceneView &sv = h->sv;
-    auto fetch = [](auto &vec, const void *src, size_t count) -> hipError_t {
-        vec.resize(count);
-        return count && src ? hipMemcpy(vec.data(), src, count * sizeof(vec[0]), hipMemcpyDeviceToHost) : hipSuccess;
-    };
-    const size_t n_leaf = h->refit.sphere_tree ? h->refit.slot.size() : 0;
-    RTX_HIP_CHECK(fetch(p.bvh4.nodes, sv.bvh_nodes, sv.n_bvh_nodes));
-    RTX_HIP_CHECK(fetch(p.q3nodes, sv.bvh_q3nodes, sv.bvh_q3nodes ? sv.n_bvh_nodes : 0));
-    RTX_HIP_CHECK(fetch(p.leaf32, sv.bvh_leaf_f32, n_leaf));
-    RTX_HIP_CHECK(fetch(p.leaf_cr, sv.bvh_leaf_cr, n_leaf));
-    RTX_HIP_CHECK(fetch(p.sph32, sv.sphere_f32, ((size_t)sv.n_spheres + 3) & ~(size_t)3));
-    RTX_HIP_CHECK(fetch(p.spheres, sv.spheres, sv.n_spheres));
-    RTX_HIP_CHECK(fetch(p.planes, sv.planes, sv.n_planes));
-    RTX_HIP_CHECK(fetch(p.mats, sv.materials, sv.n_objects));
-    p.sv.sphere_cmax = sv.sphere_cmax;
-    if (!mesh) return RTX_OK;
-    RTX_HIP_CHECK(fetch(p.tris, sv.tris, sv.n_tris));
-    RTX_HIP_CHECK(fetch(p.tri32, sv.tri_f32, sv.n_tri_filter ? 2 * ((size_t)sv.n_tri_filter + 1) : 0));      // (+ the pad record)
-    RTX_HIP_CHECK(fetch(p.tri_geo, sv.tri_geo, 2 * (size_t)sv.n_tri_tree));
-    RTX_HIP_CHECK(fetch(p.qnodes, sv.bvh_qnodes, sv.bvh_qnodes ? sv.n_bvh_nodes : 0));
-    p.sv.tri_extent = sv.tri_extent;
-    return RTX_OK;
-}
-#endif
-
-int32_t rtx_debug_host_refit(const RtxScene *scene, const uint64_t *indices, const RtxObject *objects, uint64_t n, uint32_t mode,
-                             uint64_t *stats, uint32_t *how, uint64_t *digests)
-{
-#ifdef RTX_LAB
-    return host_refit("rtx_debug_host_refit", scene, indices, objects, n, mode, stats, how, digests, nullptr);
-#else
-    (void)scene; (void)indices; (void)objects; (void)n; (void)mode; (void)stats; (void)how; (void)digests;
-    return fail(RTX_ERR_UNSUPPORTED, "rtx_debug_host_refit is a hook of the lab library (librtx_hip_lab.so)");
-#endif
-}
-
-int32_t rtx_debug_host_refit_mesh(const RtxScene *scene, const uint64_t *indices, const RtxObject *objects, uint64_t n, uint32_t mode,
-                                  uint64_t *stats, uint32_t *how, uint64_t *digests, double *info)
-{
-#ifdef RTX_LAB
-    if (!info) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_host_refit_mesh: null argument");
-    return host_refit("rtx_debug_host_refit_mesh", scene, indices, objects, n, mode, stats, how, digests, info);
-#else
-    (void)scene; (void)indices; (void)objects; (void)n; (void)mode; (void)stats; (void)how; (void)digests; (void)info;
-    return fail(RTX_ERR_UNSUPPORTED, "rtx_debug_host_refit_mesh is a hook of the lab library (librtx_hip_lab.so)");
-#endif
-}
-
-int32_t rtx_debug_resident_digests(RtxSceneHandle h, uint64_t *digests)
-{
-#ifdef RTX_LAB
-    if (!h || !digests) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_resident_digests: null argument");
-    PackedScene p;
-    if (int32_t rc = fetch_resident(h, false, p)) return rc;
-    digest_packed(p, digests);
-    return RTX_OK;
-#else
-    (void)h; (void)digests;
-    return fail(RTX_ERR_UNSUPPORTED, "rtx_debug_resident_digests is a hook of the lab library (librtx_hip_lab.so)");
-#endif
-}
-
-int32_t rtx_debug_resident_mesh_digests(RtxSceneHandle h, uint64_t *digests)
-{
-#ifdef RTX_LAB
-    if (!h || !digests) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_resident_mesh_digests: null argument");
-    PackedScene p;
-    if (int32_t rc = fetch_resident(h, true, p)) return rc;
-    digest_packed_mesh(p, digests);
-    return RTX_OK;
-#else
-    (void)h; (void)digests;
-    return fail(RTX_ERR_UNSUPPORTED, "rtx_debug_resident_mesh_digests is a hook of the lab library (librtx_hip_lab.so)");
-#endif
-}
-
-int32_t rtx_debug_paths(RtxSceneHandle h, uint32_t width, uint32_t height, uint32_t row, uint32_t max_steps, RtxPathStep *steps,
-                        uint32_t *counts)
-{
-#ifdef RTX_LAB
-    static_assert(sizeof(RtxPathStep) == sizeof(PathStep) && sizeof(PathStep) == 64, "RtxPathStep layout");
-    if (!h || !steps || !counts) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_paths: null argument");
-    if (width == 0 || row >= height || max_steps == 0) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_paths: bad row / size");
-    const uint64_t paths = (uint64_t)width * h->cfg.rays_per_pixel;
-    if (paths == 0) return RTX_OK;
-    if (paths * max_steps > (1ull << 24)) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_paths: more than 2^24 steps asked for");
-    RTX_HIP_CHECK(hipSetDevice(h->device));
-    struct Bufs {                                   // freed, and the handle's pointers cleared, on every return path
-        RtxSceneHandle_ *h; double *rgb = nullptr; uint32_t kernel;
-        ~Bufs() {
-            (void)hipDeviceSynchronize();
-            if (h->transcript) (void)hipFree(h->transcript);
-            if (h->transcript_counts) (void)hipFree(h->transcript_counts);
-            if (rgb) (void)hipFree(rgb);
-            h->transcript = nullptr; h->transcript_counts = nullptr; h->transcript_steps = 0; h->cfg.kernel = kernel;
-        }
-    } d{h, nullptr, h->cfg.kernel};
-    RTX_HIP_CHECK(hipMalloc((void **)&h->transcript, paths * max_steps * sizeof(PathStep)));
-    RTX_HIP_CHECK(hipMalloc((void **)&h->transcript_counts, paths * sizeof(uint32_t)));
-    RTX_HIP_CHECK(hipMalloc((void **)&d.rgb, (size_t)width * 3 * sizeof(double)));
-    RTX_HIP_CHECK(hipMemset(h->transcript, 0, paths * max_steps * sizeof(PathStep)));
-    h->transcript_steps = max_steps;
-    h->cfg.kernel = RTX_KERNEL_EXACT;
-    RtxStats st;
-    if (int32_t rc = render_band(h, width, height, row, 1u, 1u, 1u, d.rgb, nullptr, &st)) return rc;
-    if (st.trace_launches != 1) return fail(RTX_ERR_UNSUPPORTED, "rtx_debug_paths: the row did not fit one launch");
-    RTX_HIP_CHECK(hipMemcpy(steps, h->transcript, paths * max_steps * sizeof(PathStep), hipMemcpyDeviceToHost));
-    RTX_HIP_CHECK(hipMemcpy(counts, h->transcript_counts, paths * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return RTX_OK;
-#else
-    (void)h; (void)width; (void)height; (void)row; (void)max_steps; (void)steps; (void)counts;
-    return fail(RTX_ERR_UNSUPPORTED, "rtx_debug_paths: a lab-library hook (librtx_hip_lab.so)");
-#endif
-}
-
-int32_t rtx_debug_math(int32_t op, const double *a, const double *b, double *out, uint64_t n)
-{
-#ifndef RTX_LAB
-    (void)op; (void)a; (void)b; (void)out; (void)n;
-    return fail(RTX_ERR_UNSUPPORTED, "rtx_debug_math: a lab-library hook (librtx_hip_lab.so: the same sources, the same arithmetic)");
-#else
-    if (n == 0) return RTX_OK;
-    if (!a || !out) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_math: null argument");
-    if (op >= 17 && op <= 21)                       // the host forms of the index arithmetic: no device is touched
-        return debug_math_host(op, a, b ? b : a, out, n) ? RTX_OK : fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_math: op 18 takes three values in b");
-    if (usable_device_count() == 0) return fail(RTX_ERR_NO_DEVICE, "no gfx950 device");
-    struct Bufs {                                   // freed on every return path
-        double *p[3] = { nullptr, nullptr, nullptr };
-        ~Bufs() { for (double *q : p) if (q) (void)hipFree(q); }
-    } d;
-    RTX_HIP_CHECK(hipSetDevice(0));
-    for (double *&q : d.p) RTX_HIP_CHECK(hipMalloc((void **)&q, n * sizeof(double)));
-    RTX_HIP_CHECK(hipMemcpy(d.p[0], a, n * sizeof(double), hipMemcpyHostToDevice));
-    RTX_HIP_CHECK(hipMemcpy(d.p[1], b ? b : a, n * sizeof(double), hipMemcpyHostToDevice));
-    RTX_HIP_CHECK(launch_debug_math(op, d.p[0], d.p[1], d.p[2], n, b ? b : a, nullptr));
-    RTX_HIP_CHECK(hipMemcpy(out, d.p[2], n * sizeof(double), hipMemcpyDeviceToHost));
-    return RTX_OK;
-#endif
-}
-
-#ifdef RTX_LAB
-namespace {
-// device copies of the host arrays of rtx_debug_store_samples / _resolve / _gather: freed on every return path
-struct DebugBufs {
-    std::vector<void *> p;
-    ~DebugBufs() { for (void *q : p) if (q) (void)hipFree(q); }
-    // a device buffer of `bytes` bytes holding `host`'s, and `tail` bytes of 0xFF behind them (null host or 0 bytes: a null pointer,
-    // nothing is allocated)
-    hipError_t up(const void *host, size_t bytes, void **out, size_t tail = 0)
-    {
-        *out = nullptr;
-        if (!host || bytes == 0) return hipSuccess;
-        hipError_t e = hipMalloc(out, bytes + tail);
-        if (e != hipSuccess) return e;
-        p.push_back(*out);
-        if (tail && (e = hipMemset(static_cast<char *>(*out) + bytes, 0xFF, tail)) != hipSuccess) return e;
-        return hipMemcpy(*out, host, bytes, hipMemcpyHostToDevice);
-    }
-};
-}  // namespace
-#endif
-
-int32_t rtx_debug_store_samples(const double *rgb, const uint64_t *slots, uint64_t n, uint64_t nonzero_base, double *records,
-                                uint64_t n_records, uint32_t *mask, uint64_t n_words)
-{
-#ifndef RTX_LAB
-    (void)rgb; (void)slots; (void)n; (void)nonzero_base; (void)records; (void)n_records; (void)mask; (void)n_words;
-    return fail(RTX_ERR_UNSUPPORTED, "rtx_debug_store_samples: a lab-library hook (librtx_hip_lab.so)");
-#else
-    if (n == 0) return RTX_OK;
-    if (!rgb || !slots || !records || !mask) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_store_samples: null argument");
-    if (n > (1ull << 24) || n_records > (1ull << 26) || n_words > (1ull << 26) || nonzero_base > (1ull << 40))
-        return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_store_samples: too large");
-    {   // every record and every bit inside the caller's buffers, no slot twice
-        std::vector<uint64_t> seen(slots, slots + n);
-        std::sort(seen.begin(), seen.end());
-        for (uint64_t i = 0; i < n; ++i) {
-            if (seen[i] >= n_records || ((nonzero_base + seen[i]) >> 5) >= n_words)
-                return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_store_samples: a slot's record or bit lies outside the buffers");
-            if (i && seen[i] == seen[i - 1]) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_store_samples: a slot appears twice");
-        }
-    }
-    if (usable_device_count() == 0) return fail(RTX_ERR_NO_DEVICE, "no gfx950 device");
-    RTX_HIP_CHECK(hipSetDevice(0));
-    DebugBufs d;
-    void *d_rgb, *d_slots, *d_rec, *d_mask;
-    RTX_HIP_CHECK(d.up(rgb, n * 3 * sizeof(double), &d_rgb));
-    RTX_HIP_CHECK(d.up(slots, n * sizeof(uint64_t), &d_slots));
-    RTX_HIP_CHECK(d.up(records, n_records * 4 * sizeof(double), &d_rec));
-    RTX_HIP_CHECK(d.up(mask, n_words * sizeof(uint32_t), &d_mask));
-    RowsView rv{};
-    rv.nonzero = static_cast<uint32_t *>(d_mask);
-    rv.nonzero_base = nonzero_base;
-    RTX_HIP_CHECK(launch_debug_store_samples(static_cast<const double *>(d_rgb), static_cast<const uint64_t *>(d_slots), n,
-                                             static_cast<double *>(d_rec), rv, nullptr));
-    RTX_HIP_CHECK(hipMemcpy(records, d_rec, n_records * 4 * sizeof(double), hipMemcpyDeviceToHost));   // (the null stream: after the kernel)
-    RTX_HIP_CHECK(hipMemcpy(mask, d_mask, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return RTX_OK;
-#endif
-}
-
-int32_t rtx_debug_resolve(const double *records, const uint32_t *mask, uint32_t width, uint32_t n_rows, uint32_t tiles_x,
-                          uint32_t n_samples, uint64_t rays_per_pixel, int32_t first, int32_t last, double *acc, uint64_t acc_doubles,
-                          double *out, uint64_t out_doubles)
-{
-#ifndef RTX_LAB
-    (void)records; (void)mask; (void)width; (void)n_rows; (void)tiles_x; (void)n_samples; (void)rays_per_pixel; (void)first; (void)last;
-    (void)acc; (void)acc_doubles; (void)out; (void)out_doubles;
-    return fail(RTX_ERR_UNSUPPORTED, "rtx_debug_resolve: a lab-library hook (librtx_hip_lab.so)");
-#else
-    const uint64_t npix = (uint64_t)width * n_rows;
-    if (npix == 0) return RTX_OK;
-    if (tiles_x != 0 && tiles_x != (width + 7u) / 8u) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_resolve: tiles_x is 0 or ceil(width / 8)");
-    const uint64_t per_sample64 = tiles_x ? (uint64_t)tiles_x * ((n_rows + 7u) / 8u) * 64u : npix;     // as render_band sizes a sample
-    if (per_sample64 * ((uint64_t)n_samples + 1) > (1ull << 26)) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_resolve: too large");
-    if (n_samples != 0 && (!records || !mask)) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_resolve: null records or mask");
-    if ((!first || !last) && (!acc || acc_doubles < 3 * npix)) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_resolve: acc holds 3 doubles per pixel");
-    if (last && (!out || out_doubles < 3 * npix)) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_resolve: out holds 3 doubles per pixel");
-    if (usable_device_count() == 0) return fail(RTX_ERR_NO_DEVICE, "no gfx950 device");
-    RTX_HIP_CHECK(hipSetDevice(0));
-    const uint64_t n_rays = per_sample64 * n_samples;
-    DebugBufs d;
-    void *d_rec, *d_mask, *d_acc, *d_out;
-    // behind the caller's records and bits lie one more sample's worth of NaN records under set bits: a fold that reads a sample
-    // too many stays inside the buffers and shows in the frame
-    const size_t rec_bytes = n_rays * 4 * sizeof(double), mask_bytes = (size_t)((n_rays + 31) / 32) * sizeof(uint32_t);
-    RTX_HIP_CHECK(d.up(records, rec_bytes, &d_rec, per_sample64 * 4 * sizeof(double)));
-    RTX_HIP_CHECK(d.up(mask, mask_bytes, &d_mask, nonzero_mask_bytes(per_sample64) + sizeof(uint32_t)));
-    RTX_HIP_CHECK(d.up(acc, acc_doubles * sizeof(double), &d_acc));
-    RTX_HIP_CHECK(d.up(out, out_doubles * sizeof(double), &d_out));
-    RowsView rv{};                                     // the fields launch_resolve reads, as render_band fills them
-    rv.width = width; rv.n_rows = n_rows; rv.npix = (uint32_t)npix; rv.tiles_x = tiles_x;
-    rv.n_samples = n_samples; rv.n_rays = n_rays;
-    rv.nonzero = static_cast<uint32_t *>(d_mask); rv.nonzero_base = 0;
-    RTX_HIP_CHECK(launch_resolve(static_cast<const double *>(d_rec), static_cast<double *>(d_acc), static_cast<double *>(d_out), rv,
-                                 (uint32_t)per_sample64, rays_per_pixel, first != 0, last != 0, nullptr));
-    if (d_acc) RTX_HIP_CHECK(hipMemcpy(acc, d_acc, acc_doubles * sizeof(double), hipMemcpyDeviceToHost));
-    if (d_out) RTX_HIP_CHECK(hipMemcpy(out, d_out, out_doubles * sizeof(double), hipMemcpyDeviceToHost));
-    RTX_HIP_CHECK(hipDeviceSynchronize());
-    return RTX_OK;
-#endif
-}
-
-int32_t rtx_debug_resolve_moments(const double *records, const uint32_t *mask, uint32_t width, uint32_t n_rows, uint32_t tiles_x,
-                                  uint32_t n_samples, double *sum, uint64_t sum_doubles, double *sum_sq, uint64_t sum_sq_doubles)
-{
-#ifndef RTX_LAB
-    (void)records; (void)mask; (void)width; (void)n_rows; (void)tiles_x; (void)n_samples; (void)sum; (void)sum_doubles; (void)sum_sq;
-    (void)sum_sq_doubles;
-    return fail(RTX_ERR_UNSUPPORTED, "rtx_debug_resolve_moments: a lab-library hook (librtx_hip_lab.so)");
-#else
-    const uint64_t npix = (uint64_t)width * n_rows;
-    if (npix == 0) return RTX_OK;
-    if (tiles_x != 0 && tiles_x != (width + 7u) / 8u) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_resolve_moments: tiles_x is 0 or ceil(width / 8)");
-    const uint64_t per_sample64 = tiles_x ? (uint64_t)tiles_x * ((n_rows + 7u) / 8u) * 64u : npix;     // as render_band sizes a sample
-    if (per_sample64 * ((uint64_t)n_samples + 1) > (1ull << 26)) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_resolve_moments: too large");
-    if (n_samples != 0 && (!records || !mask)) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_resolve_moments: null records or mask");
-    if (!sum || sum_doubles < 3 * npix) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_resolve_moments: sum holds 3 doubles per pixel");
-    if (sum_sq && sum_sq_doubles < 3 * npix) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_resolve_moments: sum_sq holds 3 doubles per pixel");
-    if (usable_device_count() == 0) return fail(RTX_ERR_NO_DEVICE, "no gfx950 device");
-    RTX_HIP_CHECK(hipSetDevice(0));
-    const uint64_t n_rays = per_sample64 * n_samples;
-    DebugBufs d;
-    void *d_rec, *d_mask, *d_sum, *d_sq;
-    // (as rtx_debug_resolve: one more sample's worth of NaN records under set bits behind the caller's records and bits)
-    const size_t rec_bytes = n_rays * 4 * sizeof(double), mask_bytes = (size_t)((n_rays + 31) / 32) * sizeof(uint32_t);
-    RTX_HIP_CHECK(d.up(records, rec_bytes, &d_rec, per_sample64 * 4 * sizeof(double)));
-    RTX_HIP_CHECK(d.up(mask, mask_bytes, &d_mask, nonzero_mask_bytes(per_sample64) + sizeof(uint32_t)));
-    RTX_HIP_CHECK(d.up(sum, sum_doubles * sizeof(double), &d_sum));
-    RTX_HIP_CHECK(d.up(sum_sq, sum_sq_doubles * sizeof(double), &d_sq));
-    RowsView rv{};                                     // the fields launch_resolve reads, as render_band fills them
-    rv.width = width; rv.n_rows = n_rows; rv.npix = (uint32_t)npix; rv.tiles_x = tiles_x;
-    rv.n_samples = n_samples; rv.n_rays = n_rays;
-    rv.nonzero = static_cast<uint32_t *>(d_mask); rv.nonzero_base = 0;
-    RTX_HIP_CHECK(launch_resolve(static_cast<const double *>(d_rec), static_cast<double *>(d_sum), nullptr, rv, (uint32_t)per_sample64,
-                                 n_samples, false, false, nullptr, static_cast<double *>(d_sq)));
-    RTX_HIP_CHECK(hipMemcpy(sum, d_sum, sum_doubles * sizeof(double), hipMemcpyDeviceToHost));
-    if (d_sq) RTX_HIP_CHECK(hipMemcpy(sum_sq, d_sq, sum_sq_doubles * sizeof(double), hipMemcpyDeviceToHost));
-    RTX_HIP_CHECK(hipDeviceSynchronize());
-    return RTX_OK;
-#endif
-}
-
-int32_t rtx_debug_gather(int32_t form, const void *parts, uint32_t width, uint32_t height, uint32_t n, uint32_t cap_rows,
-                         uint32_t block, int32_t flip, void *full)
-{
-#ifndef RTX_LAB
-    (void)form; (void)parts; (void)width; (void)height; (void)n; (void)cap_rows; (void)block; (void)flip; (void)full;
-    return fail(RTX_ERR_UNSUPPORTED, "rtx_debug_gather: a lab-library hook (librtx_hip_lab.so)");
-#else
-    if (form < 0 || form > 2) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_gather: form is 0, 1 or 2");
-    const uint64_t vals = (uint64_t)width * height * 3;
-    if (vals == 0) return RTX_OK;
-    if (!parts || !full) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_gather: null argument");
-    if (vals > (1ull << 26)) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_gather: too large");
-    uint64_t in_vals = vals;                            // form 2: the band itself
-    if (form != 2) {
-        if (n == 0 || block == 0 || cap_rows == 0 || (uint64_t)n * cap_rows * width * 3 > (1ull << 26))
-            return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_gather: bad partition");
-        if (form == 0 && flip) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_gather: the f64 form has no flip");
-        for (uint32_t y = 0; y < height; ++y) {        // every row the kernel reads lies inside its part's cap_rows
-            const uint32_t b = y / block;
-            if ((uint64_t)(b / n) * block + (y - b * block) >= cap_rows)
-                return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_gather: cap_rows is below a part's row count");
-        }
-        in_vals = (uint64_t)n * cap_rows * width * 3;
-    }
-    if (usable_device_count() == 0) return fail(RTX_ERR_NO_DEVICE, "no gfx950 device");
-    RTX_HIP_CHECK(hipSetDevice(0));
-    const size_t in_bytes = form == 1 ? 1 : sizeof(double), out_bytes = form == 0 ? sizeof(double) : 1;
-    DebugBufs d;
-    void *d_parts, *d_full;
-    RTX_HIP_CHECK(d.up(parts, in_vals * in_bytes, &d_parts));
-    RTX_HIP_CHECK(d.up(full, vals * out_bytes, &d_full));
-    if (form == 0)
-        RTX_HIP_CHECK(launch_deinterleave(static_cast<const double *>(d_parts), static_cast<double *>(d_full), width, height, n, cap_rows,
-                                          block, nullptr));
-    else if (form == 1)
-        RTX_HIP_CHECK(launch_deinterleave_u8(static_cast<const uint8_t *>(d_parts), static_cast<uint8_t *>(d_full), width, height, n,
-                                             cap_rows, block, flip != 0, nullptr));
-    else
-        RTX_HIP_CHECK(launch_quantize_values(static_cast<const double *>(d_parts), static_cast<uint8_t *>(d_full), width, height, nullptr));
-    RTX_HIP_CHECK(hipMemcpy(full, d_full, vals * out_bytes, hipMemcpyDeviceToHost));
-    return RTX_OK;
-#endif
-}
-
-int32_t rtx_debug_path_bounds(RtxSceneHandle h, const RtxRay *rays, const uint32_t *objects, const float *best_up, uint64_t n, uint32_t form,
-                              uint32_t *out, double *scene_info, uint32_t *records, uint32_t *path_data, uint32_t path_steps)
-{
-#ifndef RTX_LAB
-    (void)h; (void)rays; (void)objects; (void)best_up; (void)n; (void)form; (void)out; (void)scene_info; (void)records; (void)path_data;
-    (void)path_steps;
-    return fail(RTX_ERR_UNSUPPORTED, "rtx_debug_path_bounds: a lab-library hook (librtx_hip_lab.so)");
-#else
-    if (!h) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_path_bounds: null scene");
-    if (scene_info) {
-        const SceneView &v = h->sv;
-        const double info[16] = { v.sphere_center[0], v.sphere_center[1], v.sphere_center[2], v.sphere_cmax, (double)v.bvh_origin_limit,
-                                  (double)v.bvh_inv_max, v.tri_extent, (double)v.bvh_flags, (double)v.bvh_depth, (double)v.n_bvh_nodes,
-                                  (double)v.n_tri_tree, (double)v.n_spheres, 0.0, 0.0, 0.0, 0.0 };
-        std::memcpy(scene_info, info, sizeof info);
-    }
-    if (n == 0) return RTX_OK;
-    if (!rays || !objects || !best_up || !out) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_path_bounds: null argument");
-    if (n > (1ull << 22) || (path_data && n * (uint64_t)path_steps > (1ull << 24)))
-        return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_path_bounds: too large");
-    if ((form & ~0xB03u) != 0u) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_path_bounds: unknown form");
-    const bool filter_records = (form & 0x800u) != 0u;          // a host-side option of `records`: the device sees the other bits
-    form &= ~0x800u;
-    const SceneView &sv = h->sv;
-    if ((form & 2u) && !((sv.bvh_flags & 16u) && sv.bvh_q3nodes) && !((sv.bvh_flags & 8u) && sv.bvh_qnodes))
-        return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_path_bounds: this scene's tree has no 64-byte nodes");
-    if (sv.n_bvh_nodes > (1u << 22)) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_path_bounds: the tree is too large");
-    RTX_HIP_CHECK(hipSetDevice(h->device));
-    RTX_HIP_CHECK(hipDeviceSynchronize());
-    // the resident tree and the maps from leaf entries to Scene.objects, as the device holds them
-    const bool s_tree = (sv.bvh_flags & 1u) != 0u, t_tree = (sv.bvh_flags & 2u) != 0u;
-    std::vector<Bvh4Node> nodes(sv.n_bvh_nodes);
-    std::vector<uint32_t> prims(s_tree ? sv.n_spheres : 0u), sphere_id(sv.n_spheres), tri_fidx(t_tree ? sv.n_tri_tree : 0u);
-    std::vector<TriX> tris(t_tree ? sv.n_tris : 0u);
-    auto down = [](void *dst, const void *src, size_t bytes) { return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess; };
-    RTX_HIP_CHECK(down(nodes.data(), sv.bvh_nodes, nodes.size() * sizeof(Bvh4Node)));
-    RTX_HIP_CHECK(down(prims.data(), sv.bvh_prims, prims.size() * sizeof(uint32_t)));
-    RTX_HIP_CHECK(down(sphere_id.data(), sv.sphere_id, sphere_id.size() * sizeof(uint32_t)));
-    RTX_HIP_CHECK(down(tri_fidx.data(), sv.tri_fidx, tri_fidx.size() * sizeof(uint32_t)));
-    RTX_HIP_CHECK(down(tris.data(), sv.tris, tris.size() * sizeof(TriX)));
-    // Scene.objects index -> leaf entry (kQueueTri: a triangle filter record of the tree)
-    constexpr uint32_t kTriEntry = 0x80000000u, kNoEntry = 0xFFFFFFFFu;
-    std::vector<uint32_t> entry_of(sv.n_objects, kNoEntry);
-    {
-        std::vector<uint32_t> prim_entry(sv.n_spheres, kNoEntry);
-        for (size_t k = 0; k < prims.size(); ++k) if (prims[k] < prim_entry.size()) prim_entry[prims[k]] = (uint32_t)k;
-        for (size_t s = 0; s < sphere_id.size(); ++s)
-            if (prim_entry[s] != kNoEntry && sphere_id[s] < sv.n_objects) entry_of[sphere_id[s]] = prim_entry[s];
-        for (size_t r = 0; r < tri_fidx.size(); ++r)
-            if (tri_fidx[r] < tris.size() && tris[tri_fidx[r]].id < sv.n_objects) entry_of[tris[tri_fidx[r]].id] = (uint32_t)r | kTriEntry;
-    }
-    // every leaf entry's path: one row of {link, child slot} per entry, found by one walk of the whole tree
-    const uint32_t stride = std::max(sv.bvh_depth, 1u);
-    const size_t n_rows = prims.size() + tri_fidx.size();
-    std::vector<uint32_t> steps(2 * n_rows * stride, 0u), lens(n_rows + 1, 0u);
-    auto bits = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
-    if (!nodes.empty()) {
-        struct Frame { uint32_t link; std::vector<uint32_t> path; };
-        std::vector<Frame> todo;
-        todo.push_back({sv.bvh_root, {}});
-        size_t visited = 0;
-        while (!todo.empty()) {
-            Frame f = std::move(todo.back());
-            todo.pop_back();
-            const uint32_t idx = f.link & ~kBvhFlatNode;
-            if (idx >= nodes.size() || ++visited > nodes.size() || f.path.size() / 2 >= stride)
-                return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_path_bounds: the resident tree is not a tree of the recorded depth");
-            const Bvh4Node &w = nodes[idx];
-            for (uint32_t c = 0; c < 4; ++c) {
-                uint32_t lnk, cnt;
-                if (f.link & kBvhFlatNode) {
-                    const float l4[4] = { w.b[0].x, w.b[0].y, w.b[0].z, w.b[0].w }, c4[4] = { w.b[1].x, w.b[1].y, w.b[1].z, w.b[1].w };
-                    lnk = bits(l4[c]); cnt = bits(c4[c]);
-                } else { lnk = bits(w.a[c].w); cnt = bits(w.b[c].w); }
-                if (cnt == 0xFFFFFFFFu) continue;
-                std::vector<uint32_t> path = f.path;
-                path.push_back(f.link); path.push_back(c);
-                if (cnt == 0u) { todo.push_back({lnk, std::move(path)}); continue; }
-                const bool tri = (cnt & kBvhTriLeaf) != 0u;
-                for (uint32_t k = 0; k < (cnt & 0xFFFFu); ++k) {
-                    const size_t e = (size_t)lnk + k;
-                    if (e >= (tri ? tri_fidx.size() : prims.size())) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_path_bounds: a leaf entry outside its array");
-                    const size_t row = tri ? prims.size() + e : e;
-                    lens[row] = (uint32_t)(path.size() / 2);
-                    std::copy(path.begin(), path.end(), steps.begin() + (ptrdiff_t)(2 * row * stride));
-                }
-            }
-        }
-    }
-    std::vector<uint32_t> entries(n), rows(n);
-    std::vector<Bvh4Node> leaf_nodes(n);
-    for (uint64_t i = 0; i < n; ++i) {
-        if (objects[i] >= sv.n_objects) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_path_bounds: an object index outside Scene.objects");
-        uint32_t e = entry_of[objects[i]];
-        size_t row = n_rows;                                    // (the spare row: length 0)
-        if (e != kNoEntry) {
-            row = (e & kTriEntry) ? prims.size() + (e & ~kTriEntry) : e;
-            if (lens[row] == 0u) e = kNoEntry;                  // (in no leaf: cannot happen for a tree rtx_debug_host_scene accepts)
-        }
-        if (e == kNoEntry) row = n_rows;
-        entries[i] = e; rows[i] = (uint32_t)row;
-        Bvh4Node &w = leaf_nodes[i];
-        for (int c = 0; c < 4; ++c) {
-            w.a[c] = make_float4(INFINITY, INFINITY, INFINITY, u32_as_f32(0u));
-            w.b[c] = make_float4(-INFINITY, -INFINITY, -INFINITY, u32_as_f32(0xFFFFFFFFu));
-        }
-        if (e != kNoEntry) {
-            w.a[0] = make_float4(-INFINITY, -INFINITY, -INFINITY, u32_as_f32(e & ~kTriEntry));
-            w.b[0] = make_float4(INFINITY, INFINITY, INFINITY, u32_as_f32((e & kTriEntry) ? (kBvhTriLeaf | 1u) : 1u));
-        }
-    }
-    if (records) {                                              // the object's resident f32 records, as the leaf tests read them
-        std::vector<float4> cr(prims.size()), l32(prims.size()), t32(2 * tri_fidx.size()), geo(2 * tri_fidx.size());
-        std::vector<float> s32(prims.empty() ? 0u : (((size_t)sv.n_spheres + 3) & ~(size_t)3) * 4);
-        RTX_HIP_CHECK(down(cr.data(), sv.bvh_leaf_cr, cr.size() * sizeof(float4)));
-        if (filter_records) {
-            RTX_HIP_CHECK(down(l32.data(), sv.bvh_leaf_f32, l32.size() * sizeof(float4)));
-            RTX_HIP_CHECK(down(s32.data(), sv.sphere_f32, s32.size() * sizeof(float)));
-        }
-        RTX_HIP_CHECK(down(t32.data(), sv.tri_f32, t32.size() * sizeof(float4)));
-        RTX_HIP_CHECK(down(geo.data(), sv.tri_geo, geo.size() * sizeof(float4)));
-        std::memset(records, 0, n * 16 * sizeof(uint32_t));
-        for (uint64_t i = 0; i < n; ++i) {
-            const uint32_t e = entries[i];
-            if (e == kNoEntry) continue;
-            if (e & kTriEntry) {
-                const size_t r = e & ~kTriEntry;
-                const float4 four[4] = { t32[2 * r], t32[2 * r + 1], geo[2 * r], geo[2 * r + 1] };
-                std::memcpy(records + 16 * i, four, sizeof four);
-            } else {
-                std::memcpy(records + 16 * i, &cr[e], sizeof(float4));
-                if (!filter_records) continue;
-                std::memcpy(records + 16 * i + 4, &l32[e], sizeof(float4));
-                const uint32_t k = prims[e];                    // the pair-interleaved filter record of the same sphere, as scalars
-                if ((size_t)(k | 1u) * 4 + 3 < s32.size()) {
-                    const float *f = s32.data() + (size_t)(k & ~1u) * 4 + (k & 1u);
-                    const float four[4] = { f[0], f[2], f[4], f[6] };
-                    std::memcpy(records + 16 * i + 8, four, sizeof four);
-                }
-            }
-        }
-    }
-    if (path_data && path_steps) {                              // the object's child at every step, in the form the slab test reads
-        std::vector<BvhQ3Node> q3((form & 2u) && (sv.bvh_flags & 16u) && sv.bvh_q3nodes ? nodes.size() : 0u);
-        std::vector<BvhQNode> qn((form & 2u) && q3.empty() ? nodes.size() : 0u);
-        RTX_HIP_CHECK(down(q3.data(), sv.bvh_q3nodes, q3.size() * sizeof(BvhQ3Node)));
-        RTX_HIP_CHECK(down(qn.data(), sv.bvh_qnodes, qn.size() * sizeof(BvhQNode)));
-        std::memset(path_data, 0, n * (size_t)path_steps * 16 * sizeof(uint32_t));
-        for (uint64_t i = 0; i < n; ++i) {
-            const size_t row = rows[i];
-            for (uint32_t k = 0; k < lens[row] && k < path_steps; ++k) {
-                const uint32_t link = steps[2 * (row * stride + k)], c = steps[2 * (row * stride + k) + 1], idx = link & ~kBvhFlatNode;
-                uint32_t *w = path_data + 16 * ((size_t)i * path_steps + k);
-                auto putf = [&](int at, float f) { std::memcpy(w + at, &f, 4); };
-                if (!q3.empty()) {
-                    const BvhQ3Node &q = q3[idx];
-                    w[0] = 2u;
-                    putf(1, q.ox); putf(2, q.oy); putf(3, q.oz); putf(4, q.sx); putf(5, q.sy); putf(6, q.sz);
-                    w[7] = (q.lox >> (8 * c)) & 255u; w[8] = (q.loy >> (8 * c)) & 255u; w[9] = (q.loz >> (8 * c)) & 255u;
-                    w[10] = (q.hix >> (8 * c)) & 255u; w[11] = (q.hiy >> (8 * c)) & 255u; w[12] = (q.hiz >> (8 * c)) & 255u;
-                } else if (!qn.empty()) {
-                    const BvhQNode &q = qn[idx];
-                    w[0] = 3u;
-                    putf(1, q.ox); putf(2, q.oy); putf(3, q.sx); putf(4, q.sy); w[5] = q.qx[c]; w[6] = q.qy[c];
-                } else if (link & kBvhFlatNode) {
-                    w[0] = 1u;
-                    putf(1, nodes[idx].a[c].x); putf(2, nodes[idx].a[c].y); putf(3, nodes[idx].a[c].z); putf(4, nodes[idx].a[c].w);
-                } else {
-                    w[0] = 0u;
-                    putf(1, nodes[idx].a[c].x); putf(2, nodes[idx].a[c].y); putf(3, nodes[idx].a[c].z);
-                    putf(4, nodes[idx].b[c].x); putf(5, nodes[idx].b[c].y); putf(6, nodes[idx].b[c].z);
-                }
-                w[15] = link;
-            }
-        }
-    }
-    DebugBufs d;
-    void *d_sv, *d_rays, *d_entries, *d_rows, *d_lens, *d_steps, *d_best, *d_leaf, *d_out;
-    RTX_HIP_CHECK(d.up(&sv, sizeof(SceneView), &d_sv));
-    RTX_HIP_CHECK(d.up(rays, n * sizeof(RtxRay), &d_rays));
-    RTX_HIP_CHECK(d.up(entries.data(), n * sizeof(uint32_t), &d_entries));
-    RTX_HIP_CHECK(d.up(rows.data(), n * sizeof(uint32_t), &d_rows));
-    RTX_HIP_CHECK(d.up(lens.data(), lens.size() * sizeof(uint32_t), &d_lens));
-    steps.resize(steps.size() + 2, 0u);                         // (never empty)
-    RTX_HIP_CHECK(d.up(steps.data(), steps.size() * sizeof(uint32_t), &d_steps));
-    RTX_HIP_CHECK(d.up(best_up, n * sizeof(float), &d_best));
-    RTX_HIP_CHECK(d.up(leaf_nodes.data(), n * sizeof(Bvh4Node), &d_leaf));
-    RTX_HIP_CHECK(d.up(out, n * 8 * sizeof(uint32_t), &d_out));
-    static_assert(sizeof(RtxRay) == sizeof(QueryRay), "RtxRay layout");
-    PathBoundsArgs a;
-    a.rays = static_cast<const QueryRay *>(d_rays); a.entries = static_cast<const uint32_t *>(d_entries);
-    a.rows = static_cast<const uint32_t *>(d_rows); a.lens = static_cast<const uint32_t *>(d_lens);
-    a.steps = static_cast<const uint32_t *>(d_steps); a.best_up = static_cast<const float *>(d_best);
-    a.leaf_nodes = static_cast<const float4 *>(d_leaf); a.out = static_cast<uint32_t *>(d_out);
-    a.n = n; a.stride = stride; a.form = form;
-    RTX_HIP_CHECK(launch_debug_path_bounds(static_cast<const SceneView *>(d_sv), a, nullptr));
-    RTX_HIP_CHECK(hipMemcpy(out, d_out, n * 8 * sizeof(uint32_t), hipMemcpyDeviceToHost));   // (the null stream: after the kernel)
-    return RTX_OK;
-#endif
-}
 
 int32_t rtx_scene_closest_hits(RtxSceneHandle h, const RtxRay *d_rays, uint64_t n, RtxHit *d_hits, void *stream, RtxStats *stats)
 {

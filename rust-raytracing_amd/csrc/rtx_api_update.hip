@@ -1,0 +1,149 @@
+// rtx_api_update.hip -- rtx_scene_update_objects and rtx_scene_append_objects (include/rtx_hip.h, DESIGN.md "Moving objects"): the
+// device side of an update that rtx_pack.hip planned -- the tables of the resident pack, the launches of scene_update_kernel in
+// run_update's order (rtx_pack.h: the order the host reference refit_packed runs too), and the rebuild both entry points fall back to.
+#include "rtx_host.h"
+
+#include <cstring>
+
+namespace {
+
+// A device copy of a host table (nothing is allocated for an empty one).
+template <class T>
+hipError_t put_table(T **dst, const std::vector<T> &v)
+{
+    if (v.empty()) return hipSuccess;
+    const hipError_t e = hipMalloc((void **)dst, v.size() * sizeof(T));
+    return e != hipSuccess ? e : hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+}
+
+// The device side of the refit tables of the resident pack, made at the first REFIT or RECORDS call after it.
+int32_t ensure_update_tables(RtxSceneHandle_ *h)
+{
+    auto &b = h->upd;
+    if (!b.d_status) RTX_HIP_CHECK(hipMalloc((void **)&b.d_status, 3 * sizeof(unsigned long long)));
+    if (!b.h_status) RTX_HIP_CHECK(hipHostMalloc((void **)&b.h_status, 3 * sizeof(unsigned long long), hipHostMallocDefault));
+    if (b.valid) return RTX_OK;
+    drop_update_tables(h);
+    const RefitTables &t = h->refit;
+    std::vector<float> box32;
+    std::vector<double> reach;
+    derive_all_spheres(h->objects.data(), h->objects.size(), t, h->sv.n_spheres, box32, reach);
+    RTX_HIP_CHECK(put_table(&b.box32, box32));
+    RTX_HIP_CHECK(put_table(&b.reach, reach));
+    RTX_HIP_CHECK(put_table(&b.levels, t.level_nodes));
+    b.valid = true;
+    return RTX_OK;
+}
+
+// The triangle half of the device tables (derive_all_spheres' analogue), made at the first DEFORM call that moves a triangle.
+int32_t ensure_mesh_tables(RtxSceneHandle_ *h)
+{
+    auto &b = h->upd;
+    if (b.mesh_valid) return RTX_OK;
+    const RefitTables &t = h->refit;
+    std::vector<float> tribox32;
+    std::vector<double> tri_reach;
+    derive_all_triangles(h->objects.data(), h->objects.size(), t, tribox32, tri_reach);
+    RTX_HIP_CHECK(put_table(&b.tribox32, tribox32));
+    RTX_HIP_CHECK(put_table(&b.tri_reach, tri_reach));
+    RTX_HIP_CHECK(put_table(&b.all_levels, t.all_level_nodes));
+    b.mesh_valid = true;
+    return RTX_OK;
+}
+
+// Replaces the object list by `all` and packs it again (an append, an update that rebuilds).  The new arrays are uploaded first and
+// swapped in on success (upload_packed), so a failure leaves the resident scene and the handle's list as they were.  The caller has
+// synchronised with the device: a render may still read the arrays about to be replaced.
+int32_t repack_objects(RtxSceneHandle_ *h, std::vector<RtxObject> &all)
+{
+    RtxScene sc{};
+    sc.config = h->cfg;
+    sc.camera = h->cam;
+    sc.n_objects = all.size();
+    sc.objects = all.data();
+    PackedScene p;
+    if (int32_t rc = pack_scene(&sc, p)) return rc;
+    if (int32_t rc = upload_packed(h, p)) return rc;
+    h->objects.swap(all);
+    return RTX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t rtx_scene_append_objects(RtxSceneHandle scene, const RtxObject *objects, uint64_t n_objects)
+{
+    if (!scene || (n_objects && !objects)) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_append_objects: null argument");
+    if (n_objects == 0) return RTX_OK;
+    if (scene->objects.size() + n_objects > 0xFFFFFFF0ull) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_append_objects: too many objects");
+    RTX_HIP_CHECK(hipSetDevice(scene->device));
+    RTX_HIP_CHECK(hipDeviceSynchronize());                  // a render may still read the arrays about to be replaced
+    if (int32_t rc = check_watchdog(scene, true)) return rc;
+    std::vector<RtxObject> all = scene->objects;
+    all.insert(all.end(), objects, objects + n_objects);
+    return repack_objects(scene, all);                      // (on failure the resident scene is as it was)
+}
+
+int32_t rtx_scene_update_objects(RtxSceneHandle h, const uint64_t *indices, const RtxObject *objects, uint64_t n, uint32_t mode,
+                                 void *stream_, uint32_t *how)
+{
+    if (how) *how = RTX_UPDATED_NOTHING;
+    if (!h) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_update_objects: null scene");
+    UpdatePlan plan;
+    if (int32_t rc = plan_update(h->objects, h->refit, h->sv.sphere_cmax, indices, objects, n, mode, plan)) return rc;
+    if (plan.entries.empty()) return RTX_OK;
+    RTX_HIP_CHECK(hipSetDevice(h->device));
+    if (int32_t rc = check_watchdog(h, true)) return rc;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (plan.how != RTX_UPDATED_REBUILT) {
+        auto &b = h->upd;
+        if (int32_t rc = ensure_update_tables(h)) return rc;
+        if (plan.tri_geom) if (int32_t rc = ensure_mesh_tables(h)) return rc;
+        const size_t ne = plan.entries.size(), bytes = ne * sizeof(UpdateEntry);
+        if (b.h_cap < ne) {
+            if (b.h_entries) { RTX_HIP_CHECK(hipHostFree(b.h_entries)); b.h_entries = nullptr; b.h_cap = 0; }
+            RTX_HIP_CHECK(hipHostMalloc((void **)&b.h_entries, bytes, hipHostMallocDefault));
+            b.h_cap = ne;
+        }
+        if (b.d_cap < ne) {
+            if (b.d_entries) { RTX_HIP_CHECK(hipFree(b.d_entries)); b.d_entries = nullptr; b.d_cap = 0; }
+            RTX_HIP_CHECK(hipMalloc((void **)&b.d_entries, bytes));
+            b.d_cap = ne;
+        }
+        std::memcpy(b.h_entries, plan.entries.data(), bytes);
+        {
+            if (int32_t rc = adopt_stream(h, stream)) return rc;      // the writes below wait for what earlier calls enqueued
+            DoneGuard done{h, stream};
+            const RefitTables &t = h->refit;
+            const SceneView &sv = h->sv;
+            RTX_HIP_CHECK(hipMemcpyAsync(b.d_entries, b.h_entries, bytes, hipMemcpyHostToDevice, stream));
+            const size_t status_bytes = (plan.any_tri ? 3 : 2) * sizeof(unsigned long long);      // (the third word: mode D's)
+            RTX_HIP_CHECK(hipMemsetAsync(b.d_status, 0, status_bytes, stream));
+            UpdateArgs u = update_args(sv, t, b.d_entries, b.box32, b.reach, b.tribox32, b.tri_reach, plan.tri_geom);
+            u.status = b.d_status;
+            hipError_t scene_update_launch = hipSuccess;
+            run_update(u, t, plan, b.levels, b.all_levels, sv.n_spheres, sv.n_tris,
+                       [&](const UpdateArgs &a) { return (scene_update_launch = launch_scene_update(a, stream)) == hipSuccess; });
+            RTX_HIP_CHECK(scene_update_launch);
+            RTX_HIP_CHECK(hipMemcpyAsync(b.h_status, b.d_status, status_bytes, hipMemcpyDeviceToHost, stream));
+            RTX_HIP_CHECK(hipStreamSynchronize(stream));
+        }
+        if (h->upd.h_status[0] & (kUpdateStatusNoQ3 | kUpdateStatusNoQ)) plan.how = RTX_UPDATED_REBUILT;       // every array is replaced below
+        else {
+            for (const UpdateEntry &e : plan.entries) std::memcpy(&h->objects[e.object], &e.kind, sizeof(RtxObject));
+            if (plan.any_sphere) { std::memcpy(&h->sv.sphere_cmax, &h->upd.h_status[1], sizeof(double)); h->sv_dirty = true; }
+            if (plan.any_tri) { std::memcpy(&h->sv.tri_extent, &h->upd.h_status[2], sizeof(double)); h->sv_dirty = true; }
+        }
+    }
+    if (plan.how == RTX_UPDATED_REBUILT) {                      // the update as a rebuild: rtx_scene_append_objects' path on the modified list
+        RTX_HIP_CHECK(hipDeviceSynchronize());                  // a render may still read the arrays about to be replaced
+        std::vector<RtxObject> all = h->objects;
+        for (const UpdateEntry &e : plan.entries) std::memcpy(&all[e.object], &e.kind, sizeof(RtxObject));
+        if (int32_t rc = repack_objects(h, all)) return rc;
+    }
+    if (how) *how = plan.how;
+    return RTX_OK;
+}
+
+}  // extern "C"

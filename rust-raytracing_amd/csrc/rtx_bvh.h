@@ -15,7 +15,7 @@
 //    into the tree with their (x, y) footprint rectangle and an unbounded z interval: the slab test prunes in
 //    two dimensions, and entry-distance pruning against the best hit stays valid.  Triangles whose elimination
 //    pivots are not rows (x, y), or whose projection is ill-conditioned, stay outside the tree and are tested for
-//    every segment (rtx_api.hip).
+//    every segment (rtx_pack.hip).
 //
 // The leaves run the SAME exact f64 tests as the brute-force kernels and the winner is chosen with the same
 // (t, scene index) order, so the image has the same bits.

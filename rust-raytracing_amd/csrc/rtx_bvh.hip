@@ -146,7 +146,7 @@ __global__ __launch_bounds__(kBvhThreads, kBvhWavesPerSimd) void trace_bvh_kerne
                 double t;
                 if (plane_distance(sv.planes[k], rx, &t)) hit_consider(h, t, sv.planes[k].id, 1, k);
             }
-            // triangles outside the tree, by filter record (triangles without a record can never be hit: rtx_api.hip)
+            // triangles outside the tree, by filter record (triangles without a record can never be hit: rtx_pack.hip)
             for (uint32_t k = tri_sweep_from; k < sv.n_tri_filter; ++k) {
                 const uint32_t tk = la.tri_fidx[k];
                 double t;

@@ -175,7 +175,7 @@ __global__ __launch_bounds__(kBvhThreads, mesh_wide(QUEUE, PLAIN) ? kMeshWavesQ 
                     double t;
                     if (plane_distance(sv.planes[k], rx, &t)) hit_consider(h, t, sv.planes[k].id, 1, k);
                 }
-                // triangles outside the tree, by filter record (triangles without a record can never be hit: rtx_api.hip)
+                // triangles outside the tree, by filter record (triangles without a record can never be hit: rtx_pack.hip)
                 const uint32_t tri_sweep_from = covered ? sv.n_tri_tree : 0u;
                 for (uint32_t k = tri_sweep_from; k < sv.n_tri_filter; ++k) {
                     const uint32_t tk = la.tri_fidx[k];
@@ -499,7 +499,7 @@ static hipError_t launch_mesh(const SceneView *d_sv, const SceneView &sv, const 
     const bool no_q = (sv.tuning & RTX_TUNE_NO_QNODES) != 0u;
     const int plain = (sv.bvh_flags & 4u) == 0u ? 0 : ((sv.bvh_flags & 8u) != 0u && !no_q ? 2 : 1);
 #else
-    // (the product holds instances 0 and 2: rtx_api.hip clears flag 4 of a pure footprint tree without 64-byte nodes)
+    // (the product holds instances 0 and 2: rtx_pack.hip clears flag 4 of a pure footprint tree without 64-byte nodes)
     if ((sv.bvh_flags & 12u) == 4u) return hipErrorInvalidValue;
     const int plain = (sv.bvh_flags & 4u) == 0u ? 0 : 2;
 #endif

@@ -87,7 +87,7 @@ __global__ __launch_bounds__(kBvhThreads, kBvhWavesPerSimd) void trace_bvh_regro
                 double t;
                 if (plane_distance(sv.planes[k], rx, &t)) hit_consider(h, t, sv.planes[k].id, 1, k);
             }
-            // triangles outside the tree, by filter record (triangles without a record can never be hit: rtx_api.hip)
+            // triangles outside the tree, by filter record (triangles without a record can never be hit: rtx_pack.hip)
             const uint32_t tri_sweep_from = (covered && (sv.bvh_flags & 2u)) ? sv.n_tri_tree : 0u;
             for (uint32_t k = tri_sweep_from; k < sv.n_tri_filter; ++k) {
                 const uint32_t tk = la.tri_fidx[k];

@@ -1,0 +1,115 @@
+// rtx_host.h -- what the device-facing host translation units (rtx_api.hip, rtx_api_update.hip, rtx_api_debug.hip) share: the
+// HIP error check, the scene handle, and the helpers they call across files (rtx::host, hidden: rtx_pack.h).
+#pragma once
+
+#include "rtx_launch.h"
+#include "rtx_pack.h"
+
+using namespace rtx;
+using namespace rtx::host;
+
+#define RTX_HIP_CHECK(expr)                                                                              \
+    do {                                                                                                 \
+        hipError_t e_ = (expr);                                                                          \
+        if (e_ != hipSuccess)                                                                            \
+            return fail(e_ == hipErrorOutOfMemory ? RTX_ERR_OUT_OF_MEMORY : RTX_ERR_HIP,                 \
+                        std::string(#expr) + ": " + hipGetErrorString(e_));                              \
+    } while (0)
+
+struct RtxSceneHandle_ {
+    int device = 0;
+    int n_cus = 0;
+    RtxConfig cfg{};
+    RtxCamera cam{};
+    SceneView sv{};
+    std::vector<RtxObject> objects;                       // Scene.objects as uploaded (rtx_scene_append_objects re-packs them)
+    std::vector<void *> scene_allocs;
+    // rtx_scene_update_objects: the host tables of the resident pack, and their device side -- made at the first REFIT or RECORDS
+    // call, dropped by any rebuild (upload_packed)
+    RefitTables refit;
+    struct UpdateBufs {
+        bool valid = false;
+        uint32_t *levels = nullptr; float *box32 = nullptr; double *reach = nullptr;
+        bool mesh_valid = false;                                // the triangle half: made at the first DEFORM call that moves a triangle
+        uint32_t *all_levels = nullptr; float *tribox32 = nullptr; double *tri_reach = nullptr;
+        UpdateEntry *h_entries = nullptr; size_t h_cap = 0;     // pinned staging of the update list
+        UpdateEntry *d_entries = nullptr; size_t d_cap = 0;
+        unsigned long long *d_status = nullptr, *h_status = nullptr;   // {status bits, the bits of the new sphere_cmax, of the new tri_extent}; h_status pinned
+    } upd;
+    // scratch, grown on demand
+    double *samples = nullptr;  size_t samples_bytes = 0;
+    double *acc = nullptr;      size_t acc_bytes = 0;
+    double *tables = nullptr;   size_t tables_doubles = 0;
+    double *h_tables = nullptr; size_t h_tables_doubles = 0;
+    double *state = nullptr;    size_t state_bytes = 0;
+    void *wf_state = nullptr;   size_t wf_bytes = 0;       // the wavefront kernels' ray state
+    void *pool = nullptr;       size_t pool_bytes = 0;     // (lab) the pool / pair forms of the sphere kernel's stage 2
+    void *slots = nullptr;      size_t slots_bytes = 0;    // the slot records of the sphere kernel's stage 2 (trace_sph_slots_kernel)
+    void *tile_lists = nullptr; size_t tile_lists_bytes = 0;   // what each tile's primary rays can reach (build_tile_lists_kernel)
+    PathStep *transcript = nullptr; uint32_t *transcript_counts = nullptr; uint32_t transcript_steps = 0;   // (lab) rtx_debug_paths, set for one call
+    Counters *counters = nullptr;
+    unsigned long long *work_counter = nullptr;
+    SceneView *d_sv = nullptr;  bool sv_dirty = true;     // device copy of sv (kernels take it by pointer)
+    RowsView *d_rv = nullptr;
+    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };      // [3]: the end of the sphere kernel's stage 1 (stats only)
+    // The second half's own stream and buffers when a launch runs as two halves in flight (render_band, "halves"): created on first use.
+    struct SecondHalf {
+        hipStream_t stream = nullptr;
+        hipEvent_t fork = nullptr, join = nullptr, stage1_done = nullptr;
+        Counters *counters = nullptr, *counters_stage1 = nullptr;
+        unsigned long long *work_counter = nullptr;
+        RowsView *d_rv = nullptr;
+        double *state = nullptr;    size_t state_bytes = 0;
+        void *queue = nullptr;      size_t queue_bytes = 0;
+    } half2;
+    Counters *counters_stage1 = nullptr;                   // the counters as stage 1 left them (stats only)
+    // The handle's device buffers (descriptors, tables, counters, scratch) are shared by all of its renders, so they
+    // are ordered on ONE stream at a time: when a call brings a different stream the previous one is drained first.
+    size_t scratch_limit = 0;                             // rtx_scene_set_scratch_limit (0 = default)
+    hipStream_t last_stream = nullptr;                    // compared, never used: the caller may have destroyed it since
+    bool have_last_stream = false;
+    hipEvent_t ev_done = nullptr;                         // recorded at the end of every render, on the stream it ran on
+    bool have_done = false;
+    // Round-bound watchdog of the sweep kernel (ctr[1].pad_): copied to this pinned word after every launch and looked
+    // at by the next entry point that finds the copy complete (and by rtx_scene_free), so that the asynchronous
+    // stats == NULL path reports it too.
+    unsigned long long *h_watchdog = nullptr;
+    hipEvent_t ev_watchdog = nullptr;
+    bool watchdog_pending = false;
+    // what the trig tables currently hold
+    uint32_t t_w = 0, t_h = 0, t_rb = 0, t_rs = 0, t_blk = 0, t_nr = 0;
+    double t_fov = 0.0;
+    bool t_valid = false;
+};
+
+RTX_HOST_BEGIN
+
+// the non-zero mask of a launch's sample records (store_sample, rtx_device.h): one bit per ray-queue slot, in whole 32-bit words
+inline size_t nonzero_mask_bytes(uint64_t n_rays) { return (size_t)((n_rays + 31) / 32) * sizeof(uint32_t); }
+
+// The samples a call traces and where their fold goes.  A render: [0, rays_per_pixel) from zero into out = sum / rays_per_pixel.
+// rtx_render_blocks_accumulate (sum != null): [begin, begin + n) on top of what the caller's sum (and sum_sq, or null) hold; nothing
+// is divided and no accumulator of the handle's is used -- the caller's buffers have its layout.
+struct SampleRange { uint64_t begin = 0, n = 0; double *sum = nullptr, *sum_sq = nullptr; };
+
+// From adopt_stream on, work may be enqueued on `stream`, and last_stream already names it: whatever way the call leaves -- a failed
+// HIP call after some launches, the watchdog return, the empty-scene answer -- the event a later call on ANOTHER stream waits
+// for (adopt_stream) is recorded behind everything enqueued so far, so that call never reuses the handle's scratch early.
+struct DoneGuard {
+    RtxSceneHandle_ *h; hipStream_t stream;
+    ~DoneGuard() {
+        if (hipEventRecord(h->ev_done, stream) == hipSuccess) h->have_done = true;
+        else { (void)hipGetLastError(); (void)hipDeviceSynchronize(); h->have_done = false; }   // (no event: drain instead)
+    }
+};
+
+// rtx_api.hip
+int usable_device_count();
+void drop_update_tables(RtxSceneHandle_ *h);
+int32_t upload_packed(RtxSceneHandle_ *h, const PackedScene &p);
+int32_t check_watchdog(RtxSceneHandle_ *h, bool wait);
+int32_t adopt_stream(RtxSceneHandle_ *h, hipStream_t stream);
+int32_t render_band(RtxSceneHandle_ *h, uint32_t width, uint32_t height, uint32_t row_begin, uint32_t row_stride, uint32_t row_block,
+                    uint32_t n_rows, double *d_out_rgb, void *stream_, RtxStats *stats, const SampleRange *accumulate = nullptr);
+
+RTX_HOST_END

@@ -1,5 +1,5 @@
 // rtx_refit.h -- the arithmetic of rtx_scene_update_objects, written once: scene_update_kernel (rtx_update.hip) and the host
-// reference refit_packed (rtx_api.hip) compile from this text, so the device's arrays can be held to the host's bit for bit.
+// reference refit_packed (rtx_pack.hip) compile from this text, so the device's arrays can be held to the host's bit for bit.
 //
 // Every expression that has a twin in pack_scene, sphere_box, bvh_append_tree or build_q3nodes is that twin's expression (same
 // operations in the same order; -ffp-contract=off), with two exceptions that have no device form there:
@@ -115,7 +115,7 @@ RTX_HD SphereDerived derive_sphere(const double g[4], const double centre[3], do
 
 // Everything of one triangle that is derived from its vertices, the scene's `centre` and the tree's abs_pad: pack_scene's expressions
 // in pack_scene's order (min / max as comparisons: the values of fmin / fmax for finite operands, and one answer for -0 against +0
-// on host and device).  `qualified` and `f` (the free axis) are the host's classification (classify_triangle, rtx_api.hip); a
+// on host and device).  `qualified` and `f` (the free axis) are the host's classification (classify_triangle, rtx_pack.hip); a
 // triangle that is not qualified has the "always a candidate" record and no footprint.
 struct TriDerived {
     TriX exact;

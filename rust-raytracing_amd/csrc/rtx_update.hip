@@ -1,6 +1,6 @@
 // rtx_update.hip -- scene_update_kernel: rtx_scene_update_objects on the device (include/rtx_hip.h, DESIGN.md "Moving objects").
 // One kernel, a launch-uniform mode (UpdateArgs, rtx_refit.h); the arithmetic is rtx_refit.h's, which the host reference
-// refit_packed (rtx_api.hip) compiles too.  No spin-waits, no dependence between the blocks of one launch; threads write
+// refit_packed (rtx_pack.hip) compiles too.  No spin-waits, no dependence between the blocks of one launch; threads write
 // disjoint words (mode B reads the nodes the previous launch wrote: the host enqueues the levels deepest first on one stream).
 #include "rtx_launch.h"
 

@@ -1,6 +1,6 @@
 """A model of the tree walks' f32 bound arithmetic (rtx_traverse.h box_entry32 / rect_entry32 / sphere_node_step_q3 / the sphere leaf
 bounds, rtx_mesh_step.h qrect_entry / tri_bounds, rtx_device.h tri_filter_sign) and of the builder's boxes and records (rtx_bvh.h,
-rtx_api.hip pack_scene), in which every f32 operation is formed EXACTLY and rounded ONCE, and every margin is a knob.
+rtx_pack.hip pack_scene), in which every f32 operation is formed EXACTLY and rounded ONCE, and every margin is a knob.
 
 How one rounding is kept.  All operands are f32 values held in f64.  A product of two of them is exact in f64 (48 bits).  A sum s + c
 of two f64 values is formed exactly as hi + lo (Knuth's two-sum), hi is moved to the neighbour with an odd last bit when lo != 0
@@ -359,7 +359,7 @@ def tri_bounds(A, g0, g1, f, m=SHIPPED):
     return tlo, thi, {"dn": dn, "nv": nv, "a": a, "b": b, "ea": ea, "eb": eb, "S": S, "th": th}
 
 
-# ---- the builder's boxes and records (rtx_bvh.h, rtx_api.hip pack_scene), restated ---------------------------------------------------------------
+# ---- the builder's boxes and records (rtx_bvh.h, rtx_pack.hip pack_scene), restated ---------------------------------------------------------------
 def _tri_rows(v):
     """make_triangle's pivots (triangle.rs:60-71, 81-87): (i, j) the rows Triangle::contains solves in, or None (degenerate)"""
     r, s = v[1] - v[0], v[2] - v[0]

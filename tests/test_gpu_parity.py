@@ -1081,7 +1081,7 @@ def test_product_fallback_for_a_sphere_tree_without_64_byte_nodes(gpu):
     """The product library holds the sphere kernels in their 64-byte-node instances only.  A sphere tree whose nodes have no such
     form (coordinates beyond the quantisation's exact range: |origin / step| + 256 >= 2^24) renders with the LDS sweep under every
     kernel id, with the exhaustive kernel's bits; the lab library walks its 128-byte nodes.  (A pure footprint tree always has its
-    64-byte form when the tree is built at all -- rtx_api.hip would let it walk as a joint tree otherwise.)"""
+    64-byte form when the tree is built at all -- rtx_pack.hip would let it walk as a joint tree otherwise.)"""
     import torch
     from rust_raytracing_amd import scenes
     balls = scenes.light_every(scenes.compact(scenes.random_spheres(300, 5)))

@@ -39,7 +39,7 @@ def test_every_64_byte_node_decodes_to_its_128_byte_node(rtx, name):
     objs = _layout_scenes()[name]
     st = _host_scene(rtx, objs)                                                 # raises when the check fails
     assert st["quantised_nodes"] == st["wide_nodes"], st
-    if len(objs) <= 4:                                                          # (rtx_api.hip pack_scene: four spheres or fewer get no tree)
+    if len(objs) <= 4:                                                          # (rtx_pack.hip pack_scene: four spheres or fewer get no tree)
         assert st["wide_nodes"] == 0 and st["flags"] == 0, st
         return
     assert st["flags"] == 1 + 16, st                                            # a sphere tree in its 64-byte form
