@@ -334,7 +334,7 @@ class Scene::Resident {
 public:
     Resident(const Resident &) = delete;
     Resident &operator=(const Resident &) = delete;
-    Resident(Resident &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    Resident(Resident &&o) noexcept : h_(o.h_), n_objects_(o.n_objects_) { o.h_ = nullptr; }
     ~Resident() { if (h_) rtx_scene_free(h_); }
 
     void set_camera(const Camera &camera)                              // Camera::set_position / set_direction, camera.rs:35-40
@@ -356,6 +356,7 @@ public:
         one.add_object(o);
         const std::vector<RtxObject> packed = one.pack();
         check(rtx_scene_append_objects(h_, packed.data(), packed.size()));
+        n_objects_ += packed.size();
     }
     // Scene.objects[indices[i]] = objects[i] on the resident scene (rtx_scene_update_objects): moved spheres are refitted into the
     // resident tree on the device, materials and planes are rewritten in place; anything the tree cannot take (a kind change, a
@@ -378,6 +379,22 @@ public:
         uint32_t how = RTX_UPDATED_NOTHING;
         check(rtx_scene_update_objects(h_, indices.data(), packed.data(), packed.size(), mode, hip_stream, &how));
         return how;
+    }
+    // Hides (visible = false) or shows Scene.objects[indices[i]] in place (rtx_scene_set_visible): what the reference's users do with
+    // retain / remove on the pub Vec, with the indices of all other objects unchanged and the tree kept.  A hidden object is never hit;
+    // frames are those of the list without it.  Returns RTX_UPDATED_NOTHING / RECORDS / REFIT / REBUILT.
+    uint32_t set_visible(const std::vector<std::uint64_t> &indices, bool visible, void *hip_stream = nullptr)
+    {
+        uint32_t how = RTX_UPDATED_NOTHING;
+        check(rtx_scene_set_visible(h_, indices.data(), indices.size(), visible ? 1u : 0u, hip_stream, &how));
+        return how;
+    }
+    // one entry per object of the resident list: false for a hidden one
+    std::vector<bool> visible() const
+    {
+        std::vector<std::uint8_t> mask(n_objects_, 1);
+        check(rtx_scene_get_visible(h_, mask.data()));
+        return std::vector<bool>(mask.begin(), mask.end());
     }
     // rows row_begin, row_begin + row_stride, ... (n_rows of them) of the width x height image -> d_out_rgb[n_rows][width][3]
     RtxStats render_rows(std::size_t width, std::size_t height, std::size_t row_begin, std::size_t row_stride, std::size_t n_rows,
@@ -478,9 +495,10 @@ public:
 
 private:
     friend class Scene;
-    explicit Resident(RtxSceneHandle h) : h_(h) {}
+    Resident(RtxSceneHandle h, std::size_t n_objects) : h_(h), n_objects_(n_objects) {}
     static void check(int32_t rc) { if (rc != RTX_OK) throw Panic(rc, rtx_last_error()); }
     RtxSceneHandle h_;
+    std::size_t n_objects_;
 };
 
 inline Scene::Resident Scene::upload(int device) const
@@ -490,7 +508,7 @@ inline Scene::Resident Scene::upload(int device) const
     RtxSceneHandle h = nullptr;
     int32_t rc = rtx_scene_upload(&sc, device, &h);
     if (rc != RTX_OK) throw Panic(rc, rtx_last_error());
-    return Resident(h);
+    return Resident(h, packed.size());
 }
 
 }  // namespace rtx

@@ -350,6 +350,36 @@ enum { RTX_UPDATED_NOTHING = 0, RTX_UPDATED_RECORDS = 1, RTX_UPDATED_REFIT = 2, 
 int32_t rtx_scene_update_objects(RtxSceneHandle scene, const uint64_t *indices, const RtxObject *objects, uint64_t n,
                                  uint32_t mode, void *stream, uint32_t *how);
 
+/* Hides (visible == 0) or shows (visible == 1) Scene.objects[indices[i]] of an uploaded scene, in place: the reference's users
+ * `retain` / `remove` objects of the pub Vec Scene.objects between renders, or skip one for a while; here the object keeps its index
+ * and its slot in the tree.  `indices` is a HOST array; repeated indices are fine; an entry already in the requested state is a no-op.
+ *   The contract.  After any sequence of calls on a handle, everything the handle produces -- frames under every kernel id,
+ * closest-hit and any-hit queries, the pick buffer, path radiance, sparse samples, progressive sums, a refinement round, pixel
+ * features -- equals, byte for byte, what a fresh upload of the list L_nan produces: the handle's current object list with the nine
+ * `geom` words of every hidden object set to NaN (all-NaN geometry is "never hit" in the reference for each kind: sphere.rs:22-29 with
+ * scene.rs:249's is_normal, plane.rs:21-31, triangle.rs:37-101).  L_nan has the same length, so:
+ *   - indices are stable: a hit never reports a hidden object, and no other object's index moves;
+ *   - frames, and hits after the monotone index map, also equal a fresh upload of the list with the hidden objects DELETED
+ *     (closest_object's tie-break only needs relative order, and rng_key(seed, pix, sample) does not read an object index);
+ *   - RtxStats counters may differ, as they may after an update.
+ *   *how (may be NULL) reports the path with rtx_scene_update_objects' values: RTX_UPDATED_NOTHING -- no state changes;
+ * RTX_UPDATED_RECORDS -- only planes and shapes outside the tree change state; RTX_UPDATED_REFIT -- a shape with a slot in the tree
+ * changes state: its records are rewritten and the nodes above it refitted on the device, where a leaf whose entries are all hidden and
+ * an interior child with nothing alive below become the empty slot every walk ignores (and get their words back when something below
+ * is shown); RTX_UPDATED_REBUILT -- a shape being SHOWN has geometry (given by rtx_scene_update_objects while it was hidden) that
+ * rtx_scene_update_objects would not take in place under RTX_UPDATE_DEFORM, the resident sphere_cmax is not below 1e14, or a 64-byte
+ * node has no encoding.
+ *   With the other entry points.  rtx_scene_update_objects on a hidden index updates the object and its material record and writes no
+ * geometry record: the object stays hidden and its new geometry is judged when it is shown (a kind change rebuilds as ever).
+ * rtx_scene_append_objects: the new objects are visible.  Any rebuild -- append, RTX_UPDATE_REBUILD, every fallback -- packs the list
+ * with its real geometries and then hides the hidden set on the fresh arrays, so hidden objects keep a slot and can be shown in place.
+ * The one-shot host forms and rtx_render_devices take an RtxScene, not a handle: they know no hidden set.
+ *   Errors, found before the first device write (the scene is unchanged): RTX_ERR_INVALID_ARGUMENT -- a null `indices` with n > 0, an
+ * index >= n_objects, visible > 1.  "Streams" applies exactly as for rtx_scene_update_objects; the call returns after its own device
+ * work has completed. */
+int32_t rtx_scene_set_visible(RtxSceneHandle scene, const uint64_t *indices, uint64_t n, uint32_t visible, void *stream, uint32_t *how);
+int32_t rtx_scene_get_visible(RtxSceneHandle scene, uint8_t *mask /* n_objects bytes, 1 = visible */);
+
 /* Replace the Camera of an uploaded scene without re-uploading the objects (the reference's analogue is
  * Scene.camera being a pub field, scene.rs:82, with Camera::set_direction camera.rs:35-40).  Only fov, position and
  * to_world_space are read by render. */
@@ -725,6 +755,20 @@ int32_t rtx_debug_resident_digests(RtxSceneHandle scene, uint64_t *digests);
  * tri_extent, sphere_cmax, abs_pad, the range (scale) the tree was built for (< 0: no tree), 0. */
 int32_t rtx_debug_host_refit_mesh(const RtxScene *scene, const uint64_t *indices, const RtxObject *objects, uint64_t n, uint32_t mode,
                                   uint64_t *stats, uint32_t *how, uint64_t *digests, double *info);
+
+/* Test hook of the lab library (the product returns RTX_ERR_UNSUPPORTED), needs no GPU: the host half of a handle's life with
+ * rtx_scene_set_visible.  Packs `scene`, then runs n_steps steps; step s has kind step_kind[s] and the entries
+ * [step_begin[s], step_begin[s + 1]) of `indices` / `objects` (step_begin has n_steps + 1 values):
+ *   0 hide, 1 show (indices);  2 + mode: rtx_scene_update_objects under RTX_UPDATE_* `mode` (indices, objects);  5 append (objects).
+ * how[s]: the step's RTX_UPDATED_*.  stats[16]: rtx_debug_host_scene's walk over the result, which for a hidden shape asks no
+ * containing box and for every visible one still asks its leaf's box and exactly one leaf.  digests[16], info[8] (may be NULL): as
+ * rtx_debug_host_refit_mesh, info[7] the number of wide nodes.  mask (may be NULL): one byte per object of the final list, 1 = visible.
+ * dump (may be NULL; dump_words >= 4 * 17 * wide nodes): per wide node and child 17 words -- [0] link and [1] count as they are now,
+ * [2..7] the bits of lo.xyz, hi.xyz (a footprint child: z unbounded; the nothing box when empty), [8] link and [9] count of the pack,
+ * [10] the pack's leaf entries and [11..16] their object indices. */
+int32_t rtx_debug_host_set_visible(const RtxScene *scene, const uint32_t *step_kind, const uint64_t *step_begin, uint64_t n_steps,
+                                   const uint64_t *indices, const RtxObject *objects, uint32_t *how, uint64_t *stats, uint64_t *digests,
+                                   double *info, uint8_t *mask, uint32_t *dump, uint64_t dump_words);
 
 /* Test hook of the lab library: the 16 digests of rtx_debug_host_refit_mesh, from the downloaded resident arrays of `scene`. */
 int32_t rtx_debug_resident_mesh_digests(RtxSceneHandle scene, uint64_t *digests);

@@ -463,6 +463,7 @@ class SceneHandle:
         packed = scene.packed()
         sc = _scene_c(scene.config, scene.camera, packed)
         self._check(self._lib.rtx_scene_upload(C.byref(sc), self.device, C.byref(self._h)))
+        self._n_objects = len(packed)
 
     def _check(self, status):
         abi.check(status, self._lib)                    # (the error string is thread-local in the library that set it)
@@ -487,6 +488,7 @@ class SceneHandle:
         arr = packed if isinstance(packed, np.ndarray) else pack_objects(packed)
         arr = np.ascontiguousarray(arr, dtype=OBJECT_DTYPE)
         self._check(self._lib.rtx_scene_append_objects(self._h, arr.ctypes.data, len(arr)))
+        self._n_objects += len(arr)
 
     def update_objects(self, indices, packed, mode="auto", stream=None):
         """Scene.objects[indices[i]] = packed[i] on the resident scene (rtx_scene_update_objects; a repeated index: its last entry
@@ -502,6 +504,29 @@ class SceneHandle:
         self._check(self._lib.rtx_scene_update_objects(self._h, idx.ctypes.data, arr.ctypes.data, len(arr), _update_mode(mode),
                                                        C.c_void_p(int(stream)) if stream else None, C.byref(how)))
         return UPDATE_HOW[how.value]
+
+    def set_visible(self, indices, visible, stream=None):
+        """Hides (visible False) or shows (True) Scene.objects[indices[i]] in place (rtx_scene_set_visible): the objects keep their
+        indices and their slots in the tree, and everything the handle produces equals a fresh upload of the list with the hidden
+        objects' geometry set to NaN -- frames also equal the list with them deleted.  Returns how the call ran: "nothing" (no state
+        changed), "records", "refit" or "rebuilt"."""
+        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.uint64).reshape(-1))
+        how = C.c_uint32(0)
+        self._check(self._lib.rtx_scene_set_visible(self._h, idx.ctypes.data if len(idx) else None, len(idx), int(visible),
+                                                    C.c_void_p(int(stream)) if stream else None, C.byref(how)))
+        return UPDATE_HOW[how.value]
+
+    def hide(self, indices):
+        return self.set_visible(indices, False)
+
+    def show(self, indices):
+        return self.set_visible(indices, True)
+
+    def visible(self):
+        """One bool per object of the resident list: False for a hidden one (rtx_scene_get_visible)."""
+        mask = np.zeros(self._n_objects, dtype=np.uint8)
+        self._check(self._lib.rtx_scene_get_visible(self._h, mask.ctypes.data if len(mask) else None))
+        return mask.astype(bool)
 
     def debug_resident_digests(self):
         """FNV-1a-64 digests of the resident arrays, in debug_host_refit's order (rtx_debug_resident_digests; a lab-library hook)."""
@@ -913,6 +938,62 @@ def debug_host_refit_mesh(scene, indices, packed, mode="deform", split=0):
                                             stats, C.byref(how), digests, info), lib)
     return (UPDATE_HOW[how.value], dict(zip(HOST_SCENE_STATS, (int(v) for v in stats))), tuple(int(v) for v in digests),
             dict(zip(MESH_REFIT_INFO, (float(v) for v in info))))
+
+
+HOST_STEP_KINDS = {"hide": 0, "show": 1, "auto": 2, "rebuild": 3, "deform": 4, "append": 5}       # rtx_debug_host_set_visible
+HOST_DUMP_WORDS = 17
+
+
+def debug_host_set_visible(scene, steps, dump=False):
+    """The host half of a handle's life with set_visible on `scene` (rtx_debug_host_set_visible of the lab library; needs no GPU).
+    `steps`: a list of ("hide" | "show", indices), ("auto" | "rebuild" | "deform", indices, packed) -- update_objects under that mode
+    -- and ("append", packed).  Returns (hows, stats dict, digests (16,), info dict, mask) and, with dump=True, a (wide nodes, 4, 17)
+    uint32 array as the sixth value: per child the link and count words, the bits of its box, the pack's link and count, and the
+    objects of the pack's leaf entries (include/rtx_hip.h)."""
+    import ctypes as C
+    sc = _scene_c(scene.config, scene.camera, scene.packed())
+    kinds, begin, idx_all, obj_all = [], [0], [], []
+    n_objects = len(scene.packed())
+    for st in steps:
+        kind = HOST_STEP_KINDS[st[0]]
+        if kind == 5:
+            arr = st[1] if isinstance(st[1], np.ndarray) else pack_objects(st[1])
+            idx = np.zeros(len(arr), dtype=np.uint64)
+            n_objects += len(arr)
+        elif kind >= 2:
+            arr = st[2] if isinstance(st[2], np.ndarray) else pack_objects(st[2])
+            idx = np.asarray(st[1], dtype=np.uint64).reshape(-1)
+            if len(idx) != len(arr):
+                raise ValueError("debug_host_set_visible: %d indices for %d objects" % (len(idx), len(arr)))
+        else:
+            idx = np.asarray(st[1], dtype=np.uint64).reshape(-1)
+            arr = np.zeros(len(idx), dtype=OBJECT_DTYPE)
+        kinds.append(kind)
+        idx_all.append(idx)
+        obj_all.append(np.ascontiguousarray(arr, dtype=OBJECT_DTYPE))
+        begin.append(begin[-1] + len(idx))
+    kinds_a = np.ascontiguousarray(np.asarray(kinds, dtype=np.uint32))
+    begin_a = np.ascontiguousarray(np.asarray(begin, dtype=np.uint64))
+    idx_a = np.ascontiguousarray(np.concatenate(idx_all) if idx_all else np.zeros(0, np.uint64), dtype=np.uint64)
+    obj_a = np.ascontiguousarray(np.concatenate(obj_all) if obj_all else np.zeros(0, OBJECT_DTYPE), dtype=OBJECT_DTYPE)
+    hows = np.zeros(max(len(kinds), 1), dtype=np.uint32)
+    stats, digests, info = (C.c_uint64 * 16)(), (C.c_uint64 * 16)(), (C.c_double * 8)()
+    mask = np.zeros(max(n_objects, 1), dtype=np.uint8)
+    lib = load_library(True)
+
+    def call(buf):
+        abi.check(lib.rtx_debug_host_set_visible(C.byref(sc), kinds_a.ctypes.data, begin_a.ctypes.data, len(kinds), idx_a.ctypes.data,
+                                                 obj_a.ctypes.data, hows.ctypes.data, stats, digests, info, mask.ctypes.data,
+                                                 buf.ctypes.data if buf is not None else None, buf.size if buf is not None else 0), lib)
+
+    call(None)
+    out = ([UPDATE_HOW[int(h)] for h in hows[:len(kinds)]], dict(zip(HOST_SCENE_STATS, (int(v) for v in stats))),
+           tuple(int(v) for v in digests), dict(zip(MESH_REFIT_INFO, (float(v) for v in info))), mask[:n_objects].astype(bool))
+    if not dump:
+        return out
+    buf = np.zeros((int(info[7]), 4, HOST_DUMP_WORDS), dtype=np.uint32)
+    call(buf)
+    return out + (buf,)
 
 
 # one segment of a path's transcript (RtxPathStep, include/rtx_hip.h)

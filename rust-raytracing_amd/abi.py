@@ -114,6 +114,8 @@ SYMBOLS = [
     ("rtx_scene_set_camera", C.c_int32, [C.c_void_p, C.POINTER(RtxCamera)]),
     ("rtx_scene_append_objects", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64]),
     ("rtx_scene_update_objects", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]),
+    ("rtx_scene_set_visible", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]),
+    ("rtx_scene_get_visible", C.c_int32, [C.c_void_p, C.c_void_p]),
     ("rtx_render_rows", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                     C.c_void_p, C.c_void_p, C.POINTER(RtxStats)]),
     ("rtx_blocks_row_count", C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
@@ -157,6 +159,9 @@ SYMBOLS = [
     ("rtx_debug_host_refit_mesh", C.c_int32, [C.POINTER(RtxScene), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64),
                                               C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     ("rtx_debug_resident_mesh_digests", C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    ("rtx_debug_host_set_visible", C.c_int32, [C.POINTER(RtxScene), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.c_void_p, C.c_void_p,
+                                               C.c_uint64]),
 ]
 
 

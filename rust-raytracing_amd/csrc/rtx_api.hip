@@ -118,8 +118,9 @@ int usable_device_count()
 void drop_update_tables(RtxSceneHandle_ *h)              // the device tables of one pack (the staging buffers stay)
 {
     auto &b = h->upd;
-    for (void *q : { (void *)b.levels, (void *)b.box32, (void *)b.reach, (void *)b.all_levels, (void *)b.tribox32, (void *)b.tri_reach })
+    for (void *q : { (void *)b.levels, (void *)b.box32, (void *)b.reach, (void *)b.all_levels, (void *)b.tribox32, (void *)b.tri_reach, (void *)b.keep })
         if (q) (void)hipFree(q);
+    b.keep = nullptr; b.keep_valid = false;
     b.levels = nullptr; b.box32 = nullptr; b.reach = nullptr; b.valid = false;
     b.all_levels = nullptr; b.tribox32 = nullptr; b.tri_reach = nullptr; b.mesh_valid = false;
 }

@@ -70,6 +70,20 @@ int32_t rtx_debug_host_refit_mesh(const RtxScene *scene, const uint64_t *indices
 #endif
 }
 
+int32_t rtx_debug_host_set_visible(const RtxScene *scene, const uint32_t *step_kind, const uint64_t *step_begin, uint64_t n_steps,
+                                   const uint64_t *indices, const RtxObject *objects, uint32_t *how, uint64_t *stats, uint64_t *digests,
+                                   double *info, uint8_t *mask, uint32_t *dump, uint64_t dump_words)
+{
+#ifdef RTX_LAB
+    return host_visibility("rtx_debug_host_set_visible", scene, step_kind, step_begin, n_steps, indices, objects, how, stats, digests, info, mask,
+                           dump, dump_words);
+#else
+    (void)scene; (void)step_kind; (void)step_begin; (void)n_steps; (void)indices; (void)objects; (void)how; (void)stats; (void)digests;
+    (void)info; (void)mask; (void)dump; (void)dump_words;
+    return fail(RTX_ERR_UNSUPPORTED, "rtx_debug_host_set_visible is a hook of the lab library (librtx_hip_lab.so)");
+#endif
+}
+
 int32_t rtx_debug_resident_digests(RtxSceneHandle h, uint64_t *digests)
 {
 #ifdef RTX_LAB

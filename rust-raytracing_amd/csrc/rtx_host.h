@@ -23,6 +23,7 @@ struct RtxSceneHandle_ {
     RtxCamera cam{};
     SceneView sv{};
     std::vector<RtxObject> objects;                       // Scene.objects as uploaded (rtx_scene_append_objects re-packs them)
+    std::vector<uint8_t> hidden;                          // rtx_scene_set_visible: one byte per object (1: hidden; empty: none ever was)
     std::vector<void *> scene_allocs;
     // rtx_scene_update_objects: the host tables of the resident pack, and their device side -- made at the first REFIT or RECORDS
     // call, dropped by any rebuild (upload_packed)
@@ -32,6 +33,8 @@ struct RtxSceneHandle_ {
         uint32_t *levels = nullptr; float *box32 = nullptr; double *reach = nullptr;
         bool mesh_valid = false;                                // the triangle half: made at the first DEFORM call that moves a triangle
         uint32_t *all_levels = nullptr; float *tribox32 = nullptr; double *tri_reach = nullptr;
+        bool keep_valid = false;                                // the kept words (rtx_refit.h): made by the first visibility call after a pack
+        uint32_t *keep = nullptr;
         UpdateEntry *h_entries = nullptr; size_t h_cap = 0;     // pinned staging of the update list
         UpdateEntry *d_entries = nullptr; size_t d_cap = 0;
         unsigned long long *d_status = nullptr, *h_status = nullptr;   // {status bits, the bits of the new sphere_cmax, of the new tri_extent}; h_status pinned

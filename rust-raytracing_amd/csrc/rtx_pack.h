@@ -77,25 +77,37 @@ struct UpdatePlan {
     bool tri_geom = false;                                // a triangle's geometry changes in place (RTX_UPDATE_DEFORM): the triangle tables are needed
     bool tri_refit = false;                               // ... and it has a tree record: every level is refitted, footprint nodes included
     bool any_tri = false;                                 // ... and it is qualified: tri_extent is taken again
+    bool visibility = false;                              // rtx_scene_set_visible's plan: mode B needs the kept words
+    bool capture = false;                                 // ... and the pack has none yet (the caller sets it): mode E runs first
 };
 
 int32_t plan_update(const std::vector<RtxObject> &cur, const RefitTables &t, double cmax, const uint64_t *indices, const RtxObject *objects,
-                    uint64_t n, uint32_t mode, UpdatePlan &plan);
+                    uint64_t n, uint32_t mode, UpdatePlan &plan, const uint8_t *hidden = nullptr);
+int32_t plan_visibility(const std::vector<RtxObject> &cur, const std::vector<uint8_t> &hidden, const RefitTables &t, double cmax,
+                        const uint64_t *indices, uint64_t n, uint32_t visible, UpdatePlan &plan);
 void derive_all_spheres(const RtxObject *objects, size_t n_objects, const RefitTables &t, size_t n_spheres, std::vector<float> &box32,
-                        std::vector<double> &reach);
-void derive_all_triangles(const RtxObject *objects, size_t n_objects, const RefitTables &t, std::vector<float> &tribox32, std::vector<double> &tri_reach);
+                        std::vector<double> &reach, const uint8_t *hidden = nullptr);
+void derive_all_triangles(const RtxObject *objects, size_t n_objects, const RefitTables &t, std::vector<float> &tribox32, std::vector<double> &tri_reach,
+                          const uint8_t *hidden = nullptr);
 UpdateArgs update_args(const SceneView &where, const RefitTables &t, const UpdateEntry *entries, float *box32, double *reach, float *tribox32,
-                       double *tri_reach, bool tri_geom);
+                       double *tri_reach, bool tri_geom, uint32_t *keep = nullptr);
 
 // The steps of one update in the order they run, written once for the device and for its host reference.  `run` performs one step --
 // a launch of scene_update_kernel (rtx_scene_update_objects), or rtx_refit.h's functions in a loop (refit_packed) -- and returns false
 // to stop.  Mode A over the entries; under REFIT the levels as mode B, deepest first: a node reads what its children's step wrote (a
 // moved triangle of the tree: every level, footprint nodes included -- all_levels; spheres alone: the non-flat levels, as ever);
-// mode C when a sphere moved; mode D when a qualified triangle did.
+// mode C when a sphere moved; mode D when a qualified triangle did.  A visibility plan on a pack without kept words (plan.capture)
+// starts with mode E over every wide node: the words are read before anything of this update is written.
 template <class Run>
 bool run_update(UpdateArgs u, const RefitTables &t, const UpdatePlan &plan, const uint32_t *levels, const uint32_t *all_levels,
                 uint32_t n_spheres, uint32_t n_tris, Run run)
 {
+    if (plan.capture) {
+        const bool all = !t.all_level_nodes.empty();
+        u.mode = 4u; u.n = (uint32_t)(all ? t.all_level_nodes.size() : t.level_nodes.size());
+        u.level = all ? all_levels : levels;
+        if (!run(u)) return false;
+    }
     u.mode = 0u; u.n = (uint32_t)plan.entries.size();
     if (!run(u)) return false;
     if (plan.how == RTX_UPDATED_REFIT) {
@@ -113,13 +125,19 @@ bool run_update(UpdateArgs u, const RefitTables &t, const UpdatePlan &plan, cons
 }
 
 unsigned long long refit_packed(PackedScene &p, const RefitTables &t, const UpdatePlan &plan, std::vector<float> &box32, std::vector<double> &reach,
-                                std::vector<float> &tribox32, std::vector<double> &tri_reach);
+                                std::vector<float> &tribox32, std::vector<double> &tri_reach, std::vector<uint32_t> *keep = nullptr);
 void digest_packed(const PackedScene &p, uint64_t *digests);
 void digest_packed_mesh(const PackedScene &p, uint64_t *digests);
-int32_t check_packed(const PackedScene &p, const RtxObject *objects, uint64_t *stats);
+int32_t check_packed(const PackedScene &p, const RtxObject *objects, uint64_t *stats, const uint8_t *hidden = nullptr);
 #ifdef RTX_LAB
 int32_t host_refit(const char *who, const RtxScene *scene, const uint64_t *indices, const RtxObject *objects, uint64_t n, uint32_t mode,
                    uint64_t *stats, uint32_t *how, uint64_t *digests, double *info);
+// rtx_debug_host_set_visible (include/rtx_hip.h): the kinds of its steps, and the words per child of its dump.
+enum : uint32_t { kHostStepHide = 0, kHostStepShow = 1, kHostStepUpdate = 2 /* + RTX_UPDATE_* */, kHostStepAppend = 5 };
+constexpr uint32_t kHostDumpWords = 17;
+int32_t host_visibility(const char *who, const RtxScene *scene, const uint32_t *step_kind, const uint64_t *step_begin, uint64_t n_steps,
+                        const uint64_t *indices, const RtxObject *objects, uint32_t *how, uint64_t *stats, uint64_t *digests, double *info,
+                        uint8_t *mask, uint32_t *dump, uint64_t dump_words);
 #endif
 
 RTX_HOST_END

@@ -345,8 +345,51 @@ RefitTables make_refit_tables(const PackedScene &p)
 //                   that keeps its class and free axis (classify_triangle: the decision pack_scene takes) is rewritten against the kept
 //                   centre and mode D takes tri_extent again; the class rule keeps tri_fidx, the leaf order and which records are real
 //   bvh_depth, bvh_flags, the topology   the tree keeps its shape; a sphere that turns non-finite (it would leave the tree) rebuilds
+// What one shape's NEW geometry `o.geom` means for an entry of the resident kind (the per-shape half of "Which path runs", shared by
+// plan_update and plan_visibility, which shows an object with the geometry it has now): fills e.slot / e.tri and the plan's flags,
+// raises `rebuild` when the geometry cannot be written in place, `refit` when boxes above it change.
+static void plan_shape(const RefitTables &t, uint32_t mode, const RtxObject &o, UpdateEntry &e, UpdatePlan &plan, bool &rebuild, bool &refit)
+{
+    if (o.kind == RTX_TRIANGLE) {
+        bool finite = true;
+        for (int c = 0; c < 9; ++c) finite = finite && std::isfinite(o.geom[c]);
+        const uint32_t k = e.local;
+        TriClass tc{kTriNone, 2};
+        if (mode == RTX_UPDATE_DEFORM && finite) tc = classify_triangle(make_triangle(o.geom, e.object), o.geom, t.centre);
+        if (mode != RTX_UPDATE_DEFORM || !finite || tc.cls != t.tri_class[k] || (tc.cls == kTriQualified && tc.free_axis != t.tri_axis[k]))
+            rebuild = true;                                   // AUTO: always, as ever; DEFORM: the class or the free axis changes
+        else {
+            plan.tri_geom = true;
+            e.tri = kTriEntryGeom; e.slot = t.tri_rec[k];
+            if (tc.cls == kTriQualified) {
+                e.tri |= kTriEntryQualified | ((uint32_t)tc.free_axis << kTriEntryAxisShift);
+                plan.any_tri = true;
+                BvhBox fp;
+                if (!triangle_footprint(o.geom, fp, tc.free_axis)) rebuild = true;
+                else if (t.scale >= 0.0)
+                    for (int a = 0; a < 3; ++a)
+                        if (a != tc.free_axis && (std::fabs(fp.lo[a]) > t.scale || std::fabs(fp.hi[a]) > t.scale)) rebuild = true;
+                if (e.slot < t.n_tri_tree) { e.tri |= kTriEntryTree; plan.tri_refit = true; refit = true; }
+            }
+        }
+    } else if (o.kind == RTX_SPHERE) {
+        plan.any_sphere = true;
+        BvhBox b;
+        if (!sphere_box(o.geom, b)) rebuild = true;
+        else {
+            if (t.scale >= 0.0)
+                for (int a = 0; a < 3; ++a) if (std::fabs(b.lo[a]) > t.scale || std::fabs(b.hi[a]) > t.scale) rebuild = true;
+            const double cx = o.geom[0] - t.centre[0], cy = o.geom[1] - t.centre[1], cz = o.geom[2] - t.centre[2];
+            if (!(std::sqrt(cx * cx + cy * cy + cz * cz) + std::fabs(o.geom[3]) < 1.0e14)) rebuild = true;
+        }
+        if (t.sphere_tree) { e.slot = t.slot[e.local]; refit = true; }
+    }
+}
+
+// `hidden` (null: nothing is): the handle's visibility bytes.  An entry for a hidden object updates the host's object and the material
+// record alone (kEntryNoGeom); its geometry is judged when the object is shown (plan_visibility).  A kind change rebuilds as ever.
 int32_t plan_update(const std::vector<RtxObject> &cur, const RefitTables &t, double cmax, const uint64_t *indices, const RtxObject *objects,
-                    uint64_t n, uint32_t mode, UpdatePlan &plan)
+                    uint64_t n, uint32_t mode, UpdatePlan &plan, const uint8_t *hidden)
 {
     plan = UpdatePlan();
     if (mode != RTX_UPDATE_AUTO && mode != RTX_UPDATE_REBUILD && mode != RTX_UPDATE_DEFORM) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_update_objects: unknown mode");
@@ -375,58 +418,79 @@ int32_t plan_update(const std::vector<RtxObject> &cur, const RefitTables &t, dou
         static_assert(sizeof(RtxObject) == 136 && offsetof(UpdateEntry, kind) == 16, "UpdateEntry carries an RtxObject");
         std::memcpy(&e.kind, &o, sizeof o);
         if (o.kind != cur[idx].kind) rebuild = true;
+        else if (hidden && hidden[idx]) e.tri = kEntryNoGeom;
         else if (o.kind == RTX_TRIANGLE) {
-            if (std::memcmp(o.geom, cur[idx].geom, sizeof o.geom) != 0) {          // (same geometry: a material update)
-                bool finite = true;
-                for (int c = 0; c < 9; ++c) finite = finite && std::isfinite(o.geom[c]);
-                const uint32_t k = e.local;
-                TriClass tc{kTriNone, 2};
-                if (mode == RTX_UPDATE_DEFORM && finite) tc = classify_triangle(make_triangle(o.geom, (uint32_t)idx), o.geom, t.centre);
-                if (mode != RTX_UPDATE_DEFORM || !finite || tc.cls != t.tri_class[k] || (tc.cls == kTriQualified && tc.free_axis != t.tri_axis[k]))
-                    rebuild = true;                                   // AUTO: always, as ever; DEFORM: the class or the free axis changes
-                else {
-                    plan.tri_geom = true;
-                    e.tri = kTriEntryGeom; e.slot = t.tri_rec[k];
-                    if (tc.cls == kTriQualified) {
-                        e.tri |= kTriEntryQualified | ((uint32_t)tc.free_axis << kTriEntryAxisShift);
-                        plan.any_tri = true;
-                        BvhBox fp;
-                        if (!triangle_footprint(o.geom, fp, tc.free_axis)) rebuild = true;
-                        else if (t.scale >= 0.0)
-                            for (int a = 0; a < 3; ++a)
-                                if (a != tc.free_axis && (std::fabs(fp.lo[a]) > t.scale || std::fabs(fp.hi[a]) > t.scale)) rebuild = true;
-                        if (e.slot < t.n_tri_tree) { e.tri |= kTriEntryTree; plan.tri_refit = true; refit = true; }
-                    }
-                }
-            }
-        } else if (o.kind == RTX_SPHERE && std::memcmp(o.geom, cur[idx].geom, 4 * sizeof(double)) != 0) {      // (same geometry: a material update)
-            plan.any_sphere = true;
-            BvhBox b;
-            if (!sphere_box(o.geom, b)) rebuild = true;
-            else {
-                if (t.scale >= 0.0)
-                    for (int a = 0; a < 3; ++a) if (std::fabs(b.lo[a]) > t.scale || std::fabs(b.hi[a]) > t.scale) rebuild = true;
-                const double cx = o.geom[0] - t.centre[0], cy = o.geom[1] - t.centre[1], cz = o.geom[2] - t.centre[2];
-                if (!(std::sqrt(cx * cx + cy * cy + cz * cz) + std::fabs(o.geom[3]) < 1.0e14)) rebuild = true;
-            }
-            if (t.sphere_tree) { e.slot = t.slot[e.local]; refit = true; }
-        }
+            if (std::memcmp(o.geom, cur[idx].geom, sizeof o.geom) != 0) plan_shape(t, mode, o, e, plan, rebuild, refit);      // (same geometry: a material update)
+        } else if (o.kind == RTX_SPHERE && std::memcmp(o.geom, cur[idx].geom, 4 * sizeof(double)) != 0)                       // (likewise)
+            plan_shape(t, mode, o, e, plan, rebuild, refit);
         plan.entries.push_back(e);
     }
     plan.how = rebuild ? RTX_UPDATED_REBUILT : (refit ? RTX_UPDATED_REFIT : RTX_UPDATED_RECORDS);
     return RTX_OK;
 }
 
+// rtx_scene_set_visible: what the host decides (no HIP call).  `hidden` holds the handle's bytes (1: hidden) and is NOT changed: the
+// caller flips the bytes of plan.entries after the plan ran.  Entries already in the requested state are dropped; a hide entry names
+// the records hide_record rewrites; a show entry is plan_shape's entry for the object's current geometry under RTX_UPDATE_DEFORM's
+// rules (a plane: its record alone).  REFIT when a changed shape has a slot in the tree, REBUILT when a shown shape's geometry cannot be
+// taken in place (the resident class, axis and range are those of the pack, which packed the object's real geometry of that time).
+int32_t plan_visibility(const std::vector<RtxObject> &cur, const std::vector<uint8_t> &hidden, const RefitTables &t, double cmax,
+                        const uint64_t *indices, uint64_t n, uint32_t visible, UpdatePlan &plan)
+{
+    plan = UpdatePlan();
+    if (visible > 1u) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_set_visible: visible is neither 0 nor 1");
+    if (n == 0) return RTX_OK;
+    if (!indices) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_set_visible: null indices");
+    for (uint64_t i = 0; i < n; ++i)
+        if (indices[i] >= cur.size())
+            return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_set_visible: index " + std::to_string(indices[i]) + " is not below n_objects");
+    std::vector<uint8_t> seen(cur.size(), 0);
+    bool rebuild = false, refit = false;
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t idx = indices[i];
+        if (seen[idx] || (hidden[idx] != 0) == (visible == 0u)) continue;
+        seen[idx] = 1;
+        const RtxObject &o = cur[idx];
+        UpdateEntry e;
+        std::memset(&e, 0, sizeof e);
+        e.object = (uint32_t)idx; e.local = t.local[idx]; e.slot = kNoSlot;
+        std::memcpy(&e.kind, &o, sizeof o);
+        if (visible) plan_shape(t, RTX_UPDATE_DEFORM, o, e, plan, rebuild, refit);
+        else {
+            e.tri = kEntryHide;
+            if (o.kind == RTX_SPHERE) {
+                plan.any_sphere = true;
+                if (t.sphere_tree) { e.slot = t.slot[e.local]; refit = true; }
+            } else if (o.kind == RTX_TRIANGLE) {
+                plan.tri_geom = true;
+                e.slot = t.tri_rec[e.local];
+                if (t.tri_class[e.local] == kTriQualified) plan.any_tri = true;
+                if (e.slot < t.n_tri_tree) { e.tri |= kTriEntryTree; plan.tri_refit = true; refit = true; }
+            }
+        }
+        plan.entries.push_back(e);
+    }
+    if (plan.entries.empty()) return RTX_OK;
+    plan.visibility = true;
+    if (!(cmax < 1.0e14)) rebuild = true;                     // (plan_update's rule: the resident f32 sphere records are not real ones)
+    plan.how = rebuild ? RTX_UPDATED_REBUILT : (refit ? RTX_UPDATED_REFIT : RTX_UPDATED_RECORDS);
+    return RTX_OK;
+}
+
 // box32 / reach of every sphere of `objects` (what mode B and mode C read for the spheres an update does not name).
 void derive_all_spheres(const RtxObject *objects, size_t n_objects, const RefitTables &t, size_t n_spheres, std::vector<float> &box32,
-                        std::vector<double> &reach)
+                        std::vector<double> &reach, const uint8_t *hidden)
 {
     box32.assign(n_spheres * 6, 0.f);
     reach.assign(n_spheres, 0.0);
     for (size_t k = 0; k < n_objects; ++k) {
         if (objects[k].kind != RTX_SPHERE) continue;
-        const SphereDerived d = derive_sphere(objects[k].geom, t.centre, t.abs_pad);
         const size_t q = t.local[k];
+        if (hidden && hidden[k]) {                            // hide_record's rows: the nothing box, reach 0
+            for (int a = 0; a < 3; ++a) { box32[6 * q + a] = INFINITY; box32[6 * q + 3 + a] = -INFINITY; }
+            continue;
+        }
+        const SphereDerived d = derive_sphere(objects[k].geom, t.centre, t.abs_pad);
         for (int a = 0; a < 3; ++a) { box32[6 * q + a] = d.lo[a]; box32[6 * q + 3 + a] = d.hi[a]; }
         reach[q] = d.reach;
     }
@@ -434,7 +498,8 @@ void derive_all_spheres(const RtxObject *objects, size_t n_objects, const RefitT
 
 // tribox32 (per tree record) / tri_reach (per triangle) of every triangle of `objects`: what modes B and D read for the triangles an
 // update does not name.
-void derive_all_triangles(const RtxObject *objects, size_t n_objects, const RefitTables &t, std::vector<float> &tribox32, std::vector<double> &tri_reach)
+void derive_all_triangles(const RtxObject *objects, size_t n_objects, const RefitTables &t, std::vector<float> &tribox32, std::vector<double> &tri_reach,
+                          const uint8_t *hidden)
 {
     tribox32.assign((size_t)t.n_tri_tree * 6, 0.f);
     tri_reach.assign(t.tri_class.size(), 0.0);
@@ -442,6 +507,10 @@ void derive_all_triangles(const RtxObject *objects, size_t n_objects, const Refi
         if (objects[k].kind != RTX_TRIANGLE) continue;
         const uint32_t q = t.local[k];
         if (t.tri_class[q] != kTriQualified) continue;
+        if (hidden && hidden[k]) {                            // hide_record's rows
+            if (t.tri_rec[q] < t.n_tri_tree) for (int a = 0; a < 3; ++a) { tribox32[(size_t)t.tri_rec[q] * 6 + a] = INFINITY; tribox32[(size_t)t.tri_rec[q] * 6 + 3 + a] = -INFINITY; }
+            continue;
+        }
         const TriDerived d = derive_triangle(objects[k].geom, (uint32_t)k, true, (int)t.tri_axis[q], t.centre, t.abs_pad);
         tri_reach[q] = d.reach;
         if (t.tri_rec[q] < t.n_tri_tree) for (int a = 0; a < 6; ++a) tribox32[(size_t)t.tri_rec[q] * 6 + a] = d.box[a];
@@ -450,9 +519,9 @@ void derive_all_triangles(const RtxObject *objects, size_t n_objects, const Refi
 
 // The UpdateArgs of an update of the arrays `where` points at -- a PackedScene's vectors on the host (host_view), the resident arrays
 // on the device -- with the tables of their pack; mode, n, level and status are the caller's.  The triangle half is set only when
-// the plan moves a triangle.
+// the plan moves a triangle; `keep` is the kept-words table, null while the pack has none.
 UpdateArgs update_args(const SceneView &sv, const RefitTables &t, const UpdateEntry *entries, float *box32, double *reach, float *tribox32,
-                       double *tri_reach, bool tri_geom)
+                       double *tri_reach, bool tri_geom, uint32_t *keep)
 {
     UpdateArgs u{};
     u.entries = entries;
@@ -466,6 +535,8 @@ UpdateArgs update_args(const SceneView &sv, const RefitTables &t, const UpdateEn
     u.prims = sv.bvh_prims;
     for (int c = 0; c < 3; ++c) u.centre[c] = t.centre[c];
     u.abs_pad = t.abs_pad;
+    u.keep = keep;
+    if (keep) u.qnodes = (sv.bvh_flags & 8u) ? const_cast<BvhQNode *>(sv.bvh_qnodes) : nullptr;      // (mode E reads the links of both 64-byte forms)
     if (tri_geom) {
         u.tris = const_cast<TriX *>(sv.tris); u.tri_f32 = const_cast<float4 *>(sv.tri_f32); u.tri_geo = const_cast<float4 *>(sv.tri_geo);
         u.tribox32 = tribox32; u.tri_reach = tri_reach;
@@ -489,13 +560,16 @@ static SceneView host_view(PackedScene &p)
 // Returns the status word (kUpdateStatusNoQ3 / kUpdateStatusNoQ: a 64-byte node has no encoding -- the caller rebuilds).  tribox32 /
 // tri_reach are read only when the plan moves a triangle.
 unsigned long long refit_packed(PackedScene &p, const RefitTables &t, const UpdatePlan &plan, std::vector<float> &box32, std::vector<double> &reach,
-                                std::vector<float> &tribox32, std::vector<double> &tri_reach)
+                                std::vector<float> &tribox32, std::vector<double> &tri_reach, std::vector<uint32_t> *keep)
 {
     unsigned long long status = 0ull;
-    const UpdateArgs u = update_args(host_view(p), t, plan.entries.data(), box32.data(), reach.data(), tribox32.data(), tri_reach.data(), plan.tri_geom);
+    if (keep && plan.capture) keep->assign(p.bvh4.nodes.size() * (size_t)kKeepWords, 0u);
+    const UpdateArgs u = update_args(host_view(p), t, plan.entries.data(), box32.data(), reach.data(), tribox32.data(), tri_reach.data(), plan.tri_geom,
+                                     keep && !keep->empty() ? keep->data() : nullptr);
     run_update(u, t, plan, t.level_nodes.data(), t.all_level_nodes.data(), p.sv.n_spheres, p.sv.n_tris, [&](const UpdateArgs &a) {
         if (a.mode == 0u) for (uint32_t i = 0; i < a.n; ++i) update_record(a, i);
         else if (a.mode == 1u) for (uint32_t k = 0; k < a.n; ++k) status |= refit_level_entry(a, a.level[k]);
+        else if (a.mode == 4u) for (uint32_t k = 0; k < a.n; ++k) capture_keep(a, a.level[k]);
         else {                                                // modes C and D: the max of non-negative doubles, from 0.0
             const double *src = a.mode == 2u ? a.reach : a.tri_reach;
             double m = 0.0;
@@ -544,7 +618,10 @@ void digest_packed_mesh(const PackedScene &p, uint64_t *digests)
 // The invariant walk of rtx_debug_host_scene / rtx_debug_host_refit over a packed scene and the object list it stands for: every
 // shape's box inside its leaf child's box, every child inside its parent's, every 64-byte node's decoded child box around the
 // 128-byte child's.  `stats`: include/rtx_hip.h, rtx_debug_host_scene.
-int32_t check_packed(const PackedScene &p, const RtxObject *objects, uint64_t *stats)
+// `hidden` (null: nothing is; rtx_scene_set_visible): a hidden shape needs no containing box and may lie under an empty slot; every
+// VISIBLE shape of the tree is still found in exactly one leaf, inside its box.  Nodes below an empty slot are not reached, so the
+// depth and "every node is reached" are then not held.
+int32_t check_packed(const PackedScene &p, const RtxObject *objects, uint64_t *stats, const uint8_t *hidden)
 {
     for (int k = 0; k < 16; ++k) stats[k] = 0;
     stats[0] = p.spheres.size(); stats[1] = p.tris.size(); stats[2] = p.sv.n_tri_filter; stats[3] = p.sv.n_tri_tree;
@@ -599,6 +676,7 @@ int32_t check_packed(const PackedScene &p, const RtxObject *objects, uint64_t *s
                     if (tri_seen[rec]++) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: triangle in two leaves");
                     const TriX &tx = p.tris[p.tri_fidx[rec]];
                     const RtxObject &o = objects[tx.id];
+                    if (hidden && hidden[tx.id]) continue;
                     const int free_axis = p.tri_rec_free_axis[rec];
                     if (free_axis != 3 - (int)tx.i - (int)tx.j) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: footprint plane differs from the elimination's rows");
                     if (flat && free_axis != 2) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: a flat node holds a triangle that is not solved in (x, y)");
@@ -616,6 +694,7 @@ int32_t check_packed(const PackedScene &p, const RtxObject *objects, uint64_t *s
                     if (link + k >= p.bvh.prims.size()) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: sphere entry out of range");
                     const uint32_t sidx = p.bvh.prims[link + k];
                     if (sidx >= p.spheres.size() || sphere_seen[sidx]++) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: sphere in two leaves");
+                    if (hidden && hidden[p.sphere_id[sidx]]) continue;
                     BvhBox sb;
                     if (!sphere_box(objects[p.sphere_id[sidx]].geom, sb)) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: non-finite sphere in the tree");
                     for (int a = 0; a < 3; ++a)
@@ -672,10 +751,17 @@ int32_t check_packed(const PackedScene &p, const RtxObject *objects, uint64_t *s
         }
         stats[15] = p.q3nodes.size();
     }
-    if (depth != p.bvh4.depth) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: recorded depth differs");
-    for (size_t k = 0; k < n_nodes; ++k) if (!node_seen[k]) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: unreachable node");
-    if ((p.sv.bvh_flags & 1u) && stats[8] != p.spheres.size()) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: a sphere is in no leaf");
-    if ((p.sv.bvh_flags & 2u) && stats[9] != p.sv.n_tri_tree) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: a triangle is in no leaf");
+    uint64_t live_spheres = p.spheres.size(), live_tris = p.sv.n_tri_tree;
+    if (hidden) {
+        for (size_t k = 0; k < p.spheres.size(); ++k) if (hidden[p.sphere_id[k]]) live_spheres -= 1;
+        for (uint32_t r = 0; r < p.sv.n_tri_tree; ++r) if (hidden[p.tris[p.tri_fidx[r]].id]) live_tris -= 1;
+        if (depth > p.bvh4.depth) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: deeper than recorded");
+    } else {
+        if (depth != p.bvh4.depth) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: recorded depth differs");
+        for (size_t k = 0; k < n_nodes; ++k) if (!node_seen[k]) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: unreachable node");
+    }
+    if ((p.sv.bvh_flags & 1u) && stats[8] != live_spheres) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: a sphere is in no leaf");
+    if ((p.sv.bvh_flags & 2u) && stats[9] != live_tris) return fail(RTX_ERR_INVALID_ARGUMENT, "bvh check: a triangle is in no leaf");
     return RTX_OK;
 }
 
@@ -723,6 +809,146 @@ int32_t host_refit(const char *who, const RtxScene *scene, const uint64_t *indic
         info[3] = p.sv.tri_extent; info[4] = p.sv.sphere_cmax; info[5] = t.abs_pad; info[6] = t.scale; info[7] = 0.0;
     } else digest_packed(p, digests);
     return check_packed(p, cur.data(), stats);
+}
+// ---- the host model of a resident handle (rtx_debug_host_set_visible, tools/host_pack_check.cpp): every step rtx_scene_set_visible,
+// rtx_scene_update_objects and rtx_scene_append_objects take on a handle, on a PackedScene, with refit_packed in place of the launches.
+namespace {
+
+struct HostResident {
+    RtxScene sc{};
+    std::vector<RtxObject> cur;
+    std::vector<uint8_t> hidden;
+    PackedScene p;
+    RefitTables t;
+    std::vector<float> box32, tribox32;
+    std::vector<double> reach, tri_reach;
+    std::vector<uint32_t> keep;
+    bool tables = false, mesh_tables = false, keep_valid = false;
+};
+
+// One planned update on the arrays (the device: apply_plan, rtx_api_update.hip).  True: a 64-byte node had no encoding.
+bool host_apply(HostResident &r, UpdatePlan &plan)
+{
+    if (!r.tables) { derive_all_spheres(r.cur.data(), r.cur.size(), r.t, r.p.spheres.size(), r.box32, r.reach, r.hidden.data()); r.tables = true; }
+    if (plan.tri_geom && !r.mesh_tables) { derive_all_triangles(r.cur.data(), r.cur.size(), r.t, r.tribox32, r.tri_reach, r.hidden.data()); r.mesh_tables = true; }
+    plan.capture = plan.visibility && !r.keep_valid;
+    if (plan.capture) r.keep_valid = true;
+    return (refit_packed(r.p, r.t, plan, r.box32, r.reach, r.tribox32, r.tri_reach, &r.keep) & (kUpdateStatusNoQ3 | kUpdateStatusNoQ)) != 0ull;
+}
+
+// The pack of the list with its REAL geometries, then the hide pass on the fresh arrays (the device: repack_objects).
+int32_t host_repack(HostResident &r)
+{
+    r.sc.n_objects = r.cur.size();
+    r.sc.objects = r.cur.data();
+    r.p = PackedScene();
+    if (int32_t rc = pack_scene(&r.sc, r.p)) return rc;
+    r.t = make_refit_tables(r.p);
+    r.tables = r.mesh_tables = r.keep_valid = false;
+    r.keep.clear();
+    std::vector<uint64_t> idx;
+    for (size_t k = 0; k < r.hidden.size(); ++k) if (r.hidden[k]) idx.push_back(k);
+    if (idx.empty()) return RTX_OK;
+    const std::vector<uint8_t> none(r.cur.size(), 0);
+    UpdatePlan plan;
+    if (int32_t rc = plan_visibility(r.cur, none, r.t, 0.0, idx.data(), idx.size(), 0u, plan)) return rc;
+    if (!(r.p.sv.sphere_cmax < 1.0e14)) plan.any_sphere = false;      // (mode C only runs over finite reaches; such a pack stays "every ray sweeps")
+    std::vector<uint8_t> keep_hidden;
+    keep_hidden.swap(r.hidden);                               // (the tables of the fresh pack are those of the all-visible list)
+    r.hidden = none;
+    const bool bad = host_apply(r, plan);
+    r.hidden.swap(keep_hidden);
+    if (bad) return fail(RTX_ERR_UNSUPPORTED, "hidden objects: a 64-byte node of the fresh pack has no encoding without them");
+    return RTX_OK;
+}
+
+}  // namespace
+
+int32_t host_visibility(const char *who, const RtxScene *scene, const uint32_t *step_kind, const uint64_t *step_begin, uint64_t n_steps,
+                        const uint64_t *indices, const RtxObject *objects, uint32_t *how, uint64_t *stats, uint64_t *digests, double *info,
+                        uint8_t *mask, uint32_t *dump, uint64_t dump_words)
+{
+    if (!scene || !stats || !digests || (n_steps && (!step_kind || !step_begin || !how)))
+        return fail(RTX_ERR_INVALID_ARGUMENT, std::string(who) + ": null argument");
+    if (scene->n_objects && !scene->objects) return fail(RTX_ERR_INVALID_ARGUMENT, std::string(who) + ": objects is null");
+    HostResident r;
+    r.sc = *scene;
+    r.cur.assign(scene->objects, scene->objects + scene->n_objects);
+    r.hidden.assign(r.cur.size(), 0);
+    if (int32_t rc = host_repack(r)) return rc;
+    for (uint64_t s = 0; s < n_steps; ++s) {
+        how[s] = RTX_UPDATED_NOTHING;
+        if (step_begin[s + 1] < step_begin[s]) return fail(RTX_ERR_INVALID_ARGUMENT, std::string(who) + ": step ranges do not ascend");
+        const uint64_t first = step_begin[s], count = step_begin[s + 1] - first;
+        const uint64_t *idx = indices ? indices + first : nullptr;
+        const RtxObject *obj = objects ? objects + first : nullptr;
+        UpdatePlan plan;
+        if (step_kind[s] == kHostStepAppend) {
+            if (count && !obj) return fail(RTX_ERR_INVALID_ARGUMENT, std::string(who) + ": an append step without objects");
+            if (count == 0) continue;
+            r.cur.insert(r.cur.end(), obj, obj + count);
+            r.hidden.resize(r.cur.size(), 0);
+            if (int32_t rc = host_repack(r)) return rc;
+            how[s] = RTX_UPDATED_REBUILT;
+            continue;
+        }
+        if (step_kind[s] <= kHostStepShow) {
+            if (int32_t rc = plan_visibility(r.cur, r.hidden, r.t, r.p.sv.sphere_cmax, idx, count, step_kind[s] == kHostStepShow ? 1u : 0u, plan)) return rc;
+        } else if (step_kind[s] <= kHostStepUpdate + RTX_UPDATE_DEFORM) {
+            if (int32_t rc = plan_update(r.cur, r.t, r.p.sv.sphere_cmax, idx, obj, count, step_kind[s] - kHostStepUpdate, plan, r.hidden.data())) return rc;
+        } else return fail(RTX_ERR_INVALID_ARGUMENT, std::string(who) + ": unknown step kind");
+        if (plan.entries.empty()) continue;
+        if (plan.how != RTX_UPDATED_REBUILT && host_apply(r, plan)) plan.how = RTX_UPDATED_REBUILT;
+        for (const UpdateEntry &e : plan.entries) {
+            if (plan.visibility) r.hidden[e.object] = (e.tri & kEntryHide) ? 1 : 0;
+            else std::memcpy(&r.cur[e.object], &e.kind, sizeof(RtxObject));
+        }
+        if (plan.how == RTX_UPDATED_REBUILT) if (int32_t rc = host_repack(r)) return rc;
+        how[s] = plan.how;
+    }
+    digest_packed_mesh(r.p, digests);
+    if (info) {
+        for (int c = 0; c < 3; ++c) info[c] = r.t.centre[c];
+        info[3] = r.p.sv.tri_extent; info[4] = r.p.sv.sphere_cmax; info[5] = r.t.abs_pad; info[6] = r.t.scale; info[7] = (double)r.p.bvh4.nodes.size();
+    }
+    if (mask) for (size_t k = 0; k < r.hidden.size(); ++k) mask[k] = r.hidden[k] ? 0 : 1;
+    if (dump) {
+        // per wide node and child, kHostDumpWords words: the link and count words as they are now; the six words of its box (a footprint
+        // child: z unbounded, or the nothing box when empty); the pack's link and count; the number of leaf entries (the pack's) and
+        // their objects (at most 6)
+        const size_t n_nodes = r.p.bvh4.nodes.size();
+        if (dump_words < n_nodes * 4 * (size_t)kHostDumpWords) return fail(RTX_ERR_INVALID_ARGUMENT, std::string(who) + ": the dump buffer is too small");
+        std::vector<uint8_t> flat(n_nodes, 0);
+        for (uint32_t e : r.t.all_level_nodes) if (e & kBvhFlatNode) flat[e & ~kBvhFlatNode] = 1;
+        auto bits = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
+        for (size_t k = 0; k < n_nodes; ++k) {
+            const Bvh4Node &w = r.p.bvh4.nodes[k];
+            const float lk[4] = { w.b[0].x, w.b[0].y, w.b[0].z, w.b[0].w }, ct[4] = { w.b[1].x, w.b[1].y, w.b[1].z, w.b[1].w };
+            for (int c = 0; c < 4; ++c) {
+                uint32_t *d = dump + (k * 4 + c) * (size_t)kHostDumpWords;
+                for (uint32_t j = 0; j < kHostDumpWords; ++j) d[j] = 0u;
+                float box[6];
+                if (flat[k]) {
+                    d[0] = bits(lk[c]); d[1] = bits(ct[c]);
+                    box[0] = w.a[c].x; box[1] = w.a[c].y; box[3] = w.a[c].z; box[4] = w.a[c].w;
+                    const bool nothing = !(box[0] <= box[3]);
+                    box[2] = nothing ? INFINITY : -INFINITY; box[5] = nothing ? -INFINITY : INFINITY;
+                } else {
+                    d[0] = bits(w.a[c].w); d[1] = bits(w.b[c].w);
+                    box[0] = w.a[c].x; box[1] = w.a[c].y; box[2] = w.a[c].z; box[3] = w.b[c].x; box[4] = w.b[c].y; box[5] = w.b[c].z;
+                }
+                for (int a = 0; a < 6; ++a) d[2 + a] = bits(box[a]);
+                d[8] = r.keep_valid ? r.keep[k * kKeepWords + c] : d[0];
+                d[9] = r.keep_valid ? r.keep[k * kKeepWords + 4 + c] : d[1];
+                if (d[9] == 0u || d[9] == 0xFFFFFFFFu) continue;
+                const uint32_t n = d[9] & 0xFFFFu;
+                d[10] = n;
+                for (uint32_t j = 0; j < n && j < 6u; ++j)
+                    d[11 + j] = (d[9] & kBvhTriLeaf) ? r.p.tris[r.p.tri_fidx[d[8] + j]].id : r.p.sphere_id[r.p.bvh.prims[d[8] + j]];
+            }
+        }
+    }
+    return check_packed(r.p, r.cur.data(), stats, r.hidden.data());
 }
 #endif
 

@@ -1,4 +1,4 @@
-// rtx_refit.h -- the arithmetic of rtx_scene_update_objects, written once: scene_update_kernel (rtx_update.hip) and the host
+// rtx_refit.h -- the arithmetic of rtx_scene_update_objects and rtx_scene_set_visible, written once: scene_update_kernel (rtx_update.hip) and the host
 // reference refit_packed (rtx_pack.hip) compile from this text, so the device's arrays can be held to the host's bit for bit.
 //
 // Every expression that has a twin in pack_scene, sphere_box, bvh_append_tree or build_q3nodes is that twin's expression (same
@@ -29,10 +29,17 @@ constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
 // UpdateEntry.tri: the geometry changed (RTX_UPDATE_DEFORM); the class is "qualified"; the record is a tree record (it has tri_geo and
 // tribox32 rows); the free axis of a qualified triangle in bits 4..5.  The host decides all of it (plan_update).
 constexpr uint32_t kTriEntryGeom = 1u, kTriEntryQualified = 2u, kTriEntryTree = 4u, kTriEntryAxisShift = 4u;
+// UpdateEntry.tri, any kind (rtx_scene_set_visible): kEntryHide -- the object is hidden: its records become the ones of hide_record
+// below and its material stays; kEntryNoGeom -- an update of a HIDDEN object: the material record alone (its new geometry is judged
+// when it is shown).  An entry that SHOWS an object is an ordinary entry with the object's current geometry.
+constexpr uint32_t kEntryHide = 0x100u, kEntryNoGeom = 0x200u;
+// The kept words of one wide node (UpdateArgs.keep): the pack's four link and four count words of its 128-byte form, then the four
+// link words of its 64-byte form (0 when the tree has none).
+constexpr uint32_t kKeepWords = 12u;
 
 // What one launch of scene_update_kernel works on.  `mode` is launch-uniform:
 //   0 (A) records: one thread per entry;  1 (B) one level of wide nodes: one thread per node of `level`;  2 (C) sphere_cmax;
-//   3 (D) tri_extent.  The triangle arrays are null in a launch of an update that moves no triangle: mode B then leaves triangle
+//   3 (D) tri_extent;  4 (E) the kept words: one thread per wide node (capture_keep).  The triangle arrays are null in a launch of an update that moves no triangle: mode B then leaves triangle
 //   leaves and footprint nodes as they are.
 struct UpdateArgs {
     uint32_t mode, n;
@@ -51,6 +58,8 @@ struct UpdateArgs {
     float *tribox32;                       // per tree record: lo.xyz, hi.xyz of its padded f32 footprint (-inf / +inf along its free axis)
     double *tri_reach;                     // per triangle: max |v - centre| over its nine coordinates (0: not qualified)
     BvhQNode *qnodes;                      // null when the tree has no 64-byte footprint form
+    uint32_t *keep;                        // kKeepWords per wide node, made by mode E at the first visibility call after a pack; null before
+                                           // it: mode B then touches no link or count word
     double centre[3];
     double abs_pad;
 };
@@ -170,14 +179,70 @@ RTX_HD TriDerived derive_triangle(const double g[9], uint32_t object, bool quali
 }
 
 // ---- mode A ---------------------------------------------------------------------------------------------------------------------
+// A hidden object's records (rtx_scene_set_visible): the exact record of all-NaN geometry with the id kept -- no f64 test accepts
+// it -- and f32 records that are never CERTAIN in any stage that lowers a pruning bound ("Hidden objects", reader by
+// reader):
+//   sphere_f32, leaf_f32   pack_scene's pad sentinel {0, 0, 0, 1e30}: filter_disc1 / filter_disc2 only select candidates
+//   leaf_cr                NaN coordinates: Dp = NaN, and every reader enters its bounds with `Dp >= 0`, false
+//   tri_f32, tri_geo       pack_scene's record of a triangle outside the tree {A = 0, B = 0, g0 = 0, g1 = (0, 0, NaN, 0)} with A.w = 1e30:
+//                          n = 0, so n.d = 0 and tri_bounds never reaches the block that sets t_hi; |n.(v0 - p)| = 1e30, so
+//                          tri_filter_sign drops it for every ray with a d.x or d.y (A.w = 0 would make it a candidate for all)
+//   box32, tribox32        the nothing box (+inf lo, -inf hi on every axis): it never wins a min / max;  reach, tri_reach   0
+// The NaNs that make_plane / make_triangle derive (a norm, the elimination's pivots) are written as THE quiet NaN: which NaN an
+// operation on NaNs returns is the one thing host and device need not agree on, and no test reads a NaN's sign or payload.
+RTX_HD double refit_canon(double x) { return x == x ? x : refit_bits_f64(0x7FF8000000000000ull); }
+RTX_HD V3 refit_canon3(V3 v) { return mk(refit_canon(v.x), refit_canon(v.y), refit_canon(v.z)); }
+
+RTX_HD void hide_record(const UpdateArgs &u, const UpdateEntry &e)
+{
+    const double nan = refit_bits_f64(0x7FF8000000000000ull);
+    const double g[9] = { nan, nan, nan, nan, nan, nan, nan, nan, nan };
+    const uint32_t k = e.local;
+    if (e.kind == 1u) {
+        PlaneX p = make_plane(g, e.object);
+        p.position = refit_canon3(p.position); p.normal = refit_canon3(p.normal); p.nhat = refit_canon3(p.nhat);
+        u.planes[k] = p;
+        return;
+    }
+    if (e.kind == 2u) {
+        TriX t = make_triangle(g, e.object);
+        t.v0 = refit_canon3(t.v0); t.n = refit_canon3(t.n); t.nn = refit_canon3(t.nn);
+        t.piv1 = refit_canon(t.piv1); t.f = refit_canon(t.f); t.piv2 = refit_canon(t.piv2); t.g = refit_canon(t.g);
+        u.tris[k] = t;
+        u.tri_reach[k] = 0.0;
+        if (e.slot == kNoSlot) return;
+        u.tri_f32[2 * (size_t)e.slot] = make_float4(0.f, 0.f, 0.f, 1.0e30f); u.tri_f32[2 * (size_t)e.slot + 1] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (!(e.tri & kTriEntryTree)) return;
+        u.tri_geo[2 * (size_t)e.slot] = make_float4(0.f, 0.f, 0.f, 0.f);
+        u.tri_geo[2 * (size_t)e.slot + 1] = make_float4(0.f, 0.f, refit_bits_f32(0x7FC00000u), 0.f);
+        float *b = u.tribox32 + (size_t)e.slot * 6;
+        for (int a = 0; a < 3; ++a) { b[a] = INFINITY; b[3 + a] = -INFINITY; }
+        return;
+    }
+    SphereX sp = make_sphere(g);
+    sp.rr = refit_canon(sp.rr);
+    u.spheres[k] = sp;
+    float *f = u.sphere_f32 + (size_t)(k & ~1u) * 4 + (k & 1u);
+    f[0] = 0.f; f[2] = 0.f; f[4] = 0.f; f[6] = 1.0e30f;
+    u.reach[k] = 0.0;
+    if (e.slot == kNoSlot) return;
+    const float qnan = refit_bits_f32(0x7FC00000u);
+    u.leaf_f32[e.slot] = make_float4(0.f, 0.f, 0.f, 1.0e30f);
+    u.leaf_cr[e.slot] = make_float4(qnan, qnan, qnan, 0.f);
+    float *b = u.box32 + (size_t)k * 6;
+    for (int a = 0; a < 3; ++a) { b[a] = INFINITY; b[3 + a] = -INFINITY; }
+}
+
 RTX_HD void update_record(const UpdateArgs &u, uint32_t i)
 {
     const UpdateEntry &e = u.entries[i];
+    if (e.tri & kEntryHide) { hide_record(u, e); return; }
     MaterialX m;
     m.base_color = mk(e.base_color[0], e.base_color[1], e.base_color[2]);
     m.emission_color = mk(e.emission_color[0], e.emission_color[1], e.emission_color[2]);
     m.roughness = e.roughness;
     u.materials[e.object] = m;
+    if (e.tri & kEntryNoGeom) return;
     if (e.kind == 1u) { u.planes[e.local] = make_plane(e.geom, e.object); return; }
     if (e.kind == 2u && (e.tri & kTriEntryGeom)) {                   // a triangle that keeps its class and gets new vertices (DEFORM)
         const uint32_t k = e.local;
@@ -333,33 +398,45 @@ RTX_HD bool qnode_encode(const Bvh4Node &w, BvhQNode &q)
 // triangle leaf is the min / max of tribox32 over its records, that of an interior child -- a footprint node too, refitted by the
 // previous launch -- the min / max of its four rectangles (an empty slot's {inf, inf, -inf, -inf} never wins).  This is the builder's
 // rectangle for the same topology: the builder rounds the union of the padded f64 footprints, x -> round_down_f32(x - abs_pad) is
-// monotone (round_up likewise), so the rounded union is the union of the rounded rectangles, at every level.  Empty slots, links and
-// counts are not touched.  False when the node's 64-byte form (u.qnodes != null) cannot be encoded.
+// monotone (round_up likewise), so the rounded union is the union of the rounded rectangles, at every level.  The pack's empty slots
+// stay; links and counts are not touched unless the kept words exist (refit_node).  False when the node's 64-byte form (u.qnodes !=
+// null) cannot be encoded.
 RTX_HD bool refit_flat_node(const UpdateArgs &u, uint32_t idx)
 {
     Bvh4Node &w = u.nodes[idx];
-    const uint32_t lk[4] = { refit_f32_bits(w.b[0].x), refit_f32_bits(w.b[0].y), refit_f32_bits(w.b[0].z), refit_f32_bits(w.b[0].w) };
-    const uint32_t ct[4] = { refit_f32_bits(w.b[1].x), refit_f32_bits(w.b[1].y), refit_f32_bits(w.b[1].z), refit_f32_bits(w.b[1].w) };
+    uint32_t lk[4] = { refit_f32_bits(w.b[0].x), refit_f32_bits(w.b[0].y), refit_f32_bits(w.b[0].z), refit_f32_bits(w.b[0].w) };
+    uint32_t ct[4] = { refit_f32_bits(w.b[1].x), refit_f32_bits(w.b[1].y), refit_f32_bits(w.b[1].z), refit_f32_bits(w.b[1].w) };
+    const uint32_t *kw = u.keep ? u.keep + (size_t)idx * kKeepWords : nullptr;
+    BvhQNode q;
+    if (u.qnodes) q = u.qnodes[idx];
     for (int c = 0; c < 4; ++c) {
-        if (ct[c] == 0xFFFFFFFFu) continue;
+        const uint32_t link = kw ? kw[c] : lk[c], count = kw ? kw[4 + c] : ct[c];        // the pack's words: what the slot holds when something below is alive
+        if (count == 0xFFFFFFFFu) continue;
         float lo[2] = { INFINITY, INFINITY }, hi[2] = { -INFINITY, -INFINITY };
-        if (ct[c] == 0u) {
-            const Bvh4Node &ch = u.nodes[lk[c] & ~kBvhFlatNode];
+        if (count == 0u) {
+            const Bvh4Node &ch = u.nodes[link & ~kBvhFlatNode];
             for (int k = 0; k < 4; ++k) {
                 const float l[2] = { ch.a[k].x, ch.a[k].y }, h[2] = { ch.a[k].z, ch.a[k].w };
                 for (int a = 0; a < 2; ++a) { lo[a] = l[a] < lo[a] ? l[a] : lo[a]; hi[a] = h[a] > hi[a] ? h[a] : hi[a]; }
             }
         } else {
-            const uint32_t n = ct[c] & 0xFFFFu;
+            const uint32_t n = count & 0xFFFFu;
             for (uint32_t k = 0; k < n; ++k) {
-                const float *b = u.tribox32 + (size_t)(lk[c] + k) * 6;
+                const float *b = u.tribox32 + (size_t)(link + k) * 6;
                 for (int a = 0; a < 2; ++a) { lo[a] = b[a] < lo[a] ? b[a] : lo[a]; hi[a] = b[3 + a] > hi[a] ? b[3 + a] : hi[a]; }
             }
         }
         w.a[c] = make_float4(lo[0], lo[1], hi[0], hi[1]);
+        if (!kw) continue;
+        const bool alive = lo[0] <= hi[0];                               // (nothing alive below: the union is the nothing rectangle, the slot's empty form)
+        lk[c] = alive ? link : 0u; ct[c] = alive ? count : 0xFFFFFFFFu;
+        if (u.qnodes) q.link[c] = alive ? kw[8 + c] : (kQNodeEmpty << kQNodeShift);
+    }
+    if (kw) {
+        w.b[0] = make_float4(refit_bits_f32(lk[0]), refit_bits_f32(lk[1]), refit_bits_f32(lk[2]), refit_bits_f32(lk[3]));
+        w.b[1] = make_float4(refit_bits_f32(ct[0]), refit_bits_f32(ct[1]), refit_bits_f32(ct[2]), refit_bits_f32(ct[3]));
     }
     if (!u.qnodes) return true;
-    BvhQNode q = u.qnodes[idx];
     if (!qnode_encode(w, q)) return false;
     u.qnodes[idx] = q;
     return true;
@@ -368,13 +445,22 @@ RTX_HD bool refit_flat_node(const UpdateArgs &u, uint32_t idx)
 // One non-flat wide node: the boxes of its sphere leaves from box32, of its non-flat interior children from those children's four
 // boxes (refitted by the previous launch: the levels run deepest first).  When triangles move (u.tribox32 != null) a triangle leaf
 // gets the min / max of tribox32 over its records -- unbounded along their free axis -- and a footprint child the (x, y) union of that
-// node's four rectangles, unbounded in z; otherwise triangle leaves and footprint children stay.  Empty slots stay.
-// Link and count words are not touched.  (min / max as comparisons: one answer for -0 against +0 on host and device.)  Returns false when the node's 64-byte form (u.q3nodes != null) cannot be encoded.
+// node's four rectangles, unbounded in z; otherwise triangle leaves and footprint children stay.  The pack's empty slots stay.
+// Without kept words (u.keep == null) link and count words are not touched.  With them (a visibility call has run on this pack) the
+// union is taken over what the PACK's words name, and a slot with nothing alive below -- the nothing box -- is written as the empty
+// slot, any other slot gets the pack's words back: hiding and showing are this one path (refit_flat_node likewise).
+// (min / max as comparisons: one answer for -0 against +0 on host and device.)  Returns false when the node's 64-byte form (u.q3nodes != null) cannot be encoded.
 RTX_HD bool refit_node(const UpdateArgs &u, uint32_t idx)
 {
     Bvh4Node &w = u.nodes[idx];
+    const uint32_t *kw = u.keep ? u.keep + (size_t)idx * kKeepWords : nullptr;
+    BvhQ3Node q;
+    if (u.q3nodes) q = u.q3nodes[idx];
+    uint32_t ql[4] = { 0u, 0u, 0u, 0u };
+    if (u.q3nodes) { ql[0] = q.link0; ql[1] = q.link1; ql[2] = q.link2; ql[3] = q.link3; }
     for (int c = 0; c < 4; ++c) {
-        const uint32_t link = refit_f32_bits(w.a[c].w), count = refit_f32_bits(w.b[c].w);
+        // (with the kept words: the pack's link and count, which the slot holds when something below it is alive)
+        const uint32_t link = kw ? kw[c] : refit_f32_bits(w.a[c].w), count = kw ? kw[4 + c] : refit_f32_bits(w.b[c].w);
         if (count == 0xFFFFFFFFu) continue;
         float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
         if (count & kBvhTriLeaf) {
@@ -391,7 +477,7 @@ RTX_HD bool refit_node(const UpdateArgs &u, uint32_t idx)
                 const float l[2] = { ch.a[k].x, ch.a[k].y }, h[2] = { ch.a[k].z, ch.a[k].w };
                 for (int a = 0; a < 2; ++a) { lo[a] = l[a] < lo[a] ? l[a] : lo[a]; hi[a] = h[a] > hi[a] ? h[a] : hi[a]; }
             }
-            lo[2] = -INFINITY; hi[2] = INFINITY;
+            if (lo[0] <= hi[0]) { lo[2] = -INFINITY; hi[2] = INFINITY; }             // (four empty rectangles: the nothing box)
         } else if (count == 0u) {
             const Bvh4Node &ch = u.nodes[link];
             for (int k = 0; k < 4; ++k) {
@@ -407,12 +493,36 @@ RTX_HD bool refit_node(const UpdateArgs &u, uint32_t idx)
         }
         w.a[c].x = lo[0]; w.a[c].y = lo[1]; w.a[c].z = lo[2];
         w.b[c].x = hi[0]; w.b[c].y = hi[1]; w.b[c].z = hi[2];
+        if (!kw) continue;
+        // nothing alive below (every entry hidden, every slot of the child empty): the union is the nothing box on every axis -- the
+        // pack's empty slot, link 0 and count ~0; else the pack's words again
+        const bool alive = lo[0] <= hi[0] && lo[1] <= hi[1];
+        w.a[c].w = refit_bits_f32(alive ? link : 0u);
+        w.b[c].w = refit_bits_f32(alive ? count : 0xFFFFFFFFu);
+        ql[c] = alive ? kw[8 + c] : (kQNodeEmpty << kQNodeShift);
     }
     if (!u.q3nodes) return true;
-    BvhQ3Node q = u.q3nodes[idx];
+    q.link0 = ql[0]; q.link1 = ql[1]; q.link2 = ql[2]; q.link3 = ql[3];
     if (!q3_encode(w, u.abs_pad, q)) return false;
     u.q3nodes[idx] = q;
     return true;
+}
+
+// Mode E: the kept words of wide node `idx` (flat: kBvhFlatNode was set in its level entry), read from the arrays as the pack left
+// them -- the first visibility call after a pack runs it before anything else.
+RTX_HD void capture_keep(const UpdateArgs &u, uint32_t entry)
+{
+    const uint32_t idx = entry & ~kBvhFlatNode;
+    const Bvh4Node &w = u.nodes[idx];
+    uint32_t *kw = u.keep + (size_t)idx * kKeepWords;
+    if (entry & kBvhFlatNode) {
+        const float lk[4] = { w.b[0].x, w.b[0].y, w.b[0].z, w.b[0].w }, ct[4] = { w.b[1].x, w.b[1].y, w.b[1].z, w.b[1].w };
+        for (int c = 0; c < 4; ++c) { kw[c] = refit_f32_bits(lk[c]); kw[4 + c] = refit_f32_bits(ct[c]); kw[8 + c] = u.qnodes ? u.qnodes[idx].link[c] : 0u; }
+        return;
+    }
+    for (int c = 0; c < 4; ++c) { kw[c] = refit_f32_bits(w.a[c].w); kw[4 + c] = refit_f32_bits(w.b[c].w); }
+    kw[8] = kw[9] = kw[10] = kw[11] = 0u;
+    if (u.q3nodes) { const BvhQ3Node &q = u.q3nodes[idx]; kw[8] = q.link0; kw[9] = q.link1; kw[10] = q.link2; kw[11] = q.link3; }
 }
 
 // One entry of a level list: the status bits its node raises.

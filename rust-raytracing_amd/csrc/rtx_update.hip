@@ -1,4 +1,5 @@
-// rtx_update.hip -- scene_update_kernel: rtx_scene_update_objects on the device (include/rtx_hip.h, DESIGN.md "Moving objects").
+// rtx_update.hip -- scene_update_kernel: rtx_scene_update_objects and rtx_scene_set_visible on the device (include/rtx_hip.h, DESIGN.md
+// "Moving objects", "Hidden objects").
 // One kernel, a launch-uniform mode (UpdateArgs, rtx_refit.h); the arithmetic is rtx_refit.h's, which the host reference
 // refit_packed (rtx_pack.hip) compiles too.  No spin-waits, no dependence between the blocks of one launch; threads write
 // disjoint words (mode B reads the nodes the previous launch wrote: the host enqueues the levels deepest first on one stream).
@@ -17,6 +18,10 @@ __global__ __launch_bounds__(256) void scene_update_kernel(UpdateArgs u)
         if (i < u.n) { const unsigned long long bad = refit_level_entry(u, u.level[i]); if (bad) atomicOr(u.status, bad); }
         return;
     }
+    if (u.mode == 4u) {                                   // E: the kept words of one wide node (the first visibility call after a pack)
+        if (i < u.n) capture_keep(u, u.level[i]);
+        return;
+    }
     // C: sphere_cmax = max of reach;  D: tri_extent = max of tri_reach.  Grid-stride, then the 64-lane wave, then one atomicMax per wave on the bit pattern
     // (non-negative doubles order like their bits; a launch of mode C only runs when every reach is finite).
     const double *src = u.mode == 2u ? u.reach : u.tri_reach;
@@ -30,7 +35,7 @@ hipError_t launch_scene_update(const UpdateArgs &u, hipStream_t stream)
 {
     if (u.n == 0) return hipSuccess;
     uint32_t blocks = (uint32_t)(((uint64_t)u.n + 255u) / 256u);
-    if (u.mode >= 2u && blocks > 1024u) blocks = 1024u;
+    if ((u.mode == 2u || u.mode == 3u) && blocks > 1024u) blocks = 1024u;
     hipLaunchKernelGGL(scene_update_kernel, dim3(blocks), dim3(256), 0, stream, u);
     return hipGetLastError();
 }

@@ -9,6 +9,8 @@
 // make_refit_tables, plan_update, the derivations, refit_packed or a re-pack, check_packed; split > 0: entries [0, split) are one
 // update, the rest a second one -- and prints one line:
 //   <file> status <RtxStatus> how <RTX_UPDATED_*> digests <16 hex words>       or       <file> status <RtxStatus> error <message>
+// After a case that ran, the same scene goes through one hide / show round trip (host_visibility: what rtx_debug_host_set_visible runs)
+// of its first seven objects and the update's indices; a line is printed only when the base pack's digests do not come back.
 // A refusal plan_update documents (a bad index, an unknown kind or mode) is such a line and no failure.  The exit status is 1 when a
 // case file is malformed or check_packed's walk found a broken invariant (its messages start with "bvh check:").
 #include "../rust-raytracing_amd/csrc/rtx_pack.h"
@@ -57,6 +59,27 @@ int main(int argc, char **argv)
         std::printf("%s status 0 how %u digests", argv[a], how);
         for (uint64_t d : digests) std::printf(" %016llx", (unsigned long long)d);
         std::printf("\n");
+        // one hide / show round trip of the scene's first objects and of the update's indices (rtx_scene_set_visible's host half:
+        // plan_visibility, the kept words, hide_record, the refit with empty slots): the digests of the base pack must come back.
+        // Nothing is printed unless they do not.
+        std::vector<uint64_t> hide;
+        for (uint64_t k = 0; k < head[0] && k < 7; ++k) hide.push_back(k);
+        for (uint64_t k = 0; k < head[1]; ++k) if (indices[k] < head[0]) hide.push_back(indices[k]);
+        std::vector<uint64_t> twice(hide);
+        twice.insert(twice.end(), hide.rbegin(), hide.rend());
+        const uint32_t kinds[2] = { rtx::host::kHostStepHide, rtx::host::kHostStepShow };
+        const uint64_t begin[3] = { 0, hide.size(), twice.size() };
+        uint32_t hows[2] = { 0, 0 };
+        uint64_t base[16], back[16];
+        std::vector<uint8_t> mask(head[0] + 1, 0);
+        int32_t vrc = rtx::host::host_visibility("host_pack_check", &scene, kinds, begin, 0, nullptr, nullptr, hows, stats, base, nullptr, nullptr, nullptr, 0);
+        if (vrc == RTX_OK)
+            vrc = rtx::host::host_visibility("host_pack_check", &scene, kinds, begin, 2, twice.data(), nullptr, hows, stats, back, info, mask.data(), nullptr, 0);
+        if (vrc != RTX_OK || std::memcmp(base, back, sizeof base) != 0) {
+            std::printf("%s hide/show round trip: status %d how %u %u%s %s\n", argv[a], (int)vrc, hows[0], hows[1],
+                        vrc == RTX_OK ? " digests differ" : "", vrc == RTX_OK ? "" : rtx::host::last_error().c_str());
+            failed = 1;
+        }
     }
     return failed;
 }

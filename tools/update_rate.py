@@ -27,7 +27,16 @@ only way there was before it, rtx_scene_free + rtx_scene_upload of the modified 
            and C3 at 1920x1080, --spp samples, every triangle translated by 0.1, 0.5 and 2 triangle sizes (the median edge): the
            frame's device time after the refit and after a fresh upload of the same geometry, alternating
 
-    tools/update_rate.py [--scenes C2,M1] [--legs update,frames,q3loss,mesh] [--reps 3] [--spp 4]
+  visibility   hiding and showing objects in place (SceneHandle.set_visible, rtx_scene_set_visible) on C2, C3, M1 and T1M: one object, 1 % and
+           50 % of them, the wall time of one call:
+             hide / show   the named objects hidden (shown again outside the clock), and the reverse
+             reupload      close() + Scene.upload() of the list WITHOUT them: the shorter list, every later index shifted
+             nan           update_objects with all-NaN geometry for them: "never hit" without the entry point (a rebuild; a NaN sphere
+                           costs every sphere its sub-tree)
+           and C2 / C3 at 1920x1080, --spp samples: the frame's device time after hiding 1 % and 50 %, after a fresh upload of the
+           shortened list (what the kept topology costs), and after the NaN update (C2 at 1 % only: what losing the tree costs)
+
+    tools/update_rate.py [--scenes C2,M1] [--legs update,frames,q3loss,mesh,visibility] [--reps 3] [--spp 4]
 
 The package is the one of the tree the tool lies in; in a checkout of the parent commit (copy the tool there) only the reupload leg runs
 (of the mesh leg: its auto and reupload forms).
@@ -169,6 +178,80 @@ def mesh_legs(rtx, scenes, cam, args, emit_):
             fresh.close()
 
 
+def visibility_legs(rtx, scenes, cam, args, emit_):
+    import torch
+    has_visible = hasattr(rtx.SceneHandle, "set_visible")           # (a checkout of the parent commit: the reupload and nan forms alone)
+    w, h = 1920, 1080
+    for name, make, n in (("C2", lambda: scenes.random_spheres(10000, 1), 10000), ("C3", lambda: scenes.random_triangles(100000), 100000),
+                          ("M1", lambda: scenes.random_spheres(1000000, 1), 1000000), ("T1M", lambda: scenes.random_triangles(1000000), 1000000)):
+        if name not in args.vis_scenes.split(","):
+            continue
+        objs = make()
+        cfg = rtx.Config(rays_per_pixel=args.spp, seed=scenes.RENDER_SEED)
+        for share, count in (("1", 1), ("1%", n // 100), ("50%", n // 2)):
+            idx = np.sort(np.random.default_rng(7).permutation(n)[:count]).astype(np.uint64)
+            keep = np.ones(n, dtype=bool)
+            keep[idx.astype(np.int64)] = False
+            real = objs[idx.astype(np.int64)].copy()
+            nan = real.copy()
+            nan["geom"] = np.nan
+            hnd = rtx.Scene.from_packed(cfg, cam, objs).upload(0)
+            if has_visible:
+                for form, visible in (("hide", False), ("show", True)):
+                    how = []
+                    best, worst = timed(lambda _a, _v=visible: how.append(hnd.set_visible(idx, _v)), args.reps, lambda _v=visible: hnd.set_visible(idx, not _v))
+                    emit_(scene=name, leg="visibility", form=form, objects=n, changed=count, share=share, how=sorted(set(how)), ms=round(best, 4),
+                          worst_ms=round(worst, 4), spread=round(worst / best - 1.0, 3), reps=args.reps)
+                hnd.set_visible(idx, True)
+            how = []
+            best, worst = timed(lambda _a: how.append(hnd.update_objects(idx, nan)), args.reps, lambda: hnd.update_objects(idx, real, mode="rebuild"))
+            emit_(scene=name, leg="visibility", form="nan", objects=n, changed=count, share=share, how=sorted(set(how)), ms=round(best, 4),
+                  worst_ms=round(worst, 4), spread=round(worst / best - 1.0, 3), reps=args.reps)
+            box = {"hnd": hnd}
+
+            def reupload(_a):
+                box["hnd"].close()
+                box["hnd"] = rtx.Scene.from_packed(cfg, cam, objs[keep]).upload(0)
+
+            best, worst = timed(reupload, args.reps)
+            box["hnd"].close()
+            emit_(scene=name, leg="visibility", form="reupload", objects=n, changed=count, share=share, ms=round(best, 4), worst_ms=round(worst, 4),
+                  spread=round(worst / best - 1.0, 3), reps=args.reps)
+            if name not in ("C2", "C3") or share == "1":
+                continue
+            buf = torch.zeros((h, w, 3), dtype=torch.float64, device="cuda:0")
+
+            def frame_ms(handle, reps=args.reps):
+                out = []
+                for k in range(reps + 1):
+                    st = handle.render_rows(w, h, 0, 1, h, buf.data_ptr())
+                    out.append(st.trace_ms + st.resolve_ms)
+                return min(out[1:]), max(out[1:])
+
+            handles = []
+            if has_visible:
+                hid = rtx.Scene.from_packed(cfg, cam, objs).upload(0)
+                handles.append(("after hide: " + hid.set_visible(idx, False), hid, args.reps))
+            handles.append(("fresh upload of the shortened list", rtx.Scene.from_packed(cfg, cam, objs[keep]).upload(0), args.reps))
+            if share == "1%":
+                lost = rtx.Scene.from_packed(cfg, cam, objs).upload(0)
+                handles.append(("after the NaN update: " + lost.update_objects(idx, nan), lost, 1))
+            for run in (1, 2):                                   # alternating
+                for form, handle, reps in handles:
+                    if run == 2 and reps == 1:
+                        continue                                 # (the frame without a tree is slow: taken once)
+                    b, wst = frame_ms(handle, reps)
+                    emit_(scene=name, leg="visibility-frames", form=form, run=run, share=share, spp=args.spp, ms=round(b, 4), worst_ms=round(wst, 4),
+                          spread=round(wst / b - 1.0, 3))
+            if has_visible:
+                handles[0][1].render_rows(w, h, 0, 1, h, buf.data_ptr())
+                img = buf.cpu().numpy().copy()
+                handles[1][1].render_rows(w, h, 0, 1, h, buf.data_ptr())
+                emit_(scene=name, leg="visibility-frames", form="same bits as the shortened list", share=share, equal=bool(np.array_equal(img, buf.cpu().numpy())))
+            for _, handle, _ in handles:
+                handle.close()
+
+
 def timed(fn, reps, setup=None):
     """wall ms of fn(): (best, worst) of `reps` runs after one warm-up; setup() runs before each, outside the clock"""
     import torch
@@ -194,6 +277,7 @@ def main():
     ap.add_argument("--legs", default="update,frames")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--spp", type=int, default=4)
+    ap.add_argument("--vis-scenes", default="C2,C3,M1,T1M", help="the scenes of the visibility leg")
     args = ap.parse_args()
     import torch
 
@@ -205,6 +289,11 @@ def main():
     if "mesh" in legs:
         mesh_legs(rtx, scenes, cam, args, emit)
         legs = [k for k in legs if k != "mesh"]
+        if not legs:
+            return
+    if "visibility" in legs:
+        visibility_legs(rtx, scenes, cam, args, emit)
+        legs = [k for k in legs if k != "visibility"]
         if not legs:
             return
     for name in args.scenes.split(","):
