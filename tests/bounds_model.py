@@ -1,6 +1,6 @@
 """A model of the tree walks' f32 bound arithmetic (rtx_traverse.h box_entry32 / rect_entry32 / sphere_node_step_q3 / the sphere leaf
 bounds, rtx_mesh_step.h qrect_entry / tri_bounds, rtx_device.h tri_filter_sign) and of the builder's boxes and records (rtx_bvh.h,
-rtx_pack.hip pack_scene), in which every f32 operation is formed EXACTLY and rounded ONCE, and every margin is a knob.
+rtx_pack.hip pack_scene; refit() and deform(): what an update in place must leave, from its documented contract), in which every f32 operation is formed EXACTLY and rounded ONCE, and every margin is a knob.
 
 How one rounding is kept.  All operands are f32 values held in f64.  A product of two of them is exact in f64 (48 bits).  A sum s + c
 of two f64 values is formed exactly as hi + lo (Knuth's two-sum), hi is moved to the neighbour with an odd last bit when lo != 0
@@ -384,6 +384,51 @@ def _tri_rows(v):
     return idx[0], idx[jrow]
 
 
+def tri_record(vabs, centre):
+    """One triangle as the upload and a deform write it (pack_scene's expressions in pack_scene's order; the ONE text pack() and
+    deform() share): vabs (3, 3) the vertices, centre (3,) the point the f32 records are offsets from -- the pack's own, or the KEPT
+    one.  -> None when the triangle is not QUALIFIED (no record in the model), else (f, rec (16,) f32 = A, B, g0, g1 -- B pass-all,
+    or the grown rectangle for f = 2 --, blo, bhi (3,) f64: the footprint with its relative padding, -inf / +inf along f, BEFORE
+    abs_pad and the outward rounding, reach = the largest |v - centre| component)"""
+    rows = _tri_rows(vabs)
+    if rows is None:
+        return None
+    r_, s_ = vabs[1] - vabs[0], vabs[2] - vabs[0]
+    cr = np.array([r_[1] * s_[2] - r_[2] * s_[1], r_[2] * s_[0] - r_[0] * s_[2], r_[0] * s_[1] - r_[1] * s_[0]])
+    nrm = cr / np.sqrt((cr[0] * cr[0] + cr[1] * cr[1]) + cr[2] * cr[2])
+    kabs = (nrm[0] * vabs[0, 0] + nrm[1] * vabs[0, 1]) + nrm[2] * vabs[0, 2]
+    if not (np.isfinite(kabs) and np.isfinite(nrm).all()) or kabs < -(1.0 + 1e-9):
+        return None
+    v = vabs - centre
+    fa = 3 - rows[0] - rows[1]
+    a0, a1 = (1 if fa == 0 else 0), (1 if fa == 2 else 2)
+    r0, r1, s0, s1 = v[1, a0] - v[0, a0], v[1, a1] - v[0, a1], v[2, a0] - v[0, a0], v[2, a1] - v[0, a1]
+    det = r0 * s1 - r1 * s0
+    if not (np.isfinite(vabs).all() and rows[0] != rows[1] and abs(det) > 1e-6 * np.hypot(r0, r1) * np.hypot(s0, s1)):
+        return None
+    blo, bhi = np.full(3, np.nan), np.full(3, np.nan)
+    for a in range(3):
+        if a == fa:
+            blo[a], bhi[a] = -np.inf, np.inf
+            continue
+        l, h = vabs[:, a].min(), vabs[:, a].max()
+        pad = max(abs(l), abs(h)) * (1.0 / 1048576.0) + 1e-300
+        blo[a], bhi[a] = l - pad, h + pad
+    rec = np.zeros(16, dtype=F32)
+    kc = (nrm[0] * v[0, 0] + nrm[1] * v[0, 1]) + nrm[2] * v[0, 2]
+    rec[0:4] = np.array([nrm[0], nrm[1], nrm[2], kc]).astype(F32)
+    rec[4:8] = np.array([0.0, 0.0, 1.0e30, 1.0e30]).astype(F32)
+    rec[8:12] = np.array([v[0, a0], v[0, a1], s1 / det, -s0 / det]).astype(F32)
+    rec[12:16] = np.array([-r1 / det, r0 / det, kabs, 2 - fa]).astype(F32)
+    if fa == 2:
+        xl, xh, yl, yh = v[:, 0].min(), v[:, 0].max(), v[:, 1].min(), v[:, 1].max()
+        grow = 1.0 + 1.0 / 1048576.0
+        rec[4:6] = np.array([0.5 * (xl + xh), 0.5 * (yl + yh)]).astype(F32)
+        rec[6] = ru32(0.5 * (xh - xl) * grow + 1e-30)
+        rec[7] = ru32(0.5 * (yh - yl) * grow + 1e-30)
+    return fa, rec, blo, bhi, float(np.abs(v).max())
+
+
 def pack(objs, m=SHIPPED):
     """What the walks' bound functions read for every object of the tree: dict with centre, cmax, limit32 (origin_limit), inv_max32,
     tri_extent, in_tree (bool per object), kind, rec (n_objects, 16) f32 -- a sphere's {c - centre, r} or a triangle's A, B, g0, g1 --,
@@ -425,42 +470,11 @@ def pack(objs, m=SHIPPED):
         for k in range(n):
             if kind[k] != 2:
                 continue
-            vabs = geom[k, :9].reshape(3, 3)
-            rows = _tri_rows(vabs)
-            if rows is None:
+            t = tri_record(geom[k, :9].reshape(3, 3), centre)
+            if t is None:
                 continue
-            r_, s_ = vabs[1] - vabs[0], vabs[2] - vabs[0]
-            cr = np.array([r_[1] * s_[2] - r_[2] * s_[1], r_[2] * s_[0] - r_[0] * s_[2], r_[0] * s_[1] - r_[1] * s_[0]])
-            nrm = cr / np.sqrt((cr[0] * cr[0] + cr[1] * cr[1]) + cr[2] * cr[2])
-            kabs = (nrm[0] * vabs[0, 0] + nrm[1] * vabs[0, 1]) + nrm[2] * vabs[0, 2]
-            if not (np.isfinite(kabs) and np.isfinite(nrm).all()) or kabs < -(1.0 + 1e-9):
-                continue
-            v = vabs - centre
-            fa = 3 - rows[0] - rows[1]
-            a0, a1 = (1 if fa == 0 else 0), (1 if fa == 2 else 2)
-            r0, r1, s0, s1 = v[1, a0] - v[0, a0], v[1, a1] - v[0, a1], v[2, a0] - v[0, a0], v[2, a1] - v[0, a1]
-            det = r0 * s1 - r1 * s0
-            if not (np.isfinite(vabs).all() and rows[0] != rows[1] and abs(det) > 1e-6 * np.hypot(r0, r1) * np.hypot(s0, s1)):
-                continue
-            for a in range(3):
-                if a == fa:
-                    blo[k, a], bhi[k, a] = -np.inf, np.inf
-                    continue
-                l, h = vabs[:, a].min(), vabs[:, a].max()
-                pad = max(abs(l), abs(h)) * (1.0 / 1048576.0) + 1e-300
-                blo[k, a], bhi[k, a] = l - pad, h + pad
-            kc = (nrm[0] * v[0, 0] + nrm[1] * v[0, 1]) + nrm[2] * v[0, 2]
-            rec[k, 0:4] = np.array([nrm[0], nrm[1], nrm[2], kc]).astype(F32)
-            rec[k, 4:8] = np.array([0.0, 0.0, 1.0e30, 1.0e30]).astype(F32)
-            rec[k, 8:12] = np.array([v[0, a0], v[0, a1], s1 / det, -s0 / det]).astype(F32)
-            rec[k, 12:16] = np.array([-r1 / det, r0 / det, kabs, 2 - fa]).astype(F32)
-            if fa == 2:
-                xl, xh, yl, yh = v[:, 0].min(), v[:, 0].max(), v[:, 1].min(), v[:, 1].max()
-                grow = 1.0 + 1.0 / 1048576.0
-                rec[k, 4:6] = np.array([0.5 * (xl + xh), 0.5 * (yl + yh)]).astype(F32)
-                rec[k, 6] = ru32(0.5 * (xh - xl) * grow + 1e-30)
-                rec[k, 7] = ru32(0.5 * (yh - yl) * grow + 1e-30)
-            tri_extent = max(tri_extent, float(np.abs(v).max()))
+            fa, rec[k], blo[k], bhi[k], reach = t
+            tri_extent = max(tri_extent, reach)
             free[k] = fa
             classes[fa].append(k)
         for fa, ks in classes.items():
@@ -569,21 +583,18 @@ def pack_for(objs, m=SHIPPED):
     return pk
 
 
-def refit(base_objs, indices, new, m=SHIPPED):
-    """What rtx_scene_update_objects' REFIT of the tree of `base_objs` by objects[indices[i]] = new[i] (in order: the last entry of a
-    repeated index wins) must leave, from its contract (include/rtx_hip.h) and not from the kernel's text: a dict as
-    pack_for() returns it.  KEPT from the base pack: centre, limit32 / limit (origin_limit), abs_pad, inv_max32, tri_extent, in_tree,
-    kind, free and every triangle's record and box.  NEW, for every sphere of the updated list against the KEPT centre: rec[:, :3] =
-    f32(c - centre), rec[:, 3] = |r| rounded up (the leaf record), fw = f32(|c - centre|^2 - r^2) (the filter record's fourth
-    scalar; `filt` is the whole filter record {f32(c - centre), fw}), lo / hi = sphere_box() widened by the base abs_pad and rounded
-    outward, and scene-wide cmax = max(sqrt(cc) + |r|).
-    A sphere the update does not name keeps the bits pack() gave it (the expressions are pack()'s).  numpy f64, one rounding per
-    operation, sums left to right."""
+def _updated(base_objs, indices, new, m):
+    """(the base pack, the updated list: entries in order, the last entry of a repeated index wins)"""
     pk = pack_for(base_objs, m)
     now = np.array(base_objs, copy=True)
     for i, o in zip(np.asarray(indices).astype(np.int64), new):
         now[int(i)] = o
-    assert np.array_equal(np.asarray(now["kind"]).astype(int), pk["kind"]), "a refit keeps every object's kind"
+    assert np.array_equal(np.asarray(now["kind"]).astype(int), pk["kind"]), "an update in place keeps every object's kind"
+    return pk, now
+
+
+def _refit_spheres(pk, now, m):
+    """refit()'s and deform()'s common part: the base pack with every sphere of the updated list written against the KEPT centre"""
     geom = np.asarray(now["geom"], dtype=np.float64)
     sph = pk["kind"] == 0
     out = dict(pk)
@@ -604,6 +615,52 @@ def refit(base_objs, indices, new, m=SHIPPED):
         lo[sph] = rd32(((s - r[:, None]) - pad) - pk["abs_pad"] * m.abs_pad)
         hi[sph] = ru32(((s + r[:, None]) + pad) + pk["abs_pad"] * m.abs_pad)
     out.update(rec=rec, lo=lo, hi=hi, lo128=lo, hi128=hi, fw=fw, filt=filt, cmax=float(reach.max()) if sph.any() else 0.0, objs=now)
+    return out
+
+
+def refit(base_objs, indices, new, m=SHIPPED):
+    """What rtx_scene_update_objects' REFIT of the tree of `base_objs` by objects[indices[i]] = new[i] (in order: the last entry of a
+    repeated index wins) must leave when NO TRIANGLE GETS NEW VERTICES (the REFIT of RTX_UPDATE_AUTO; a triangle that moves under
+    RTX_UPDATE_DEFORM is deform()'s), from its contract (include/rtx_hip.h) and not from the kernel's text: a dict as
+    pack_for() returns it.  KEPT from the base pack: centre, limit32 / limit (origin_limit), abs_pad, inv_max32, in_tree, kind, free
+    and -- because no triangle moves -- tri_extent and every triangle's record and box.  NEW, for every sphere of the updated list
+    against the KEPT centre: rec[:, :3] = f32(c - centre), rec[:, 3] = |r| rounded up (the leaf record), fw = f32(|c - centre|^2 -
+    r^2) (the filter record's fourth scalar; `filt` is the whole filter record {f32(c - centre), fw}), lo / hi = sphere_box() widened
+    by the base abs_pad and rounded outward, and scene-wide cmax = max(sqrt(cc) + |r|).
+    A sphere the update does not name keeps the bits pack() gave it (the expressions are pack()'s).  numpy f64, one rounding per
+    operation, sums left to right."""
+    pk, now = _updated(base_objs, indices, new, m)
+    tri = pk["kind"] == 2
+    assert np.asarray(now["geom"])[tri].tobytes() == np.asarray(base_objs["geom"])[tri].tobytes(), "a triangle with new vertices: deform()"
+    return _refit_spheres(pk, now, m)
+
+
+def deform(base_objs, indices, new, m=SHIPPED):
+    """What a REFIT under RTX_UPDATE_DEFORM must leave (DESIGN.md 3.13 "Moving triangles", include/rtx_hip.h "Triangles"; not from the
+    kernel's text): a dict as pack_for() returns it.  KEPT from the base pack: centre, limit32 / limit, abs_pad, inv_max32, in_tree,
+    kind, free.  NEW, for every QUALIFIED triangle the update names, tri_record() against the KEPT centre -- pack()'s expressions in
+    pack()'s order, v = vabs - kept centre: rec[:, 0:16] = A, B (pass-all, or the grown rectangle for f = 2), g0, g1; lo / hi = the
+    footprint with its relative padding, widened by the BASE abs_pad, rounded outward, -inf / +inf along f.  Scene-wide: tri_extent =
+    the largest |v| component over ALL qualified triangles of the updated list against the kept centre.  The spheres named in the same
+    call get what refit() gives them (cmax included).  A triangle the update does not name keeps pack()'s bits.
+    The premise -- class and free axis of every triangle are the resident ones, or the library rebuilds -- is asserted."""
+    pk, now = _updated(base_objs, indices, new, m)
+    out = _refit_spheres(pk, now, m)
+    named = {int(i) for i in np.asarray(indices).astype(np.int64)}
+    geom = np.asarray(now["geom"], dtype=np.float64)
+    rec, lo, hi = out["rec"], out["lo"].copy(), out["hi"].copy()
+    tri_extent = 0.0
+    with np.errstate(all="ignore"):
+        for k in np.nonzero(pk["kind"] == 2)[0]:
+            t = tri_record(geom[k, :9].reshape(3, 3), pk["centre"])
+            assert (-1 if t is None else t[0]) == pk["free"][k], "triangle %d: class / free axis %s is not the resident %d" % (k, t and t[0], pk["free"][k])
+            if t is None:
+                continue
+            tri_extent = max(tri_extent, t[4])
+            if k in named:
+                rec[k] = t[1]
+                lo[k], hi[k] = rd32(t[2] - pk["abs_pad"] * m.abs_pad), ru32(t[3] + pk["abs_pad"] * m.abs_pad)
+    out.update(rec=rec, lo=lo, hi=hi, lo128=lo, hi128=hi, tri_extent=tri_extent)
     return out
 
 
