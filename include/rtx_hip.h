@@ -69,16 +69,18 @@ enum {
     RTX_KERNEL_BVH = 4,    /* spheres and triangles found by traversal of a flat BVH built at upload (SURVEY 8f N2:
                               3-D sphere boxes; (x, y) footprints for triangles, which keeps the reference's phantom
                               hits), exact f64 leaf tests; planes and shapes outside the tree tested for every
-                              segment; same bits as RTX_KERNEL_EXACT.  RtxStats.box_tests counts child boxes tested */
-    RTX_KERNEL_BVH_REGROUP = 5, /* RTX_KERNEL_BVH's tree and step under a different schedule: lanes whose traversal ended
-                              wait until enough of them can go on together, instead of every lane waiting for the
-                              wave's longest traversal; pays off on large triangle meshes; same bits */
+                              segment; same bits as RTX_KERNEL_EXACT.  RtxStats.box_tests counts child boxes tested.  The
+                              kernels of this id are the sphere tree's; a tree that holds triangles runs RTX_KERNEL_BVH_REGROUP's,
+                              whichever of the two ids is asked for ("Product and lab" below) */
+    RTX_KERNEL_BVH_REGROUP = 5, /* the same tree under a different schedule: lanes whose traversal ended wait until enough
+                              of them can go on together, instead of every lane waiting for the wave's longest traversal;
+                              the kernel of trees that hold triangles (a sphere tree runs RTX_KERNEL_BVH's); same bits */
     RTX_KERNEL_WAVEFRONT = 6   /* the same tree walked by a kernel of its own per bounce level (f32 only; level 0 of a mesh:
                               one wave-uniform walk per 8x8 tile of primary rays), the f64 exact tests + ray_hit in a
                               second kernel, the ray state structure-of-arrays in HBM between them.  For a mesh the
                               levels after the first run in RTX_KERNEL_BVH_REGROUP's kernel, fed from the level-1 queue.
-                              For trees that hold triangles (level 0 of a joint tree needs the tiled ray queue and a
-                              depth <= 42) or nothing but spheres, any other scene takes RTX_KERNEL_BVH_REGROUP; same bits */
+                              For trees that hold triangles (level 0 needs the tiled ray queue and a depth <= 42); any
+                              other tree with triangles takes RTX_KERNEL_BVH_REGROUP; same bits */
 };
 
 /* One entry of Scene.objects (scene.rs:80), flattened: Object{shape, material} (object.rs:9-15)
@@ -110,18 +112,18 @@ typedef struct RtxConfig {
  * the library reads no environment variable for any of this.  The two tree-build fields (TRI_LEAF, BVH_MEDIAN) are read
  * when the tree is built (rtx_scene_upload / rtx_scene_append_objects / rtx_render), the others per render.
  *
- * Product and lab.  librtx_hip.so holds the kernels RTX_KERNEL_AUTO can reach plus RTX_KERNEL_EXACT / RTX_KERNEL_MIXED.  The
- * experiments that lost (profiles/LAB_NOTEBOOK.md) are compiled only into librtx_hip_lab.so -- the same sources with -DRTX_LAB,
- * the same ABI, loaded by the lab tests and A/B tools.  In the product library
- *   - a tuning word with a bit of RTX_TUNE_LAB_MASK (or a bit this header does not name) is refused with RTX_ERR_UNSUPPORTED by
- *     every entry point that takes a config;
+ * Product and lab.  librtx_hip.so holds the kernels RTX_KERNEL_AUTO can reach plus RTX_KERNEL_EXACT / RTX_KERNEL_MIXED.
+ * librtx_hip_lab.so -- the same sources with -DRTX_LAB, the same ABI, the same dispatch, loaded by the lab tests and A/B tools --
+ * adds the rtx_debug_* hooks and the A/B forms behind the RTX_TUNE_LAB_MASK bits.  In both libraries
+ *   - a tuning word with a bit this header does not name is refused with RTX_ERR_UNSUPPORTED by every entry point that takes a
+ *     config; the product library refuses the bits of RTX_TUNE_LAB_MASK the same way;
  *   - RTX_KERNEL_BVH, RTX_KERNEL_BVH_REGROUP and RTX_KERNEL_WAVEFRONT each run the tree kernel that exists for the scene's tree
  *     (sphere tree: trace_sph_packet_kernel / trace_bvh_spheres_kernel; a tree that holds triangles: trace_bvh_mesh_kernel, as
- *     RTX_KERNEL_WAVEFRONT with the packet kernels in front); RtxStats.kernel reports the id whose kernels ran.  The lab library
- *     keeps one kernel family per (id, tree kind) pair, as the enumerators' comments describe. */
+ *     RTX_KERNEL_WAVEFRONT with the packet kernels in front; no tree: the LDS sweep); RtxStats.kernel reports the id whose
+ *     kernels ran.
+ * Bits 1, 19, 21, 22, 24 and 26 are retired with the experiments they selected (profiles/LAB_NOTEBOOK.md): refused, never to be reused. */
 enum {
     RTX_TUNE_NO_TILES    = 1u << 0,  /* BVH kernels: ray queue in image rows instead of 8x8 pixel tiles (no packets then) */
-    RTX_TUNE_BVH_CLASSIC = 1u << 1,  /* round 1's trace_bvh_kernel / trace_bvh_regroup_kernel instead of the f32-only steps */
     RTX_TUNE_NO_QNODES   = 1u << 2,  /* 96-byte footprint nodes instead of the 64-byte quantised ones */
     RTX_TUNE_NO_PACKETS  = 1u << 3,  /* primary rays walk per lane instead of one wave-uniform walk per tile */
     RTX_TUNE_WF_PURE     = 1u << 4,  /* RTX_KERNEL_WAVEFRONT on a pure (x, y)-footprint tree: every level in that form */
@@ -132,31 +134,18 @@ enum {
     RTX_TUNE_THRESH_SHIFT   = 12,    /* bits 12..18: lanes that wait before the regrouping kernels' f64 phase runs, 1..64
                                         (0 = default) */
     RTX_TUNE_PK_LDS_STACK = 1u << 20, /* mesh packets: the wave-uniform stack in LDS (round 2) instead of in the lanes of a VGPR */
-    RTX_TUNE_STAGE2_POOL = 1u << 21, /* sphere trees, two stages: stage 2 as a wave-local pool of ray slots (trace_sph_pool_kernel;
-                                        an experiment, slower than the lock-step form that ships) */
-    RTX_TUNE_STAGE2_PAIR = 1u << 22, /* sphere trees, two stages: stage 2 with two rays per lane (trace_sph_pair_kernel) */
-    RTX_TUNE_BEAMS = 1u << 24,       /* RTX_KERNEL_WAVEFRONT on a pure footprint tree: level 0 as beams (the lanes across nodes, one interval
-                                        test per node for the tile's 64 rays: wf_trace_beam_kernel; an experiment, slower than the
-                                        packets that ship: the leaf records, not the node visits, are what a mesh tile pays for) */
     RTX_TUNE_INLINE_LEAVES = 1u << 25, /* sphere trees, 64-byte nodes: a node's leaf children are bounded inside the node visit (the
                                         earlier form) instead of being pushed and visited when popped, leaf visits apart from node visits */
     RTX_TUNE_NO_CUT = 1u << 23,      /* sphere trees: every round of a lock-step wave lasts until its longest walk ends (round 2's
                                         form) instead of leaving the last few walkers to continue beside the next segments */
-    RTX_TUNE_STAGE2_SLOTS = 1u << 26, /* sphere trees, two stages: stage 2 over ray slots (trace_sph_slots_kernel: a wave owns ~90 rays, a lane
-                                        whose walk ends takes the next READY one from LDS, the f64 phase runs for 64 finished walks at once;
-                                        round 4's experiment: 12 % fewer instructions, the same time -- LAB_NOTEBOOK R4.3) */
     RTX_TUNE_HALVES = 1u << 27,      /* sphere trees, two stages: the launch as two halves of the samples in flight on two streams
                                       * (bit-identical, measured slower: not the default) */
     RTX_TUNE_NO_HALVES = 1u << 28,   /* ... never (today's default, spelled out) */
-    RTX_TUNE_NO_TILE_LISTS = 1u << 29, /* sphere trees, two stages: every packet of primary rays walks the tree (rounds 3's form) instead of
+    RTX_TUNE_NO_TILE_LISTS = 1u << 29  /* sphere trees, two stages: every packet of primary rays walks the tree (rounds 3's form) instead of
                                         * running over its tile's list of reachable spheres */
-    RTX_TUNE_SORT_SURVIVORS = 1u << 19 /* sphere trees, two stages: stage 2 reads the survivors ordered by the distance at which
-                                        their ray leaves the scene's box and by direction octant (a counting sort in between) */
 };
 
-#define RTX_TUNE_LAB_MASK (RTX_TUNE_BVH_CLASSIC | RTX_TUNE_NO_QNODES | RTX_TUNE_NO_PACKETS | RTX_TUNE_WF_PURE | RTX_TUNE_PK_LDS_STACK | \
-                           RTX_TUNE_STAGE2_POOL | RTX_TUNE_STAGE2_PAIR | RTX_TUNE_BEAMS | RTX_TUNE_INLINE_LEAVES | RTX_TUNE_SORT_SURVIVORS | \
-                           RTX_TUNE_STAGE2_SLOTS)
+#define RTX_TUNE_LAB_MASK (RTX_TUNE_NO_QNODES | RTX_TUNE_NO_PACKETS | RTX_TUNE_WF_PURE | RTX_TUNE_PK_LDS_STACK | RTX_TUNE_INLINE_LEAVES)
 #define RTX_TUNE_KNOWN_MASK (RTX_TUNE_LAB_MASK | RTX_TUNE_NO_TILES | RTX_TUNE_ONE_STAGE | RTX_TUNE_TWO_STAGE | RTX_TUNE_BVH_MEDIAN | \
                              (15u << RTX_TUNE_TRI_LEAF_SHIFT) | (127u << RTX_TUNE_THRESH_SHIFT) | RTX_TUNE_NO_CUT | RTX_TUNE_HALVES | \
                              RTX_TUNE_NO_HALVES | RTX_TUNE_NO_TILE_LISTS)

@@ -19,8 +19,8 @@ import math
 import numpy as np
 
 from . import abi
-from .abi import (RTX_TUNE_NO_TILES, RTX_TUNE_BVH_CLASSIC, RTX_TUNE_NO_QNODES, RTX_TUNE_NO_PACKETS, RTX_TUNE_WF_PURE, RTX_TUNE_ONE_STAGE,
-                  RTX_TUNE_TWO_STAGE, RTX_TUNE_BVH_MEDIAN, RTX_TUNE_TRI_LEAF_SHIFT, RTX_TUNE_THRESH_SHIFT, RTX_TUNE_SORT_SURVIVORS, RTX_TUNE_PK_LDS_STACK, RTX_TUNE_STAGE2_POOL, RTX_TUNE_STAGE2_PAIR, RTX_TUNE_NO_CUT, RTX_TUNE_BEAMS, RTX_TUNE_INLINE_LEAVES, RTX_TUNE_STAGE2_SLOTS, RTX_TUNE_HALVES, RTX_TUNE_NO_HALVES, RTX_TUNE_NO_TILE_LISTS)
+from .abi import (RTX_TUNE_NO_TILES, RTX_TUNE_NO_QNODES, RTX_TUNE_NO_PACKETS, RTX_TUNE_WF_PURE, RTX_TUNE_ONE_STAGE,
+                  RTX_TUNE_TWO_STAGE, RTX_TUNE_BVH_MEDIAN, RTX_TUNE_TRI_LEAF_SHIFT, RTX_TUNE_THRESH_SHIFT, RTX_TUNE_PK_LDS_STACK, RTX_TUNE_NO_CUT, RTX_TUNE_INLINE_LEAVES, RTX_TUNE_HALVES, RTX_TUNE_NO_HALVES, RTX_TUNE_NO_TILE_LISTS)
 from .abi import (OBJECT_DTYPE, RTX_KERNEL_WAVEFRONT, RTX_KERNEL_AUTO, RTX_KERNEL_BVH, RTX_KERNEL_EXACT, RTX_KERNEL_MIXED, RTX_KERNEL_MIXED_VERIFY, RTX_KERNEL_BVH_REGROUP,
                   RTX_PLANE, RTX_SPHERE, RTX_TRIANGLE, RtxError, load_library, RAY_DTYPE, HIT_DTYPE, FEATURE_DTYPE)
 
@@ -161,7 +161,8 @@ def pack_objects(objects):
 # Config (scene.rs:16-65) + the build's seed / kernel fields
 # ---------------------------------------------------------------------------------------------
 class LabKernel(int):
-    """A RTX_KERNEL_* id that asks for the lab library's kernel family of that id (the test suite's loops over kernel ids)."""
+    """A RTX_KERNEL_* id that is rendered through the lab library (the test suite's loops over kernel ids): the same dispatch and the
+    same kernels as the product's, from the -DRTX_LAB build."""
     lab = True
 
     def __repr__(self):

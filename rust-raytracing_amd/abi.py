@@ -10,31 +10,25 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RTX_HIP_LIB") or os.path.join(HERE, "librtx_hip.so")   # RTX_HIP_LIB: A/B builds
-# the lab library: same sources with -DRTX_LAB, same ABI, + the experiments behind RTX_TUNE_LAB_MASK bits and the older kernel
-# families (include/rtx_hip.h, "Product and lab").  Loaded only for a Config that asks for it (Config.lab / a lab tuning bit).
+# the lab library: same sources with -DRTX_LAB, same ABI, same dispatch, + the rtx_debug_* hooks and the A/B forms behind the
+# RTX_TUNE_LAB_MASK bits (include/rtx_hip.h, "Product and lab").  Loaded only for a Config that asks for it (Config.lab / a lab tuning bit).
 LAB_LIB_PATH = os.environ.get("RTX_HIP_LAB_LIB") or os.path.join(HERE, "librtx_hip_lab.so")
 
 RTX_SPHERE, RTX_PLANE, RTX_TRIANGLE = 0, 1, 2
 RTX_KERNEL_AUTO, RTX_KERNEL_EXACT, RTX_KERNEL_MIXED, RTX_KERNEL_MIXED_VERIFY, RTX_KERNEL_BVH, RTX_KERNEL_BVH_REGROUP = 0, 1, 2, 3, 4, 5
 RTX_KERNEL_WAVEFRONT = 6
 # RtxConfig.tuning bits (include/rtx_hip.h): A/B switches, every combination renders the same bits
-RTX_TUNE_NO_TILES, RTX_TUNE_BVH_CLASSIC, RTX_TUNE_NO_QNODES, RTX_TUNE_NO_PACKETS = 1, 2, 4, 8
+# (bits 1, 19, 21, 22, 24 and 26 are retired: refused by both libraries, never to be reused)
+RTX_TUNE_NO_TILES, RTX_TUNE_NO_QNODES, RTX_TUNE_NO_PACKETS = 1, 4, 8
 RTX_TUNE_WF_PURE, RTX_TUNE_ONE_STAGE, RTX_TUNE_TWO_STAGE, RTX_TUNE_BVH_MEDIAN = 16, 32, 64, 128
 RTX_TUNE_TRI_LEAF_SHIFT, RTX_TUNE_THRESH_SHIFT = 8, 12
-RTX_TUNE_SORT_SURVIVORS = 1 << 19
 RTX_TUNE_PK_LDS_STACK = 1 << 20
-RTX_TUNE_STAGE2_POOL = 1 << 21
-RTX_TUNE_STAGE2_PAIR = 1 << 22
 RTX_TUNE_NO_CUT = 1 << 23
 RTX_TUNE_HALVES = 1 << 27
 RTX_TUNE_NO_HALVES = 1 << 28
 RTX_TUNE_NO_TILE_LISTS = 1 << 29
-RTX_TUNE_BEAMS = 1 << 24
 RTX_TUNE_INLINE_LEAVES = 1 << 25
-RTX_TUNE_STAGE2_SLOTS = 1 << 26
-RTX_TUNE_LAB_MASK = (RTX_TUNE_BVH_CLASSIC | RTX_TUNE_NO_QNODES | RTX_TUNE_NO_PACKETS | RTX_TUNE_WF_PURE | RTX_TUNE_PK_LDS_STACK |
-                     RTX_TUNE_STAGE2_POOL | RTX_TUNE_STAGE2_PAIR | RTX_TUNE_BEAMS | RTX_TUNE_INLINE_LEAVES | RTX_TUNE_SORT_SURVIVORS |
-                     RTX_TUNE_STAGE2_SLOTS)
+RTX_TUNE_LAB_MASK = RTX_TUNE_NO_QNODES | RTX_TUNE_NO_PACKETS | RTX_TUNE_WF_PURE | RTX_TUNE_PK_LDS_STACK | RTX_TUNE_INLINE_LEAVES
 RTX_TUNE_KNOWN_MASK = (RTX_TUNE_LAB_MASK | RTX_TUNE_NO_TILES | RTX_TUNE_ONE_STAGE | RTX_TUNE_TWO_STAGE | RTX_TUNE_BVH_MEDIAN |
                        (15 << RTX_TUNE_TRI_LEAF_SHIFT) | (127 << RTX_TUNE_THRESH_SHIFT) | RTX_TUNE_NO_CUT | RTX_TUNE_HALVES | RTX_TUNE_NO_HALVES | RTX_TUNE_NO_TILE_LISTS)
 RTX_UPDATE_AUTO, RTX_UPDATE_REBUILD, RTX_UPDATE_DEFORM = 0, 1, 2

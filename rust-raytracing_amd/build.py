@@ -5,9 +5,8 @@ with the gpurun snapshot, so nothing is JIT-compiled there.
 
 Two libraries from the same sources (include/rtx_hip.h, "Product and lab"):
   librtx_hip.so       what RTX_KERNEL_AUTO can reach + RTX_KERNEL_EXACT / MIXED: the kernels that ship
-  librtx_hip_lab.so   -DRTX_LAB: + every experiment behind a RTX_TUNE_LAB_MASK bit and the older kernel families
-                      (rtx_bvh.hip, rtx_bvh_regroup.hip, rtx_bvh_spheres_pool.hip, rtx_wavefront_spheres.hip, rtx_bvh_spheres_lab.h);
-                      loaded by the lab tests and the A/B tools, never by the product path
+  librtx_hip_lab.so   -DRTX_LAB: the same files and the same dispatch + the rtx_debug_* hooks and the A/B forms behind the
+                      RTX_TUNE_LAB_MASK bits; loaded by the lab tests and the A/B tools, never by the product path
 
 Every .hip file is its own translation unit (no cross-file device calls), so the objects are
 compiled in parallel and cached by content hash of (source, headers, flags); the link is one
@@ -26,9 +25,8 @@ LAB_LIB = os.path.join(HERE, "librtx_hip_lab.so")
 OBJ_DIR = os.path.join(HERE, "build")
 SOURCES = ["rtx_kernels.hip", "rtx_bvh_spheres.hip", "rtx_bvh_mesh.hip", "rtx_wavefront.hip", "rtx_query.hip", "rtx_update.hip", "rtx_pack.hip",
            "rtx_api.hip", "rtx_api_update.hip", "rtx_api_debug.hip"]
-LAB_SOURCES = SOURCES + ["rtx_bvh.hip", "rtx_bvh_spheres_pool.hip", "rtx_bvh_regroup.hip", "rtx_wavefront_spheres.hip"]
 HEADERS = ["rtx_math.h", "rtx_scene.h", "rtx_bvh.h", "rtx_device.h", "rtx_traverse.h", "rtx_mesh_step.h", "rtx_wavefront.h",
-           "rtx_launch.h", "rtx_bvh_spheres_lab.h", "rtx_refit.h", "rtx_pack.h", "rtx_host.h"]
+           "rtx_launch.h", "rtx_refit.h", "rtx_pack.h", "rtx_host.h"]
 # -ffp-contract=off: the exact path must round like the reference (Rust never fuses a*b+c);
 # the f32 filter asks for FMAs explicitly.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
@@ -63,11 +61,10 @@ def build(force=False, extra_flags=(), verbose=False, lib=None, jobs=None, lab=F
     if lib is None:
         lib = LAB_LIB if lab else LIB
     flags = FLAGS + (LAB_FLAGS if lab else []) + list(extra_flags)
-    sources = LAB_SOURCES if lab else SOURCES
     os.makedirs(OBJ_DIR, exist_ok=True)
     exe = hipcc()
     objs, todo = [], []
-    for s in sources:
+    for s in SOURCES:
         obj = os.path.join(OBJ_DIR, "%s.%s.o" % (s[:-4], _digest(s, flags)))
         objs.append(obj)
         if force or not os.path.exists(obj):

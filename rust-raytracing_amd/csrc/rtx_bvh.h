@@ -352,11 +352,6 @@ struct Bvh4Node {
 };
 static_assert(sizeof(Bvh4Node) == 128, "Bvh4Node must be 128 bytes");
 
-#ifndef RTX_BVH_STACK
-#define RTX_BVH_STACK 30
-#endif
-constexpr int kBvh4StackEntries = RTX_BVH_STACK;     // per-ray traversal stack (LDS); deeper trees may overflow it (handled)
-
 // Footprint nodes (every child box unbounded in z: the triangle sub-tree) use a flat layout in the same 128 bytes,
 // which needs 6 of the 8 loads and a 2-D slab test:
 //   a[c] = {lo.x, lo.y, hi.x, hi.y} of child c;  b[0] = the four links, b[1] = the four counts;  b[2], b[3] unused.

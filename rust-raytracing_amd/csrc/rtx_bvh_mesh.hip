@@ -1,10 +1,9 @@
 // rtx_bvh_mesh.hip -- trace_bvh_mesh_kernel: RTX_KERNEL_BVH_REGROUP for trees that hold triangles (C3, C5).
 //
-// The schedule of trace_bvh_regroup_kernel (rtx_bvh_regroup.hip: a lane is TRAV / FIN / IDLE, the wave alternates between
-// traversal steps for the TRAV lanes and an f64 phase that runs when enough lanes wait for it), the same tree, the same
-// exact tests, the same bits -- with a traversal step that holds no f64 value:
+// The regrouping schedule (a lane is TRAV / FIN / IDLE, the wave alternates between traversal steps for the TRAV lanes and an
+// f64 phase that runs when enough lanes wait for it) with a traversal step that holds no f64 value:
 //
-//   * Spheres in a joint tree: the closest-approach bounds of bvh_traverse_spheres (rtx_traverse.h).
+//   * Spheres in a joint tree: the closest-approach bounds of sphere_step (rtx_traverse.h).
 //   * Triangles: a candidate that passes the footprint filter (rtx_device.h) gets its distance and its barycentric
 //     coordinates evaluated in f32 with explicit error bounds (tri_bounds below).  When the cull test, the plane
 //     distance and the inside test all hold with margin, the reference CERTAINLY reports the hit (triangle.rs:108-127)

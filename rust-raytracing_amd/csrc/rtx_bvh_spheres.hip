@@ -1,15 +1,14 @@
 // rtx_bvh_spheres.hip -- RTX_KERNEL_BVH for trees that hold spheres only (C2, C4).
 //
-// Same rays, same tree, same exact tests and the same bits as trace_bvh_kernel<false, *> (rtx_bvh.hip); what differs is the
-// traversal, which holds no f64 value: it prunes with the conservative f32 distance bounds of rtx_traverse.h instead of the
+// The traversal holds no f64 value: it prunes with the conservative f32 distance bounds of rtx_traverse.h instead of the
 // exact winner's distance, and the candidates that can still be the winner get their exact f64 test (sphere.rs:19-30) once,
 // after the walk.  What is in this file, in the order a big launch runs it (history in profiles/LAB_NOTEBOOK.md):
 //   * trace_sph_packet_kernel      stage 1: the primary rays, ONE wave-uniform walk per 8x8 tile through the scalar cache
 //   * trace_bvh_spheres_kernel     stage 2 (MODE 2, from the survivors' queue) and small launches (MODE 0): per-lane walks over
 //                                  the 64-byte nodes, node visits and leaf visits apart (sphere_walk_phased), a wave leaving
 //                                  its round when few lanes still walk (the walk is resumable); MODE 1 = stage 1 per lane (A/B)
-// (Experiments behind RtxConfig.tuning bits -- trace_sph_pool_kernel, trace_sph_pair_kernel, sph_sort_*, MODE 1, the 128-byte-node and
-// inline-leaf instances -- are compiled with -DRTX_LAB only: rtx_bvh_spheres_lab.h, librtx_hip_lab.so.)
+// (Experiments behind RtxConfig.tuning bits -- MODE 1, the 128-byte-node and inline-leaf instances -- are compiled with -DRTX_LAB
+// only: librtx_hip_lab.so.)
 // The traversal loops are free of scratch traffic (tools/isa_spills.py): what the allocator spills (the f64 path state) is touched
 // only between walks.  4 workgroups per CU: the loops are VALU-issue bound, more waves only add spill reloads inside them
 // (5 / 6 / 8 per SIMD measured in round 1), 3 without any spill are 3 % slower (round 3).
@@ -47,7 +46,7 @@ struct SphSurvivor {
 static_assert(sizeof(SphSurvivor) == 64, "SphSurvivor must be one 64-byte line");
 struct SphQueue {
     SphSurvivor *rec;
-    const uint32_t *perm;                     // stage 2 reads rec[perm[k]] (the survivors ordered by sph_sort_*), or null: queue order
+    const uint32_t *perm;                     // stage 2 reads rec[perm[k]] when set; null (every launcher today): queue order
     unsigned long long *count;                // slots reserved by stage 1 = the length stage 2 walks
     unsigned long long capacity;
     uint32_t cut_walkers;                     // sphere_walk_resumable's threshold for the lock-step kernels (0: walks are never cut)
@@ -397,11 +396,8 @@ constexpr int kSpkStack = 63;                // wave-uniform stack entries: the 
 #define RTX_SPK_WAVES 4
 #endif
 constexpr int kSpkWaves = RTX_SPK_WAVES;     // workgroups per CU
-#ifdef RTX_LAB                               // launch flags of the lab forms (rtx_api.hip builds them from RtxConfig.tuning)
+#ifdef RTX_LAB                               // launch flag of the lab form (rtx_api.hip builds it from RtxConfig.tuning)
 constexpr uint32_t kSphNoPackets = 1u;       // stage 1 per lane (A/B runs)
-constexpr uint32_t kSphPair = 8u;            // stage 2 with two rays per lane (trace_sph_pair_kernel)
-constexpr uint32_t kSphPool = 4u;            // stage 2 as the wave-local pool (an experiment: slower) instead of lock-step
-constexpr uint32_t kSphSortSurvivors = 2u;   // stage 2 reads the survivors ordered by exit distance and octant
 #endif
 
 // (sph_packet_leaf_test, the packet kernel's leaf test of one sphere, lives in rtx_traverse.h next to sphere_leaf_step_at: the lab
@@ -751,10 +747,6 @@ __global__ __launch_bounds__(kBvhThreads, kSpkWaves) void trace_sph_packet_kerne
     }
 }
 
-#ifdef RTX_LAB
-#include "rtx_bvh_spheres_lab.h"      // trace_sph_pool_kernel, trace_sph_pair_kernel, sph_sort_* : librtx_hip_lab.so only
-#endif
-
 uint32_t bvh_spheres_spill_entries(const SceneView &sv)
 {
     const uint32_t need = 3u * sv.bvh_depth + 2u;       // a 4-wide node pushes at most 3 entries per level
@@ -763,14 +755,7 @@ uint32_t bvh_spheres_spill_entries(const SceneView &sv)
 
 size_t bvh_spheres_spill_bytes(const SceneView &sv, int n_cus)
 {
-#ifdef RTX_LAB
-    const int lds_rows = kSlotStack < kPoolStack ? kSlotStack : kPoolStack;      // (the shortest LDS stack of the kernels that share the columns)
-#else
-    const int lds_rows = kSphStack;
-#endif
-    const uint32_t need = 3u * sv.bvh_depth + 2u;
-    const uint32_t entries = need > (uint32_t)lds_rows ? need - (uint32_t)lds_rows : 0u;
-    return (size_t)entries * (size_t)n_cus * kSphWavesPerSimd * kBvhThreads * sizeof(uint32_t);
+    return (size_t)bvh_spheres_spill_entries(sv) * (size_t)n_cus * kSphWavesPerSimd * kBvhThreads * sizeof(uint32_t);
 }
 
 // the survivors' queue of the two-stage form: one 64-byte record per slot; capacity = the launch's rays (every ray can
@@ -791,11 +776,7 @@ size_t bvh_spheres_tile_list_bytes(uint64_t rays_per_sample)
 size_t bvh_spheres_queue_bytes(uint64_t n_rays, int n_cus)
 {
     const uint64_t cap = sph_queue_capacity(n_rays, n_cus);
-    size_t bytes = (size_t)(cap * sizeof(SphSurvivor) + 2 * 256);
-#ifdef RTX_LAB
-    bytes += (size_t)((cap * 5 + 255) & ~(uint64_t)255) + 4 * 256 + 256;      // + the lab sort's keys, permutation, histogram
-#endif
-    return bytes;
+    return (size_t)(cap * sizeof(SphSurvivor) + 2 * 256);
 }
 
 // may stage 1 walk as packets?  The ray queue in 8x8 tiles and a tree the wave-uniform stack holds.
@@ -817,7 +798,7 @@ bool bvh_spheres_two_stage_ok(const SceneView &sv, bool tiled)
 hipError_t launch_trace_bvh_spheres(const SceneView *d_sv, const SceneView &sv, const RowsView *d_rv, const RowsView &rv,
                                     double *samples, Counters *counters, unsigned long long *work_counter, uint32_t *spill, int n_cus,
                                     void *queue_mem, uint32_t flags, hipStream_t stream, Counters *stage1_snapshot, hipEvent_t stage1_done,
-                                    void *pool_mem, void *slots_mem, void *tile_list_mem, bool build_tile_lists)
+                                    void *tile_list_mem, bool build_tile_lists)
 {
     const uint64_t want = (rv.n_rays + kBvhThreads - 1) / kBvhThreads;
     const uint64_t cap = (uint64_t)n_cus * kSphWavesPerSimd;
@@ -838,7 +819,7 @@ hipError_t launch_trace_bvh_spheres(const SceneView *d_sv, const SceneView &sv, 
 #else
     // the product holds the 64-byte-node instances only (the API sends a sphere tree without that form to the LDS sweep)
     if ((sv.bvh_flags & 16u) == 0u || sv.bvh_q3nodes == nullptr) return hipErrorInvalidValue;
-    (void)pool_mem; (void)flags;
+    (void)flags;
 #endif
     const bool tiled = rv.tiles_x != 0u && (rv.n_rays & 63ull) == 0ull;
     if (!queue_mem || sv.max_bounces == 0) {     // one stage (small launches): per-lane walks over the 64-byte nodes as in stage 2
@@ -891,9 +872,6 @@ hipError_t launch_trace_bvh_spheres(const SceneView *d_sv, const SceneView &sv, 
     if (stage1_snapshot && (e = hipMemcpyAsync(stage1_snapshot, counters, sizeof(Counters) * kCounterShards, hipMemcpyDeviceToDevice, stream)) != hipSuccess) return e;
     if (stage1_done && (e = hipEventRecord(stage1_done, stream)) != hipSuccess) return e;
 #ifdef RTX_LAB
-    if (hipError_t le = launch_sph_lab_stage2(d_sv, sv, d_rv, rv, samples, counters, spill, spill_entries, n_cus, p, capacity, ctrs, sq, la, nodes,
-                                              flags, pool_mem, stream); le != hipErrorNotReady)
-        return le;                                       // a lab form of stage 2 ran (or failed); hipErrorNotReady: none was asked for
     if (!q3 || inl) {
         auto k2 = !q3 ? (deep ? trace_bvh_spheres_kernel<true, 2> : trace_bvh_spheres_kernel<false, 2>)
                       : (deep ? trace_bvh_spheres_kernel<true, 2, 1> : trace_bvh_spheres_kernel<false, 2, 1>);
@@ -901,19 +879,6 @@ hipError_t launch_trace_bvh_spheres(const SceneView *d_sv, const SceneView &sv, 
                            spill_entries, sq);
         return hipGetLastError();
     }
-#endif
-#ifdef RTX_LAB
-    if (slots_mem) {                                     // stage 2 over ray slots: the grid is the resident waves, each with its own slots
-        if (!q3) return hipErrorInvalidValue;
-        const uint32_t se = spill ? bvh_spheres_slots_spill_entries(sv) : 0u;
-        if (bvh_spheres_slots_spill_entries(sv) != 0u && !spill) return hipErrorInvalidValue;
-        auto ks = se ? trace_sph_slots_kernel<true> : trace_sph_slots_kernel<false>;
-        hipLaunchKernelGGL(ks, dim3((uint32_t)cap), dim3(kBvhThreads), 0, stream, d_sv, d_rv, samples, counters, ctrs + 1, q3nodes, la, spill, se, sq,
-                           reinterpret_cast<SlotRec *>(slots_mem));
-        return hipGetLastError();
-    }
-#else
-    (void)slots_mem;
 #endif
     // the queue-fed stage walks per lane over the 64-byte nodes: half the L1 requests per visit
     auto k2 = deep ? trace_bvh_spheres_kernel<true, 2, 2> : trace_bvh_spheres_kernel<false, 2, 2>;

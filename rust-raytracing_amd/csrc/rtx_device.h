@@ -328,7 +328,7 @@ __device__ __forceinline__ bool light_is_zero(const RayState &r)               /
     return r.light.x == 0.0 && r.light.y == 0.0 && r.light.z == 0.0;
 }
 
-// ---- conservative f32 sphere filter (trace_mixed_kernel's sweep, trace_bvh_kernel's leaves); see rtx_kernels.hip
+// ---- conservative f32 sphere filter (trace_mixed_kernel's sweep); see rtx_kernels.hip
 struct FilterParams { float dx, dy, dz, npd, p2x, p2y, p2z, nppE; };
 
 __device__ __forceinline__ void filter_idle(FilterParams &f)      // D = -3e30 - w < 0: nothing passes

@@ -46,8 +46,6 @@ struct RtxSceneHandle_ {
     double *h_tables = nullptr; size_t h_tables_doubles = 0;
     double *state = nullptr;    size_t state_bytes = 0;
     void *wf_state = nullptr;   size_t wf_bytes = 0;       // the wavefront kernels' ray state
-    void *pool = nullptr;       size_t pool_bytes = 0;     // (lab) the pool / pair forms of the sphere kernel's stage 2
-    void *slots = nullptr;      size_t slots_bytes = 0;    // the slot records of the sphere kernel's stage 2 (trace_sph_slots_kernel)
     void *tile_lists = nullptr; size_t tile_lists_bytes = 0;   // what each tile's primary rays can reach (build_tile_lists_kernel)
     PathStep *transcript = nullptr; uint32_t *transcript_counts = nullptr; uint32_t transcript_steps = 0;   // (lab) rtx_debug_paths, set for one call
     Counters *counters = nullptr;

@@ -274,7 +274,7 @@ __device__ __forceinline__ bool mesh_step(const float4 *__restrict__ nodes, cons
             }
         } else if constexpr (!PLAIN) {
             for (uint32_t k = 0; k < n; ++k) {
-                const float4 rec = ma.sphere_cr[first + k];                              // {c - centre, r}: bvh_traverse_spheres' bounds
+                const float4 rec = ma.sphere_cr[first + k];                              // {c - centre, r}: sphere_step's bounds
                 const float ox = rec.x - sr.px, oy = rec.y - sr.py, oz = rec.z - sr.pz;
                 const float b = __builtin_fmaf(ox, sr.dx, __builtin_fmaf(oy, sr.dy, oz * sr.dz));
                 const float lx = __builtin_fmaf(-b, sr.dx, ox), ly = __builtin_fmaf(-b, sr.dy, oy), lz = __builtin_fmaf(-b, sr.dz, oz);
@@ -589,7 +589,7 @@ __device__ __forceinline__ bool jleaf_read(const MeshArrays &ma, const SphereRay
         }
     } else {
         for (uint32_t k = 0; k < n; ++k) {
-            const float4 rec = ma.sphere_cr[first + k];                              // {c - centre, r}: bvh_traverse_spheres' bounds
+            const float4 rec = ma.sphere_cr[first + k];                              // {c - centre, r}: sphere_step's bounds
             const float ox = rec.x - sr.px, oy = rec.y - sr.py, oz = rec.z - sr.pz;
             const float b = __builtin_fmaf(ox, sr.dx, __builtin_fmaf(oy, sr.dy, oz * sr.dz));
             const float lx = __builtin_fmaf(-b, sr.dx, ox), ly = __builtin_fmaf(-b, sr.dy, oy), lz = __builtin_fmaf(-b, sr.dz, oz);

@@ -227,7 +227,7 @@ int32_t pack_scene(const RtxScene *scene, PackedScene &p)
     p.sv.n_tri_tree = (uint32_t)n_in_tree;
     for (const TriRec &r : demoted) { tri32.push_back(r.A); tri32.push_back(r.B); tri_fidx.push_back(r.tri); }
     for (const TriRec &r : always_recs) { tri32.push_back(r.A); tri32.push_back(r.B); tri_fidx.push_back(r.tri); }
-    if (!tri32.empty()) {                       // one pad record: bvh_step reads records in pairs
+    if (!tri32.empty()) {                       // one pad record (a walk may read records in pairs)
         tri32.push_back(make_float4(0.f, 0.f, 0.f, 0.f));
         tri32.push_back(make_float4(0.f, 0.f, 0.f, 0.f));
     }

@@ -2,7 +2,7 @@
 // or for the zero-offset primary ray of every pixel of a frame (rtx_scene_primary_hits, the pick buffer).
 //
 // Persistent waves; a wave takes rays from the launch's atomic head in chunks (wf_take) and each lane owns one ray: the
-// segment body of trace_bvh_kernel (rtx_bvh.hip) -- the origin-range gate, the walk, the exhaustive fallback, planes and
+// segment body of a tree kernel -- the origin-range gate, the walk, the exhaustive fallback, planes and
 // shapes outside the tree swept for every ray, the (t, scene index) minimum -- on the product's faster steps:
 //   TRIS = false  a sphere tree: the 64-byte nodes, node and leaf visits apart (sphere_walk_phased), candidates queued with
 //                 their f32 lower bound, the exact tests after the walk;

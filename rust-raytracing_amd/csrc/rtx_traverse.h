@@ -1,4 +1,4 @@
-// rtx_traverse.h -- the flat-BVH traversal shared by trace_bvh_kernel and trace_bvh_regroup_kernel.
+// rtx_traverse.h -- the rays, slab tests and sphere-tree walks that the sphere, mesh, wavefront and query kernels share.
 #pragma once
 
 #include "rtx_device.h"
@@ -102,7 +102,7 @@ __device__ __forceinline__ void make_ray64(const V3 &pos, const V3 &dirn, double
 }
 
 // f64 slab test on the same f32 boxes (same widening, far more than the f64 roundings need); the entry distance is
-// returned as an f32 rounded DOWN, so the f32 ordering / pruning code of bvh_step is shared.
+// returned as an f32 rounded DOWN, so the f32 ordering / pruning code of the walks is shared.
 __device__ __forceinline__ float box_entry32(const float4 lo, const float4 hi, const Ray64 &r, float best_up)
 {
     const double x0 = __builtin_fma((double)lo.x, r.ix, r.nx), x1 = __builtin_fma((double)hi.x, r.ix, r.nx);
@@ -199,7 +199,6 @@ __device__ __forceinline__ float rtx_min_f32_bits(float a, float b)
     return m;
 }
 
-constexpr int kBvhQueue = 8;                // candidate shapes a lane may hold between two exact passes
 constexpr uint32_t kQueueTri = 0x80000000u; // queue entry: a triangle filter record (else a local sphere index)
 
 struct LeafArrays {                         // the arrays the leaves index (kernel arguments: global address space)
@@ -212,164 +211,14 @@ struct LeafArrays {                         // the arrays the leaves index (kern
     const TriX *tris;
 };
 
-// Exact f64 tests (sphere.rs:19-30, triangle.rs:108-127) of the queued candidates; updates the winner and the
-// pruning bound.
-template <bool TRIS>
-__device__ __forceinline__ void flush_candidates(const LeafArrays &la, const RayX &rx, const uint32_t *lds_q, uint32_t tid,
-                                                 uint32_t &qcnt, Hit &h, float &best_up, unsigned long long &exact)
-{
-#pragma unroll 1
-    for (uint32_t k = 0; k < qcnt; ++k) {         // not unrolled: 8 inlined copies of the f64 tests per call site bloat the traversal loop
-        const uint32_t idx = lds_q[(size_t)k * kBvhThreads + tid];
-        double t;
-        if (TRIS && (idx & kQueueTri)) {
-            const uint32_t tk = la.tri_fidx[idx & ~kQueueTri];
-            if (triangle_distance(la.tris[tk], rx, &t)) hit_consider(h, t, la.tris[tk].id, 2, tk);
-        } else {
-            if (sphere_distance(la.spheres[idx], rx, &t)) hit_consider(h, t, la.sphere_ids[idx], 0, idx);
-        }
-    }
-    exact += qcnt;
-    qcnt = 0;
-    if (h.id != kNone) best_up = round_up32(h.t);
-}
-
-
-// ---- shared by trace_bvh_kernel (rtx_bvh.hip) and trace_bvh_regroup_kernel (rtx_bvh_regroup.hip) ----------------------
-#ifndef RTX_BVH_WPE
-#define RTX_BVH_WPE 4
-#endif
-constexpr int kBvhWavesPerSimd = RTX_BVH_WPE;     // = workgroups per CU (4 waves each)
-
 __device__ __forceinline__ uint32_t bvh_mbcnt(unsigned long long mask)
 {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
-// One traversal step of one lane: open wide node `node`, filter its leaf children into the candidate queue, push
-// the interior children still in reach (farthest first) and move to the nearest (or pop).  node == kNone afterwards
-// means the traversal is complete.  lds_stack has one row more than kBvh4StackEntries: the sink of the branch-free
-// pushes.
-template <bool TRIS, bool SPILL, class RAY>
-__device__ __forceinline__ void bvh_step(const float4 *__restrict__ nodes, const LeafArrays &la, const RAY &q,
-                                         const FilterParams &fpar, const TriFilterParams &tpar, const RayX &rx, uint32_t &node,
-                                         uint32_t &sp, uint32_t &qcnt, bool &overflow, Hit &h, float &best_up,
-                                         uint32_t *lds_stack, uint32_t *lds_q, uint32_t tid, uint32_t *__restrict__ spill,
-                                         uint32_t spill_entries, size_t spill_stride, size_t glane,
-                                         uint32_t &nbox, uint32_t &nleaf, unsigned long long &exact)
-{
-    // one 128-byte node: the boxes of up to four children (rtx_bvh.h Bvh4Node; 8 loads), or -- in the triangle
-    // sub-tree -- their footprint rectangles, links and counts (6 loads)
-    const float4 *np = nodes + 8 * (size_t)(node & ~kBvhFlatNode);
-    float tc[4];
-    uint32_t lnk[4], cnt[4];
-    if (TRIS && (node & kBvhFlatNode)) {
-        float4 rc[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) rc[c] = np[c];
-        const float4 lk = np[4], ct = np[5];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) tc[c] = rect_entry32(rc[c], q, best_up);
-        lnk[0] = __float_as_uint(lk.x); lnk[1] = __float_as_uint(lk.y); lnk[2] = __float_as_uint(lk.z); lnk[3] = __float_as_uint(lk.w);
-        cnt[0] = __float_as_uint(ct.x); cnt[1] = __float_as_uint(ct.y); cnt[2] = __float_as_uint(ct.z); cnt[3] = __float_as_uint(ct.w);
-    } else {
-        float4 ca[4], cb[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) { ca[c] = np[c]; cb[c] = np[4 + c]; }
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            tc[c] = box_entry32(ca[c], cb[c], q, best_up);
-            lnk[c] = __float_as_uint(ca[c].w);
-            cnt[c] = __float_as_uint(cb[c].w);
-        }
-    }
-    nbox += 4;
-    // leaf children that the ray enters: f32 filter now, survivors are queued; the exact f64 tests run
-    // every 4th step (and at the end) for all lanes together, so their cost is not paid per (step, child,
-    // shape) under divergence.  The pruning bound lags by at most 4 steps, which only costs visits.
-    uint32_t leafmask = 0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-        if (tc[c] < __builtin_inff() && cnt[c] - 1u < 0x1FFFFu) leafmask |= 1u << c;          // neither interior (0) nor empty (~0)
-    while (leafmask != 0u) {                  // one copy of the leaf code, however many of the four children are leaves
-        const uint32_t c = (uint32_t)__builtin_ctz(leafmask);
-        leafmask &= leafmask - 1u;
-        const uint32_t first = c == 0 ? lnk[0] : (c == 1 ? lnk[1] : (c == 2 ? lnk[2] : lnk[3]));
-        const uint32_t count = c == 0 ? cnt[0] : (c == 1 ? cnt[1] : (c == 2 ? cnt[2] : cnt[3]));
-        const uint32_t n = count & 0xFFFFu;
-        if (TRIS && (count & kBvhTriLeaf)) {
-            // two records per round, their four loads in flight together (the array is padded by one record, so the
-            // second pair may be read even when it belongs to the next leaf)
-            for (uint32_t k = 0; k < n; k += 2u) {
-                const float4 *rp = la.tri_f32 + 2 * (size_t)(first + k);
-                const float4 A0 = rp[0], B0 = rp[1], A1 = rp[2], B1 = rp[3];
-                uint32_t m = (int)tri_filter_sign(A0, B0, tpar) >= 0 ? 1u : 0u;      // q may be above the footprint
-                if (k + 1u < n && (int)tri_filter_sign(A1, B1, tpar) >= 0) m |= 2u;
-                while (m != 0u) {
-                    const uint32_t j = (uint32_t)__builtin_ctz(m);
-                    m &= m - 1u;
-                    if (qcnt == (uint32_t)kBvhQueue) flush_candidates<TRIS>(la, rx, lds_q, tid, qcnt, h, best_up, exact);
-                    lds_q[(size_t)qcnt * kBvhThreads + tid] = (first + k + j) | kQueueTri;
-                    qcnt += 1;
-                }
-            }
-        } else {
-            for (uint32_t k = 0; k < n; ++k) {
-                const float4 rec = la.sphere_f32[first + k];
-                if ((int)__float_as_uint(filter_disc1(rec, fpar)) >= 0) {            // D >= 0: cannot be excluded
-                    if (qcnt == (uint32_t)kBvhQueue) flush_candidates<TRIS>(la, rx, lds_q, tid, qcnt, h, best_up, exact);
-                    lds_q[(size_t)qcnt * kBvhThreads + tid] = la.sphere_prims[first + k];
-                    qcnt += 1;
-                }
-            }
-        }
-        nleaf += n;
-    }
-    // interior children still in reach, nearest first: keys = entry distance (inf = not to be visited)
-    float key[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) key[c] = cnt[c] == 0u ? tc[c] : __builtin_inff();     // (tc is already inf for a box out of reach)
-#define RTX_CSWAP(i, j) { if (key[j] < key[i]) { float tk = key[i]; key[i] = key[j]; key[j] = tk; uint32_t tl = lnk[i]; lnk[i] = lnk[j]; lnk[j] = tl; } }
-    RTX_CSWAP(0, 1) RTX_CSWAP(2, 3) RTX_CSWAP(0, 2) RTX_CSWAP(1, 3) RTX_CSWAP(1, 2)
-#undef RTX_CSWAP
-    // push the farther ones (farthest first), descend into the nearest.  The keys are sorted, so the children to push
-    // are lnk[1..npush]; lnk[i] goes to row sp + npush - i, the others to the sink row -- three unconditional stores.
-    // (stack + queue = 39 words of LDS per lane, which is what 16 waves per CU leave; entries beyond the 30 in LDS go
-    // to the lane's column of the HBM spill area, which the launcher sizes from the tree's depth so that it cannot run
-    // out -- the exhaustive sweep after an overflow is only a guard)
-    const uint32_t npush = (key[1] < __builtin_inff() ? 1u : 0u) + (key[2] < __builtin_inff() ? 1u : 0u) +
-                           (key[3] < __builtin_inff() ? 1u : 0u);
-    if (sp + 3u <= (uint32_t)kBvh4StackEntries) {
-#pragma unroll
-        for (uint32_t i = 1; i <= 3; ++i) {
-            const uint32_t row = i <= npush ? sp + npush - i : (uint32_t)kBvh4StackEntries;
-            lds_stack[(size_t)row * kBvhThreads + tid] = lnk[i];
-        }
-        sp += npush;
-    } else {
-#define RTX_PUSH(v)                                                                                      \
-        {                                                                                                \
-            if (sp < (uint32_t)kBvh4StackEntries) { lds_stack[(size_t)sp * kBvhThreads + tid] = (v); sp += 1; } \
-            else if (SPILL && sp - (uint32_t)kBvh4StackEntries < spill_entries) {                        \
-                spill[(size_t)(sp - (uint32_t)kBvh4StackEntries) * spill_stride + glane] = (v); sp += 1; \
-            } else overflow = true;                                                                      \
-        }
-        if (key[3] < __builtin_inff()) RTX_PUSH(lnk[3])
-        if (key[2] < __builtin_inff()) RTX_PUSH(lnk[2])
-        if (key[1] < __builtin_inff()) RTX_PUSH(lnk[1])
-#undef RTX_PUSH
-    }
-    node = key[0] < __builtin_inff() ? lnk[0] : kNone;
-    if (node == kNone && sp != 0u) {
-        sp -= 1;                        // its boxes are re-tested against the current bound when it is opened
-        node = (!SPILL || sp < (uint32_t)kBvh4StackEntries) ? lds_stack[(size_t)sp * kBvhThreads + tid]
-                                                : spill[(size_t)(sp - (uint32_t)kBvh4StackEntries) * spill_stride + glane];
-    }
-}
-
 // ---- spheres-only trees: a traversal loop without f64 -----------------------------------------------------------------
-// bvh_step above interleaves the exact f64 tests with the walk (every 4th step) because its pruning bound is the exact
-// winner's distance.  For spheres an f32 evaluation bounds the hit distance tightly from both sides when it is done
+// A walk whose pruning bound is the exact winner's distance has to interleave the exact f64 tests with its steps.  For spheres
+// an f32 evaluation bounds the hit distance tightly from both sides when it is done
 // relative to the RAY ORIGIN (the sweep filter's expanded form cancels |c|^2 ~ M^2 against itself: its error 24uM^2 is
 // the size of r^2 for the small spheres of C2; here the cancellation is over |l| <= r):
 //     o = c - p        beta = o.d        l = o - beta d        Delta = r^2 - |l|^2        t = beta - sqrt(Delta)
@@ -481,7 +330,7 @@ __device__ __forceinline__ void sphere_step(const float4 *__restrict__ nodes, co
         }
         nleaf += n;
     }
-    // interior children still in reach, nearest first (as bvh_step)
+    // interior children still in reach, nearest first
     float key[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) key[c] = (cnt[c] == 0u && tc[c] <= best_up) ? tc[c] : __builtin_inff();
@@ -673,21 +522,6 @@ __device__ __forceinline__ void sphere_step_q3(const float4 *__restrict__ qnodes
         node = (!SPILL || sp < (uint32_t)STACK) ? lds_stack[(size_t)sp * kBvhThreads + tid]
                                                 : spill[(size_t)(sp - (uint32_t)STACK) * spill_stride + glane];
     }
-}
-
-template <int STACK, bool SPILL, class RAY>
-__device__ __forceinline__ void bvh_traverse_spheres(const float4 *__restrict__ nodes, const float4 *__restrict__ leaf_f32,
-                                                     const uint32_t *__restrict__ leaf_prims, const RAY &q, const SphereRay &sr,
-                                                     uint32_t root, uint32_t *lds_stack, uint32_t *lds_q,
-                                                     uint32_t tid, uint32_t *__restrict__ spill, uint32_t spill_entries,
-                                                     size_t spill_stride, size_t glane, float &best_up, uint32_t &qcnt, bool &overflow,
-                                                     uint32_t &nbox, uint32_t &nleaf)
-{
-    uint32_t sp = 0;
-    uint32_t node = root;
-    while (node != kNone)
-        sphere_step<STACK, SPILL>(nodes, leaf_f32, leaf_prims, q, sr, node, sp, lds_stack, lds_q, tid, spill, spill_entries,
-                                  spill_stride, glane, best_up, qcnt, overflow, nbox, nleaf);
 }
 
 // ---- the walk in two phases: node visits and leaf visits apart -----------------------------------------------------------------
@@ -1071,49 +905,6 @@ __device__ __forceinline__ void sphere_walk_resumable(const float4 *__restrict__
         const uint32_t still = (uint32_t)__popcll(__ballot(node != kNone));
         if (still < cut_walkers && n_alive - still >= cut_done) break;
     }
-}
-
-template <int STACK, bool SPILL, class RAY>
-__device__ __forceinline__ void bvh_traverse_spheres_q3(const float4 *__restrict__ qnodes, const float4 *__restrict__ leaf_f32,
-                                                        const uint32_t *__restrict__ leaf_prims, const RAY &q, const SphereRay &sr,
-                                                        uint32_t root, uint32_t *lds_stack, uint32_t *lds_q,
-                                                        uint32_t tid, uint32_t *__restrict__ spill, uint32_t spill_entries,
-                                                        size_t spill_stride, size_t glane, float &best_up, uint32_t &qcnt, bool &overflow,
-                                                        uint32_t &nbox, uint32_t &nleaf)
-{
-    uint32_t sp = 0;
-    uint32_t node = root;
-    while (node != kNone)
-        sphere_step_q3<STACK, SPILL>(qnodes, leaf_f32, leaf_prims, q, sr, node, sp, lds_stack, lds_q, tid, spill, spill_entries,
-                                     spill_stride, glane, best_up, qcnt, overflow, nbox, nleaf);
-}
-
-// A whole traversal of one lane's segment: steps until the stack is empty, the queued candidates' exact f64 tests
-// every 4th step (and at the end) for all lanes together, so their cost is not paid per (step, child, shape) under
-// divergence -- the pruning bound lags by at most 4 steps, which only costs visits.
-template <bool TRIS, bool SPILL, class RAY>
-__device__ __forceinline__ void bvh_traverse(const float4 *__restrict__ nodes, const LeafArrays &la, const RAY &q,
-                                             const FilterParams &fpar, const TriFilterParams &tpar, const RayX &rx,
-                                             uint32_t root, bool &overflow, Hit &h, uint32_t *lds_stack, uint32_t *lds_q, uint32_t tid,
-                                             uint32_t *__restrict__ spill, uint32_t spill_entries, size_t spill_stride, size_t glane,
-                                             unsigned long long &box_tests, unsigned long long &leaf_filters, unsigned long long &exact,
-                                             unsigned long long &wave_steps)
-{
-    float best_up = __builtin_inff();
-    uint32_t sp = 0, qcnt = 0, step = 0, nbox = 0, nleaf = 0;
-    uint32_t node = root;                    // wide node 0 (with kBvhFlatNode when it is a footprint node)
-    while (node != kNone) {
-#ifdef RTX_BVH_STATS
-        { const unsigned long long am = __ballot(true); if ((tid & 63u) == (uint32_t)(__ffsll((long long)am) - 1)) wave_steps += 1; }
-#endif
-        bvh_step<TRIS, SPILL>(nodes, la, q, fpar, tpar, rx, node, sp, qcnt, overflow, h, best_up, lds_stack, lds_q, tid, spill,
-                              spill_entries, spill_stride, glane, nbox, nleaf, exact);
-        step += 1;
-        if ((step & 3u) == 0u) flush_candidates<TRIS>(la, rx, lds_q, tid, qcnt, h, best_up, exact);
-    }
-    box_tests += nbox;
-    leaf_filters += nleaf;
-    flush_candidates<TRIS>(la, rx, lds_q, tid, qcnt, h, best_up, exact);
 }
 
 }  // namespace rtx

@@ -1,5 +1,5 @@
-// rtx_wavefront.h -- what the two wavefront forms (rtx_wavefront.hip: pure triangle meshes; rtx_wavefront_spheres.hip:
-// sphere trees) share: the ray state in HBM, the per-level queues, the wave-aggregated append.
+// rtx_wavefront.h -- what the wavefront form (rtx_wavefront.hip) and the query kernel (rtx_query.hip) share: the ray state in
+// HBM, the per-level queues, the wave-aggregated append.
 #pragma once
 
 #include "rtx_device.h"

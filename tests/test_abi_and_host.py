@@ -38,7 +38,9 @@ def test_library_exports_every_declared_symbol(rtx):
 def test_product_library_holds_only_what_auto_can_reach():
     """include/rtx_hip.h, "Product and lab": librtx_hip.so = the kernels RTX_KERNEL_AUTO can reach + RTX_KERNEL_EXACT / MIXED and the
     epilogues -- at most 25 kernel instances (round 3's cut; rtx_debug_math's kernel went to the lab library, the tile-list builder of round 4 -- one kernel for sphere, mesh and joint trees -- is on AUTO's path),
-    none of the experiments (tools/kernel_instances.py reads the code objects); the lab library holds them all.  A config check needs no GPU: the product refuses lab tuning bits, the lab library takes them."""
+    no lab kernel (tools/kernel_instances.py reads the code objects).  The lab library holds the product's kernels and the A/B forms that
+    are left (wf_trace_kernel, the per-lane stage 1, the 128-byte-node and inline-leaf instances, the debug hooks' kernels); the stage-2
+    experiments, the pool kernel, the per-level sphere wavefront, round 1's kernels and the beam kernel are in neither library."""
     import importlib.util
     spec = importlib.util.spec_from_file_location("_ki", os.path.join(ROOT, "tools", "kernel_instances.py"))
     ki = importlib.util.module_from_spec(spec)
@@ -46,17 +48,42 @@ def test_product_library_holds_only_what_auto_can_reach():
     prod = ki.kernel_names(os.path.join(ROOT, "rust-raytracing_amd", "librtx_hip.so"))
     lab = ki.kernel_names(os.path.join(ROOT, "rust-raytracing_amd", "librtx_hip_lab.so"))
     assert 10 <= len(prod) <= 25, prod
-    assert set(prod) <= set(lab) and len(lab) > len(prod) + 20
-    for experiment in ("trace_sph_pool_kernel", "trace_sph_pair_kernel", "sph_sort_", "trace_bvh_spheres_pool_kernel", "trace_bvh_kernel",
-                       "trace_bvh_regroup_kernel", "wf_trace_beam_kernel", "wf_trace_kernel", "wf_trace_spheres_kernel"):
-        assert not any(k.startswith(experiment) for k in prod), experiment
-        assert any(k.startswith(experiment) for k in lab), experiment
+    assert set(prod) <= set(lab) and len(lab) > len(prod)
+    for deleted in ("trace_sph_pool_kernel", "trace_sph_pair_kernel", "trace_sph_slots_kernel", "sph_sort_", "trace_bvh_spheres_pool_kernel",
+                    "trace_bvh_kernel", "trace_bvh_regroup_kernel", "wf_trace_beam_kernel", "wf_trace_spheres_kernel"):
+        assert not any(k.startswith(deleted) for k in prod), deleted
+        assert not any(k.startswith(deleted) for k in lab), deleted
+    assert not any(k.startswith("wf_trace_kernel") for k in prod)
+    assert any(k.startswith("wf_trace_kernel") for k in lab)
     for shipped in ("build_mesh_tile_lists_kernel", "trace_sph_packet_kernel", "trace_bvh_spheres_kernel<false, 2, 2>", "trace_bvh_spheres_kernel<false, 0, 2>",
                     "wf_trace_packet_kernel<1>", "trace_bvh_mesh_kernel<false, 2, true>", "trace_exact_kernel", "resolve_kernel"):
         assert shipped in prod, shipped
     # no "wrong images" timing branches in the product sources any more
     for f in os.listdir(os.path.join(ROOT, "rust-raytracing_amd", "csrc")):
         assert "RTX_SPK_LAB" not in open(os.path.join(ROOT, "rust-raytracing_amd", "csrc", f)).read(), f
+
+
+def test_retired_tuning_bits_are_refused_by_both_libraries(rtx):
+    """The six tuning values whose kernels were deleted (include/rtx_hip.h: bits 1, 19, 21, 22, 24, 26), alone and with
+    RTX_TUNE_TWO_STAGE: the config check of either library answers RTX_ERR_UNSUPPORTED.  No GPU: rtx_scene_upload checks the
+    config before it looks for a device."""
+    a = rtx.abi
+    sc = rtx._scene_c(rtx.Config(rays_per_pixel=1), rtx.Camera((0, 0, 0), (1, 0, 0), 1.0), np.zeros(0, dtype=a.OBJECT_DTYPE))
+    for lab in (False, True):
+        lib = rtx.load_library(lab)
+        for bit in (1, 19, 21, 22, 24, 26):
+            assert not (1 << bit) & a.RTX_TUNE_KNOWN_MASK, bit
+            for tune in (1 << bit, 1 << bit | a.RTX_TUNE_TWO_STAGE):
+                sc.config.tuning = tune
+                h = C.c_void_p()
+                assert lib.rtx_scene_upload(C.byref(sc), 0, C.byref(h)) == a.RTX_ERR_UNSUPPORTED, (lab, bit, tune)
+                assert not h.value and b"tuning" in lib.rtx_last_error()
+        sc.config.tuning = a.RTX_TUNE_TWO_STAGE              # the other half of each pair alone is a config both libraries take
+        h = C.c_void_p()
+        rc = lib.rtx_scene_upload(C.byref(sc), 0, C.byref(h))
+        assert rc in (a.RTX_OK, a.RTX_ERR_NO_DEVICE), (lab, rc)
+        if rc == a.RTX_OK:
+            assert lib.rtx_scene_free(h) == a.RTX_OK
 
 
 def test_struct_layouts_match_the_header(rtx, tmp_path):

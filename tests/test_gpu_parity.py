@@ -47,11 +47,11 @@ def two_sided(oracle, img, objs, w, h, cam=DEFAULT_CAM, flips=1, **cfg):
 
 def _kernels(rtx):
     """Every kernel id through the product library (librtx_hip.so: one tree-kernel family per kind of tree, whichever tree id is
-    asked for) and the three tree ids through the lab library (librtx_hip_lab.so: one family per id -- round 1's lock-step and
-    regrouping kernels, the pool kernel, the all-levels wavefront forms).  Same bits everywhere."""
+    asked for) and, through the lab library (librtx_hip_lab.so: the same dispatch from the -DRTX_LAB build), the tree ids that
+    can differ there: RTX_KERNEL_BVH (= RTX_KERNEL_BVH_REGROUP on every tree) and RTX_KERNEL_WAVEFRONT.  Same bits everywhere."""
     L = rtx.LabKernel
     return [rtx.RTX_KERNEL_EXACT, rtx.RTX_KERNEL_MIXED, rtx.RTX_KERNEL_BVH, rtx.RTX_KERNEL_BVH_REGROUP, rtx.RTX_KERNEL_WAVEFRONT,
-            L(rtx.RTX_KERNEL_BVH), L(rtx.RTX_KERNEL_BVH_REGROUP), L(rtx.RTX_KERNEL_WAVEFRONT)]
+            L(rtx.RTX_KERNEL_BVH), L(rtx.RTX_KERNEL_WAVEFRONT)]
 
 
 # ---- device arithmetic ---------------------------------------------------------------------------
@@ -306,8 +306,7 @@ def test_closed_box_at_two_stage_size_every_ray_survives(gpu):
     import closed_form as cf
     box = cf.closed_box(gpu.OBJECT_DTYPE, 300, seed=8)
     w = h = 1024
-    for tune in (0, gpu.RTX_TUNE_STAGE2_SLOTS, gpu.RTX_TUNE_NO_PACKETS, gpu.RTX_TUNE_NO_CUT, gpu.RTX_TUNE_INLINE_LEAVES, gpu.RTX_TUNE_STAGE2_PAIR,
-                 gpu.RTX_TUNE_STAGE2_POOL):
+    for tune in (0, gpu.RTX_TUNE_NO_PACKETS, gpu.RTX_TUNE_NO_CUT, gpu.RTX_TUNE_INLINE_LEAVES):
         hnd = hip_scene(gpu, box, cam=((0.3, -0.2, 0.1), (1.0, 0.1, -0.05), 1.5), rays_per_pixel=1, seed=3, tuning=tune).upload(0)
         buf = torch.zeros((h, w, 3), dtype=torch.float64, device="cuda:0")
         st = hnd.render_rows(w, h, 0, 1, h, buf.data_ptr())
@@ -406,8 +405,8 @@ def test_bvh_triangle_footprint_tree_is_bit_identical_to_exact_kernel(gpu, n_tri
         out[repr(kern) if getattr(kern, "lab", False) else kern] = (buf.cpu().numpy(), st.segments, st.exact_tests, st.kernel)
         hnd.close()
     a, b, c = out[gpu.RTX_KERNEL_EXACT], out[gpu.RTX_KERNEL_BVH], out[gpu.RTX_KERNEL_AUTO]
-    lock = out["lab:%d" % gpu.RTX_KERNEL_BVH]                          # round 1's lock-step kernel (librtx_hip_lab.so)
-    assert lock[3] == gpu.RTX_KERNEL_BVH and np.array_equal(a[0], lock[0]) and a[1] == lock[1]
+    lab = out["lab:%d" % gpu.RTX_KERNEL_BVH]                           # the same id through librtx_hip_lab.so: the mesh kernel there too
+    assert lab[3] == gpu.RTX_KERNEL_BVH_REGROUP and np.array_equal(a[0], lab[0]) and a[1] == lab[1]
     assert a[0].mean() > 0.01 and np.isfinite(a[0]).all()
     assert np.array_equal(a[0], b[0]) and a[1] == b[1]
     g = out[gpu.RTX_KERNEL_BVH_REGROUP]
@@ -484,9 +483,8 @@ def test_spheres_kernel_paths(gpu, oracle):
     C2 does not reach: a tree deep enough for the HBM stack column, origins far outside the scene (f64 slab walk) and
     beyond any walk (every sphere tested), axis-parallel rays, more coincident candidates than the 4-entry queue holds,
     nested shells (every shell a certain hit, the nearest wins), and spheres whose radius is at the f32 resolution of
-    their centre (no certain hit exists: the bounds only ever add candidates).  The same step under its two other
-    schedules runs beside it: RTX_KERNEL_BVH_REGROUP (trace_bvh_spheres_pool_kernel: a pool of rays per lane, waiting lanes
-    served together) and RTX_KERNEL_WAVEFRONT (walk / shade kernels per bounce level, far origins with the f32 slack)."""
+    their centre (no certain hit exists: the bounds only ever add candidates).  RTX_KERNEL_BVH_REGROUP and RTX_KERNEL_WAVEFRONT
+    run beside it: on this tree both resolve to the same kernels."""
     import torch
     from rust_raytracing_amd import scenes
 
@@ -495,20 +493,16 @@ def test_spheres_kernel_paths(gpu, oracle):
         # frames -- stage 1 as one packet walk per 8x8 tile (trace_sph_packet_kernel) and per lane --, so that every edge
         # case below also crosses the packets, the survivors' queue and the queue-fed stage 2
         out = []
-        # (a lab tuning bit, or a LabKernel id, renders through librtx_hip_lab.so; in the product library the three tree ids all
+        # (a lab tuning bit, or a LabKernel id, renders through librtx_hip_lab.so; in both libraries the three tree ids all
         #  run the sphere kernels on this tree)
         L, BVH = gpu.LabKernel, gpu.RTX_KERNEL_BVH
         for kern, tune, ran in ((BVH, 0, BVH), (BVH, gpu.RTX_TUNE_TWO_STAGE, BVH),
                                 (BVH, gpu.RTX_TUNE_TWO_STAGE | gpu.RTX_TUNE_NO_CUT, BVH),
-                                (BVH, gpu.RTX_TUNE_TWO_STAGE | gpu.RTX_TUNE_STAGE2_SLOTS, BVH),
                                 (gpu.RTX_KERNEL_BVH_REGROUP, 0, BVH), (gpu.RTX_KERNEL_WAVEFRONT, gpu.RTX_TUNE_TWO_STAGE, BVH),
                                 (L(BVH), 0, BVH), (L(BVH), gpu.RTX_TUNE_TWO_STAGE, BVH),
                                 (BVH, gpu.RTX_TUNE_TWO_STAGE | gpu.RTX_TUNE_NO_PACKETS, BVH),
-                                (BVH, gpu.RTX_TUNE_TWO_STAGE | gpu.RTX_TUNE_STAGE2_PAIR, BVH),
                                 (BVH, gpu.RTX_TUNE_TWO_STAGE | gpu.RTX_TUNE_INLINE_LEAVES, BVH),
-                                (BVH, gpu.RTX_TUNE_TWO_STAGE | gpu.RTX_TUNE_STAGE2_POOL | gpu.RTX_TUNE_NO_QNODES, BVH),
-                                (L(gpu.RTX_KERNEL_BVH_REGROUP), 0, gpu.RTX_KERNEL_BVH_REGROUP),
-                                (L(gpu.RTX_KERNEL_WAVEFRONT), 0, gpu.RTX_KERNEL_WAVEFRONT), (gpu.RTX_KERNEL_EXACT, 0, gpu.RTX_KERNEL_EXACT)):
+                                (gpu.RTX_KERNEL_EXACT, 0, gpu.RTX_KERNEL_EXACT)):
             hnd = hip_scene(gpu, objs, cam=cam, kernel=kern, rays_per_pixel=spp, seed=42, tuning=tune, **cfg).upload(0)
             hnd.set_scratch_limit(scratch)
             buf = torch.zeros((h, w, 3), dtype=torch.float64, device="cuda:0")
@@ -597,12 +591,10 @@ def test_mesh_kernel_paths(gpu, oracle):
     def both(objs, cam, w=64, h=36, spp=2, scratch=0, **cfg):
         out = []
         # RTX_KERNEL_WAVEFRONT twice: every level in the wavefront form / the megakernel from level 1 on (the default)
-        # and with level 0 as beams (the lanes across nodes) instead of packets (one node per step)
-        # (WF_PURE and BEAMS are lab bits: those two render through librtx_hip_lab.so, as does LabKernel(BVH) = round 1's lock-step kernel;
-        #  RTX_KERNEL_BVH in the product library runs the mesh kernel on a tree that holds triangles)
+        # (WF_PURE is a lab bit: it renders through librtx_hip_lab.so, as does LabKernel(BVH);
+        #  RTX_KERNEL_BVH runs the mesh kernel on a tree that holds triangles, in both libraries)
         for kern, tune in ((gpu.RTX_KERNEL_BVH_REGROUP, 0), (gpu.RTX_KERNEL_BVH, 0), (gpu.LabKernel(gpu.RTX_KERNEL_BVH), 0),
-                           (gpu.RTX_KERNEL_WAVEFRONT, gpu.RTX_TUNE_WF_PURE),
-                           (gpu.RTX_KERNEL_WAVEFRONT, gpu.RTX_TUNE_BEAMS), (gpu.RTX_KERNEL_WAVEFRONT, 0), (gpu.RTX_KERNEL_EXACT, 0)):
+                           (gpu.RTX_KERNEL_WAVEFRONT, gpu.RTX_TUNE_WF_PURE), (gpu.RTX_KERNEL_WAVEFRONT, 0), (gpu.RTX_KERNEL_EXACT, 0)):
             hnd = hip_scene(gpu, objs, cam=cam, kernel=kern, rays_per_pixel=spp, seed=42, tuning=tune, **cfg).upload(0)
             hnd.set_scratch_limit(scratch)
             buf = torch.zeros((h, w, 3), dtype=torch.float64, device="cuda:0")
@@ -700,8 +692,6 @@ def test_auto_takes_the_wavefront_form_for_a_resident_mesh(gpu, oracle):
     assert np.array_equal(auto, mega) and st.segments == stm.segments
     pure, stp = render(gpu.RTX_KERNEL_WAVEFRONT, tuning=gpu.RTX_TUNE_WF_PURE)
     assert np.array_equal(auto, pure) and stp.segments == st.segments
-    bm, stb = render(gpu.RTX_KERNEL_WAVEFRONT, tuning=gpu.RTX_TUNE_BEAMS)       # level 0 as beams (wf_trace_beam_kernel)
-    assert np.array_equal(auto, bm) and stb.segments == st.segments and stb.box_tests != st.box_tests
     for mode in (gpu.RTX_TUNE_WF_PURE, 0):                                     # every level in the wavefront form / the hybrid
         lanes, stl = render(gpu.RTX_KERNEL_WAVEFRONT, tuning=gpu.RTX_TUNE_NO_PACKETS | mode)
         assert np.array_equal(auto, lanes) and stl.segments == st.segments
@@ -731,7 +721,7 @@ def test_auto_takes_the_wavefront_form_for_a_resident_mesh(gpu, oracle):
 def test_ab_knobs_keep_the_bits(gpu):
     """Every A/B switch of RtxConfig.tuning selects another schedule, node format or tree build -- never other bits (and the
     library reads no environment variable for any of them).  Each one, on a pure mesh, a sphere scene and a joint scene, for
-    the tree kernels, against the exhaustive f64 kernel: RTX_TUNE_BVH_CLASSIC (round 1's kernels), NO_QNODES (96-byte instead
+    the tree kernels, against the exhaustive f64 kernel: NO_QNODES (96-byte instead
     of 64-byte nodes), NO_TILES (ray queue in rows instead of 8x8 tiles: also no packets), TRI_LEAF (1 / 2 / 6 triangles per
     leaf instead of the default; larger values are clamped to 6), THRESH (regrouping threshold), BVH_MEDIAN (median splits
     instead of SAH), TWO_STAGE / ONE_STAGE / NO_PACKETS (the sphere kernel's stages)."""
@@ -751,24 +741,23 @@ def test_ab_knobs_keep_the_bits(gpu):
 
     ref = {name: render(o, gpu.RTX_KERNEL_EXACT) for name, o in (("mesh", mesh), ("balls", balls), ("joint", joint))}
     leaf, thresh = gpu.RTX_TUNE_TRI_LEAF_SHIFT, gpu.RTX_TUNE_THRESH_SHIFT
-    knobs = [0, gpu.RTX_TUNE_BVH_CLASSIC, gpu.RTX_TUNE_NO_QNODES, gpu.RTX_TUNE_NO_TILES, 1 << leaf, 2 << leaf, 6 << leaf, 8 << leaf,
+    knobs = [0, gpu.RTX_TUNE_NO_QNODES, gpu.RTX_TUNE_NO_TILES, 1 << leaf, 2 << leaf, 6 << leaf, 8 << leaf,
              4 << thresh, 48 << thresh, gpu.RTX_TUNE_BVH_MEDIAN, gpu.RTX_TUNE_NO_QNODES | gpu.RTX_TUNE_WF_PURE, 6 << leaf,
              gpu.RTX_TUNE_TWO_STAGE, gpu.RTX_TUNE_TWO_STAGE | gpu.RTX_TUNE_NO_PACKETS, gpu.RTX_TUNE_TWO_STAGE | gpu.RTX_TUNE_NO_TILES,
-             gpu.RTX_TUNE_ONE_STAGE | gpu.RTX_TUNE_TWO_STAGE, gpu.RTX_TUNE_TWO_STAGE | gpu.RTX_TUNE_STAGE2_PAIR,
-             gpu.RTX_TUNE_TWO_STAGE | gpu.RTX_TUNE_STAGE2_POOL, gpu.RTX_TUNE_TWO_STAGE | gpu.RTX_TUNE_SORT_SURVIVORS,
-             gpu.RTX_TUNE_TWO_STAGE | gpu.RTX_TUNE_STAGE2_PAIR | gpu.RTX_TUNE_NO_QNODES, gpu.RTX_TUNE_PK_LDS_STACK, gpu.RTX_TUNE_BEAMS, gpu.RTX_TUNE_BEAMS | gpu.RTX_TUNE_PK_LDS_STACK, gpu.RTX_TUNE_TWO_STAGE | gpu.RTX_TUNE_NO_CUT, gpu.RTX_TUNE_ONE_STAGE | gpu.RTX_TUNE_NO_CUT,
+             gpu.RTX_TUNE_ONE_STAGE | gpu.RTX_TUNE_TWO_STAGE,
+             gpu.RTX_TUNE_PK_LDS_STACK, gpu.RTX_TUNE_TWO_STAGE | gpu.RTX_TUNE_NO_CUT, gpu.RTX_TUNE_ONE_STAGE | gpu.RTX_TUNE_NO_CUT,
              gpu.RTX_TUNE_TWO_STAGE | gpu.RTX_TUNE_INLINE_LEAVES, gpu.RTX_TUNE_INLINE_LEAVES | gpu.RTX_TUNE_NO_CUT,
-             gpu.RTX_TUNE_TWO_STAGE | gpu.RTX_TUNE_STAGE2_SLOTS, gpu.RTX_TUNE_STAGE2_SLOTS,
              gpu.RTX_TUNE_TWO_STAGE | gpu.RTX_TUNE_HALVES, gpu.RTX_TUNE_TWO_STAGE | gpu.RTX_TUNE_NO_HALVES,
              gpu.RTX_TUNE_TWO_STAGE | gpu.RTX_TUNE_HALVES | gpu.RTX_TUNE_NO_PACKETS, gpu.RTX_TUNE_HALVES,
              gpu.RTX_TUNE_TWO_STAGE | gpu.RTX_TUNE_NO_TILE_LISTS, gpu.RTX_TUNE_NO_TILE_LISTS]
     # a knob with a RTX_TUNE_LAB_MASK bit renders through librtx_hip_lab.so (the product library refuses it, below); the others
-    # through the product library and, as LabKernel ids, through the lab library's kernel family of each id
+    # through the product library and, as LabKernel ids, through the lab library (RTX_KERNEL_BVH_REGROUP there is RTX_KERNEL_BVH's
+    # dispatch on every tree)
     L = gpu.LabKernel
     for tune in knobs:
         for name, o in (("mesh", mesh), ("balls", balls), ("joint", joint)):
             for kern in (gpu.RTX_KERNEL_BVH, gpu.RTX_KERNEL_BVH_REGROUP, gpu.RTX_KERNEL_WAVEFRONT, L(gpu.RTX_KERNEL_BVH),
-                         L(gpu.RTX_KERNEL_BVH_REGROUP), L(gpu.RTX_KERNEL_WAVEFRONT)):
+                         L(gpu.RTX_KERNEL_WAVEFRONT)):
                 if (tune & gpu.abi.RTX_TUNE_LAB_MASK) and getattr(kern, "lab", False):
                     continue                                   # (the plain id already went to the lab library)
                 img, segs = render(o, kern, tune)
@@ -1080,7 +1069,7 @@ def test_fuzz_tile_lists_against_the_exhaustive_kernel(gpu):
 def test_product_fallback_for_a_sphere_tree_without_64_byte_nodes(gpu):
     """The product library holds the sphere kernels in their 64-byte-node instances only.  A sphere tree whose nodes have no such
     form (coordinates beyond the quantisation's exact range: |origin / step| + 256 >= 2^24) renders with the LDS sweep under every
-    kernel id, with the exhaustive kernel's bits; the lab library walks its 128-byte nodes.  (A pure footprint tree always has its
+    kernel id, with the exhaustive kernel's bits; the lab library dispatches the same way.  (A pure footprint tree always has its
     64-byte form when the tree is built at all -- rtx_pack.hip would let it walk as a joint tree otherwise.)"""
     import torch
     from rust_raytracing_amd import scenes
@@ -1094,7 +1083,7 @@ def test_product_fallback_for_a_sphere_tree_without_64_byte_nodes(gpu):
     L = gpu.LabKernel
     for kern, ran in ((gpu.RTX_KERNEL_AUTO, gpu.RTX_KERNEL_MIXED), (gpu.RTX_KERNEL_BVH, gpu.RTX_KERNEL_MIXED),
                       (gpu.RTX_KERNEL_BVH_REGROUP, gpu.RTX_KERNEL_MIXED), (gpu.RTX_KERNEL_WAVEFRONT, gpu.RTX_KERNEL_MIXED),
-                      (L(gpu.RTX_KERNEL_BVH), gpu.RTX_KERNEL_BVH), (L(gpu.RTX_KERNEL_AUTO), gpu.RTX_KERNEL_BVH)):
+                      (L(gpu.RTX_KERNEL_BVH), gpu.RTX_KERNEL_MIXED)):
         hnd = hip_scene(gpu, balls, cam=cam, kernel=kern, rays_per_pixel=2, seed=4, tuning=gpu.RTX_TUNE_TWO_STAGE).upload(0)
         buf = torch.zeros((32, 48, 3), dtype=torch.float64, device="cuda:0")
         stt = hnd.render_rows(48, 32, 0, 1, 32, buf.data_ptr())
@@ -1552,7 +1541,7 @@ def test_c3_full_size_against_the_oracle(gpu, oracle):
     (= the wavefront form: packets at level 0, the regrouping kernel from the level-1 queue).  (1) two renders are bit-identical, (2) segments within [rays, 11 rays], (3) 300+
     scattered pixels -- corners, edge columns, the brightest pixels, random ones -- equal the oracle's
     (rtxo_render_pixels: every triangle tested per segment, triangle.rs:108-127, scene.rs:243-251) within ATOL,
-    (4) the lock-step BVH kernel, the regrouping kernel alone and the wavefront form at every level produce the same frame
+    (4) the regrouping kernel alone, in both libraries, and the wavefront form at every level produce the same frame
     bit for bit."""
     import torch
     from rust_raytracing_amd import scenes
@@ -1575,13 +1564,13 @@ def test_c3_full_size_against_the_oracle(gpu, oracle):
         st2 = hnd.render_rows(w, h, 0, 1, h, buf.data_ptr())
         assert st2.kernel == gpu.RTX_KERNEL_BVH_REGROUP and np.array_equal(a, buf.cpu().numpy()) and st2.segments == st.segments
     hnd.close()
-    # the lab library: round 1's lock-step kernel, and every level in the wavefront form
+    # the lab library: the same dispatch (the mesh kernel alone under RTX_KERNEL_BVH), and every level in the wavefront form
     hnd = sc.upload(0, lab=True)
-    for kern, tune in ((gpu.RTX_KERNEL_BVH, 0), (gpu.RTX_KERNEL_WAVEFRONT, gpu.RTX_TUNE_WF_PURE)):
+    for kern, tune, ran in ((gpu.RTX_KERNEL_BVH, 0, gpu.RTX_KERNEL_BVH_REGROUP), (gpu.RTX_KERNEL_WAVEFRONT, gpu.RTX_TUNE_WF_PURE, gpu.RTX_KERNEL_WAVEFRONT)):
         hnd.set_config(gpu.Config(rays_per_pixel=spp, seed=42, kernel=kern, tuning=tune))
         buf.zero_()
         st3 = hnd.render_rows(w, h, 0, 1, h, buf.data_ptr())
-        assert st3.kernel == kern and np.array_equal(a, buf.cpu().numpy()) and st3.segments == st.segments
+        assert st3.kernel == ran and np.array_equal(a, buf.cpu().numpy()) and st3.segments == st.segments
     hnd.close()
     xs, ys = _scattered_pixels(a, 200, 100, seed=11)
     assert len(xs) >= 256

@@ -28,10 +28,11 @@ def gpu(rtx):
 
 
 def _kernels(rtx):
-    """every kernel id through the product library and the three tree ids through the lab library (as test_gpu_parity._kernels)"""
+    """every kernel id through the product library, and RTX_KERNEL_BVH and RTX_KERNEL_WAVEFRONT through the lab library (as
+    test_gpu_parity._kernels: the lab library's RTX_KERNEL_BVH_REGROUP is its RTX_KERNEL_BVH on every tree)"""
     L = rtx.LabKernel
     return [rtx.RTX_KERNEL_EXACT, rtx.RTX_KERNEL_MIXED, rtx.RTX_KERNEL_BVH, rtx.RTX_KERNEL_BVH_REGROUP, rtx.RTX_KERNEL_WAVEFRONT,
-            L(rtx.RTX_KERNEL_BVH), L(rtx.RTX_KERNEL_BVH_REGROUP), L(rtx.RTX_KERNEL_WAVEFRONT)]
+            L(rtx.RTX_KERNEL_BVH), L(rtx.RTX_KERNEL_WAVEFRONT)]
 
 
 def three_ways(gpu, objs, o, d, want, what, cam=CAM):

@@ -27,7 +27,8 @@ def gpu(rtx):
 
 
 def _families(rtx):
-    """(name, kernel id, tuning): the kernel families tests/test_gpu_parity.py::_kernels() lists, and the sphere kernel's two stages"""
+    """(name, kernel id, tuning): every kernel id through the product library, the three tree ids through the lab library (the same
+    dispatch from the -DRTX_LAB build: on these sphere scenes all three run the sphere kernels there), and the sphere kernel's two stages"""
     L = rtx.LabKernel
     out = [("exact", rtx.RTX_KERNEL_EXACT, 0), ("mixed", rtx.RTX_KERNEL_MIXED, 0), ("bvh", rtx.RTX_KERNEL_BVH, 0),
            ("regroup", rtx.RTX_KERNEL_BVH_REGROUP, 0), ("wavefront", rtx.RTX_KERNEL_WAVEFRONT, 0), ("lab-bvh", L(rtx.RTX_KERNEL_BVH), 0),

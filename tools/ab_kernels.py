@@ -1,6 +1,6 @@
 """Variants against each other on a BASELINE config (same box, same process): time, rates, counters and bit equality of the frames.
     tools/ab_kernels.py CONFIG SPP SPEC [SPEC ...] [band]
-        SPEC = [L]KERNEL[:TUNING]   KERNEL = RTX_KERNEL_* id (L4: the lab library's family of id 4), TUNING = RtxConfig.tuning bits
+        SPEC = [L]KERNEL[:TUNING]   KERNEL = RTX_KERNEL_* id (L4: id 4 through the lab library), TUNING = RtxConfig.tuning bits
                                     (decimal or 0x..; a RTX_TUNE_LAB_MASK bit renders through librtx_hip_lab.so)
         e.g.  C2 64 4 4:8 4:32      (two stages with packets | stage 1 per lane | one stage)
               C3 8 5 6   |   C5 4 5 6 band

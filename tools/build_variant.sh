@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B builds of the library with other tuning macros (RTX_WF_TRACE_WAVES, RTX_WF_SERVICE, RTX_POOL_K, RTX_MESH_WAVES, RTX_SPK_WAVES, ...):
+# A/B builds of the library with other tuning macros (RTX_WF_TRACE_WAVES, RTX_WF_SERVICE, RTX_MESH_WAVES, RTX_SPK_WAVES, ...):
 #   tools/build_variant.sh NAME FLAGS...   -> rust-raytracing_amd/lib_variant_NAME.so (git-ignored; travels to the GPU box)
 #   (LAB=1 tools/build_variant.sh ...: a variant of the lab library)
 #   RTX_HIP_LIB=$PWD/rust-raytracing_amd/lib_variant_NAME.so python tools/ab_kernels.py C3 8 5 6

@@ -47,7 +47,7 @@ def run(name, objs, w, h, spp, kernels):
 
 if __name__ == "__main__":
     scale = float(sys.argv[1]) if len(sys.argv) > 1 else 1.0
-    # the product library's kernels under each tree id and the LDS sweep; LAB=1 adds the lab library's kernel family of each id
+    # the product library's kernels under each tree id and the LDS sweep; LAB=1 adds the same ids through the lab library
     L = rtx.LabKernel
     LABK = [L(rtx.RTX_KERNEL_BVH), L(rtx.RTX_KERNEL_BVH_REGROUP), L(rtx.RTX_KERNEL_WAVEFRONT)] if os.environ.get("LAB") else []
     K = [rtx.RTX_KERNEL_BVH, rtx.RTX_KERNEL_BVH_REGROUP, rtx.RTX_KERNEL_WAVEFRONT, rtx.RTX_KERNEL_MIXED] + LABK
