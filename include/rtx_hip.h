@@ -762,6 +762,25 @@ int32_t rtx_debug_host_set_visible(const RtxScene *scene, const uint32_t *step_k
 /* Test hook of the lab library: the 16 digests of rtx_debug_host_refit_mesh, from the downloaded resident arrays of `scene`. */
 int32_t rtx_debug_resident_mesh_digests(RtxSceneHandle scene, uint64_t *digests);
 
+/* rtx_debug_tile_lists (lab library; the product returns RTX_ERR_UNSUPPORTED): the per-tile candidate lists of the primary rays that
+ * the LAST render call on `scene` built and used (build_mesh_tile_lists_kernel, DESIGN.md 3.3 "Tile lists"), read out of the handle's
+ * own buffer and carved as the launch carved it.  The handle remembers that call's form and tile grid; the hook synchronises the
+ * device.  All arrays are HOST arrays.
+ * info[8]: [0] the form -- 0 the call built no lists (no packet path, RTX_TUNE_NO_TILE_LISTS, two halves in flight, no render yet;
+ *       the lab's forms whose primary rays walk per lane), 1 a sphere tree's lists in the sphere packets' 32-byte entries {the leaf's
+ *       f32 record (4 words), the sphere's index, t_lb, 0, 0}, 2 the {entry, t_lb} pairs of a footprint or joint tree (entry: a filter
+ *       record, or with bit 31 a sphere leaf entry);  [1] tiles per row of the band's 8 x 8 tile grid, [2] tiles -- tile t holds the
+ *       band's local rows 8 (t / info[1]) ... and columns 8 (t % info[1]) ...;  [3] the cap: entries a tile's list may hold;
+ *       [4] words of a stored entry (8 or 2);  [5..7] 0.
+ * counts and entries may both be NULL (info alone); else they hold max_tiles >= info[2] tiles.
+ * counts[t]: entries of tile t's list; 0xFFFFFFFF: the tile has no list (its packets walk the tree).
+ * entries: 12 words per slot, [tile][cap][12]; the slots below counts[t] are written, the others 0 --
+ *   [0..7] the stored words (form 2: two, the others 0);  [8] the bits of t_lb, the f32 lower bound of the distance the sweep stops by;
+ *   [9] the index in Scene.objects the entry stands for, through the tables the kernels read (a sphere: bvh_prims, sphere_id; a filter
+ *       record: tri_fidx and the triangle table), 0xFFFFFFFF where they name none;  [10] 1 a filter record, 0 a sphere;  [11] 0.
+ * tests/test_tile_lists_gpu.py holds the lists to the f64 text on the extreme rays of every tile's ray family. */
+int32_t rtx_debug_tile_lists(RtxSceneHandle scene, uint32_t *info, uint32_t *counts, uint32_t *entries, uint64_t max_tiles);
+
 #ifdef __cplusplus
 }
 #endif

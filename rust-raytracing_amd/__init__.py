@@ -452,6 +452,9 @@ class Scene:
         return _split_features(out)
 
 
+TILE_LIST_WALK = 0xFFFFFFFF                                        # debug_tile_lists: a tile without a list (its packets walk the tree)
+
+
 class SceneHandle:
     """Split form of the C ABI: scene resident on one device, rows rendered into device buffers."""
 
@@ -570,6 +573,23 @@ class SceneHandle:
                                                     info.ctypes.data if extra else None, rec.ctypes.data if extra else None,
                                                     path.ctypes.data if int(path_steps) > 0 else None, int(path_steps)))
         return (out, info, rec, path) if extra else out
+
+    def debug_tile_lists(self):
+        """The per-tile candidate lists the last render call on this handle built and used (rtx_debug_tile_lists, include/rtx_hip.h;
+        a lab-library hook: upload with lab=True).  A dict: form (0 none, 1 a sphere tree's entries, 2 a mesh or joint tree's pairs),
+        tiles_x, n_tiles, cap, count (n_tiles,) uint32 -- TILE_LIST_WALK: the tile has no list --, and per slot [tile][cap]: raw (.., 8)
+        uint32 the stored words, t_lb float32, object int64 (-1: none) the index in Scene.objects, is_record bool (a filter record)."""
+        info = np.zeros(8, dtype=np.uint32)
+        self._check(self._lib.rtx_debug_tile_lists(self._h, info.ctypes.data, None, None, 0))
+        form, tiles_x, n_tiles, cap = (int(v) for v in info[:4])
+        count = np.zeros(n_tiles, dtype=np.uint32)
+        ent = np.zeros((n_tiles, cap, 12), dtype=np.uint32)
+        if form and n_tiles:
+            self._check(self._lib.rtx_debug_tile_lists(self._h, info.ctypes.data, count.ctypes.data, ent.ctypes.data, n_tiles))
+        obj = ent[:, :, 9].astype(np.int64)
+        obj[obj == 0xFFFFFFFF] = -1
+        return {"form": form, "tiles_x": tiles_x, "n_tiles": n_tiles, "cap": cap, "count": count, "raw": ent[:, :, :8].copy(),
+                "t_lb": np.ascontiguousarray(ent[:, :, 8]).view(np.float32), "object": obj, "is_record": ent[:, :, 10] == 1}
 
     def render_rows(self, width, height, row_begin, row_stride, n_rows, d_out_ptr, stream=None, want_stats=True):
         """d_out_ptr: device address of n_rows*width*3 doubles (e.g. a torch tensor's data_ptr())."""

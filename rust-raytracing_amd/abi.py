@@ -156,6 +156,7 @@ SYMBOLS = [
     ("rtx_debug_host_set_visible", C.c_int32, [C.POINTER(RtxScene), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.c_void_p, C.c_void_p,
                                                C.c_uint64]),
+    ("rtx_debug_tile_lists", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
 ]
 
 

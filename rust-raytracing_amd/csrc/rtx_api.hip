@@ -613,8 +613,8 @@ int32_t plan_batch(const RtxSceneHandle_ *h, BandPlan &plan, uint32_t width, uin
     const uint64_t per_ray = 4 * sizeof(double) + (kernel == RTX_KERNEL_WAVEFRONT ? wavefront_state_bytes(1u << 20, 1) >> 20 : 0) +
                              (sph2 ? 64 + 5 : 0);
     const size_t cap_bytes = scratch_cap(h, h->samples_bytes + h->wf_bytes + h->tile_lists_bytes);
-    // tile lists for the primary rays (sphere trees: build_tile_lists_kernel; pure footprint trees in the wavefront form:
-    // build_mesh_tile_lists_kernel) -- 2 KB resp. 4 KB per tile, so only where they stay a small part of the scratch cap
+    // tile lists for the primary rays (build_mesh_tile_lists_kernel: sphere trees through launch_build_sphere_tile_lists; footprint
+    // and joint trees in the wavefront form) -- 2 KB resp. 4 KB per tile, so only where they stay a small part of the scratch cap
     if ((tuning & RTX_TUNE_NO_TILE_LISTS) == 0u && plan.tiled) {
         if (sph2) plan.tile_list_bytes = bvh_spheres_tile_list_bytes(per_sample64);
         else if (kernel == RTX_KERNEL_WAVEFRONT) plan.tile_list_bytes = wavefront_tile_list_bytes(per_sample64);
@@ -956,6 +956,18 @@ int32_t render_band(RtxSceneHandle h, uint32_t width, uint32_t height, uint32_t 
     plan.kernel = choose_kernel(h->sv, h->cfg, npix, spp);
     if (int32_t rc = plan_batch(h, plan, width, n_rows, spp)) return rc;
     plan_forms(h, plan, spp, accumulate == nullptr);       // (an accumulating call takes the batch path: one resolve per batch into the caller's sums)
+#ifdef RTX_LAB
+    // what rtx_debug_tile_lists reads back: the lists launch_batch hands this call's first launch (the halves' packets walk; the
+    // lab's per-lane forms of level 0 and stage 1 build none)
+    h->tl_form = 0;
+    if (plan.tile_list_bytes != 0 && spp > 0 && !plan.halves) {
+        const bool no_packets = (h->cfg.tuning & RTX_TUNE_NO_PACKETS) != 0u;
+        if (plan.kernel == RTX_KERNEL_WAVEFRONT) h->tl_form = (no_packets && (h->sv.bvh_flags & 4u) != 0u) ? 0u : 2u;   // (a joint tree has packets only)
+        else if (plan.kernel == RTX_KERNEL_BVH && plan.spheres_two_stage) h->tl_form = no_packets ? 0u : 1u;
+    }
+    h->tl_tiles_x = plan.tiles_x;
+    h->tl_tiles = (uint32_t)(plan.per_sample64 >> 6);
+#endif
     if (int32_t rc = ensure_tables(h, width, height, row_begin, row_stride, row_block, n_rows, stream)) return rc;
     if (int32_t rc = grow_scratch(h, plan, npix, spp, accumulate == nullptr)) return rc;
 

@@ -564,4 +564,70 @@ int32_t rtx_debug_path_bounds(RtxSceneHandle h, const RtxRay *rays, const uint32
 #endif
 }
 
+int32_t rtx_debug_tile_lists(RtxSceneHandle h, uint32_t *info, uint32_t *counts, uint32_t *entries, uint64_t max_tiles)
+{
+#ifndef RTX_LAB
+    (void)h; (void)info; (void)counts; (void)entries; (void)max_tiles;
+    return fail(RTX_ERR_UNSUPPORTED, "rtx_debug_tile_lists: a lab-library hook (librtx_hip_lab.so)");
+#else
+    if (!h || !info) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_tile_lists: null argument");
+    const SceneView &sv = h->sv;
+    const uint32_t form = h->tl_form, n_tiles = form ? h->tl_tiles : 0u;
+    // the launches' own sizes: one tile's share of the bytes they ask for is its cap x the entry's size
+    const size_t head = ((size_t)n_tiles * sizeof(uint32_t) + 255) & ~(size_t)255;
+    const size_t entry_bytes = form == 1u ? sizeof(TileEntry) : sizeof(uint2);
+    const size_t bytes = form == 1u ? bvh_spheres_tile_list_bytes((uint64_t)n_tiles << 6) : wavefront_tile_list_bytes((uint64_t)n_tiles << 6);
+    const uint32_t cap = form == 0u ? 0u : (uint32_t)((form == 1u ? bvh_spheres_tile_list_bytes(64) - 256 : wavefront_tile_list_bytes(64) - 256) / entry_bytes);
+    const uint32_t words = (uint32_t)(entry_bytes / sizeof(uint32_t));
+    const uint32_t head_info[8] = { form, h->tl_tiles_x, n_tiles, cap, words, 0u, 0u, 0u };
+    std::memcpy(info, head_info, sizeof head_info);
+    if (form == 0u || n_tiles == 0u || (!counts && !entries)) return RTX_OK;
+    if (!counts || !entries || max_tiles < n_tiles) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_tile_lists: counts and entries hold info[2] tiles");
+    if ((uint64_t)n_tiles * cap > (1ull << 22)) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_tile_lists: too large");
+    if (!h->tile_lists || h->tile_lists_bytes < bytes || bytes != head + (size_t)n_tiles * cap * entry_bytes)
+        return fail(RTX_ERR_HIP, "internal: the handle's tile lists are smaller than the last launch's");
+    RTX_HIP_CHECK(hipSetDevice(h->device));
+    RTX_HIP_CHECK(hipDeviceSynchronize());
+    std::vector<uint32_t> raw(bytes / sizeof(uint32_t));
+    RTX_HIP_CHECK(hipMemcpy(raw.data(), h->tile_lists, bytes, hipMemcpyDeviceToHost));
+    // leaf entry -> Scene.objects, through the tables the kernels themselves go through
+    const bool s_tree = (sv.bvh_flags & 1u) != 0u, t_tree = (sv.bvh_flags & 2u) != 0u;
+    std::vector<uint32_t> prims(s_tree ? sv.n_spheres : 0u), sphere_id(sv.n_spheres), tri_fidx(t_tree ? sv.n_tri_tree : 0u);
+    std::vector<TriX> tris(t_tree ? sv.n_tris : 0u);
+    auto down = [](void *dst, const void *src, size_t b) { return b ? hipMemcpy(dst, src, b, hipMemcpyDeviceToHost) : hipSuccess; };
+    RTX_HIP_CHECK(down(prims.data(), sv.bvh_prims, prims.size() * sizeof(uint32_t)));
+    RTX_HIP_CHECK(down(sphere_id.data(), sv.sphere_id, sphere_id.size() * sizeof(uint32_t)));
+    RTX_HIP_CHECK(down(tri_fidx.data(), sv.tri_fidx, tri_fidx.size() * sizeof(uint32_t)));
+    RTX_HIP_CHECK(down(tris.data(), sv.tris, tris.size() * sizeof(TriX)));
+    constexpr uint32_t kNoObject = 0xFFFFFFFFu, kSphereEntry = 0x80000000u;
+    auto sphere_object = [&](uint32_t prim) { return prim < sphere_id.size() && sphere_id[prim] < sv.n_objects ? sphere_id[prim] : kNoObject; };
+    std::memcpy(counts, raw.data(), (size_t)n_tiles * sizeof(uint32_t));
+    std::memset(entries, 0, (size_t)n_tiles * cap * 12 * sizeof(uint32_t));
+    const uint32_t *lists = raw.data() + head / sizeof(uint32_t);
+    for (uint32_t t = 0; t < n_tiles; ++t) {
+        if (counts[t] > cap) continue;                          // (kTileListWalk: the tile has no list; anything else above the cap: the caller's finding)
+        for (uint32_t k = 0; k < counts[t]; ++k) {
+            const uint32_t *src = lists + ((size_t)t * cap + k) * words;
+            uint32_t *dst = entries + ((size_t)t * cap + k) * 12;
+            std::memcpy(dst, src, entry_bytes);
+            uint32_t object = kNoObject, kind = 0u;
+            if (form == 1u) {                                   // TileEntry {rec, prim, t_lb, pad, pad}
+                dst[8] = src[5];
+                object = sphere_object(src[4]);
+            } else {                                            // {entry, t_lb}: a sphere leaf entry (the flag) or a filter record
+                dst[8] = src[1];
+                const uint32_t e = src[0] & ~kSphereEntry;
+                if (src[0] & kSphereEntry) object = e < prims.size() ? sphere_object(prims[e]) : kNoObject;
+                else {
+                    kind = 1u;
+                    if (e < tri_fidx.size() && tri_fidx[e] < tris.size() && tris[tri_fidx[e]].id < sv.n_objects) object = tris[tri_fidx[e]].id;
+                }
+            }
+            dst[9] = object; dst[10] = kind;
+        }
+    }
+    return RTX_OK;
+#endif
+}
+
 }  // extern "C"

@@ -859,7 +859,7 @@ hipError_t launch_trace_bvh_spheres(const SceneView *d_sv, const SceneView &sv, 
         const uint32_t pblocks = (uint32_t)(want < pcap ? want : pcap);
         TileLists tl{};
         if (tile_list_mem && tiled && (sv.tuning & RTX_TUNE_NO_TILE_LISTS) == 0u) {
-            // what each tile's primary rays can hit, once per tile (build_tile_lists_kernel); the packets then run over the lists
+            // what each tile's primary rays can hit, once per tile (build_mesh_tile_lists_kernel, rtx_wavefront.hip); the packets then run over the lists
             const uint32_t n_tiles = (uint32_t)((rv.n_rays / rv.n_samples) >> 6);
             tl.count = reinterpret_cast<uint32_t *>(tile_list_mem);
             tl.entries = reinterpret_cast<TileEntry *>(static_cast<char *>(tile_list_mem) + (((size_t)n_tiles * sizeof(uint32_t) + 255) & ~(size_t)255));

@@ -46,7 +46,12 @@ struct RtxSceneHandle_ {
     double *h_tables = nullptr; size_t h_tables_doubles = 0;
     double *state = nullptr;    size_t state_bytes = 0;
     void *wf_state = nullptr;   size_t wf_bytes = 0;       // the wavefront kernels' ray state
-    void *tile_lists = nullptr; size_t tile_lists_bytes = 0;   // what each tile's primary rays can reach (build_tile_lists_kernel)
+    void *tile_lists = nullptr; size_t tile_lists_bytes = 0;   // what each tile's primary rays can reach (build_mesh_tile_lists_kernel)
+#ifdef RTX_LAB
+    // (lab) rtx_debug_tile_lists: the shape of the lists the last render call asked its launch to build -- 0 none, 1 a sphere tree's
+    // TileEntry lists, 2 the {entry, t_lb} pairs of a mesh or joint tree --, its tile grid
+    uint32_t tl_form = 0, tl_tiles_x = 0, tl_tiles = 0;
+#endif
     PathStep *transcript = nullptr; uint32_t *transcript_counts = nullptr; uint32_t transcript_steps = 0;   // (lab) rtx_debug_paths, set for one call
     Counters *counters = nullptr;
     unsigned long long *work_counter = nullptr;

@@ -226,7 +226,7 @@ __global__ __launch_bounds__(kBvhThreads, kWfTraceWaves) void wf_trace_kernel(co
 // front, and the footprint filter (tri_filter_sign, rtx_device.h) is the only geometry there is:
 //     e_x = (p_x - c_x) |n.d| + d_x |n.(v0 - p)|,    candidate <=> |e_x| <= h_x |n.d| + A     (and the same in y).
 // One thread per tile walks the footprint tree with the beam's (x, y) slabs (an interval origin and an interval direction: linear
-// inequalities in the ray parameter, as build_tile_lists_kernel) and evaluates those two inequalities for each record it reaches in
+// inequalities in the ray parameter, the slab test of the sphere lists this same kernel builds) and evaluates those two inequalities for each record it reaches in
 // INTERVAL arithmetic over p in O and the unit directions d of the beam: a record some ray of the tile can pass has min |e_x| <=
 // h_x max |n.d| + 2 A (twice the filter's own error allowance: whatever the f32 filter passes for a ray of the tile is in the list).
 // C3: ~1500 records lie under a tile's strip, a few dozen survive.  Entry: {record index, a lower bound of |t| over the beam =

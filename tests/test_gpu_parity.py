@@ -859,7 +859,7 @@ def test_stage1_stats_do_not_depend_on_the_batching(gpu):
 
 
 def test_tile_lists_of_the_primary_rays_keep_the_bits(gpu, oracle):
-    """Stage 1 of the sphere path: what an 8x8 tile's primary rays can hit is found once per tile (build_tile_lists_kernel: a walk
+    """Stage 1 of the sphere path: what an 8x8 tile's primary rays can hit is found once per tile (build_mesh_tile_lists_kernel: a walk
     with an interval origin and an interval direction) and every packet of the tile runs the walk's leaf test over that list
     instead of walking (rtx_bvh_spheres.hip).  Same image and segment count as the packets' own walks (RTX_TUNE_NO_TILE_LISTS) and
     as the exhaustive kernel, where the list is short, where it overflows (a dense cluster: those tiles walk), where both happen in

@@ -1,7 +1,7 @@
 """The primary rays of the device path -- the pixel -> angle map, vertical_fov, get_ray_dir, the camera's un-normalised basis, the
 [y][x] layout, render_to_image's flip and the lens (scene.rs:144-222, camera.rs:42-49) -- against frames the reference's TEXT
 determines (tests/closed_form.py): no oracle in the loop.  Every comparison is bit for bit; the statistical lens cases are 5 sigma of
-a known Bernoulli plus an analytic systematic term.  The per-tile candidate lists of the primary rays (build_tile_lists_kernel,
+a known Bernoulli plus an analytic systematic term.  The per-tile candidate lists of the primary rays (both built by
 build_mesh_tile_lists_kernel) assume exactly this map and the [0, offset) lens box: the 1024 x 1024 frames check them against the
 text, and test_tile_list_bound_on_a_stack_of_nearly_coplanar_triangles aims at the list builder's sorting bound."""
 import math
