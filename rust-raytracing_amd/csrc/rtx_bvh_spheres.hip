@@ -13,6 +13,7 @@
 // only between walks.  4 workgroups per CU: the loops are VALU-issue bound, more waves only add spill reloads inside them
 // (5 / 6 / 8 per SIMD measured in round 1), 3 without any spill are 3 % slower (round 3).
 #include "rtx_launch.h"
+#include "rtx_spk_units.h"
 #include "rtx_traverse.h"
 
 #include <cmath>
@@ -396,6 +397,15 @@ constexpr int kSpkStack = 63;                // wave-uniform stack entries: the 
 #define RTX_SPK_WAVES 4
 #endif
 constexpr int kSpkWaves = RTX_SPK_WAVES;     // workgroups per CU
+// What a packet does not owe the frame (LAB_NOTEBOOK round 10).  0 builds each without its cut, for A/B runs of the cut alone; the 0 form
+// of RTX_SPK_UNITS is the former schedule, not the former code (its grab loop is nested, the list's count is read whether or not a
+// lane walks), so the yardstick of the whole stays the parent commit's library
+#ifndef RTX_SPK_LAZY_RAY
+#define RTX_SPK_LAZY_RAY 1                   // the box walk's ray (make_ray32, ray32_slack, the octant vote) inside the branch that walks
+#endif
+#ifndef RTX_SPK_UNITS
+#define RTX_SPK_UNITS 1                      // a wave meets a tile for a run of samples (rtx_spk_units.h): the pixel's part of a ray once per run
+#endif
 #ifdef RTX_LAB                               // launch flag of the lab form (rtx_api.hip builds it from RtxConfig.tuning)
 constexpr uint32_t kSphNoPackets = 1u;       // stage 1 per lane (A/B runs)
 #endif
@@ -590,7 +600,9 @@ __global__ __launch_bounds__(kBvhThreads, kSpkWaves) void trace_sph_packet_kerne
     const unsigned long long n_rays = rv.n_rays;                        // a multiple of 64: the padded tile grid
     const PkConst4 cnodes = pk_const(nodes), csph = pk_const(la.sphere_f32);
     const PkConstU32 cprims = pk_const(la.sphere_prims);
+#if !RTX_SPK_UNITS
     unsigned long long wave_next = 0, wave_end = 0;                     // this wave's share of the ray queue, in rays
+#endif
     unsigned long long out_next = 0, out_end = 0;                       // its reserved slots of the survivors' queue
     unsigned long long segs = 0, box_tests = 0, leaf_filters = 0, exact = 0;
 
@@ -600,8 +612,49 @@ __global__ __launch_bounds__(kBvhThreads, kSpkWaves) void trace_sph_packet_kerne
 #define RTX_SPK_GRAB_MUL 2
 #endif
     const unsigned long long pk_grab = (unsigned long long)rv.grab * RTX_SPK_GRAB_MUL;
+#if RTX_SPK_UNITS
+    // A grab is a run of samples of ONE tile (rtx_spk_units.h) instead of as many tiles of one sample: a ray's index, slot, key and
+    // bits are what they were, but what depends on the pixel alone -- the pixel arithmetic, the pixel half of the key, the focal
+    // point, the tile's list -- is found once per run.  A run is as many samples as the former grab had packets (16 for big launches),
+    // so the work counter is asked as often as before: one atomic per run.  (Shorter runs lose in stage 1; stage 2 pays 0.3 % for a tile's
+    // samples side by side in its queue, whatever their number above one; an atomic per run of 4 or 2 samples makes the counter's one
+    // address the kernel's bound.  LAB_NOTEBOOK round 10.)
+    const uint32_t per_sample = rv.div_per_sample.d, n_tiles = per_sample >> 6;
+    const uint32_t unit_run = (uint32_t)(pk_grab >> 6) != 0u ? (uint32_t)(pk_grab >> 6) : 1u;
+    const unsigned long long n_units = n_rays != 0ull ? spk_unit_count(n_tiles, rv.n_samples, unit_run) : 0ull;
+#endif
     for (;;) {
-        if (wave_next >= wave_end) {
+#if RTX_SPK_UNITS
+        unsigned long long unit = 0;
+        if (lane == 0) unit = atomicAdd(work_counter, 1ull);
+        unit = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(unit >> 32)) << 32) |
+               __builtin_amdgcn_readfirstlane((uint32_t)unit);
+        if (unit >= n_units) break;
+        const SpkUnit wu = spk_unit((uint32_t)unit, n_tiles, rv.n_samples, unit_run);       // (units <= packets < 2^26)
+        const uint32_t tile_of = wu.tile;
+        uint32_t list_n = kTileListWalk;
+        if (tl.count != nullptr) list_n = pk_const(tl.count)[tile_of];
+        const uint32_t tile_ray = tile_of * 64u + lane;                 // the lane's ray of the launch's first sample
+        uint32_t pl = 0, smp0 = 0;
+        const bool valid = ray_index_to_pixel_tiled(rv, tile_ray, pl, smp0);       // false: the padding of a partial tile
+        uint64_t pixel_half = 0;
+        V3 focal_point = mk(0., 0., 0.);
+        if (valid) {                                                    // gen_primary's pixel arithmetic (the tables end with the band)
+            const uint32_t k = fastdiv(pl, rv.div_width), x = pl - k * rv.width;
+            pixel_half = rng_key_pixel(sv.seed, (uint64_t)image_row(rv, k) * rv.width + x);
+            focal_point = primary_focal_point(sv, rv, pl);
+        }
+        const PkConst4 ent = pk_const(reinterpret_cast<const float4 *>(tl.entries + (size_t)tile_of * kTileListCap));
+#pragma unroll 1
+        for (uint32_t us = 0; us < wu.count; ++us) {
+            const uint32_t smp = wu.first + us;
+            const uint32_t ridx = smp * per_sample + tile_ray;              // (the host keeps rv.n_rays below 2^32)
+            bool alive = valid;
+            RayState r;
+            if (alive) gen_primary_at(sv, pixel_half, focal_point, rv.sample_begin + smp, r);
+            else { r.pos = mk(0., 0., 0.); r.dir = mk(1., 0., 0.); r.result = mk(0., 0., 0.); r.light = mk(1., 1., 1.); r.key = 0; r.draw = 6; r.bounce = 0; }
+#else
+        {
             unsigned long long base = 0;
             if (lane == 0) base = atomicAdd(work_counter, pk_grab);     // (a multiple of 64)
             base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
@@ -610,124 +663,141 @@ __global__ __launch_bounds__(kBvhThreads, kSpkWaves) void trace_sph_packet_kerne
             wave_next = base;
             wave_end = base + pk_grab < n_rays ? base + pk_grab : n_rays;
         }
-        const unsigned long long my = wave_next + lane;
-        wave_next += 64ull;
-        // ---- render_pixel's prologue for the tile's 64 rays (scene.rs:196-207)
-        uint32_t pl = 0, smp = 0;
-        bool alive = ray_index_to_pixel_tiled(rv, my, pl, smp);         // false: the padding of a partial tile
-        RayState r;
-        if (alive) gen_primary(sv, rv, pl, rv.sample_begin + smp, r);
-        else { r.pos = mk(0., 0., 0.); r.dir = mk(1., 0., 0.); r.result = mk(0., 0., 0.); r.light = mk(1., 1., 1.); r.key = 0; r.draw = 6; r.bounce = 0; }
-        const uint32_t ridx = (uint32_t)my;                             // (the host keeps rv.n_rays below 2^32)
-        const RayX rx = make_rayx(r.pos, r.dir);
-
-        // ---- closest_object (scene.rs:243-251), phase 1: one walk for the tile, f32 only
-        float best_up = -__builtin_inff();                              // -inf: this lane enters nothing
-        uint32_t qcnt = 0, nbox = 0, nleaf = 0;
-        bool overflow = false, walked = false;
-        Ray32S q;
-        SphereRay sr;
-        q.ix = q.iy = q.iz = 1.0f; q.nx = q.ny = q.nz = 0.0f; q.e = 0.0f;
-        sr.px = sr.py = sr.pz = sr.dx = sr.dy = sr.dz = sr.Kg = sr.K = 0.f; sr.c0 = __builtin_inff();
-        if (alive) {
-            const float omax = fmaxf(fmaxf(__builtin_fabsf((float)r.pos.x), __builtin_fabsf((float)r.pos.y)),
-                                     __builtin_fabsf((float)r.pos.z));
-            const bool in32 = omax <= sv.bvh_origin_limit;                                  // NaN origin -> exhaustive branch
-            if (in32 || omax <= sv.bvh_origin_limit * kBvhRange64) {
-                sphere_ray_from(sv, r.pos, r.dir, sr);
-                Ray32 q0;
-                make_ray32(r.pos, rx.dirn, (double)sv.bvh_inv_max, q0);
-                q.ix = q0.ix; q.iy = q0.iy; q.iz = q0.iz; q.nx = q0.nx; q.ny = q0.ny; q.nz = q0.nz;
-                q.e = ray32_slack(q0, in32);           // 0 inside origin_limit: the bits of Ray32
-                best_up = __builtin_inff();
-                walked = true;
-            }
-        }
-        const unsigned long long wm = __ballot(walked);
-        // the tile's list, if it has one (wave-uniform: scalar loads)
-        uint32_t list_n = kTileListWalk;
-        const uint32_t tile_of = __builtin_amdgcn_readfirstlane((uint32_t)(((uint32_t)my - smp * rv.div_per_sample.d) >> 6));
-        if (tl.count != nullptr && wm != 0ull) list_n = pk_const(tl.count)[tile_of];
-        if (wm != 0ull && list_n != kTileListWalk) {
+        for (; wave_next < wave_end; wave_next += 64ull) {
+            const unsigned long long my = wave_next + lane;
+            // ---- render_pixel's prologue for the tile's 64 rays (scene.rs:196-207)
+            uint32_t pl = 0, smp = 0;
+            bool alive = ray_index_to_pixel_tiled(rv, my, pl, smp);         // false: the padding of a partial tile
+            // the tile's list, if it has one (wave-uniform: scalar loads)
+            uint32_t list_n = kTileListWalk;
+            const uint32_t tile_of = __builtin_amdgcn_readfirstlane((uint32_t)(((uint32_t)my - smp * rv.div_per_sample.d) >> 6));
+            if (tl.count != nullptr) list_n = pk_const(tl.count)[tile_of];
             const PkConst4 ent = pk_const(reinterpret_cast<const float4 *>(tl.entries + (size_t)tile_of * kTileListCap));
-            for (uint32_t k = 0; k < list_n; ++k) {
-                const float4 rec = ent[2 * k], tail = ent[2 * k + 1];
-                const float t_lb = tail.y;
-                const bool in = walked && t_lb <= best_up;
-                if (__ballot(in) == 0ull) break;          // sorted by t_lb: nothing further can beat any lane's certain hit
-                if (in) {
-                    nleaf += 1;
-                    sph_packet_leaf_test(rec, __float_as_uint(tail.x), sr, lq, tid, best_up, qcnt, overflow);
+            RayState r;
+            if (alive) gen_primary(sv, rv, pl, rv.sample_begin + smp, r);
+            else { r.pos = mk(0., 0., 0.); r.dir = mk(1., 0., 0.); r.result = mk(0., 0., 0.); r.light = mk(1., 1., 1.); r.key = 0; r.draw = 6; r.bounce = 0; }
+            const uint32_t ridx = (uint32_t)my;                             // (the host keeps rv.n_rays below 2^32)
+#endif
+            const RayX rx = make_rayx(r.pos, r.dir);
+
+            // ---- closest_object (scene.rs:243-251), phase 1: one walk for the tile, f32 only
+            float best_up = -__builtin_inff();                              // -inf: this lane enters nothing
+            uint32_t qcnt = 0, nbox = 0, nleaf = 0;
+            bool overflow = false, walked = false, in32 = false;
+            SphereRay sr;
+            sr.px = sr.py = sr.pz = sr.dx = sr.dy = sr.dz = sr.Kg = sr.K = 0.f; sr.c0 = __builtin_inff();
+#if !RTX_SPK_LAZY_RAY
+            Ray32S q;
+            q.ix = q.iy = q.iz = 1.0f; q.nx = q.ny = q.nz = 0.0f; q.e = 0.0f;
+#endif
+            if (alive) {
+                const float omax = fmaxf(fmaxf(__builtin_fabsf((float)r.pos.x), __builtin_fabsf((float)r.pos.y)),
+                                         __builtin_fabsf((float)r.pos.z));
+                in32 = omax <= sv.bvh_origin_limit;                                             // NaN origin -> exhaustive branch
+                if (in32 || omax <= sv.bvh_origin_limit * kBvhRange64) {
+                    sphere_ray_from(sv, r.pos, r.dir, sr);
+#if !RTX_SPK_LAZY_RAY
+                    Ray32 q0;
+                    make_ray32(r.pos, rx.dirn, (double)sv.bvh_inv_max, q0);
+                    q.ix = q0.ix; q.iy = q0.iy; q.iz = q0.iz; q.nx = q0.nx; q.ny = q0.ny; q.nz = q0.nz;
+                    q.e = ray32_slack(q0, in32);           // 0 inside origin_limit: the bits of Ray32
+#endif
+                    best_up = __builtin_inff();
+                    walked = true;
                 }
             }
-        } else if (wm != 0ull) {
-            const uint32_t my_sgn = (q.ix < 0.0f ? 1u : 0u) | (q.iy < 0.0f ? 2u : 0u) | (q.iz < 0.0f ? 4u : 0u);
-            const uint32_t sgn = __builtin_amdgcn_readlane(my_sgn, (int)(__ffsll((long long)wm) - 1));
-            const uint32_t oct = __ballot(walked && my_sgn != sgn) == 0ull ? sgn : 8u;      // 8: the tile straddles an axis
-#define RTX_SPK_WALK(S) sph_packet_walk<S>(cnodes, csph, cprims, sv.bvh_root, q, sr, lq, tid, lane, best_up, qcnt, overflow, nbox, nleaf)
-            switch (oct) {
-                case 0: RTX_SPK_WALK(0); break;
-                case 1: RTX_SPK_WALK(1); break;
-                case 2: RTX_SPK_WALK(2); break;
-                case 3: RTX_SPK_WALK(3); break;
-                case 4: RTX_SPK_WALK(4); break;
-                case 5: RTX_SPK_WALK(5); break;
-                case 6: RTX_SPK_WALK(6); break;
-                case 7: RTX_SPK_WALK(7); break;
-                default: RTX_SPK_WALK(8); break;
-            }
-#undef RTX_SPK_WALK
-        }
-        // ---- phase 2, f64, all lanes together: the exact tests of the candidates that can still be the winner, the shapes
-        //      outside the tree, ray_hit
-        uint32_t first_id = 0;
-        if (alive) {
-            Hit h;
-            hit_init(h);
-            ++segs;
-            box_tests += nbox;
-            leaf_filters += nleaf;
-            if (walked && !overflow) {
-#pragma unroll 1
-                for (uint32_t e = 0; e < qcnt; ++e) {
-                    if (__uint_as_float(lq[(size_t)(kSphQueue + e) * kBvhThreads + tid]) <= best_up) {
-                        const uint32_t idx = lq[(size_t)e * kBvhThreads + tid];
-                        double t;
-                        if (sphere_distance(la.spheres[idx], rx, &t)) hit_consider(h, t, la.sphere_ids[idx], 0, idx);
-                        exact += 1;
+            const unsigned long long wm = __ballot(walked);
+            if (wm != 0ull && list_n != kTileListWalk) {       // the tile has a list: the leaf test over its entries, which reads sr alone
+                for (uint32_t k = 0; k < list_n; ++k) {
+                    const float4 rec = ent[2 * k], tail = ent[2 * k + 1];
+                    const float t_lb = tail.y;
+                    const bool in = walked && t_lb <= best_up;
+                    if (__ballot(in) == 0ull) break;          // sorted by t_lb: nothing further can beat any lane's certain hit
+                    if (in) {
+                        nleaf += 1;
+                        sph_packet_leaf_test(rec, __float_as_uint(tail.x), sr, lq, tid, best_up, qcnt, overflow);
                     }
                 }
-            } else {                                  // no walk (origin out of range / NaN) or a dropped candidate: every sphere
-                for (uint32_t k = 0; k < sv.n_spheres; ++k) {
-                    double t;
-                    if (sphere_distance(la.spheres[k], rx, &t)) hit_consider(h, t, la.sphere_ids[k], 0, k);
+            } else if (wm != 0ull) {
+#if RTX_SPK_LAZY_RAY
+                // the box walk's ray, made where it is read: the three f64 divisions per axis are not owed by a tile with a list
+                Ray32S q;
+                q.ix = q.iy = q.iz = 1.0f; q.nx = q.ny = q.nz = 0.0f; q.e = 0.0f;
+                if (walked) {
+                    Ray32 q0;
+                    make_ray32(r.pos, rx.dirn, (double)sv.bvh_inv_max, q0);
+                    q.ix = q0.ix; q.iy = q0.iy; q.iz = q0.iz; q.nx = q0.nx; q.ny = q0.ny; q.nz = q0.nz;
+                    q.e = ray32_slack(q0, in32);           // 0 inside origin_limit: the bits of Ray32
                 }
-                exact += sv.n_spheres;
+#endif
+                const uint32_t my_sgn = (q.ix < 0.0f ? 1u : 0u) | (q.iy < 0.0f ? 2u : 0u) | (q.iz < 0.0f ? 4u : 0u);
+                const uint32_t sgn = __builtin_amdgcn_readlane(my_sgn, (int)(__ffsll((long long)wm) - 1));
+                const uint32_t oct = __ballot(walked && my_sgn != sgn) == 0ull ? sgn : 8u;      // 8: the tile straddles an axis
+#define RTX_SPK_WALK(S) sph_packet_walk<S>(cnodes, csph, cprims, sv.bvh_root, q, sr, lq, tid, lane, best_up, qcnt, overflow, nbox, nleaf)
+                switch (oct) {
+                    case 0: RTX_SPK_WALK(0); break;
+                    case 1: RTX_SPK_WALK(1); break;
+                    case 2: RTX_SPK_WALK(2); break;
+                    case 3: RTX_SPK_WALK(3); break;
+                    case 4: RTX_SPK_WALK(4); break;
+                    case 5: RTX_SPK_WALK(5); break;
+                    case 6: RTX_SPK_WALK(6); break;
+                    case 7: RTX_SPK_WALK(7); break;
+                    default: RTX_SPK_WALK(8); break;
+                }
+#undef RTX_SPK_WALK
             }
-            for (uint32_t k = 0; k < sv.n_planes; ++k) {
-                double t;
-                if (plane_distance(sv.planes[k], rx, &t)) hit_consider(h, t, sv.planes[k].id, 1, k);
-            }
-            for (uint32_t k = 0; k < sv.n_tri_filter; ++k) {       // the few triangles of a sphere scene (none of them in the tree)
-                const uint32_t tk = la.tri_fidx[k];
-                double t;
-                if (triangle_distance(la.tris[tk], rx, &t)) hit_consider(h, t, la.tris[tk].id, 2, tk);
-            }
-            exact += sv.n_planes + sv.n_tri_filter;
+            // ---- phase 2, f64, all lanes together: the exact tests of the candidates that can still be the winner, the shapes
+            //      outside the tree, ray_hit
+            uint32_t first_id = 0;
+            if (alive) {
+                Hit h;
+                hit_init(h);
+                ++segs;
+                box_tests += nbox;
+                leaf_filters += nleaf;
+                if (walked && !overflow) {
+#pragma unroll 1
+                    for (uint32_t e = 0; e < qcnt; ++e) {
+                        if (__uint_as_float(lq[(size_t)(kSphQueue + e) * kBvhThreads + tid]) <= best_up) {
+                            const uint32_t idx = lq[(size_t)e * kBvhThreads + tid];
+                            double t;
+                            if (sphere_distance(la.spheres[idx], rx, &t)) hit_consider(h, t, la.sphere_ids[idx], 0, idx);
+                            exact += 1;
+                        }
+                    }
+                } else {                                  // no walk (origin out of range / NaN) or a dropped candidate: every sphere
+                    for (uint32_t k = 0; k < sv.n_spheres; ++k) {
+                        double t;
+                        if (sphere_distance(la.spheres[k], rx, &t)) hit_consider(h, t, la.sphere_ids[k], 0, k);
+                    }
+                    exact += sv.n_spheres;
+                }
+                for (uint32_t k = 0; k < sv.n_planes; ++k) {
+                    double t;
+                    if (plane_distance(sv.planes[k], rx, &t)) hit_consider(h, t, sv.planes[k].id, 1, k);
+                }
+                for (uint32_t k = 0; k < sv.n_tri_filter; ++k) {       // the few triangles of a sphere scene (none of them in the tree)
+                    const uint32_t tk = la.tri_fidx[k];
+                    double t;
+                    if (triangle_distance(la.tris[tk], rx, &t)) hit_consider(h, t, la.tris[tk].id, 2, tk);
+                }
+                exact += sv.n_planes + sv.n_tri_filter;
 
-            // ---- render_ray's match arm + ray_hit (scene.rs:232-239, 260-278)
-            bool done = true;
-            if (h.id != kNone) {
-                advance_and_shade<kRoundGlobal>(sv, h, r);
-                first_id = h.id;
-                done = (r.bounce >= bounce_limit) || light_is_zero(r);            // scene.rs:227-228
+                // ---- render_ray's match arm + ray_hit (scene.rs:232-239, 260-278)
+                bool done = true;
+                if (h.id != kNone) {
+                    advance_and_shade<kRoundGlobal>(sv, h, r);
+                    first_id = h.id;
+                    done = (r.bounce >= bounce_limit) || light_is_zero(r);            // scene.rs:227-228
+                }
+                if (done) {
+                    store_sample<kRoundGlobal>(samples, rv, ridx, r.result);
+                    alive = false;
+                }
             }
-            if (done) {
-                store_sample<kRoundGlobal>(samples, rv, ridx, r.result);
-                alive = false;
-            }
+            sph_queue_append(sq, ctr, alive, r, ridx, first_id, lane, out_next, out_end);
         }
-        sph_queue_append(sq, ctr, alive, r, ridx, first_id, lane, out_next, out_end);
     }
     sph_queue_close(sq, lane, out_next, out_end);
     unsigned long long filt = box_tests + leaf_filters;

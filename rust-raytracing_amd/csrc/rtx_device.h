@@ -274,6 +274,26 @@ __device__ __forceinline__ void gen_primary(const SceneView &sv, const RowsView 
     r.bounce = 0;
 }
 
+// gen_primary with what does not depend on the sample handed in: pixel_half = rng_key_pixel(sv.seed, the pixel's index in the full
+// image), focal_point = primary_focal_point(sv, rv, pl).  The same operations on the same values in the same order: the same ray.
+__device__ __forceinline__ void gen_primary_at(const SceneView &sv, uint64_t pixel_half, V3 focal_point, uint32_t sample, RayState &r)
+{
+    r.key = rng_key_sample(pixel_half, sample);
+    V3 rnd1;
+    rnd1.x = rng_u01(r.key, 0); rnd1.y = rng_u01(r.key, 1); rnd1.z = rng_u01(r.key, 2);
+    V3 ray_position = vadd(sv.cam_pos, vmuls(rnd1, sv.non_focal_offset));      // scene.rs:202
+    V3 rnd2;
+    rnd2.x = rng_u01(r.key, 3); rnd2.y = rng_u01(r.key, 4); rnd2.z = rng_u01(r.key, 5);
+    V3 target_point = vadd(focal_point, vmuls(rnd2, sv.focal_offset));         // scene.rs:204
+    V3 ray_direction = vsub(target_point, ray_position);                       // scene.rs:205
+    r.pos = ray_position;
+    r.dir = vnorm(ray_direction);                                              // scene.rs:207
+    r.result = mk(0.0, 0.0, 0.0);
+    r.light = mk(1.0, 1.0, 1.0);
+    r.draw = 6;
+    r.bounce = 0;
+}
+
 // Vector3::random_direction (vector.rs:36-45)
 __device__ __forceinline__ V3 random_direction(double u_z, double u_theta)
 {

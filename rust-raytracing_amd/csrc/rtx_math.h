@@ -68,6 +68,11 @@ RTX_HD uint64_t rng_key(uint64_t seed, uint64_t pixel_index, uint64_t sample_ind
     return mix64(a ^ (0xD1B54A32D192ED03ULL * (sample_index + 1)));
 }
 
+// rng_key in its two halves, for a caller that meets one pixel with many samples (the packet kernel's sample loop):
+// rng_key(seed, p, s) == rng_key_sample(rng_key_pixel(seed, p), s), the same operations in the same order
+RTX_HD uint64_t rng_key_pixel(uint64_t seed, uint64_t pixel_index) { return mix64(seed + 0x9E3779B97F4A7C15ULL * (pixel_index + 1)); }
+RTX_HD uint64_t rng_key_sample(uint64_t pixel_half, uint64_t sample_index) { return mix64(pixel_half ^ (0xD1B54A32D192ED03ULL * (sample_index + 1))); }
+
 RTX_HD double rng_u01(uint64_t key, uint32_t draw_index)              // fastrand::f64(): [1,2) - 1.0
 {
     uint64_t z = mix64(key + 0x9E3779B97F4A7C15ULL * ((uint64_t)draw_index + 1));
