@@ -781,6 +781,31 @@ int32_t rtx_debug_resident_mesh_digests(RtxSceneHandle scene, uint64_t *digests)
  * tests/test_tile_lists_gpu.py holds the lists to the f64 text on the extreme rays of every tile's ray family. */
 int32_t rtx_debug_tile_lists(RtxSceneHandle scene, uint32_t *info, uint32_t *counts, uint32_t *entries, uint64_t max_tiles);
 
+/* rtx_debug_sweep_filter (lab library; the product returns RTX_ERR_UNSUPPORTED): what the LDS sweep's two f32 filters
+ * (trace_mixed_kernel) decide for single rays.  One device thread per entry runs the sweep's own filter_from_ray,
+ * filter_disc2 and filter_disc1, tri_filter_from_ray (the idle parameters when the scene has no triangle filter record, as the sweep
+ * sets them) and tri_filter_sign on the handle's resident sphere_f32 and tri_f32.  rays, objects and out are HOST arrays; the hook
+ * copies, launches once, copies back and synchronises.
+ * pairs (objects != NULL): entry i is ray i and Scene.objects[objects[i]], whose filter record is found through sphere_id, or through
+ *   tri_fidx and the triangle table.  out: 24 words per entry --
+ *   [0] flags: 1 a triangle; 2 the object has a filter record (else every other word is 0: planes, triangles that can never be hit);
+ *       4 the ray's filter of that kind is pass-all; 8 the record is a CANDIDATE (the sign bit the sweep tests is clear)
+ *   [1..8] a sphere: the eight FilterParams words {d.xyz, -p.d, 2p.xyz, E - p.p}; a triangle: the seven TriFilterParams words
+ *       {d.xyz, -p.xyz, A} and 0
+ *   [9..16] the record as the kernel read it: a sphere's {c - centre, |c - centre|^2 - r^2}, taken out of its pair, then 0; a triangle's
+ *       A = {n, n.(v0 - centre)} and B = {cx, cy, hx, hy}
+ *   [17] a sphere: D of filter_disc2 on the resident pair (this sphere's half); a triangle: tri_filter_sign's word, bits(sx) | bits(sy)
+ *   [18] a sphere: D of filter_disc1 on the record of [9..12]   [19] the record's index (sphere_f32 / tri_f32)   [20..23] 0.
+ * counts (objects == NULL): out holds 4 words per ray -- [0] the records of the WHOLE padded sphere array (n_spheres rounded up to a
+ *   multiple of 4) and [1] of the n_tri_filter triangle records whose sign bit is clear: what the sweep queues for the ray;
+ *   [2] 4: the sphere filter is pass-all, 16: the triangle filter is; [3] 0.
+ * scene_info[16] (may be NULL; written even when n is 0): the centre the records are relative to (3), sphere_cmax, tri_extent,
+ *   n_spheres, n_tri_filter, the sweep's queue sizes Q and kOverflowQ of the shipped instance, planes, triangles, objects, triangle
+ *   records in the tree, 0, 0, 0.
+ * tests/test_sweep_filters.py holds both filters to the f64 text on rays aimed at them. */
+int32_t rtx_debug_sweep_filter(RtxSceneHandle scene, const RtxRay *rays, const uint32_t *objects, uint64_t n, uint32_t *out,
+                               double *scene_info);
+
 #ifdef __cplusplus
 }
 #endif

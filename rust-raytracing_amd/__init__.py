@@ -591,6 +591,20 @@ class SceneHandle:
         return {"form": form, "tiles_x": tiles_x, "n_tiles": n_tiles, "cap": cap, "count": count, "raw": ent[:, :, :8].copy(),
                 "t_lb": np.ascontiguousarray(ent[:, :, 8]).view(np.float32), "object": obj, "is_record": ent[:, :, 10] == 1}
 
+    def debug_sweep_filter(self, origins, directions, objects=None):
+        """What the LDS sweep's f32 filters decide for single rays (rtx_debug_sweep_filter, include/rtx_hip.h; a lab-library hook:
+        upload with lab=True).  objects given: the pairs (ray i, Scene.objects[objects[i]]) -> (out (n, 24) uint32, scene_info (16,)
+        float64); objects None: the counts mode -> (out (n, 4) uint32: sphere candidates, triangle candidates, the pass-all flags,
+        scene_info)."""
+        rays = make_rays(origins, directions)
+        n = len(rays)
+        info = np.zeros(16, dtype=np.float64)
+        obj = None if objects is None else np.ascontiguousarray(np.broadcast_to(np.asarray(objects, dtype=np.uint32), (n,)))
+        out = np.zeros((n, 4 if obj is None else 24), dtype=np.uint32)
+        self._check(self._lib.rtx_debug_sweep_filter(self._h, rays.ctypes.data if n else None, None if obj is None or not n else obj.ctypes.data,
+                                                     n, out.ctypes.data if n else None, info.ctypes.data))
+        return out, info
+
     def render_rows(self, width, height, row_begin, row_stride, n_rows, d_out_ptr, stream=None, want_stats=True):
         """d_out_ptr: device address of n_rows*width*3 doubles (e.g. a torch tensor's data_ptr())."""
         stats = abi.RtxStats()

@@ -157,6 +157,7 @@ SYMBOLS = [
                                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.c_void_p, C.c_void_p,
                                                C.c_uint64]),
     ("rtx_debug_tile_lists", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    ("rtx_debug_sweep_filter", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
 ]
 
 

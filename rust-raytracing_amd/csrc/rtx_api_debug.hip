@@ -630,4 +630,61 @@ int32_t rtx_debug_tile_lists(RtxSceneHandle h, uint32_t *info, uint32_t *counts,
 #endif
 }
 
+int32_t rtx_debug_sweep_filter(RtxSceneHandle h, const RtxRay *rays, const uint32_t *objects, uint64_t n, uint32_t *out, double *scene_info)
+{
+#ifndef RTX_LAB
+    (void)h; (void)rays; (void)objects; (void)n; (void)out; (void)scene_info;
+    return fail(RTX_ERR_UNSUPPORTED, "rtx_debug_sweep_filter: a lab-library hook (librtx_hip_lab.so)");
+#else
+    if (!h) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_sweep_filter: null scene");
+    const SceneView &sv = h->sv;
+    if (scene_info) {
+        uint32_t q = 0, overflow = 0;
+        mixed_queue_sizes(&q, &overflow);
+        const double info[16] = { sv.sphere_center[0], sv.sphere_center[1], sv.sphere_center[2], sv.sphere_cmax, sv.tri_extent,
+                                  (double)sv.n_spheres, (double)sv.n_tri_filter, (double)q, (double)overflow, (double)sv.n_planes,
+                                  (double)sv.n_tris, (double)sv.n_objects, (double)sv.n_tri_tree, 0.0, 0.0, 0.0 };
+        std::memcpy(scene_info, info, sizeof info);
+    }
+    if (n == 0) return RTX_OK;
+    if (!rays || !out) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_sweep_filter: null argument");
+    if (n > (1ull << 22)) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_sweep_filter: too large");
+    RTX_HIP_CHECK(hipSetDevice(h->device));
+    RTX_HIP_CHECK(hipDeviceSynchronize());
+    constexpr uint32_t kTriEntry = 0x80000000u, kNoEntry = 0xFFFFFFFFu;
+    std::vector<uint32_t> entries;
+    if (objects) {                                              // Scene.objects index -> the filter record, through the sweep's own tables
+        std::vector<uint32_t> sphere_id(sv.n_spheres), tri_fidx(sv.n_tri_filter);
+        std::vector<TriX> tris(sv.n_tri_filter ? sv.n_tris : 0u);
+        auto down = [](void *dst, const void *src, size_t bytes) { return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess; };
+        RTX_HIP_CHECK(down(sphere_id.data(), sv.sphere_id, sphere_id.size() * sizeof(uint32_t)));
+        RTX_HIP_CHECK(down(tri_fidx.data(), sv.tri_fidx, tri_fidx.size() * sizeof(uint32_t)));
+        RTX_HIP_CHECK(down(tris.data(), sv.tris, tris.size() * sizeof(TriX)));
+        std::vector<uint32_t> entry_of(sv.n_objects, kNoEntry);
+        for (size_t k = 0; k < sphere_id.size(); ++k) if (sphere_id[k] < sv.n_objects) entry_of[sphere_id[k]] = (uint32_t)k;
+        for (size_t r = 0; r < tri_fidx.size(); ++r)
+            if (tri_fidx[r] < tris.size() && tris[tri_fidx[r]].id < sv.n_objects) entry_of[tris[tri_fidx[r]].id] = (uint32_t)r | kTriEntry;
+        entries.resize(n);
+        for (uint64_t i = 0; i < n; ++i) {
+            if (objects[i] >= sv.n_objects) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_sweep_filter: an object index outside Scene.objects");
+            entries[i] = entry_of[objects[i]];
+        }
+    }
+    const size_t out_bytes = n * (objects ? 24 : 4) * sizeof(uint32_t);
+    DebugBufs d;
+    void *d_sv, *d_rays, *d_entries, *d_out;
+    RTX_HIP_CHECK(d.up(&sv, sizeof(SceneView), &d_sv));
+    RTX_HIP_CHECK(d.up(rays, n * sizeof(RtxRay), &d_rays));
+    RTX_HIP_CHECK(d.up(entries.data(), entries.size() * sizeof(uint32_t), &d_entries));
+    RTX_HIP_CHECK(d.up(out, out_bytes, &d_out));
+    static_assert(sizeof(RtxRay) == sizeof(QueryRay), "RtxRay layout");
+    SweepFilterArgs a;
+    a.rays = static_cast<const QueryRay *>(d_rays); a.entries = static_cast<const uint32_t *>(d_entries);
+    a.out = static_cast<uint32_t *>(d_out); a.n = n;
+    RTX_HIP_CHECK(launch_debug_sweep_filter(static_cast<const SceneView *>(d_sv), a, nullptr));
+    RTX_HIP_CHECK(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));                  // (the null stream: after the kernel)
+    return RTX_OK;
+#endif
+}
+
 }  // extern "C"

@@ -177,7 +177,8 @@ constexpr uint32_t kInvalid = 0xFFFFFFFFu;
 // discriminant for |d| = 1, sphere.rs:22-25) in the expanded form
 //     b = c.d - p.d            q = 2 c.p - p.p + E            D = b*b + (q - (c.c - r*r))
 // with all points relative to the scene centre.  E bounds the f32 evaluation error, so a sphere the
-// reference could report (discriminant > 1e-100) always has D_f32 >= 0 and is queued.
+// reference could report (discriminant > 1e-100) always has D_f32 >= 0 and is queued (held by tests/test_sweep_filters.py on rays
+// aimed at the filter; the measured use of E is in rtx_device.h, filter_from_ray).
 // Two spheres are evaluated per instruction (v_pk_fma_f32): LDS holds the records pair-interleaved,
 //     float4 A = {x0, x1, y0, y1}   float4 B = {z0, z1, w0, w1},   w = |c|^2 - r^2
 // and the slot holds {d.xyz, -p.d, 2p.xyz, -p.p + E}.
@@ -206,6 +207,66 @@ __device__ __forceinline__ f32x2 filter_disc2(const float4 A, const float4 B, co
 // generation, exact tests, shading) exists once and loops over the slots instead of being unrolled S times.
 constexpr int kOverflowQ = 24;             // candidates per slot beyond the LDS queue, kept in HBM (rare)
 constexpr size_t kSlotBytes = 12 * sizeof(double) + 16 * sizeof(float) + (3 + kOverflowQ) * sizeof(uint32_t);
+
+#ifdef RTX_LAB
+// rtx_debug_sweep_filter: the sweep's two f32 filters for single rays, by the functions the sweep itself calls (filter_from_ray /
+// tri_filter_from_ray as the refill calls them, filter_disc2 on the resident pair records, filter_disc1, tri_filter_sign), one thread
+// per entry.  pairs (a.entries != null): 24 words per entry (include/rtx_hip.h), entry i = ray i and the record a.entries[i] -- a
+// sphere's index, or bit 31 | a triangle filter record, or ~0: the object has no filter record.  counts (a.entries == null): 4 words
+// per ray -- the records of the whole padded sphere array and of the n_tri_filter triangle records whose sign bit is clear: what the
+// sweep queues for that ray -- and the two pass-all flags.
+__global__ __launch_bounds__(256) void debug_sweep_filter_kernel(const SceneView *__restrict__ svp, SweepFilterArgs a)
+{
+    const SceneView &sv = *svp;
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    const QueryRay ray = a.rays[i];
+    const V3 pos = mk(ray.position[0], ray.position[1], ray.position[2]), dir = mk(ray.direction[0], ray.direction[1], ray.direction[2]);
+    FilterParams f;
+    filter_from_ray(sv, pos, dir, f);
+    TriFilterParams tf;
+    if (sv.n_tri_filter != 0) tri_filter_from_ray(sv, pos, dir, tf); else tri_filter_idle(tf);
+    const bool s_all = f.nppE == 1.0e30f, t_all = tf.A == 1.0e30f;      // (inside the range gates |nppE| and A stay below 1e24)
+    if (!a.entries) {
+        uint32_t *o = a.out + i * 4;
+        uint32_t n_s = 0, n_t = 0;
+        const uint32_t ns4 = (sv.n_spheres + 3u) & ~3u;
+        for (uint32_t j = 0; j < ns4; j += 2) {
+            const f32x2 d = filter_disc2(sv.sphere_f32[j], sv.sphere_f32[j + 1], f);
+            n_s += ((int)__float_as_uint(d.x) >= 0) + ((int)__float_as_uint(d.y) >= 0);
+        }
+        for (uint32_t r = 0; r < sv.n_tri_filter; ++r)
+            n_t += (int)tri_filter_sign(sv.tri_f32[2 * (size_t)r], sv.tri_f32[2 * (size_t)r + 1], tf) >= 0;
+        o[0] = n_s; o[1] = n_t; o[2] = (s_all ? 4u : 0u) | (t_all ? 16u : 0u); o[3] = 0u;
+        return;
+    }
+    uint32_t *o = a.out + i * 24;
+    for (int w = 0; w < 24; ++w) o[w] = 0u;
+    const uint32_t e = a.entries[i];
+    if (e == 0xFFFFFFFFu) return;
+    if (e & 0x80000000u) {
+        const uint32_t r = e & 0x7FFFFFFFu;
+        const float4 A = sv.tri_f32[2 * (size_t)r], B = sv.tri_f32[2 * (size_t)r + 1];
+        const uint32_t sg = tri_filter_sign(A, B, tf);
+        o[0] = 1u | 2u | (t_all ? 4u : 0u) | ((int)sg >= 0 ? 8u : 0u);
+        const float p[8] = { tf.dx, tf.dy, tf.dz, tf.npx, tf.npy, tf.npz, tf.A, tf.pad };
+        const float rec[8] = { A.x, A.y, A.z, A.w, B.x, B.y, B.z, B.w };
+        for (int w = 0; w < 8; ++w) { o[1 + w] = __float_as_uint(p[w]); o[9 + w] = __float_as_uint(rec[w]); }
+        o[17] = sg; o[19] = r;
+        return;
+    }
+    const uint32_t k = e, odd = k & 1u;
+    const float4 A = sv.sphere_f32[(size_t)(k & ~1u)], B = sv.sphere_f32[(size_t)(k | 1u)];      // the pair's two float4
+    const f32x2 d2 = filter_disc2(A, B, f);
+    const float4 s = odd ? make_float4(A.y, A.w, B.y, B.w) : make_float4(A.x, A.z, B.x, B.z);
+    const float D2 = odd ? d2.y : d2.x, D1 = filter_disc1(s, f);
+    o[0] = 2u | (s_all ? 4u : 0u) | ((int)__float_as_uint(D2) >= 0 ? 8u : 0u);
+    const float p[8] = { f.dx, f.dy, f.dz, f.npd, f.p2x, f.p2y, f.p2z, f.nppE };
+    for (int w = 0; w < 8; ++w) o[1 + w] = __float_as_uint(p[w]);
+    o[9] = __float_as_uint(s.x); o[10] = __float_as_uint(s.y); o[11] = __float_as_uint(s.z); o[12] = __float_as_uint(s.w);
+    o[17] = __float_as_uint(D2); o[18] = __float_as_uint(D1); o[19] = k;
+}
+#endif
 
 template <int S, int THREADS, int CHUNK, int Q, int WAVES_PER_EU>
 __global__ __launch_bounds__(THREADS, WAVES_PER_EU) void trace_mixed_kernel(const SceneView *__restrict__ svp,
@@ -860,6 +921,19 @@ hipError_t launch_debug_store_samples(const double *rgb, const uint64_t *slots, 
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(debug_store_samples_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, rgb, slots, n, samples, rv);
     return hipGetLastError();
+}
+
+hipError_t launch_debug_sweep_filter(const SceneView *d_sv, const SweepFilterArgs &a, hipStream_t stream)
+{
+    if (a.n == 0) return hipSuccess;
+    hipLaunchKernelGGL(debug_sweep_filter_kernel, dim3((uint32_t)((a.n + 255) / 256)), dim3(256), 0, stream, d_sv, a);
+    return hipGetLastError();
+}
+
+void mixed_queue_sizes(uint32_t *q, uint32_t *overflow)
+{
+    *q = (uint32_t)mix_variant().q;
+    *overflow = (uint32_t)kOverflowQ;
 }
 
 // ops 17-21 need no kernel: the HOST forms (RTX_HD) that size launches and fill the row tables.  17: fastdiv(a[i], make_fastdiv(b[0]));

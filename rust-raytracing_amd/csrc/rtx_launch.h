@@ -195,6 +195,13 @@ struct PathBoundsArgs {
     uint32_t *out; uint64_t n; uint32_t stride, form;
 };
 hipError_t launch_debug_path_bounds(const SceneView *d_sv, const PathBoundsArgs &a, hipStream_t stream);
+// rtx_debug_sweep_filter (rtx_kernels.hip): one thread per entry runs the sweep's own filter functions.  entries[i]: a sphere's
+// local index (below n_spheres), or bit 31 | a triangle filter record (below n_tri_filter), or ~0: no filter record; null: the
+// counts mode.  out: 24 words per entry, or 4 per ray (include/rtx_hip.h).  mixed_queue_sizes: Q and kOverflowQ of the sweep's
+// shipped instance.
+struct SweepFilterArgs { const QueryRay *rays; const uint32_t *entries; uint32_t *out; uint64_t n; };
+hipError_t launch_debug_sweep_filter(const SceneView *d_sv, const SweepFilterArgs &a, hipStream_t stream);
+void mixed_queue_sizes(uint32_t *q, uint32_t *overflow);
 #endif
 
 }  // namespace rtx

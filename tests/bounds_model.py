@@ -18,6 +18,12 @@ Margins (class Margins): each is a factor on the shipped constant, 1.0 as shippe
   abs_pad2  the 64-byte sphere nodes' second abs_pad        slack     Ray32S's slack for origins beyond origin_limit (both terms)
   K, G      the sphere bounds' K = 24uM and G = 128uMr + 8192u^2M^2
   e_nv, e_dn, e_ab   tri_bounds' 16uS, 8u and the (a, b) margins ea / eb
+  E         the sweep's sphere filter: E = 64uM^2 of filter_from_ray (sweep_params)
+  A         the triangle filter's allowance A = 64uS of tri_filter_from_ray (tri_params; tri_bounds takes its S from the same word)
+
+The LDS sweep's filters (trace_mixed_kernel, rtx_kernels.hip): sweep_record() restates the sphere_f32 records of pack_scene /
+derive_sphere, sweep_params() filter_from_ray, sweep_disc() filter_disc1 and filter_disc2 (one nesting), tri_filter_sxy()
+tri_filter_sign; tests/test_sweep_filters.py holds them to the f64 text and to the device (rtx_debug_sweep_filter).
 """
 from dataclasses import dataclass, replace
 from fractions import Fraction
@@ -42,10 +48,12 @@ class Margins:
     e_nv: float = 1.0
     e_dn: float = 1.0
     e_ab: float = 1.0
+    E: float = 1.0
+    A: float = 1.0
 
 
 SHIPPED = Margins()
-WEAKENED = {name: replace(SHIPPED, **{name: 0.0}) for name in ("widen", "abs_pad", "abs_pad2", "slack", "K", "G", "e_nv", "e_dn", "e_ab")}
+WEAKENED = {name: replace(SHIPPED, **{name: 0.0}) for name in ("widen", "abs_pad", "abs_pad2", "slack", "K", "G", "e_nv", "e_dn", "e_ab", "E", "A")}
 
 
 # ---- f32 operations, one rounding each --------------------------------------------------------------------------------------------------
@@ -291,7 +299,8 @@ def sphere_leaf(rec, sr, best_up):
 
 
 # ---- triangle bounds --------------------------------------------------------------------------------------------------------------------------
-def tri_params(pos, dirs, centre, tri_extent):
+def tri_params(pos, dirs, centre, tri_extent, m=SHIPPED):
+    """tri_filter_from_ray: d, np = -p, A = 64uS (times m.A), off: the pass-all filter (A = 1e30) of S >= 1e14 or a NaN origin"""
     pos, dirs = _d(pos), _d(dirs)
     with np.errstate(all="ignore"):
         p = pos - _d(centre)[None, :]
@@ -299,7 +308,7 @@ def tri_params(pos, dirs, centre, tri_extent):
         off = ~(S < 1.0e14)
         z = F32(0.0)
         return {"d": np.where(off[:, None], z, dirs.astype(F32)), "np": np.where(off[:, None], z, (-p).astype(F32)),
-                "A": np.where(off, F32(1.0e30), (S * (64.0 / 16777216.0)).astype(F32)), "off": off}
+                "A": np.where(off, F32(1.0e30), ((S * (64.0 / 16777216.0)) * m.A).astype(F32)), "off": off}
 
 
 def _dn_nv(A, f):
@@ -308,7 +317,8 @@ def _dn_nv(A, f):
     return dn, nv
 
 
-def tri_filter_pass(A, B, f):
+def tri_filter_sxy(A, B, f):
+    """tri_filter_sign's two values: the record is a candidate <=> neither has its sign bit set"""
     dn, nv = _dn_nv(A, f)
     adn, anv = np.abs(dn), np.abs(nv)
     ax, ay = sub32(-f["np"][:, 0], B[:, 0]), sub32(-f["np"][:, 1], B[:, 1])
@@ -316,6 +326,11 @@ def tri_filter_pass(A, B, f):
     ey = fma32(ay, adn, mul32(f["d"][:, 1], anv))
     sx = sub32(fma32(B[:, 2], adn, f["A"]), np.abs(ex))
     sy = sub32(fma32(B[:, 3], adn, f["A"]), np.abs(ey))
+    return sx, sy
+
+
+def tri_filter_pass(A, B, f):
+    sx, sy = tri_filter_sxy(A, B, f)
     return ~(np.signbit(sx) | np.signbit(sy))
 
 
@@ -533,6 +548,74 @@ def q_node(r4):
     return lo.astype(F32), sc.astype(F32), l[:, 0] | (h[:, 0] << 16), l[:, 1] | (h[:, 1] << 16)
 
 
+# ---- the LDS sweep's sphere filter (rtx_device.h filter_from_ray / filter_disc1, rtx_kernels.hip filter_disc2) ---------------------------
+def sweep_cmax(objs, centre, hidden=None):
+    """pack_scene's sphere_cmax against `centre`: max of |c - centre| + |r| in scene order, a NaN reach propagating (`!(reach <=
+    cmax)`); a hidden sphere's reach is 0 (hide_record)"""
+    geom = np.asarray(objs["geom"], dtype=np.float64)
+    cmax = 0.0
+    with np.errstate(all="ignore"):
+        for k in np.nonzero(np.asarray(objs["kind"]).astype(int) == 0)[0]:
+            c = geom[k, :3] - _d(centre)
+            reach = 0.0 if hidden is not None and hidden[k] else np.sqrt((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]) + abs(geom[k, 3])
+            if not reach <= cmax:
+                cmax = reach
+    return float(cmax)
+
+
+def sweep_record(objs, centre, hidden=None):
+    """The sphere_f32 record of every sphere in scene order, UN-interleaved: (ns4, 4) f32 rows {c - centre, f32(|c - centre|^2 - r^2)},
+    ns4 = the sphere count rounded up to a multiple of 4.  f64 in pack_scene's operation order (cc = (cx cx + cy cy) + cz cz, rr = r r,
+    each value rounded once to f32).  Rows behind the last sphere and the rows of hidden spheres (`hidden`: a bool per object) are the
+    sentinel (0, 0, 0, 1e30); a pack whose cmax is not below 1e14 holds (0, 0, 0, -1e30) in EVERY row.  The device holds rows 2k and
+    2k + 1 as the pair {x0, x1, y0, y1} {z0, z1, w0, w1}."""
+    kind = np.asarray(objs["kind"]).astype(int)
+    geom = np.asarray(objs["geom"], dtype=np.float64)
+    sph = np.nonzero(kind == 0)[0]
+    ns4 = (len(sph) + 3) & ~3
+    rec = np.zeros((ns4, 4), dtype=F32)
+    rec[:, 3] = F32(1.0e30)
+    if not sweep_cmax(objs, centre, hidden) < 1.0e14:
+        rec[:, 3] = F32(-1.0e30)
+        return rec
+    with np.errstate(all="ignore"):
+        c = geom[sph, :3] - _d(centre)[None, :]
+        cc = (c[:, 0] * c[:, 0] + c[:, 1] * c[:, 1]) + c[:, 2] * c[:, 2]
+        rows = np.concatenate([c, (cc - geom[sph, 3] * geom[sph, 3])[:, None]], axis=1).astype(F32)
+    keep = np.ones(len(sph), dtype=bool) if hidden is None else ~np.asarray(hidden, dtype=bool)[sph]
+    rec[:len(sph)][keep] = rows[keep]
+    return rec
+
+
+def sweep_params(pos, dirs, centre, cmax, m=SHIPPED):
+    """filter_from_ray: -> (words (n, 8) f32 = {d.xyz, -p.d, 2p.xyz, E - p.p}, pass_all (n,) bool, M (n,) f64).  All in f64 in the
+    function's order, one rounding to f32 each; E = 64uM^2 times m.E.  pass_all = !(M < 1e14) || !(M > 1e-12), M = cmax + |p| -- true
+    for a NaN origin and a NaN cmax too --: the words are then (0, ..., 0, 1e30)."""
+    pos, dirs = _d(pos), _d(dirs)
+    with np.errstate(all="ignore"):
+        p = pos - _d(centre)[None, :]
+        pp = (p[:, 0] * p[:, 0] + p[:, 1] * p[:, 1]) + p[:, 2] * p[:, 2]
+        pd = (p[:, 0] * dirs[:, 0] + p[:, 1] * dirs[:, 1]) + p[:, 2] * dirs[:, 2]
+        M = cmax + np.sqrt(pp)
+        off = ~(M < 1.0e14) | ~(M > 1.0e-12)
+        E = (M * M * (64.0 / 16777216.0)) * m.E
+        w = np.concatenate([dirs, (-pd)[:, None], 2.0 * p, (E - pp)[:, None]], axis=1).astype(F32)
+    w = np.where(off[:, None], F32(0.0), w)
+    w[:, 7] = np.where(off, F32(1.0e30), w[:, 7])
+    return w.astype(F32), off, M
+
+
+def sweep_disc(rec, f):
+    """D of one record per ray, rec (n, 4) f32 and f (n, 8) the FilterParams words, in the kernel's fma order:
+        b = fma(x, dx, fma(y, dy, fma(z, dz, npd)));  q = fma(x, p2x, fma(y, p2y, fma(z, p2z, nppE)));  D = fma(b, b, q - w).
+    filter_disc1 and filter_disc2 nest their fmas the SAME way (z innermost, then y, then x; q - w one rounded subtraction), so one
+    function stands for both; the device returns both values and the gpu part holds each to this one.  The record is a candidate <=>
+    D's sign bit is clear."""
+    b = fma32(rec[:, 0], f[:, 0], fma32(rec[:, 1], f[:, 1], fma32(rec[:, 2], f[:, 2], f[:, 3])))
+    q = fma32(rec[:, 0], f[:, 4], fma32(rec[:, 1], f[:, 5], fma32(rec[:, 2], f[:, 6], f[:, 7])))
+    return fma32(b, b, sub32(q, rec[:, 3]))
+
+
 # ---- one case through the model ------------------------------------------------------------------------------------------------------------
 def own_steps(pk, target, node_form, m=SHIPPED):
     """The tightest path the builder can give an object: ONE node visit whose child is the object's own padded box (a leaf of one
@@ -615,6 +698,7 @@ def _refit_spheres(pk, now, m):
         lo[sph] = rd32(((s - r[:, None]) - pad) - pk["abs_pad"] * m.abs_pad)
         hi[sph] = ru32(((s + r[:, None]) + pad) + pk["abs_pad"] * m.abs_pad)
     out.update(rec=rec, lo=lo, hi=hi, lo128=lo, hi128=hi, fw=fw, filt=filt, cmax=float(reach.max()) if sph.any() else 0.0, objs=now)
+    out["sweep"] = sweep_record(now, pk["centre"])          # the sweep's records of the updated list against the KEPT centre
     return out
 
 
@@ -626,7 +710,8 @@ def refit(base_objs, indices, new, m=SHIPPED):
     and -- because no triangle moves -- tri_extent and every triangle's record and box.  NEW, for every sphere of the updated list
     against the KEPT centre: rec[:, :3] = f32(c - centre), rec[:, 3] = |r| rounded up (the leaf record), fw = f32(|c - centre|^2 -
     r^2) (the filter record's fourth scalar; `filt` is the whole filter record {f32(c - centre), fw}), lo / hi = sphere_box() widened
-    by the base abs_pad and rounded outward, and scene-wide cmax = max(sqrt(cc) + |r|).
+    by the base abs_pad and rounded outward, and scene-wide cmax = max(sqrt(cc) + |r|).  `sweep`: sweep_record() of the updated list
+    against the kept centre, the LDS sweep's records with their padding (deform() yields it too, next to its tri_extent).
     A sphere the update does not name keeps the bits pack() gave it (the expressions are pack()'s).  numpy f64, one rounding per
     operation, sums left to right."""
     pk, now = _updated(base_objs, indices, new, m)
@@ -716,7 +801,7 @@ def leaf_bounds(kind, rec, o, d, centre, cmax, tri_extent, best_up, m=SHIPPED):
     """-> dict of (n,) arrays: cand (the end of the sqrt interval that hurts), tlo_hi / tlo_lo, certain_any / certain_all, thi_lo / thi_hi"""
     n = len(o)
     sph = sphere_leaf(rec[:, :4], sphere_ray(o, d, centre, cmax, m), best_up)
-    f = tri_params(o, d, centre, tri_extent)
+    f = tri_params(o, d, centre, tri_extent, m)
     ok = tri_filter_pass(rec[:, 0:4], rec[:, 4:8], f)
     tlo, thi, dbg = tri_bounds(rec[:, 0:4], rec[:, 8:12], rec[:, 12:16], f, m)
     off = f["off"]                                          # the pass-all filter: A = 1e30, S = inf -- every bound is then vacuous

@@ -162,7 +162,7 @@ def test_pack_is_the_parents_pack_and_an_empty_deform_is_pack():
         same = bm.deform(objs, np.zeros(0, dtype=np.uint64), objs[:0])
         a, b = _bits(pk), _bits(same)
         assert [k for k in a if a[k] != b[k]] == [], name
-        assert sorted(set(b) - set(a)) == ["filt", "fw"], name
+        assert sorted(set(b) - set(a)) == ["filt", "fw", "sweep"], name        # (sweep: the LDS sweep's records, tests/test_sweep_filters.py)
 
 
 def test_a_deform_keeps_what_the_rays_are_built_from():

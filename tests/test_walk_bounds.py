@@ -54,7 +54,9 @@ EXACT_OUTSIDE = {("spheres200", "surface")}
 #       knob is live (test_every_margin_knob_reaches_the_model: the quantised boxes change);
 #   K -- G enlarges sqrt(Delta) by at least G / 2r = 64uM, four times beta's 16uM that K was derived for; also on near ties
 #       (test_near_ties_in_the_model: pairs less than K apart, each under the other's t_hi, with K = 0).
-SHARP = ("slack", "G", "e_nv", "e_dn", "e_ab")
+#   A (the triangle filter's allowance 64uS, tri_filter_from_ray; tests/test_sweep_filters.py holds it on the sweep) is sharp: with
+#       A = 0 the filter drops reported triangles at edges and vertices before tri_bounds is asked.
+SHARP = ("slack", "G", "e_nv", "e_dn", "e_ab", "A")
 LOOSE = ("widen", "abs_pad", "abs_pad2", "K")
 
 
