@@ -254,6 +254,22 @@ public:
         return out;
     }
 
+    // The k nearest objects along each ray, sorted by (distance, object index) (rtx_multi_hits): hits[i * k + j] is entry j of ray i;
+    // the entries behind counts[i] (optional) are closest_hits' miss.  t_max as for any_hits; 1 <= k <= RTX_MULTI_HIT_MAX.
+    std::vector<RtxHit> multi_hits(const std::vector<RtxRay> &rays, std::uint32_t k, const std::vector<double> &t_max = {},
+                                   std::vector<std::uint32_t> *counts = nullptr) const
+    {
+        if (!t_max.empty() && t_max.size() != rays.size()) throw Panic(RTX_ERR_INVALID_ARGUMENT, "multi_hits: one limit per ray, or none");
+        std::vector<RtxHit> hits(rays.size() * k);
+        if (counts) counts->assign(rays.size(), 0u);
+        std::vector<RtxObject> packed = pack();
+        RtxScene sc = to_c(packed);
+        int32_t rc = rtx_multi_hits(&sc, rays.data(), t_max.empty() ? nullptr : t_max.data(), rays.size(), k, hits.data(),
+                                    counts ? counts->data() : nullptr);
+        if (rc != RTX_OK) throw Panic(rc, rtx_last_error());
+        return hits;
+    }
+
     // The denoising guide buffers of a width x height frame (rtx_pixel_features): per pixel [y][x] the first hits of render_pixel's own
     // lens-jittered rays, folded in sample order -- mean albedo / emission / normal, mean depth, coverage, sample 0's object.
     std::vector<RtxPixelFeatures> pixel_features(std::size_t width, std::size_t height) const
@@ -461,6 +477,19 @@ public:
                   RtxStats *stats = nullptr)
     {
         check(rtx_scene_any_hits(h_, d_rays, d_t_max, n, d_out, hip_stream, stats));
+    }
+    // the k nearest objects along each of n rays of DEVICE memory, sorted: d_hits[n * k] (ray i's list at i * k), d_counts[n] or
+    // nullptr, d_t_max[n] or nullptr (no limit)
+    void multi_hits(const RtxRay *d_rays, const double *d_t_max, std::size_t n, std::uint32_t k, RtxHit *d_hits,
+                    std::uint32_t *d_counts = nullptr, void *hip_stream = nullptr, RtxStats *stats = nullptr)
+    {
+        check(rtx_scene_multi_hits(h_, d_rays, d_t_max, n, k, d_hits, d_counts, hip_stream, stats));
+    }
+    // the same for the pick buffer's rays: d_hits[height][width][k], d_counts[height][width] or nullptr
+    void primary_multi_hits(std::size_t width, std::size_t height, std::uint32_t k, RtxHit *d_hits, std::uint32_t *d_counts = nullptr,
+                            void *hip_stream = nullptr, RtxStats *stats = nullptr)
+    {
+        check(rtx_scene_primary_multi_hits(h_, (uint32_t)width, (uint32_t)height, k, d_hits, d_counts, hip_stream, stats));
     }
     // render_ray from n rays of DEVICE memory: d_rgb[3 n] = each path's colour, d_ids (nullptr: (i, 0)) the (pixel, sample) pairs that
     // key the RNG, d_segments (or nullptr) the closest_object calls of each path

@@ -473,6 +473,44 @@ int32_t rtx_scene_any_hits(RtxSceneHandle scene, const RtxRay *d_rays, const dou
 /* One-shot host form (upload to device 0, query, copy back), as rtx_closest_hits.  rays / t_max (or NULL) / occluded: HOST arrays. */
 int32_t rtx_any_hits(const RtxScene *scene, const RtxRay *rays, const double *t_max, uint64_t n, uint8_t *occluded);
 
+/* Multi-hit queries: the k nearest surfaces along each ray -- select-through picking, x-ray and thickness views, transparency done by
+ * the caller, counting the surfaces between two points.  For ray i, with L_i = the objects of Scene.objects whose
+ * Object::distance(position, direction) = Some(t) has t.is_normal() && t.is_sign_positive() (closest_object's filter, scene.rs:249)
+ * and t < t_max[i] (strict), sorted by (t, index in Scene.objects):
+ *   d_hits[i * k + j], j < min(k, |L_i|) = the j-th element, filled in as RtxHit describes for closest hits (distance, object,
+ *       position = position + direction * distance, normal = normal_at(position) of that object);
+ *   d_hits[i * k + j], j >= min(k, |L_i|) = the "nothing" record of a closest-hit miss (NaN position and normal, +inf distance, -1);
+ *   d_counts[i] = min(k, |L_i|)                                                               (d_counts may be NULL)
+ * -- entry j is what closest_object returns once the winners of entries 0 .. j-1 have been retain()ed out of Scene.objects: the
+ * stable order of min_by + total_cmp, applied k times.  Every distance is the reference's f64 test, bit for bit.
+ *  - 1 <= k <= RTX_MULTI_HIT_MAX, else RTX_ERR_INVALID_ARGUMENT; n < 2^32; i * k + j is 64-bit arithmetic.
+ *  - One entry per object: a sphere gives its entry root only, and nothing when the ray starts inside it (sphere.rs:29).
+ *  - Equal distances come in index order.  Hidden objects (rtx_scene_set_visible) are absent, as from every product of the handle.
+ *  - t_max is compared as given, as for rtx_scene_any_hits: d_t_max == NULL means +inf for every ray; NaN, zero or a negative limit
+ *    gives count 0 and k nothing records, and nothing is tested.  The list for a limit is the prefix of the unlimited list below it.
+ *  - Directions are used as given; no epsilon, no t_min: the |t| ~ 1e-16 self-hits are found like any other hit.
+ *  - With k = 1 and d_t_max == NULL the record is rtx_scene_closest_hits' record, byte for byte; count > 0 is rtx_scene_any_hits'
+ *    answer for the same limit.  A scene without objects writes the nothing records.
+ * d_rays: n RtxRay; d_t_max: n doubles or NULL; d_hits: n * k RtxHit; d_counts: n uint32_t or NULL.  DEVICE arrays, pairwise
+ * non-overlapping.  While a ray is walked its k records hold the lane's sorted list (DESIGN.md "Multi-hit queries"): their content is
+ * undefined until the call's work on the stream has finished.  Streams, stats == NULL asynchrony, RtxConfig.tuning bits of
+ * RTX_TUNE_LAB_MASK, RTX_KERNEL_EXACT (every shape of every ray in f64), the exhaustive sweep for rays the f32 bounds were not
+ * derived for: as rtx_scene_closest_hits.  stats: segments = n, exact_tests, filter_tests, box_tests, trace_ms, trace_launches = 1,
+ * kernel = RTX_KERNEL_BVH | RTX_KERNEL_EXACT. */
+#define RTX_MULTI_HIT_MAX 32
+int32_t rtx_scene_multi_hits(RtxSceneHandle scene, const RtxRay *d_rays, const double *d_t_max, uint64_t n, uint32_t k,
+                             RtxHit *d_hits, uint32_t *d_counts, void *stream, RtxStats *stats);
+
+/* The same for the pick buffer's rays: rtx_scene_primary_hits' zero-offset primary ray of every pixel, no limit.  d_hits: DEVICE array
+ * [y][x][j] of width * height * k records; d_counts: [y][x] or NULL; width * height < 2^32; stats: segments = width * height. */
+int32_t rtx_scene_primary_multi_hits(RtxSceneHandle scene, uint32_t width, uint32_t height, uint32_t k,
+                                     RtxHit *d_hits, uint32_t *d_counts, void *stream, RtxStats *stats);
+
+/* One-shot host form (upload to device 0, query, copy back), as rtx_closest_hits.  rays / t_max (or NULL) / hits / counts (or NULL):
+ * HOST arrays. */
+int32_t rtx_multi_hits(const RtxScene *scene, const RtxRay *rays, const double *t_max, uint64_t n, uint32_t k,
+                       RtxHit *hits, uint32_t *counts);
+
 /* Path-radiance queries: render_ray (scene.rs:223-242), the bounce loop that turns a ray into a colour, for the caller's rays -- the
  * path tracer without the reference's camera (panoramas, stereo pairs, light probes at pick() / query() points, debug rays).
  * For entry i, with the handle's RtxConfig supplying max_bounces and seed (rays_per_pixel, focal_* and the camera are not read):

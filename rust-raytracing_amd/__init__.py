@@ -421,6 +421,22 @@ class Scene:
                                    occ.ctypes.data), lib)
         return occ.astype(bool)
 
+    def multi_hits(self, origins, directions, k, t_max=None):
+        """The k nearest objects along each ray, in (distance, object index) order (rtx_multi_hits: upload to device 0, query, copy
+        back).  t_max as for any_hits.  Returns numpy (distance (n, k), object (n, k) int64, position (n, k, 3), normal (n, k, 3),
+        count (n,) uint32); the entries behind a ray's count are closest_hits' miss: +inf, -1 and NaNs."""
+        rays = make_rays(origins, directions)
+        n, k = len(rays), int(k)
+        lim = _limits(t_max, n)
+        hits = np.zeros((n, max(k, 0)), dtype=HIT_DTYPE)
+        counts = np.zeros(n, dtype=np.uint32)
+        packed = self.packed()
+        sc = _scene_c(self.config, self.camera, packed)
+        lib = load_library(self.config.wants_lab())
+        abi.check(lib.rtx_multi_hits(C.byref(sc), rays.ctypes.data, lim.ctypes.data if lim is not None else None, n, k, hits.ctypes.data,
+                                     counts.ctypes.data), lib)
+        return _split_hits(hits) + (counts,)
+
     def trace_paths(self, origins, directions, ids=None):
         """render_ray (scene.rs:223-242) from each ray, with the config's max_bounces and seed (rtx_trace_paths: upload to device 0,
         trace, copy back).  ids: None (entry i draws as (pixel i, sample 0)) or (n, 2) (pixel index, sample index) pairs.  Returns
@@ -708,6 +724,59 @@ class SceneHandle:
         torch.cuda.synchronize(dev)
         self.any_hits(d_rays.data_ptr(), d_lim.data_ptr() if d_lim is not None else None, n, d_out.data_ptr(), want_stats=True)
         return d_out[:n].cpu().numpy().astype(bool)
+
+    def multi_hits(self, d_rays_ptr, d_t_max_ptr, n, k, d_hits_ptr, d_counts_ptr=None, stream=None, want_stats=True):
+        """The k nearest objects along each of n rays, sorted by (distance, object index): d_rays_ptr / d_t_max_ptr / d_hits_ptr /
+        d_counts_ptr are device addresses of n RtxRay (48 B), n doubles (or None: +inf for every ray), n * k RtxHit (64 B; ray i's list
+        at records i * k ..) and n uint32 (or None).  want_stats=False: asynchronous on `stream`."""
+        stats = abi.RtxStats()
+        self._check(self._lib.rtx_scene_multi_hits(self._h, C.c_void_p(int(d_rays_ptr)) if d_rays_ptr else None,
+                                                   C.c_void_p(int(d_t_max_ptr)) if d_t_max_ptr else None, int(n), int(k),
+                                                   C.c_void_p(int(d_hits_ptr)) if d_hits_ptr else None,
+                                                   C.c_void_p(int(d_counts_ptr)) if d_counts_ptr else None,
+                                                   C.c_void_p(int(stream)) if stream else None, C.byref(stats) if want_stats else None))
+        return stats if want_stats else None
+
+    def primary_multi_hits(self, width, height, k, d_hits_ptr, d_counts_ptr=None, stream=None, want_stats=True):
+        """multi_hits for the pick buffer's rays: width * height * k RtxHit records [y][x][j] at d_hits_ptr, width * height uint32
+        [y][x] at d_counts_ptr (or None)."""
+        stats = abi.RtxStats()
+        self._check(self._lib.rtx_scene_primary_multi_hits(self._h, int(width), int(height), int(k),
+                                                           C.c_void_p(int(d_hits_ptr)) if d_hits_ptr else None,
+                                                           C.c_void_p(int(d_counts_ptr)) if d_counts_ptr else None,
+                                                           C.c_void_p(int(stream)) if stream else None, C.byref(stats) if want_stats else None))
+        return stats if want_stats else None
+
+    def query_all(self, origins, directions, k, t_max=None):
+        """Host convenience of multi_hits (device buffers through torch): numpy (distance (n, k), object (n, k), position (n, k, 3),
+        normal (n, k, 3), count (n,)) -- the k nearest objects along each ray before t_max (None: no limit; a scalar or n limits)."""
+        import torch
+        rays = make_rays(origins, directions)
+        n, k = len(rays), int(k)
+        lim = _limits(t_max, n)
+        dev = torch.device("cuda", self.device)
+        d_rays = torch.from_numpy(rays.view(np.uint8)).to(dev)
+        d_lim = torch.from_numpy(lim).to(dev) if lim is not None and n else None
+        d_hits = torch.empty(max(n * k, 1) * HIT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_counts = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.multi_hits(d_rays.data_ptr(), d_lim.data_ptr() if d_lim is not None else None, n, k, d_hits.data_ptr(), d_counts.data_ptr(),
+                        want_stats=True)                                                       # (synchronises)
+        hits = d_hits[:n * k * HIT_DTYPE.itemsize].cpu().numpy().view(HIT_DTYPE).reshape(n, k)
+        return _split_hits(hits) + (d_counts[:n].cpu().numpy().view(np.uint32),)
+
+    def pick_through(self, width, height, k):
+        """Host convenience of primary_multi_hits: numpy (distance, object, position, normal), each indexed [y][x][j], and count [y][x]."""
+        import torch
+        width, height, k = int(width), int(height), int(k)
+        n = width * height
+        dev = torch.device("cuda", self.device)
+        d_hits = torch.empty(max(n * k, 1) * HIT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_counts = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.primary_multi_hits(width, height, k, d_hits.data_ptr(), d_counts.data_ptr(), want_stats=True)
+        hits = d_hits[:n * k * HIT_DTYPE.itemsize].cpu().numpy().view(HIT_DTYPE).reshape(height, width, k)
+        return _split_hits(hits) + (d_counts[:n].cpu().numpy().view(np.uint32).reshape(height, width),)
 
     def trace_paths(self, d_rays_ptr, d_ids_ptr, n, d_rgb_ptr, d_segments_ptr=None, stream=None, want_stats=True):
         """render_ray from n rays: d_rays_ptr / d_ids_ptr / d_rgb_ptr / d_segments_ptr are device addresses of n RtxRay (48 B), n

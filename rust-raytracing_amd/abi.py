@@ -33,6 +33,7 @@ RTX_TUNE_KNOWN_MASK = (RTX_TUNE_LAB_MASK | RTX_TUNE_NO_TILES | RTX_TUNE_ONE_STAG
                        (15 << RTX_TUNE_TRI_LEAF_SHIFT) | (127 << RTX_TUNE_THRESH_SHIFT) | RTX_TUNE_NO_CUT | RTX_TUNE_HALVES | RTX_TUNE_NO_HALVES | RTX_TUNE_NO_TILE_LISTS)
 RTX_UPDATE_AUTO, RTX_UPDATE_REBUILD, RTX_UPDATE_DEFORM = 0, 1, 2
 RTX_UPDATED_NOTHING, RTX_UPDATED_RECORDS, RTX_UPDATED_REFIT, RTX_UPDATED_REBUILT = 0, 1, 2, 3
+RTX_MULTI_HIT_MAX = 32                       # rtx_scene_multi_hits: 1 <= k <= this
 RTX_OK, RTX_ERR_INVALID_ARGUMENT, RTX_ERR_NO_DEVICE, RTX_ERR_HIP, RTX_ERR_UNSUPPORTED, RTX_ERR_OUT_OF_MEMORY = range(6)
 
 # RtxObject, 136 bytes: one entry of Scene.objects (scene.rs:80; object.rs:9-15,78-86)
@@ -122,6 +123,11 @@ SYMBOLS = [
     ("rtx_closest_hits", C.c_int32, [C.POINTER(RtxScene), C.c_void_p, C.c_uint64, C.c_void_p]),
     ("rtx_scene_any_hits", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(RtxStats)]),
     ("rtx_any_hits", C.c_int32, [C.POINTER(RtxScene), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    ("rtx_scene_multi_hits", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.POINTER(RtxStats)]),
+    ("rtx_scene_primary_multi_hits", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.POINTER(RtxStats)]),
+    ("rtx_multi_hits", C.c_int32, [C.POINTER(RtxScene), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("rtx_scene_trace_paths", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtxStats)]),
     ("rtx_trace_paths", C.c_int32, [C.POINTER(RtxScene), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("rtx_scene_trace_samples", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -1012,6 +1012,9 @@ struct QueryRequest {
     double threshold = 0.0, floor = 0.0;
     uint32_t sample_begin = 0, n_more = 0, max_samples = 0, rounds = 0;
     uint64_t *result = nullptr;                                  //   HOST: the three counts (or null)
+    // kQueryMulti (rtx_scene_multi_hits, rtx_scene_primary_multi_hits): n * k records in `hits`, the limits in `t_max` (null: +inf), n
+    // list lengths (or null); rays == null with a frame: the pick form's rays
+    uint32_t k = 0; uint32_t *counts = nullptr;
 };
 
 }  // namespace
@@ -1088,6 +1091,10 @@ static int32_t query_run(RtxSceneHandle_ *h, const QueryRequest &req, void *stre
     else if (req.mode == kQueryFeatures) qa.features = reinterpret_cast<QueryFeatures *>(req.features);
     else if (refine) {
         qa.sum = req.sum; qa.sum_sq = req.sum_sq; qa.extra = req.extra;
+    }
+    else if (req.mode == kQueryMulti) {
+        qa.mode = kQueryMulti | (req.k << kQueryMultiShift);
+        qa.hits = reinterpret_cast<QueryHit *>(req.hits); qa.t_max = req.t_max; qa.counts = req.counts;
     }
     else qa.hits = reinterpret_cast<QueryHit *>(req.hits);
     if (stats) RTX_HIP_CHECK(hipEventRecord(h->ev[0], stream));
@@ -1403,6 +1410,41 @@ int32_t rtx_scene_primary_hits(RtxSceneHandle h, uint32_t width, uint32_t height
     return query_run(h, req, stream, stats);
 }
 
+int32_t rtx_scene_multi_hits(RtxSceneHandle h, const RtxRay *d_rays, const double *d_t_max, uint64_t n, uint32_t k, RtxHit *d_hits,
+                             uint32_t *d_counts, void *stream, RtxStats *stats)
+{
+    if (!h) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_multi_hits: null scene");
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (k == 0 || k > RTX_MULTI_HIT_MAX) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_multi_hits: k must be 1 .. RTX_MULTI_HIT_MAX");
+    if (n == 0) return RTX_OK;
+    if (!d_rays || !d_hits) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_multi_hits: null rays or hits");
+    if (n >= 0xFFFFFFFFull) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_multi_hits: n must be below 2^32");
+    const Range r[4] = { { d_rays, n * sizeof(RtxRay) }, { d_hits, n * k * sizeof(RtxHit) }, { d_t_max, n * sizeof(double) },
+                         { d_counts, n * sizeof(uint32_t) } };
+    if (ranges_overlap(r, 4)) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_multi_hits: rays, limits, hits and counts overlap");
+    QueryRequest req;
+    req.mode = kQueryMulti; req.n = n; req.k = k; req.rays = d_rays; req.hits = d_hits; req.t_max = d_t_max; req.counts = d_counts;
+    return query_run(h, req, stream, stats);
+}
+
+int32_t rtx_scene_primary_multi_hits(RtxSceneHandle h, uint32_t width, uint32_t height, uint32_t k, RtxHit *d_hits, uint32_t *d_counts,
+                                     void *stream, RtxStats *stats)
+{
+    if (!h) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_primary_multi_hits: null scene");
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (k == 0 || k > RTX_MULTI_HIT_MAX) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_primary_multi_hits: k must be 1 .. RTX_MULTI_HIT_MAX");
+    const uint64_t n = (uint64_t)width * height;
+    if (n == 0) return RTX_OK;
+    if (!d_hits) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_primary_multi_hits: null hits");
+    if (n >= 0xFFFFFFFFull) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_primary_multi_hits: more than 2^32 pixels");
+    const Range r[2] = { { d_hits, n * k * sizeof(RtxHit) }, { d_counts, n * sizeof(uint32_t) } };
+    if (ranges_overlap(r, 2)) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_primary_multi_hits: hits and counts overlap");
+    QueryRequest req;
+    req.mode = kQueryMulti; req.width = width; req.height = height; req.n_rows = height; req.n = n; req.k = k; req.hits = d_hits;
+    req.counts = d_counts;
+    return query_run(h, req, stream, stats);
+}
+
 // The feature buffers of a band (rtx_render_blocks' partition): validation that touches no device, then one query_run.
 static int32_t pixel_features_band(RtxSceneHandle h, const char *who, uint32_t width, uint32_t height, uint32_t block_rows, uint32_t part,
                                    uint32_t n_parts, RtxPixelFeatures *d_features, void *stream, RtxStats *stats)
@@ -1524,6 +1566,21 @@ int32_t rtx_any_hits(const RtxScene *scene, const RtxRay *rays, const double *t_
     const HostArray arrays[] = { { rays, nullptr, n * sizeof(RtxRay), (void **)&req.rays }, { nullptr, occluded, n, (void **)&req.occluded },
                                  { t_max, nullptr, n * sizeof(double), (void **)&req.t_max } };
     return query_once(scene, "rtx_any_hits", req, arrays, 3);
+}
+
+int32_t rtx_multi_hits(const RtxScene *scene, const RtxRay *rays, const double *t_max, uint64_t n, uint32_t k, RtxHit *hits, uint32_t *counts)
+{
+    if (int32_t rc = check_scene_args(scene, "rtx_multi_hits")) return rc;
+    if (k == 0 || k > RTX_MULTI_HIT_MAX) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_multi_hits: k must be 1 .. RTX_MULTI_HIT_MAX");
+    if (n == 0) return RTX_OK;
+    if (!rays || !hits) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_multi_hits: null rays or hits");
+    if (n >= 0xFFFFFFFFull) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_multi_hits: n must be below 2^32");
+    QueryRequest req;
+    req.mode = kQueryMulti; req.n = n; req.k = k;
+    const HostArray arrays[] = { { rays, nullptr, n * sizeof(RtxRay), (void **)&req.rays }, { nullptr, hits, n * k * sizeof(RtxHit), (void **)&req.hits },
+                                 { t_max, nullptr, n * sizeof(double), (void **)&req.t_max },
+                                 { nullptr, counts, n * sizeof(uint32_t), (void **)&req.counts } };
+    return query_once(scene, "rtx_multi_hits", req, arrays, 4);
 }
 
 int32_t rtx_trace_paths(const RtxScene *scene, const RtxRay *rays, const uint64_t *ids, uint64_t n, double *rgb, uint32_t *segments)

@@ -130,7 +130,8 @@ struct QueryArgs {
                                    // band's RowsView (row_begin, row_stride, row_block as render_band sets them), entry i = local pixel i; the
                                    // path mode's sample form (rays == null): the frame's RowsView, as the pick form's; else null
     union {                        // the answers, by mode (the modes share the slots: one kernel argument layout for the three loops)
-        QueryHit *hits;            // closest hits: n records
+        QueryHit *hits;            // closest hits: n records; multi-hit: n * k records, ray i's list at hits[i * k ..] (the lane that owns
+                                   // the ray keeps its list there while it walks)
         uint8_t *occluded;         // any-hit: n bytes, 1 / 0
         double *rgb;               // paths: 3 n doubles, rgb[3 i .. 3 i + 2] = resulting_color of the path that starts with ray i
         double *sum;               // refine: the band's running sums, 3 n doubles (rtx_render_blocks_accumulate's d_sum)
@@ -141,9 +142,10 @@ struct QueryArgs {
     uint32_t mode;                 // kQueryClosest; kQueryAnyHit: occluded[i] = some object's distance is normal, positive and < t_max[i];
                                    // kQueryPaths: render_ray (scene.rs:223-242) from ray i; kQueryFeatures: the first hits of
                                    // sv.rays_per_pixel gen_primary rays per pixel, folded (query_feature_loop); kQueryRefine:
-                                   // entry i = local pixel i of the band, sampled while the rule selects it (query_refine_loop)
+                                   // entry i = local pixel i of the band, sampled while the rule selects it (query_refine_loop);
+                                   // kQueryMulti | k << kQueryMultiShift: the k nearest objects of ray i, sorted (query_multi_loop)
     union {
-        const double *t_max;       // any-hit: n limits, compared as given (null: +inf for every ray)
+        const double *t_max;       // any-hit, multi-hit: n limits, compared as given (null: +inf for every ray)
         const unsigned long long *ids;   // paths: n (pixel index, sample index) pairs that key the RNG (null: (i, 0)); the sample form
                                          // (rays == null; never null): the pair also names the ray -- gen_primary's of that pixel and sample
         double *sum_sq;            // refine: the running sums of the samples' squares, 3 n doubles
@@ -151,6 +153,7 @@ struct QueryArgs {
     union {
         uint32_t *segments;        // paths: n closest_object counts, or null
         uint32_t *extra;           // refine: n counts, the samples pixel i has had beyond sample_begin
+        uint32_t *counts;          // multi-hit: n list lengths, or null
     };
 };
 // The refine mode's rule (rtx_render_blocks_refine), read from device memory -- the four words behind the launch's counts, so that the
@@ -162,7 +165,8 @@ struct QueryRefineRule {
 };
 static_assert(sizeof(QueryRefineRule) == 32, "QueryRefineRule");
 constexpr int kQueryRefineCounts = 1, kQueryRefineRule = 4, kQueryRefineWords = 8;   // u64 words of `head` in the refine mode
-constexpr uint32_t kQueryClosest = 0u, kQueryAnyHit = 1u, kQueryPaths = 2u, kQueryFeatures = 3u, kQueryRefine = 4u;
+constexpr uint32_t kQueryClosest = 0u, kQueryAnyHit = 1u, kQueryPaths = 2u, kQueryFeatures = 3u, kQueryRefine = 4u, kQueryMulti = 5u;
+constexpr uint32_t kQueryModeMask = 0xFFu, kQueryMultiShift = 8;     // the multi-hit mode carries its k (1 .. RTX_MULTI_HIT_MAX) above the mode
 uint32_t query_tree_kind(const SceneView &sv);        // 0 no walk, 1 sphere tree, 2 a tree that holds triangles
 uint32_t query_spill_entries(const SceneView &sv);    // HBM stack entries per lane a walk may need beyond its LDS rows
 size_t query_spill_bytes(uint32_t entries, int n_cus);

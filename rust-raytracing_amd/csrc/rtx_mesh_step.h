@@ -149,7 +149,9 @@ __device__ __forceinline__ void mesh_load_node(const float4 *__restrict__ nodes,
 // Returns false when the lane has to wait for the exact tests of what its queue holds (the queue cannot take the next
 // leaf's records): `resume` then holds the leaf children still to be read and `resume_node` the node they belong to; the
 // caller flushes, reloads nd for resume_node and calls again -- that call reads only those children and moves on to `node`.
-template <bool SPILL, int PLAIN, int STACK, class RAY>
+// TIGHTEN = false (the multi-hit query walk): a certain hit does not lower best_up -- the caller's bound is the k-th distance of
+// its list; the boxes, the candidate rule, the queue and its compaction read the caller's bound as they stand.
+template <bool SPILL, int PLAIN, int STACK, bool TIGHTEN = true, class RAY>
 __device__ __forceinline__ bool mesh_step(const float4 *__restrict__ nodes, const MeshArrays &ma, const RAY &q, const SphereRay &sr,
                                           const TriFilterParams &tpar, float4 (&nd)[MeshNode<PLAIN>::n], uint32_t &node, uint32_t &sp, uint32_t &qcnt,
                                           bool &overflow, float &best_up, uint32_t &resume, uint32_t &resume_node, uint32_t *lds_stack,
@@ -263,7 +265,7 @@ __device__ __forceinline__ bool mesh_step(const float4 *__restrict__ nodes, cons
                     float thi;
                     const float tlo = tri_bounds(j == 0u ? A0 : A1, g0, g1, tpar, thi);
                     if (tlo <= best_up && tlo < __builtin_inff()) {                 // (+inf: certainly no hit -- also while best_up is still +inf)
-                        best_up = fminf(best_up, thi);
+                        if constexpr (TIGHTEN) best_up = fminf(best_up, thi);
                         if (qcnt < (uint32_t)kMeshQueue) {
                             lds_q[(size_t)qcnt * kBvhThreads + tid] = (first + k + j) | kQueueTri;
                             lds_q[(size_t)(kMeshQueue + qcnt) * kBvhThreads + tid] = __float_as_uint(tlo);
@@ -287,7 +289,7 @@ __device__ __forceinline__ bool mesh_step(const float4 *__restrict__ nodes, cons
                     const float Dm = Dl - G;
                     const float thi = Dm > 0.0f ? b - __builtin_amdgcn_sqrtf(Dm) * (1.0f - 4.76837158e-7f) + sr.K : __builtin_inff();
                     if (tlo <= best_up && !(thi < 0.0f)) {
-                        if (tlo > sr.K) best_up = fminf(best_up, thi);
+                        if constexpr (TIGHTEN) { if (tlo > sr.K) best_up = fminf(best_up, thi); }
                         if (qcnt < (uint32_t)kMeshQueue) {
                             lds_q[(size_t)qcnt * kBvhThreads + tid] = ma.sphere_prims[first + k];
                             lds_q[(size_t)(kMeshQueue + qcnt) * kBvhThreads + tid] = __float_as_uint(tlo);

@@ -42,6 +42,10 @@
 // launch-uniform loop of the same two instances.  A lane owns a PIXEL of the band: for every sample it builds render_pixel's own
 // lens-jittered ray (gen_primary), asks query_closest_ray, and adds the winner's colours, normal and distance to the sums, which live in
 // the pixel's output record, not in registers.
+//
+// The multi-hit mode (QueryArgs.mode, rtx_scene_multi_hits / rtx_scene_primary_multi_hits; DESIGN.md "Multi-hit queries"): the k nearest
+// objects along each ray, sorted -- the sixth launch-uniform loop of the same two instances.  The lane's sorted list lives in the
+// ray's own k output records; the walks prune against the list's k-th distance and their leaf code never lowers that bound itself.
 #include "rtx_launch.h"
 #include "rtx_mesh_step.h"
 #include "rtx_wavefront.h"
@@ -659,6 +663,269 @@ __device__ __forceinline__ void query_refine_loop(const SceneView &sv, const Que
     }
 }
 
+// ---- the multi-hit mode --------------------------------------------------------------------------------------------------------
+// The k nearest objects of ray i in (distance, scene index) order (rtx_scene_multi_hits; DESIGN.md "Multi-hit queries"): what
+// closest_object returns when it is asked k times with the earlier winners retained out of Scene.objects -- every object whose
+// distance passes closest_object's filter and lies before t_max[i], sorted.  The lane's list lives in the ray's own k output records
+// (the lane owns them; 16 doubles per entry are more than the kernel's registers hold): while the ray is walked an entry is
+// {word 0: kind << 32 | local, word 6: distance, word 7: scene index} of the record's eight 64-bit words, kept sorted by insertion;
+// position and normal are written over them at the ray's end.  Every access goes through the same unsigned long long view.
+//
+// The bound.  The walks prune against best_up; here it is max(round_up32(t_max), FLT_MIN) -- the any-hit mode's seed -- while the
+// list holds fewer than k entries and min(that, round_up32(list[k-1].distance)) once it is full.  An object that belongs to the final
+// list has (t, id) <= the k-th entry of every intermediate list (entries only ever move down), so t <= list[k-1].distance <= the
+// bound, its boxes and its own t_lo are lower bounds of t, and `t_lo <= bound` keeps it -- also at a tie with the k-th distance.
+// Only exact hits already in the list lower the bound: the leaf code runs in its TIGHTEN = false form.
+__device__ __forceinline__ double multi_distance(const unsigned long long *rec, uint32_t j) { return __longlong_as_double((long long)rec[8u * j + 6u]); }
+
+__device__ __forceinline__ float multi_bound(const unsigned long long *rec, uint32_t k, uint32_t cnt, float bound0)
+{
+    return cnt == k ? fminf(bound0, round_up32(multi_distance(rec, k - 1u))) : bound0;
+}
+
+// closest_object's filter and the limit, then the sorted insert; a full list drops its last entry.  Returns whether the list changed.
+__device__ __forceinline__ bool multi_insert(unsigned long long *rec, uint32_t k, uint32_t &cnt, double t_max, double t, uint32_t id, uint32_t kind,
+                                             uint32_t local)
+{
+    if (!query_before(t, t_max)) return false;
+    uint32_t j = cnt;
+    if (cnt == k) {
+        j = k - 1u;
+        const double tl = multi_distance(rec, j);
+        if (!(t < tl || (t == tl && id < (uint32_t)rec[8u * j + 7u]))) return false;
+    } else cnt += 1u;
+#pragma unroll 1
+    while (j != 0u) {
+        const unsigned long long dp = rec[8u * (j - 1u) + 6u], ip = rec[8u * (j - 1u) + 7u];
+        const double tp = __longlong_as_double((long long)dp);
+        if (!(t < tp || (t == tp && id < (uint32_t)ip))) break;
+        rec[8u * j] = rec[8u * (j - 1u)];
+        rec[8u * j + 6u] = dp;
+        rec[8u * j + 7u] = ip;
+        j -= 1u;
+    }
+    rec[8u * j] = ((unsigned long long)kind << 32) | local;
+    rec[8u * j + 6u] = (unsigned long long)__double_as_longlong(t);
+    rec[8u * j + 7u] = id;
+    return true;
+}
+
+// query_sweep into the list
+__device__ __forceinline__ void multi_sweep(const SceneView &sv, const LeafArrays &la, const RayX &rx, bool spheres, bool tris,
+                                            unsigned long long *rec, uint32_t k, uint32_t &cnt, double t_max, unsigned long long &exact)
+{
+    double t;
+    if (spheres) {
+        for (uint32_t s = 0; s < sv.n_spheres; ++s)
+            if (sphere_distance(la.spheres[s], rx, &t)) (void)multi_insert(rec, k, cnt, t_max, t, la.sphere_ids[s], 0, s);
+        exact += sv.n_spheres;
+    }
+    for (uint32_t s = 0; s < sv.n_planes; ++s)
+        if (plane_distance(sv.planes[s], rx, &t)) (void)multi_insert(rec, k, cnt, t_max, t, sv.planes[s].id, 1, s);
+    exact += sv.n_planes;
+    if (tris) {
+        for (uint32_t s = 0; s < sv.n_tris; ++s)
+            if (triangle_distance(la.tris[s], rx, &t)) (void)multi_insert(rec, k, cnt, t_max, t, la.tris[s].id, 2, s);
+        exact += sv.n_tris;
+    }
+}
+
+// query_flush into the list; the bound follows the list from one candidate to the next
+__device__ __forceinline__ void multi_flush(const LeafArrays &la, const RayX &rx, const uint32_t *lq, uint32_t tid, uint32_t queue, uint32_t qcnt,
+                                            float bound0, float &bound, unsigned long long *rec, uint32_t k, uint32_t &cnt, double t_max,
+                                            unsigned long long &exact)
+{
+#pragma unroll 1
+    for (uint32_t e = 0; e < qcnt; ++e) {
+        if (__uint_as_float(lq[(size_t)(queue + e) * kBvhThreads + tid]) <= bound) {
+            const uint32_t idx = lq[(size_t)e * kBvhThreads + tid];
+            double t;
+            bool in = false;
+            if (idx & kQueueTri) {
+                const uint32_t tk = la.tri_fidx[idx & ~kQueueTri];
+                if (triangle_distance(la.tris[tk], rx, &t)) in = multi_insert(rec, k, cnt, t_max, t, la.tris[tk].id, 2, tk);
+            } else {
+                if (sphere_distance(la.spheres[idx], rx, &t)) in = multi_insert(rec, k, cnt, t_max, t, la.sphere_ids[idx], 0, idx);
+            }
+            if (in) bound = multi_bound(rec, k, cnt, bound0);
+            exact += 1;
+        }
+    }
+}
+
+// query_mesh_walk's loop with the list's bound: the step never lowers it (TIGHTEN = false), a flush does
+template <int PLAIN, class RAY>
+__device__ __forceinline__ void query_mesh_walk_multi(const float4 *__restrict__ nodes, const LeafArrays &la, const MeshArrays &ma, const RAY &q,
+                                                      const SphereRay &sr, const TriFilterParams &tpar, const RayX &rx, uint32_t root, float bound0,
+                                                      unsigned long long *rec, uint32_t k, uint32_t &cnt, double t_max, bool &overflow, uint32_t *ls,
+                                                      uint32_t *lq, uint32_t tid, uint32_t *__restrict__ spill, uint32_t spill_entries,
+                                                      size_t spill_stride, size_t glane, unsigned long long &exact, uint32_t &nbox, uint32_t &nleaf)
+{
+    float bound = multi_bound(rec, k, cnt, bound0);
+    uint32_t node = root, sp = 0, qcnt = 0, resume = 0, resume_node = 0;
+    float4 nd[MeshNode<PLAIN>::n];
+    if constexpr (kMeshPipe) mesh_load_node<PLAIN>(nodes, node, nd);
+    while (node != kNone || resume != 0u) {
+        if (mesh_step<true, PLAIN, kQueryMeshStack, false>(nodes, ma, q, sr, tpar, nd, node, sp, qcnt, overflow, bound, resume, resume_node, ls,
+                                                            lq, tid, spill, spill_entries, spill_stride, glane, nbox, nleaf))
+            continue;
+        multi_flush(la, rx, lq, tid, kMeshQueue, qcnt, bound0, bound, rec, k, cnt, t_max, exact);
+        qcnt = 0;
+        if constexpr (kMeshPipe) mesh_load_node<PLAIN>(nodes, resume_node, nd);
+    }
+    multi_flush(la, rx, lq, tid, kMeshQueue, qcnt, bound0, bound, rec, k, cnt, t_max, exact);
+}
+
+// One ray of the multi-hit mode, t_max > 0 (the caller's gate): the list of its objects before t_max, the first k of them.
+template <bool TRIS>
+__device__ __forceinline__ void query_multi_ray(const SceneView &sv, const float4 *__restrict__ nodes, const LeafArrays &la, const MeshArrays &ma,
+                                                V3 pos, V3 dir, const RayX &rx, bool walk, bool in32, double t_max, unsigned long long *rec,
+                                                uint32_t k, uint32_t &cnt, uint32_t *ls, uint32_t *lq, uint32_t tid, uint32_t *__restrict__ spill,
+                                                uint32_t spill_entries, size_t spill_stride, size_t glane, unsigned long long &exact,
+                                                unsigned long long &box_tests, unsigned long long &leaf_filters)
+{
+    cnt = 0;
+    if (!walk) { multi_sweep(sv, la, rx, true, true, rec, k, cnt, t_max, exact); return; }
+    // the shapes the tree does not answer for, BEFORE the walk (as the any-hit mode): every plane, the spheres and the triangle records
+    // outside it -- whatever they put into the list bounds the walk from its first box on
+    multi_sweep(sv, la, rx, (sv.bvh_flags & 1u) == 0u, false, rec, k, cnt, t_max, exact);
+    const uint32_t from = (sv.bvh_flags & 2u) ? sv.n_tri_tree : 0u;
+    for (uint32_t s = from; s < sv.n_tri_filter; ++s) {
+        const uint32_t tk = la.tri_fidx[s];
+        double t;
+        if (triangle_distance(la.tris[tk], rx, &t)) (void)multi_insert(rec, k, cnt, t_max, t, la.tris[tk].id, 2, tk);
+    }
+    exact += sv.n_tri_filter - from;
+    const float bound0 = fmaxf(round_up32(t_max), 1.17549435e-38f);     // (+inf when t_max is; never a denormal a compare may flush)
+    bool overflow = false;
+    uint32_t nbox = 0, nleaf = 0;
+    if constexpr (TRIS) {
+        SphereRay sr;
+        sr.px = sr.py = sr.pz = sr.dx = sr.dy = sr.dz = sr.Kg = sr.K = 0.f; sr.c0 = __builtin_inff();
+        if (sv.bvh_flags & 1u) sphere_ray_from(sv, pos, dir, sr);
+        TriFilterParams tpar;
+        tri_filter_from_ray(sv, pos, dir, tpar);
+        const bool plain = (sv.bvh_flags & 4u) != 0u;
+        if (in32) {
+            Ray32 q;
+            make_ray32(pos, rx.dirn, (double)sv.bvh_inv_max, q);
+            if (plain) query_mesh_walk_multi<2>(nodes, la, ma, q, sr, tpar, rx, sv.bvh_root, bound0, rec, k, cnt, t_max, overflow, ls, lq, tid, spill,
+                                                spill_entries, spill_stride, glane, exact, nbox, nleaf);
+            else query_mesh_walk_multi<0>(nodes, la, ma, q, sr, tpar, rx, sv.bvh_root, bound0, rec, k, cnt, t_max, overflow, ls, lq, tid, spill,
+                                          spill_entries, spill_stride, glane, exact, nbox, nleaf);
+        } else {
+            Ray64 q;
+            make_ray64(pos, rx.dirn, (double)sv.bvh_inv_max, q);
+            if (plain) query_mesh_walk_multi<2>(nodes, la, ma, q, sr, tpar, rx, sv.bvh_root, bound0, rec, k, cnt, t_max, overflow, ls, lq, tid, spill,
+                                                spill_entries, spill_stride, glane, exact, nbox, nleaf);
+            else query_mesh_walk_multi<0>(nodes, la, ma, q, sr, tpar, rx, sv.bvh_root, bound0, rec, k, cnt, t_max, overflow, ls, lq, tid, spill,
+                                          spill_entries, spill_stride, glane, exact, nbox, nleaf);
+        }
+    } else {
+        SphereRay sr;
+        sphere_ray_from(sv, pos, dir, sr);
+        Ray32 q0;
+        make_ray32(pos, rx.dirn, (double)sv.bvh_inv_max, q0);
+        Ray32S q;
+        q.ix = q0.ix; q.iy = q0.iy; q.iz = q0.iz; q.nx = q0.nx; q.ny = q0.ny; q.nz = q0.nz;
+        q.e = ray32_slack(q0, in32);
+        float bound = multi_bound(rec, k, cnt, bound0);
+        uint32_t node = sv.bvh_root, sp = 0, qcnt = 0;
+        // sphere_walk_phased's iteration, as the any-hit mode runs it; a lane whose queue may not take the leaf's records has its
+        // candidates tested first (with k > 1 nothing overtakes them: four live candidates are the rule, not the exception)
+        while (node != kNone) {
+            const bool at_leaf = (node >> 29) != 0u;
+            const unsigned long long lm = __ballot(at_leaf), am = __ballot(true);
+            if ((uint32_t)__popcll(lm) >= kQueryLeafLanes || lm == am) {
+                if (at_leaf) {
+                    if (qcnt + (node >> 29) > (uint32_t)kSphQueue) {
+                        multi_flush(la, rx, lq, tid, kSphQueue, qcnt, bound0, bound, rec, k, cnt, t_max, exact);
+                        qcnt = 0;
+                    }
+                    sphere_leaf_step<kQuerySphStack, true, false>(la.sphere_f32, la.sphere_prims, sr, node, sp, ls, lq, tid, spill, spill_stride,
+                                                                  glane, bound, qcnt, overflow, nleaf);
+                }
+            } else if (!at_leaf) {
+                sphere_node_step_q3<kQuerySphStack, true>(nodes, q, node, sp, ls, tid, spill, spill_entries, spill_stride, glane, bound, overflow,
+                                                          nbox);
+            }
+        }
+        if (!overflow) multi_flush(la, rx, lq, tid, kSphQueue, qcnt, bound0, bound, rec, k, cnt, t_max, exact);
+    }
+    box_tests += nbox;
+    leaf_filters += nleaf;
+    if (overflow) {                                   // a walk cut short by a full stack or queue: start over, every shape exactly
+        cnt = 0;
+        multi_sweep(sv, la, rx, true, true, rec, k, cnt, t_max, exact);
+    }
+}
+
+// The kernel's ray loop in the multi-hit mode.  A loop of its own, entered once per launch: the other loops carry none of its
+// arguments or state.
+template <bool TRIS>
+__device__ __forceinline__ void query_multi_loop(const SceneView &sv, const QueryArgs &qa, const float4 *__restrict__ nodes, const LeafArrays &la,
+                                                 const MeshArrays &ma, uint32_t *ls, uint32_t *lq, uint32_t tid, uint32_t *__restrict__ spill,
+                                                 uint32_t spill_entries, size_t spill_stride, size_t glane, unsigned long long *__restrict__ head,
+                                                 unsigned long long &segs, unsigned long long &exact, unsigned long long &box_tests,
+                                                 unsigned long long &leaf_filters)
+{
+    const unsigned long long grab = wf_grab_size(qa.n);
+    const uint32_t k = qa.mode >> kQueryMultiShift;
+    WfChunk ch{0ull, 0ull, false};
+    for (;;) {
+        unsigned long long i = 0;
+        const bool mine = wf_take(ch, head, grab, qa.n, true, i);
+        if (ch.drained && __ballot(mine) == 0ull) break;
+        if (!mine) continue;
+        ++segs;
+        unsigned long long *const rec = reinterpret_cast<unsigned long long *>(qa.hits) + 8ull * k * i;
+        const double t_max = qa.t_max ? qa.t_max[i] : __builtin_inf();
+        uint32_t cnt = 0;
+        V3 pos, dir;
+        if (qa.rv) {                                                     // the pick buffer's ray, as the closest-hit loop builds it
+            pos = sv.cam_pos;
+            dir = vnorm(vsub(primary_focal_point(sv, *qa.rv, (uint32_t)i), pos));
+        } else {
+            const QueryRay &qr = qa.rays[i];
+            pos = mk(qr.position[0], qr.position[1], qr.position[2]);
+            dir = mk(qr.direction[0], qr.direction[1], qr.direction[2]);
+        }
+        if (t_max > 0.0) {                                               // (NaN, zero, negative: an empty list, nothing is tested)
+            const RayX rx = make_rayx(pos, dir);
+            bool in32;
+            const bool walk = query_walkable(sv, qa.walk, pos, dir, in32);
+            query_multi_ray<TRIS>(sv, nodes, la, ma, pos, dir, rx, walk, in32, t_max, rec, k, cnt, ls, lq, tid, spill, spill_entries, spill_stride,
+                                  glane, exact, box_tests, leaf_filters);
+        }
+        // the answers over the list: scene.rs:234's hit point and object.rs:37-39's normal there, as the closest-hit loop writes them;
+        // behind them the closest-hit loop's miss
+#pragma unroll 1
+        for (uint32_t j = 0; j < k; ++j) {
+            unsigned long long *const w = rec + 8u * j;
+            if (j < cnt) {
+                Hit h;
+                h.t = __longlong_as_double((long long)w[6]);
+                h.id = (uint32_t)w[7];
+                h.kind = (uint32_t)(w[0] >> 32);
+                h.local = (uint32_t)w[0];
+                const V3 p = vadd(pos, vmuls(dir, h.t));
+                const V3 nrm = normal_at(sv, h, p);
+                w[0] = (unsigned long long)__double_as_longlong(p.x); w[1] = (unsigned long long)__double_as_longlong(p.y);
+                w[2] = (unsigned long long)__double_as_longlong(p.z);
+                w[3] = (unsigned long long)__double_as_longlong(nrm.x); w[4] = (unsigned long long)__double_as_longlong(nrm.y);
+                w[5] = (unsigned long long)__double_as_longlong(nrm.z);
+                w[7] = (unsigned long long)(long long)h.id;
+            } else {
+                const unsigned long long nan = (unsigned long long)__double_as_longlong(__builtin_nan(""));
+                w[0] = w[1] = w[2] = w[3] = w[4] = w[5] = nan;
+                w[6] = (unsigned long long)__double_as_longlong(__builtin_inf());
+                w[7] = ~0ull;
+            }
+        }
+        if (qa.counts) qa.counts[i] = cnt;
+    }
+}
+
 template <bool TRIS>
 __global__ __launch_bounds__(kBvhThreads, kQueryWaves) void query_closest_kernel(const SceneView *__restrict__ svp, const QueryArgs qa,
                                                                                  const float4 *__restrict__ nodes, const LeafArrays la,
@@ -692,6 +959,9 @@ __global__ __launch_bounds__(kBvhThreads, kQueryWaves) void query_closest_kernel
     else if (qa.mode == kQueryRefine)                                    // launch-uniform: and the refine mode
         query_refine_loop<TRIS>(sv, qa, nodes, la, ma, ls, lq, tid, spill, spill_entries, spill_stride, glane, head, segs, exact, box_tests,
                                 leaf_filters);
+    else if ((qa.mode & kQueryModeMask) == kQueryMulti)                  // launch-uniform: and the multi-hit mode (k above the mode)
+        query_multi_loop<TRIS>(sv, qa, nodes, la, ma, ls, lq, tid, spill, spill_entries, spill_stride, glane, head, segs, exact, box_tests,
+                               leaf_filters);
     else for (;;) {
         unsigned long long i = 0;
         const bool mine = wf_take(ch, head, grab, qa.n, true, i);         // (every lane of the wave is here: lane 0 takes the chunk)

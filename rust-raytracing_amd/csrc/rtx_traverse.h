@@ -678,7 +678,9 @@ __device__ __forceinline__ void sphere_node_step_q3(const float4 *__restrict__ q
 // The leaf `ref` (type << 29 | first record, type = its 1..6 spheres): sphere_step's bounds for each record, then the next entry.
 // The candidate queue is column `qcol` of an LDS array of 2 * kSphQueue rows, QS words per row (the lock-step kernels: the lane's
 // own column of lds_q[.][kBvhThreads]; the slot kernel: the column of the ray slot the lane walks).
-template <int STACK, bool SPILL, int QS>
+// TIGHTEN = false (the multi-hit query walk): a certain hit does not lower best_up -- the caller's bound is the k-th distance of
+// its list, which one certain hit says nothing about; everything else is the same text.
+template <int STACK, bool SPILL, int QS, bool TIGHTEN = true>
 __device__ __forceinline__ void sphere_leaf_step_at(const float4 *__restrict__ leaf_f32, const uint32_t *__restrict__ leaf_prims,
                                                     const SphereRay &sr, uint32_t &node, uint32_t &sp, uint32_t *lds_stack, uint32_t *lds_q,
                                                     uint32_t tid, uint32_t qcol, uint32_t *__restrict__ spill, size_t spill_stride, size_t glane,
@@ -699,7 +701,7 @@ __device__ __forceinline__ void sphere_leaf_step_at(const float4 *__restrict__ l
             const float Dm = Dl - G;
             const float thi = Dm > 0.0f ? b - __builtin_amdgcn_sqrtf(Dm) * (1.0f - 4.76837158e-7f) + sr.K : __builtin_inff();
             if (tlo <= best_up && !(thi < 0.0f)) {
-                if (tlo > sr.K) best_up = fminf(best_up, thi);
+                if constexpr (TIGHTEN) { if (tlo > sr.K) best_up = fminf(best_up, thi); }
                 if (qcnt == (uint32_t)kSphQueue) {
                     uint32_t w = 0;
 #pragma unroll
@@ -774,13 +776,13 @@ __device__ __forceinline__ void sph_packet_leaf_test(const float4 rec, const uin
     }
 }
 
-template <int STACK, bool SPILL>
+template <int STACK, bool SPILL, bool TIGHTEN = true>
 __device__ __forceinline__ void sphere_leaf_step(const float4 *__restrict__ leaf_f32, const uint32_t *__restrict__ leaf_prims,
                                                  const SphereRay &sr, uint32_t &node, uint32_t &sp, uint32_t *lds_stack, uint32_t *lds_q,
                                                  uint32_t tid, uint32_t *__restrict__ spill, size_t spill_stride, size_t glane,
                                                  float &best_up, uint32_t &qcnt, bool &overflow, uint32_t &nleaf)
 {
-    sphere_leaf_step_at<STACK, SPILL, kBvhThreads>(leaf_f32, leaf_prims, sr, node, sp, lds_stack, lds_q, tid, tid, spill, spill_stride, glane,
+    sphere_leaf_step_at<STACK, SPILL, kBvhThreads, TIGHTEN>(leaf_f32, leaf_prims, sr, node, sp, lds_stack, lds_q, tid, tid, spill, spill_stride, glane,
                                                    best_up, qcnt, overflow, nleaf);
 }
 

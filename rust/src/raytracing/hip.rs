@@ -142,6 +142,9 @@ extern "C" {
     pub fn rtx_closest_hits(scene: *const RtxScene, rays: *const RtxRay, n: u64, hits: *mut RtxHit) -> i32;
     pub fn rtx_scene_any_hits(scene: RtxSceneHandle, d_rays: *const RtxRay, d_t_max: *const f64, n: u64, d_occluded: *mut u8, stream: *mut c_void, stats: *mut RtxStats) -> i32;
     pub fn rtx_any_hits(scene: *const RtxScene, rays: *const RtxRay, t_max: *const f64, n: u64, occluded: *mut u8) -> i32;
+    pub fn rtx_scene_multi_hits(scene: RtxSceneHandle, d_rays: *const RtxRay, d_t_max: *const f64, n: u64, k: u32, d_hits: *mut RtxHit, d_counts: *mut u32, stream: *mut c_void, stats: *mut RtxStats) -> i32;
+    pub fn rtx_scene_primary_multi_hits(scene: RtxSceneHandle, width: u32, height: u32, k: u32, d_hits: *mut RtxHit, d_counts: *mut u32, stream: *mut c_void, stats: *mut RtxStats) -> i32;
+    pub fn rtx_multi_hits(scene: *const RtxScene, rays: *const RtxRay, t_max: *const f64, n: u64, k: u32, hits: *mut RtxHit, counts: *mut u32) -> i32;
     pub fn rtx_scene_trace_paths(scene: RtxSceneHandle, d_rays: *const RtxRay, d_ids: *const u64, n: u64, d_rgb: *mut f64, d_segments: *mut u32, stream: *mut c_void, stats: *mut RtxStats) -> i32;
     pub fn rtx_trace_paths(scene: *const RtxScene, rays: *const RtxRay, ids: *const u64, n: u64, rgb: *mut f64, segments: *mut u32) -> i32;
     pub fn rtx_scene_trace_samples(scene: RtxSceneHandle, width: u32, height: u32, d_ids: *const u64, n: u64, d_rgb: *mut f64, d_segments: *mut u32, stream: *mut c_void, stats: *mut RtxStats) -> i32;

@@ -25,6 +25,9 @@ generators and the same parameters:
                and at 0 (two lines; the second is what `features` at 1 spp and `paths_primary` trace), and rtx_render_rows of the frame
                at 1 spp (the same samples through the render's tiles and packets)
   samples_sparse  a random tenth of the frame's pixels, samples 0..7 of each, sample-major: per sample against samples_frame
+  multi1, multi4, multi16   rtx_scene_multi_hits on the incoherent set at k = 1, 4, 16: the k nearest objects of each ray, sorted (no limit)
+  multi4_pick  rtx_scene_primary_multi_hits of the 1920x1080 pick buffer at k = 4
+  peel4        the same four layers the old way, for 32 rays: hide(winners so far) + closest_hits + show per layer and ray -- wall time
   refine       the 1920x1080 frame with the bench camera: rtx_render_blocks_accumulate of 8 samples, then ONE rtx_render_blocks_refine
                call to max_samples = 64 (8 samples per round, 7 rounds, threshold 0.5, floor 0.01: on C2 the oracle's samples of twelve
                rows of the frame leave 14 % of the pixels selected after the base; 0.4 leaves 15 %, 0.6 6 %), against
@@ -92,7 +95,7 @@ def primary_rays(rtx, cam, width, height):
 
 
 LEGS = ("incoherent", "pick", "exact", "any", "any_short", "any_aimed", "paths", "paths_1seg", "paths_pick", "render_pick", "paths_primary",
-        "features", "accumulate", "samples_frame", "samples_sparse", "refine")
+        "features", "accumulate", "samples_frame", "samples_sparse", "refine", "multi1", "multi4", "multi16", "multi4_pick", "peel4")
 REFINE = dict(base=8, step=8, cap=64, threshold=0.5, floor=0.01)
 
 
@@ -128,6 +131,8 @@ def main():
             legs = [l for l in legs if not l.startswith("samples")]
         if not hasattr(probe, "rtx_render_blocks_refine"):
             legs = [l for l in legs if l != "refine"]
+        if not hasattr(probe, "rtx_scene_multi_hits"):
+            legs = [l for l in legs if not l.startswith("multi") and l != "peel4"]
         have_accumulate = hasattr(probe, "rtx_render_blocks_accumulate")
     else:
         have_accumulate = True
@@ -318,6 +323,48 @@ def main():
                                   "mrays_per_s": round(k / (st.trace_ms * 1e-3) / 1e6, 1), "kernel": int(st.kernel),
                                   "exact_tests_per_ray": round(st.exact_tests / k, 2), "box_tests_per_ray": round(st.box_tests / k, 2),
                                   "occluded_fraction": round(float(d_hits[:k].float().mean().item()), 4)}), flush=True)
+                hnd.close()
+                continue
+            if leg.startswith("multi"):
+                kk = int(leg[5:].split("_")[0])
+                k = W * H if leg.endswith("_pick") else n
+                d_multi = torch.empty(k * kk * 64, dtype=torch.uint8, device=dev)           # (multi16 of 2^24 rays: 16 GiB)
+                d_cnt = torch.empty(k, dtype=torch.int32, device=dev)
+                if leg.endswith("_pick"):
+                    st = best(lambda: hnd.primary_multi_hits(W, H, kk, d_multi.data_ptr(), d_cnt.data_ptr()))
+                else:
+                    st = best(lambda: hnd.multi_hits(d_rays.data_ptr(), None, k, kk, d_multi.data_ptr(), d_cnt.data_ptr()))
+                cnt = d_cnt.cpu().numpy()
+                print(json.dumps({"scene": name, "leg": leg, "k": kk, "rays": k, "trace_ms": round(st.trace_ms, 3),
+                                  "mrays_per_s": round(k / (st.trace_ms * 1e-3) / 1e6, 1), "kernel": int(st.kernel),
+                                  "exact_tests_per_ray": round(st.exact_tests / k, 2), "box_tests_per_ray": round(st.box_tests / k, 2),
+                                  "entries_per_ray": round(float(cnt.mean()), 3), "full_fraction": round(float((cnt == kk).mean()), 4),
+                                  "empty_fraction": round(float((cnt == 0).mean()), 4)}), flush=True)
+                del d_multi, d_cnt
+                hnd.close()
+                continue
+            if leg == "peel4":
+                # what a caller did before multi-hit queries: per ray and layer hide(the winners so far) + closest_hits + show -- a scene
+                # edit and a launch per layer, one ray at a time (visibility is per scene).  Wall time, 32 rays that have 4 layers
+                import time
+                dist, obj, _, _, cnt = hnd.query_all(o[:4096], d[:4096], 4)
+                rows = np.nonzero(cnt == 4)[0][:32]
+                one = torch.empty(64, dtype=torch.uint8, device=dev)
+                torch.cuda.synchronize(dev)
+                t0 = time.perf_counter()
+                for r in rows:
+                    won = []
+                    for layer in range(4):
+                        if won:
+                            hnd.hide(won)
+                        hnd.closest_hits(d_rays.data_ptr() + 48 * int(r), 1, one.data_ptr())
+                        if won:
+                            hnd.show(won)
+                        won.append(int(one.cpu().numpy().view(rtx.HIT_DTYPE)["object"][0]))
+                    assert won == [int(v) for v in obj[r]], (r, won, obj[r])
+                dt = time.perf_counter() - t0
+                print(json.dumps({"scene": name, "leg": leg, "k": 4, "rays": int(len(rows)), "wall_ms": round(dt * 1e3, 3),
+                                  "ms_per_ray": round(dt * 1e3 / max(len(rows), 1), 4)}), flush=True)
                 hnd.close()
                 continue
             if leg == "pick":
