@@ -801,7 +801,7 @@ int32_t rtx_debug_host_set_visible(const RtxScene *scene, const uint32_t *step_k
 int32_t rtx_debug_resident_mesh_digests(RtxSceneHandle scene, uint64_t *digests);
 
 /* rtx_debug_tile_lists (lab library; the product returns RTX_ERR_UNSUPPORTED): the per-tile candidate lists of the primary rays that
- * the LAST render call on `scene` built and used (build_mesh_tile_lists_kernel, DESIGN.md 3.3 "Tile lists"), read out of the handle's
+ * the LAST render call on `scene` used -- built by it, or by an earlier call of the same frame -- (build_mesh_tile_lists_kernel, DESIGN.md 3.3 "Tile lists"), read out of the handle's
  * own buffer and carved as the launch carved it.  The handle remembers that call's form and tile grid; the hook synchronises the
  * device.  All arrays are HOST arrays.
  * info[8]: [0] the form -- 0 the call built no lists (no packet path, RTX_TUNE_NO_TILE_LISTS, two halves in flight, no render yet;
@@ -809,7 +809,9 @@ int32_t rtx_debug_resident_mesh_digests(RtxSceneHandle scene, uint64_t *digests)
  *       f32 record (4 words), the sphere's index, t_lb, 0, 0}, 2 the {entry, t_lb} pairs of a footprint or joint tree (entry: a filter
  *       record, or with bit 31 a sphere leaf entry);  [1] tiles per row of the band's 8 x 8 tile grid, [2] tiles -- tile t holds the
  *       band's local rows 8 (t / info[1]) ... and columns 8 (t % info[1]) ...;  [3] the cap: entries a tile's list may hold;
- *       [4] words of a stored entry (8 or 2);  [5..7] 0.
+ *       [4] words of a stored entry (8 or 2);  [5] the launches this handle's render calls have asked to BUILD lists so far (a call
+ *       that renders the frame of the call before it -- same camera, band and scene -- finds them in the buffer and adds none:
+ *       DESIGN.md 3.3);  [6..7] 0.
  * counts and entries may both be NULL (info alone); else they hold max_tiles >= info[2] tiles.
  * counts[t]: entries of tile t's list; 0xFFFFFFFF: the tile has no list (its packets walk the tree).
  * entries: 12 words per slot, [tile][cap][12]; the slots below counts[t] are written, the others 0 --

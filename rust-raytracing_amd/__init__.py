@@ -593,7 +593,7 @@ class SceneHandle:
     def debug_tile_lists(self):
         """The per-tile candidate lists the last render call on this handle built and used (rtx_debug_tile_lists, include/rtx_hip.h;
         a lab-library hook: upload with lab=True).  A dict: form (0 none, 1 a sphere tree's entries, 2 a mesh or joint tree's pairs),
-        tiles_x, n_tiles, cap, count (n_tiles,) uint32 -- TILE_LIST_WALK: the tile has no list --, and per slot [tile][cap]: raw (.., 8)
+        tiles_x, n_tiles, cap, builds (the launches this handle's render calls asked to build lists so far), count (n_tiles,) uint32 -- TILE_LIST_WALK: the tile has no list --, and per slot [tile][cap]: raw (.., 8)
         uint32 the stored words, t_lb float32, object int64 (-1: none) the index in Scene.objects, is_record bool (a filter record)."""
         info = np.zeros(8, dtype=np.uint32)
         self._check(self._lib.rtx_debug_tile_lists(self._h, info.ctypes.data, None, None, 0))
@@ -604,7 +604,7 @@ class SceneHandle:
             self._check(self._lib.rtx_debug_tile_lists(self._h, info.ctypes.data, count.ctypes.data, ent.ctypes.data, n_tiles))
         obj = ent[:, :, 9].astype(np.int64)
         obj[obj == 0xFFFFFFFF] = -1
-        return {"form": form, "tiles_x": tiles_x, "n_tiles": n_tiles, "cap": cap, "count": count, "raw": ent[:, :, :8].copy(),
+        return {"form": form, "tiles_x": tiles_x, "n_tiles": n_tiles, "cap": cap, "builds": int(info[5]), "count": count, "raw": ent[:, :, :8].copy(),
                 "t_lb": np.ascontiguousarray(ent[:, :, 8]).view(np.float32), "object": obj, "is_record": ent[:, :, 10] == 1}
 
     def debug_sweep_filter(self, origins, directions, objects=None):

@@ -130,6 +130,7 @@ void drop_update_tables(RtxSceneHandle_ *h)              // the device tables of
 // leaves the resident scene as it was.
 int32_t upload_packed(RtxSceneHandle_ *h, const PackedScene &p)
 {
+    touch_scene(h);                                       // (an append, a rebuilding update or show: every array is replaced)
     const SceneView sv_before = h->sv;                    // restored if an upload fails: the handle then still holds the old scene
     std::vector<void *> old_allocs;
     old_allocs.swap(h->scene_allocs);
@@ -452,6 +453,7 @@ int32_t rtx_scene_set_config(RtxSceneHandle scene, const RtxConfig *config)
     if (!scene || !config) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_set_config: null argument");
     if (int32_t rc = check_config(*config)) return rc;
     if (int32_t rc = check_watchdog(scene, false)) return rc;
+    touch_scene(scene);
     apply_config(scene, *config);
     return RTX_OK;
 }
@@ -459,6 +461,7 @@ int32_t rtx_scene_set_config(RtxSceneHandle scene, const RtxConfig *config)
 int32_t rtx_scene_set_scratch_limit(RtxSceneHandle scene, uint64_t bytes)
 {
     if (!scene) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_set_scratch_limit: null scene");
+    touch_scene(scene);                       // (the cap decides whether a frame has lists, and may move the buffer)
     scene->scratch_limit = (size_t)bytes;
     return RTX_OK;
 }
@@ -467,6 +470,7 @@ int32_t rtx_scene_set_camera(RtxSceneHandle scene, const RtxCamera *camera)
 {
     if (!scene || !camera) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_set_camera: null argument");
     if (int32_t rc = check_watchdog(scene, false)) return rc;
+    touch_scene(scene);
     scene->cam = *camera;
     scene->sv.cam_pos = mk(camera->position[0], camera->position[1], camera->position[2]);
     scene->sv.to_world_x = mk(camera->to_world_space[0], camera->to_world_space[1], camera->to_world_space[2]);
@@ -655,6 +659,25 @@ void plan_forms(const RtxSceneHandle_ *h, BandPlan &plan, uint64_t spp, bool may
                   ((tuning & RTX_TUNE_HALVES) != 0u || plan.per_sample64 * spp <= kHalvesBelowRays);
 }
 
+// ---- the tile lists across render calls (rtx_host.h, tl_key); -DRTX_TILE_LIST_REUSE=0: every call builds its lists, for A/B runs
+#ifndef RTX_TILE_LIST_REUSE
+#define RTX_TILE_LIST_REUSE 1
+#endif
+bool tile_list_key_equal(const RtxSceneHandle_::TileListKey &a, const RtxSceneHandle_::TileListKey &b)
+{
+    return a.valid && b.valid && a.scene_gen == b.scene_gen && std::memcmp(&a.cam, &b.cam, sizeof(RtxCamera)) == 0 &&
+           a.width == b.width && a.height == b.height && a.row_begin == b.row_begin && a.row_stride == b.row_stride &&
+           a.row_block == b.row_block && a.n_rows == b.n_rows && a.tiles_x == b.tiles_x && a.kernel == b.kernel && a.tuning == b.tuning &&
+           a.buffer == b.buffer && a.bytes == b.bytes;
+}
+
+// the list buffer at `bytes` or more; a buffer that is replaced takes the key with it (the new one may get the old one's address)
+int32_t grow_tile_lists(RtxSceneHandle_ *h, size_t bytes)
+{
+    if (!h->tile_lists || h->tile_lists_bytes < bytes) h->tl_key.valid = false;
+    return grow(&h->tile_lists, &h->tile_lists_bytes, bytes);
+}
+
 // ---- scratch: one RGB per ray of a sample batch, the running per-pixel sum, the SoA ray state
 int32_t grow_scratch(RtxSceneHandle_ *h, const BandPlan &plan, uint32_t npix, uint64_t spp, bool own_acc)
 {
@@ -676,13 +699,13 @@ int32_t grow_scratch(RtxSceneHandle_ *h, const BandPlan &plan, uint32_t npix, ui
     if (plan.spheres_two_stage) {
         if (int32_t rc = grow(&h->wf_state, &h->wf_bytes, bvh_spheres_queue_bytes(batch_rays, h->n_cus))) return rc;
         if (plan.tile_list_bytes != 0)
-            if (int32_t rc = grow(&h->tile_lists, &h->tile_lists_bytes, (size_t)plan.tile_list_bytes)) return rc;
+            if (int32_t rc = grow_tile_lists(h, (size_t)plan.tile_list_bytes)) return rc;
     }
     if (kernel == RTX_KERNEL_WAVEFRONT) {
         if (int32_t rc = grow((void **)&h->state, &h->state_bytes, wavefront_spill_bytes(h->sv, h->n_cus))) return rc;
         if (int32_t rc = grow(&h->wf_state, &h->wf_bytes, wavefront_state_bytes(batch_rays, wavefront_levels(h->sv)))) return rc;
         if (plan.tile_list_bytes != 0)
-            if (int32_t rc = grow(&h->tile_lists, &h->tile_lists_bytes, (size_t)plan.tile_list_bytes)) return rc;
+            if (int32_t rc = grow_tile_lists(h, (size_t)plan.tile_list_bytes)) return rc;
     }
     return RTX_OK;
 }
@@ -783,12 +806,17 @@ int32_t launch_halves(RtxSceneHandle_ *h, const BandPlan &plan, RowsView rv, dou
     return RTX_OK;
 }
 
-// The trace launch of one sample batch (its samples: rv.sample_begin, rv.n_samples), by kernel.  first_batch: the first of THIS call --
-// build the tile lists; the call's later batches reuse them (the camera may have changed since an earlier call: every call rebuilds).
-int32_t launch_batch(RtxSceneHandle_ *h, const BandPlan &plan, const RowsView &rv, bool first_batch, hipStream_t stream, bool stats)
+// The trace launch of one sample batch (its samples: rv.sample_begin, rv.n_samples), by kernel.  build_lists: build the tile lists --
+// the first batch of a call whose frame's lists are not in the handle's buffer; the call's later batches, and a later call of the same
+// frame (render_band, tl_key), reuse them.
+int32_t launch_batch(RtxSceneHandle_ *h, const BandPlan &plan, const RowsView &rv, bool build_lists, hipStream_t stream, bool stats)
 {
     const uint32_t kernel = plan.kernel, tuning = h->cfg.tuning;
     uint32_t *const state = reinterpret_cast<uint32_t *>(h->state);
+#ifdef RTX_LAB
+    if (build_lists && plan.tile_list_bytes != 0 && (kernel == RTX_KERNEL_WAVEFRONT || (kernel == RTX_KERNEL_BVH && plan.spheres_two_stage)))
+        ++h->tl_builds;
+#endif
     if (kernel != RTX_KERNEL_EXACT && kernel != RTX_KERNEL_WAVEFRONT)         // the queue's head of the persistent kernels
         RTX_HIP_CHECK(hipMemsetAsync(h->work_counter, 0, sizeof(unsigned long long), stream));
     if (kernel == RTX_KERNEL_EXACT) {
@@ -799,7 +827,7 @@ int32_t launch_batch(RtxSceneHandle_ *h, const BandPlan &plan, const RowsView &r
 #endif
     } else if (kernel == RTX_KERNEL_WAVEFRONT) {
         RTX_HIP_CHECK(launch_trace_wavefront(h->d_sv, h->sv, h->d_rv, rv, h->samples, h->wf_state, h->counters, state, h->n_cus, stream,
-                                             plan.tile_list_bytes != 0 ? h->tile_lists : nullptr, first_batch));   // (a call's later sample batches reuse its lists)
+                                             plan.tile_list_bytes != 0 ? h->tile_lists : nullptr, build_lists));
     } else if (kernel == RTX_KERNEL_BVH_REGROUP) {
         RTX_HIP_CHECK(launch_trace_bvh_mesh(h->d_sv, h->sv, h->d_rv, rv, h->samples, h->counters, h->work_counter, state, h->n_cus, stream));
     } else if (kernel == RTX_KERNEL_BVH) {
@@ -807,7 +835,7 @@ int32_t launch_batch(RtxSceneHandle_ *h, const BandPlan &plan, const RowsView &r
         RTX_HIP_CHECK(launch_trace_bvh_spheres(h->d_sv, h->sv, h->d_rv, rv, h->samples, h->counters, h->work_counter, state, h->n_cus,
                                                two ? h->wf_state : nullptr, sphere_flags(tuning), stream,
                                                stats && two ? h->counters_stage1 : nullptr, stats && two ? h->ev[3] : nullptr,
-                                               two && plan.tile_list_bytes != 0 ? h->tile_lists : nullptr, first_batch));
+                                               two && plan.tile_list_bytes != 0 ? h->tile_lists : nullptr, build_lists));
     } else {
         RTX_HIP_CHECK(launch_trace_mixed(h->d_sv, h->sv, h->d_rv, rv, h->samples, h->state, h->counters, h->work_counter, h->n_cus,
                                          kernel == RTX_KERNEL_MIXED_VERIFY, stream));
@@ -818,7 +846,7 @@ int32_t launch_batch(RtxSceneHandle_ *h, const BandPlan &plan, const RowsView &r
 // The samples of a call, plan.batch per launch: a trace launch and a resolve per batch (the left fold over the batches happens in
 // resolve's accumulator: the handle's, or -- sr.sum -- the caller's, which also holds what earlier calls folded).
 int32_t launch_batches(RtxSceneHandle_ *h, const BandPlan &plan, RowsView rv, const SampleRange &sr, double *d_out_rgb, hipStream_t stream,
-                       bool stats, BandRun &run)
+                       bool stats, BandRun &run, bool lists_current)
 {
     const uint64_t spp = sr.n;
     const bool accumulate = sr.sum != nullptr;
@@ -831,7 +859,7 @@ int32_t launch_batches(RtxSceneHandle_ *h, const BandPlan &plan, RowsView rv, co
         RTX_HIP_CHECK(hipMemcpyAsync(h->d_rv, &rv, sizeof(RowsView), hipMemcpyHostToDevice, stream));   // pageable: staged before return
         RTX_HIP_CHECK(hipMemsetAsync(rv.nonzero, 0, nonzero_mask_bytes(rv.n_rays), stream));            // no record yet: the last batch's bits go
         if (stats) RTX_HIP_CHECK(hipEventRecord(h->ev[0], stream));
-        if (int32_t rc = launch_batch(h, plan, rv, s0 == 0, stream, stats)) return rc;
+        if (int32_t rc = launch_batch(h, plan, rv, s0 == 0 && !lists_current, stream, stats)) return rc;
         ++run.launches;
         if (stats) RTX_HIP_CHECK(hipEventRecord(h->ev[1], stream));
         if (accumulate)
@@ -970,6 +998,18 @@ int32_t render_band(RtxSceneHandle h, uint32_t width, uint32_t height, uint32_t 
 #endif
     if (int32_t rc = ensure_tables(h, width, height, row_begin, row_stride, row_block, n_rows, stream)) return rc;
     if (int32_t rc = grow_scratch(h, plan, npix, spp, accumulate == nullptr)) return rc;
+    // the lists of this frame, if the call before left them in the buffer (rtx_host.h, tl_key); the key is dropped until this call's
+    // launches have been enqueued without an error, and for good by a call that hands its launches no lists (no packet path, the halves)
+    const bool uses_lists = plan.tile_list_bytes != 0 && spp > 0 && !plan.halves &&
+                            (plan.kernel == RTX_KERNEL_WAVEFRONT || (plan.kernel == RTX_KERNEL_BVH && plan.spheres_two_stage));
+    RtxSceneHandle_::TileListKey key;
+    key.valid = true; key.scene_gen = h->scene_gen; key.cam = h->cam;
+    key.width = width; key.height = height; key.row_begin = row_begin; key.row_stride = row_stride; key.row_block = row_block;
+    key.n_rows = n_rows; key.tiles_x = plan.tiles_x;
+    key.kernel = plan.kernel; key.tuning = h->cfg.tuning;
+    key.buffer = h->tile_lists; key.bytes = (size_t)plan.tile_list_bytes;
+    const bool lists_current = RTX_TILE_LIST_REUSE != 0 && uses_lists && !h->sv_dirty && tile_list_key_equal(h->tl_key, key);
+    h->tl_key.valid = false;
 
     RowsView rv = rows_view(h, width, height, row_begin, row_stride, row_block, n_rows, plan.tiles_x, (uint32_t)plan.per_sample64);
     rv.nonzero = spp > 0 ? reinterpret_cast<uint32_t *>(h->samples + (size_t)(plan.batch * plan.per_sample64) * 4) : nullptr;
@@ -982,7 +1022,8 @@ int32_t render_band(RtxSceneHandle h, uint32_t width, uint32_t height, uint32_t 
     } else if (plan.halves) {
         if (int32_t rc = launch_halves(h, plan, rv, d_out_rgb, stream, stats != nullptr, run)) return rc;
     } else {
-        if (int32_t rc = launch_batches(h, plan, rv, sr, d_out_rgb, stream, stats != nullptr, run)) return rc;
+        if (int32_t rc = launch_batches(h, plan, rv, sr, d_out_rgb, stream, stats != nullptr, run, lists_current)) return rc;
+        if (uses_lists) h->tl_key = key;
     }
     return finish_stats(h, plan, run, (uint64_t)npix * spp, stream, stats);
 }

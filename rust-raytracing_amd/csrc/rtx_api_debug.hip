@@ -579,7 +579,7 @@ int32_t rtx_debug_tile_lists(RtxSceneHandle h, uint32_t *info, uint32_t *counts,
     const size_t bytes = form == 1u ? bvh_spheres_tile_list_bytes((uint64_t)n_tiles << 6) : wavefront_tile_list_bytes((uint64_t)n_tiles << 6);
     const uint32_t cap = form == 0u ? 0u : (uint32_t)((form == 1u ? bvh_spheres_tile_list_bytes(64) - 256 : wavefront_tile_list_bytes(64) - 256) / entry_bytes);
     const uint32_t words = (uint32_t)(entry_bytes / sizeof(uint32_t));
-    const uint32_t head_info[8] = { form, h->tl_tiles_x, n_tiles, cap, words, 0u, 0u, 0u };
+    const uint32_t head_info[8] = { form, h->tl_tiles_x, n_tiles, cap, words, h->tl_builds, 0u, 0u };
     std::memcpy(info, head_info, sizeof head_info);
     if (form == 0u || n_tiles == 0u || (!counts && !entries)) return RTX_OK;
     if (!counts || !entries || max_tiles < n_tiles) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_debug_tile_lists: counts and entries hold info[2] tiles");

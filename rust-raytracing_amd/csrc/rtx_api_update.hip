@@ -60,6 +60,7 @@ int32_t ensure_mesh_tables(RtxSceneHandle_ *h)
 int32_t apply_plan(RtxSceneHandle_ *h, UpdatePlan &plan, hipStream_t stream)
 {
     auto &b = h->upd;
+    touch_scene(h);                                       // (the resident arrays are rewritten in place: a refit, new records, a hide or show)
     if (int32_t rc = ensure_update_tables(h)) return rc;
     if (plan.tri_geom) if (int32_t rc = ensure_mesh_tables(h)) return rc;
     const RefitTables &t = h->refit;
@@ -150,6 +151,7 @@ int32_t rtx_scene_append_objects(RtxSceneHandle scene, const RtxObject *objects,
 {
     if (!scene || (n_objects && !objects)) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_append_objects: null argument");
     if (n_objects == 0) return RTX_OK;
+    touch_scene(scene);
     if (scene->objects.size() + n_objects > 0xFFFFFFF0ull) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_append_objects: too many objects");
     RTX_HIP_CHECK(hipSetDevice(scene->device));
     RTX_HIP_CHECK(hipDeviceSynchronize());                  // a render may still read the arrays about to be replaced
@@ -165,6 +167,7 @@ int32_t rtx_scene_update_objects(RtxSceneHandle h, const uint64_t *indices, cons
 {
     if (how) *how = RTX_UPDATED_NOTHING;
     if (!h) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_update_objects: null scene");
+    touch_scene(h);
     UpdatePlan plan;
     if (int32_t rc = plan_update(h->objects, h->refit, h->sv.sphere_cmax, indices, objects, n, mode, plan, h->hidden.empty() ? nullptr : h->hidden.data()))
         return rc;
@@ -192,6 +195,7 @@ int32_t rtx_scene_set_visible(RtxSceneHandle h, const uint64_t *indices, uint64_
 {
     if (how) *how = RTX_UPDATED_NOTHING;
     if (!h) return fail(RTX_ERR_INVALID_ARGUMENT, "rtx_scene_set_visible: null scene");
+    touch_scene(h);
     std::vector<uint8_t> hidden = hidden_bytes(h, h->objects.size());
     UpdatePlan plan;
     if (int32_t rc = plan_visibility(h->objects, hidden, h->refit, h->sv.sphere_cmax, indices, n, visible, plan)) return rc;

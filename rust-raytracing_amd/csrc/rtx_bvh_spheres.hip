@@ -13,6 +13,7 @@
 // only between walks.  4 workgroups per CU: the loops are VALU-issue bound, more waves only add spill reloads inside them
 // (5 / 6 / 8 per SIMD measured in round 1), 3 without any spill are 3 % slower (round 3).
 #include "rtx_launch.h"
+#include "rtx_spk_pool.h"
 #include "rtx_spk_units.h"
 #include "rtx_traverse.h"
 
@@ -406,9 +407,64 @@ constexpr int kSpkWaves = RTX_SPK_WAVES;     // workgroups per CU
 #ifndef RTX_SPK_UNITS
 #define RTX_SPK_UNITS 1                      // a wave meets a tile for a run of samples (rtx_spk_units.h): the pixel's part of a ray once per run
 #endif
+#ifndef RTX_SPK_POOL
+#define RTX_SPK_POOL 1                       // the shading block behind the exact tests runs with full lanes from a wave's pool of hits (rtx_spk_pool.h)
+#endif
+#ifndef RTX_SPK_POOL_COUNT
+#define RTX_SPK_POOL_COUNT 0                 // (A/B builds) the passes of that block counted into counters[0].pad_, RtxStats' mismatch word
+#endif
 #ifdef RTX_LAB                               // launch flag of the lab form (rtx_api.hip builds it from RtxConfig.tuning)
 constexpr uint32_t kSphNoPackets = 1u;       // stage 1 per lane (A/B runs)
 #endif
+
+// A pooled hit: what advance_and_shade and the code behind it read of a primary ray and its winner, 80 bytes in five rows of 16
+// (row f of slot s of a wave: pw[f * kBvhThreads + s]).  r.result, r.light, r.draw and r.bounce are every primary ray's constants.
+// A wave's LDS accesses are executed in order, and the fences keep the compiler from moving a lane's reads above the writes of
+// another's: a slot is written and read by different lanes.
+constexpr int kSpkPoolRows = 5;
+__device__ __forceinline__ void spk_pool_push(double2 *pw, uint32_t slot, const RayState &r, const Hit &h, uint32_t ridx)
+{
+    pw[0 * kBvhThreads + slot] = make_double2(r.pos.x, r.pos.y);
+    pw[1 * kBvhThreads + slot] = make_double2(r.pos.z, r.dir.x);
+    pw[2 * kBvhThreads + slot] = make_double2(r.dir.y, r.dir.z);
+    pw[3 * kBvhThreads + slot] = make_double2(__longlong_as_double((long long)r.key), h.t);
+    pw[4 * kBvhThreads + slot] = make_double2(__longlong_as_double(((long long)h.kind << 32) | (long long)h.id),
+                                              __longlong_as_double(((long long)ridx << 32) | (long long)h.local));
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+}
+
+__device__ __forceinline__ void spk_pool_pull(const double2 *pw, uint32_t slot, RayState &r, Hit &h, uint32_t &ridx)
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const double2 a = pw[0 * kBvhThreads + slot], b = pw[1 * kBvhThreads + slot], c = pw[2 * kBvhThreads + slot],
+                  d = pw[3 * kBvhThreads + slot], e = pw[4 * kBvhThreads + slot];
+    r.pos = mk(a.x, a.y, b.x);
+    r.dir = mk(b.y, c.x, c.y);
+    r.result = mk(0., 0., 0.); r.light = mk(1., 1., 1.); r.draw = 6; r.bounce = 0;
+    r.key = (uint64_t)__double_as_longlong(d.x);
+    h.t = d.y;
+    const uint64_t ik = (uint64_t)__double_as_longlong(e.x), lr = (uint64_t)__double_as_longlong(e.y);
+    h.id = (uint32_t)ik; h.kind = (uint32_t)(ik >> 32);
+    h.local = (uint32_t)lr; ridx = (uint32_t)(lr >> 32);
+}
+
+// The block behind a packet's exact tests, as it stood inside the packet loop: render_ray's match arm + ray_hit (scene.rs:232-239,
+// 260-278) for the lanes that hold a hit, the finished samples stored, the survivors appended to stage 2's queue.
+__device__ __forceinline__ void spk_shade_hits(const SceneView &sv, const RowsView &rv, double *__restrict__ samples, const SphQueue &sq,
+                                               Counters *__restrict__ ctr, bool have, RayState &r, const Hit &h, uint32_t ridx,
+                                               uint32_t bounce_limit, uint32_t lane, unsigned long long &out_next, unsigned long long &out_end)
+{
+    uint32_t first_id = 0;
+    bool go = false;
+    if (have) {
+        advance_and_shade<kRoundGlobal>(sv, h, r);
+        first_id = h.id;
+        const bool done = (r.bounce >= bounce_limit) || light_is_zero(r);            // scene.rs:227-228
+        if (done) store_sample<kRoundGlobal>(samples, rv, ridx, r.result);
+        go = !done;
+    }
+    sph_queue_append(sq, ctr, go, r, ridx, first_id, lane, out_next, out_end);
+}
 
 // (sph_packet_leaf_test, the packet kernel's leaf test of one sphere, lives in rtx_traverse.h next to sphere_leaf_step_at: the lab
 // library's rtx_debug_path_bounds calls it too)
@@ -605,6 +661,14 @@ __global__ __launch_bounds__(kBvhThreads, kSpkWaves) void trace_sph_packet_kerne
 #endif
     unsigned long long out_next = 0, out_end = 0;                       // its reserved slots of the survivors' queue
     unsigned long long segs = 0, box_tests = 0, leaf_filters = 0, exact = 0;
+#if RTX_SPK_POOL
+    __shared__ double2 lds_pool[kSpkPoolRows][kBvhThreads];            // 64 slots per wave, a row per 16 bytes of a pooled hit
+    double2 *const pw = &lds_pool[0][0] + (tid & ~63u);                 // this wave's slot 0 of row 0
+    uint32_t pool = 0;                                                  // hits pooled, < 64 (wave-uniform)
+#if RTX_SPK_POOL_COUNT
+    unsigned long long shade_passes = 0;
+#endif
+#endif
 
     // a packet over its tile's list is ~10 us of work, so the grabs are twice the launch's size for them (the host sizes rv.grab for
     // stage 2's longer segments): rank 0's band of the C2 frame at N = 8: stage 1 1.83 -> 1.44 ms (x4: 1.42, x8: 1.52); the full frame: level
@@ -749,10 +813,16 @@ __global__ __launch_bounds__(kBvhThreads, kSpkWaves) void trace_sph_packet_kerne
             }
             // ---- phase 2, f64, all lanes together: the exact tests of the candidates that can still be the winner, the shapes
             //      outside the tree, ray_hit
+#if RTX_SPK_POOL
+            Hit h;
+            hit_init(h);
+            if (alive) {
+#else
             uint32_t first_id = 0;
             if (alive) {
                 Hit h;
                 hit_init(h);
+#endif
                 ++segs;
                 box_tests += nbox;
                 leaf_filters += nleaf;
@@ -783,6 +853,25 @@ __global__ __launch_bounds__(kBvhThreads, kSpkWaves) void trace_sph_packet_kerne
                     if (triangle_distance(la.tris[tk], rx, &t)) hit_consider(h, t, la.tris[tk].id, 2, tk);
                 }
                 exact += sv.n_planes + sv.n_tri_filter;
+#if RTX_SPK_POOL
+            }
+            // ---- render_ray's match arm + ray_hit (scene.rs:232-239, 260-278) through the wave's pool (rtx_spk_pool.h): the lanes with
+            //      a hit wait in the pool until the block behind can run with all 64 lanes; a lane without one (a miss: its sample is zero
+            //      and is not stored; the padding of a partial tile) then shades a pooled hit, which carries its own ridx and key
+            const unsigned long long hm = __ballot(alive && h.id != kNone);
+            const SpkPoolStep ps = spk_pool_lane(hm, lane, pool);
+            if (spk_pool_shades(hm, pool)) {
+                uint32_t hridx = ridx;
+                if (ps.action == kSpkPoolPull) spk_pool_pull(pw, ps.slot, r, h, hridx);
+                spk_shade_hits(sv, rv, samples, sq, ctr, true, r, h, hridx, bounce_limit, lane, out_next, out_end);
+#if RTX_SPK_POOL_COUNT
+                ++shade_passes;
+#endif
+            } else if (ps.action == kSpkPoolPush) {
+                spk_pool_push(pw, ps.slot, r, h, ridx);
+            }
+            pool = spk_pool_next(hm, pool);
+#else
 
                 // ---- render_ray's match arm + ray_hit (scene.rs:232-239, 260-278)
                 bool done = true;
@@ -797,8 +886,27 @@ __global__ __launch_bounds__(kBvhThreads, kSpkWaves) void trace_sph_packet_kerne
                 }
             }
             sph_queue_append(sq, ctr, alive, r, ridx, first_id, lane, out_next, out_end);
+#endif
         }
     }
+#if RTX_SPK_POOL
+    if (pool != 0u) {                                                   // the wave leaves: what is still pooled, once
+        const SpkPoolStep ps = spk_pool_flush_lane(lane, pool);
+        RayState r;
+        Hit h;
+        uint32_t hridx = 0;
+        hit_init(h);
+        r.pos = mk(0., 0., 0.); r.dir = mk(1., 0., 0.); r.result = mk(0., 0., 0.); r.light = mk(1., 1., 1.); r.key = 0; r.draw = 6; r.bounce = 0;
+        if (ps.action == kSpkPoolPull) spk_pool_pull(pw, ps.slot, r, h, hridx);
+        spk_shade_hits(sv, rv, samples, sq, ctr, ps.action == kSpkPoolPull, r, h, hridx, bounce_limit, lane, out_next, out_end);
+#if RTX_SPK_POOL_COUNT
+        ++shade_passes;
+#endif
+    }
+#if RTX_SPK_POOL_COUNT
+    if (lane == 0 && shade_passes) atomicAdd(&ctr[0].pad_, shade_passes);       // (lab A/B builds: read back as RtxStats' mismatch word)
+#endif
+#endif
     sph_queue_close(sq, lane, out_next, out_end);
     unsigned long long filt = box_tests + leaf_filters;
 #pragma unroll

@@ -47,10 +47,24 @@ struct RtxSceneHandle_ {
     double *state = nullptr;    size_t state_bytes = 0;
     void *wf_state = nullptr;   size_t wf_bytes = 0;       // the wavefront kernels' ray state
     void *tile_lists = nullptr; size_t tile_lists_bytes = 0;   // what each tile's primary rays can reach (build_mesh_tile_lists_kernel)
+    // The lists depend on the tree, the camera and the frame's geometry alone, so a call that renders the frame of the call before it
+    // (a progressive render's next samples, an adaptive round, the same band again) builds none: tl_key says what the buffer holds.
+    // scene_gen: bumped by whatever can change the tree, the shapes, the camera, the config or the scratch cap (touch_scene); any
+    // doubt -- a buffer that grew, a launch that failed, a call without lists -- clears tl_key.valid and the next call builds.
+    uint64_t scene_gen = 0;
+    struct TileListKey {
+        bool valid = false;
+        uint64_t scene_gen = 0;
+        RtxCamera cam{};
+        uint32_t width = 0, height = 0, row_begin = 0, row_stride = 0, row_block = 0, n_rows = 0, tiles_x = 0;
+        uint32_t kernel = 0, tuning = 0;                      // the list form: RTX_KERNEL_BVH a sphere tree's entries, RTX_KERNEL_WAVEFRONT a mesh's pairs
+        const void *buffer = nullptr; size_t bytes = 0;       // the handle's buffer and what the plan carved of it
+    } tl_key;
 #ifdef RTX_LAB
-    // (lab) rtx_debug_tile_lists: the shape of the lists the last render call asked its launch to build -- 0 none, 1 a sphere tree's
-    // TileEntry lists, 2 the {entry, t_lb} pairs of a mesh or joint tree --, its tile grid
-    uint32_t tl_form = 0, tl_tiles_x = 0, tl_tiles = 0;
+    // (lab) rtx_debug_tile_lists: the shape of the lists the last render call handed its launch -- 0 none, 1 a sphere tree's
+    // TileEntry lists, 2 the {entry, t_lb} pairs of a mesh or joint tree --, its tile grid; the launches this handle's calls
+    // asked to BUILD lists (info[5]: a call that finds its frame's lists in the buffer adds none)
+    uint32_t tl_form = 0, tl_tiles_x = 0, tl_tiles = 0, tl_builds = 0;
 #endif
     PathStep *transcript = nullptr; uint32_t *transcript_counts = nullptr; uint32_t transcript_steps = 0;   // (lab) rtx_debug_paths, set for one call
     Counters *counters = nullptr;
@@ -89,6 +103,10 @@ struct RtxSceneHandle_ {
 };
 
 RTX_HOST_BEGIN
+
+// Called by every entry point and helper that may change what the tile lists were built from (the resident arrays, h->sv, the camera,
+// the config, the scratch cap), before it changes anything: the lists in the handle's buffer are then nobody's (tl_key).
+inline void touch_scene(RtxSceneHandle_ *h) { ++h->scene_gen; h->tl_key.valid = false; }
 
 // the non-zero mask of a launch's sample records (store_sample, rtx_device.h): one bit per ray-queue slot, in whole 32-bit words
 inline size_t nonzero_mask_bytes(uint64_t n_rays) { return (size_t)((n_rays + 31) / 32) * sizeof(uint32_t); }
