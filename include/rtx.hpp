@@ -350,7 +350,7 @@ class Scene::Resident {
 public:
     Resident(const Resident &) = delete;
     Resident &operator=(const Resident &) = delete;
-    Resident(Resident &&o) noexcept : h_(o.h_), n_objects_(o.n_objects_) { o.h_ = nullptr; }
+    Resident(Resident &&o) noexcept : h_(o.h_), n_objects_(o.n_objects_), device_(o.device_) { o.h_ = nullptr; }
     ~Resident() { if (h_) rtx_scene_free(h_); }
 
     void set_camera(const Camera &camera)                              // Camera::set_position / set_direction, camera.rs:35-40
@@ -521,13 +521,22 @@ public:
     {
         check(rtx_scene_pixel_features_blocks(h_, (uint32_t)width, (uint32_t)height, block_rows, part, n_parts, d_features, hip_stream, stats));
     }
+    // the denoiser on this scene's device (rtx_denoise_device; it reads no scene): the full frame d_rgb[height][width][3] with its
+    // guides d_features (pixel_features) and, or null, the variance of the mean d_var -> d_out (and d_var_out, or null).  d_work:
+    // rtx::denoise_work_bytes(width, height, params) bytes.  Only enqueues on hip_stream.
+    void denoise(std::size_t width, std::size_t height, const double *d_rgb, const double *d_var, const RtxPixelFeatures *d_features,
+                 const RtxDenoiseParams &params, double *d_out, double *d_var_out, void *d_work, void *hip_stream = nullptr)
+    {
+        check(rtx_denoise_device(d_rgb, d_var, d_features, (uint32_t)width, (uint32_t)height, &params, d_out, d_var_out, d_work, device_, hip_stream));
+    }
 
 private:
     friend class Scene;
-    Resident(RtxSceneHandle h, std::size_t n_objects) : h_(h), n_objects_(n_objects) {}
+    Resident(RtxSceneHandle h, std::size_t n_objects, int device) : h_(h), n_objects_(n_objects), device_(device) {}
     static void check(int32_t rc) { if (rc != RTX_OK) throw Panic(rc, rtx_last_error()); }
     RtxSceneHandle h_;
     std::size_t n_objects_;
+    int device_;
 };
 
 inline Scene::Resident Scene::upload(int device) const
@@ -537,7 +546,35 @@ inline Scene::Resident Scene::upload(int device) const
     RtxSceneHandle h = nullptr;
     int32_t rc = rtx_scene_upload(&sc, device, &h);
     if (rc != RTX_OK) throw Panic(rc, rtx_last_error());
-    return Resident(h, packed.size());
+    return Resident(h, packed.size(), device);
+}
+
+// The denoiser of include/rtx_hip.h ("Denoising"): an edge-avoiding a-trous filter guided by a frame's pixel features and, when there
+// is one, by the variance of its mean.
+inline RtxDenoiseParams denoise_default_params()
+{
+    RtxDenoiseParams p;
+    rtx_denoise_default_params(&p);
+    return p;
+}
+inline std::uint64_t denoise_work_bytes(std::size_t width, std::size_t height, const RtxDenoiseParams &params)
+{
+    return rtx_denoise_work_bytes((uint32_t)width, (uint32_t)height, &params);
+}
+// host form (rtx_denoise: device 0, copies both ways): rgb [height][width][3], features from Scene::pixel_features, var (may be empty: no
+// colour term) the per-channel variance of the mean -> the denoised frame; var_out (optional, needs var): the filtered variance
+inline std::vector<double> denoise(const std::vector<double> &rgb, const std::vector<RtxPixelFeatures> &features, std::size_t width,
+                                   std::size_t height, const RtxDenoiseParams &params = denoise_default_params(),
+                                   const std::vector<double> &var = {}, std::vector<double> *var_out = nullptr)
+{
+    if (rgb.size() != 3 * width * height || features.size() != width * height || (!var.empty() && var.size() != rgb.size()))
+        throw Panic(RTX_ERR_INVALID_ARGUMENT, "denoise: rgb, var and features must hold width * height pixels");
+    std::vector<double> out(rgb.size());
+    if (var_out) var_out->assign(var.empty() ? 0 : rgb.size(), 0.0);
+    int32_t rc = rtx_denoise(rgb.data(), var.empty() ? nullptr : var.data(), features.data(), (uint32_t)width, (uint32_t)height, &params,
+                             out.data(), (var_out && !var.empty()) ? var_out->data() : nullptr);
+    if (rc != RTX_OK) throw Panic(rc, rtx_last_error());
+    return out;
 }
 
 }  // namespace rtx

@@ -638,6 +638,91 @@ int32_t rtx_pixel_features(const RtxScene *scene, uint32_t width, uint32_t heigh
 int32_t rtx_quantize_image_device(const double *d_rgb, uint32_t width, uint32_t height,
                                   uint8_t *d_rgb8, int32_t device, void *stream);
 
+/* Denoising a low-sample frame: an edge-avoiding a-trous (dilated B3-spline) wavelet filter over a full [y][x] f64 frame in device
+ * memory, guided by the frame's RtxPixelFeatures and, when the caller has it, by the per-pixel variance of the mean, which is filtered
+ * along with the colour (the spatial filter of SVGF, no temporal part).  What a 4 to 64 spp frame of rtx_render_blocks_accumulate goes
+ * through before rtx_quantize_image_device.  The call takes no scene handle.  Only the FULL frame: a band cannot be filtered without
+ * its neighbours' rows, so the bands of a multi-device render are gathered first; multi-device denoising is out of scope.
+ *
+ * This comment is the specification: every operation below is one separately rounded f64 operation (IEEE add, subtract, multiply,
+ * divide; never fused), in exactly the written order and bracketing, so plain numpy (tests/denoise_model.py) gives the same bits.
+ * Comparisons with a NaN are false.  "finite" means neither NaN nor an infinity.  Pixel p = (x, y), row 0 = the reference's row 0;
+ * c = d_rgb[3 p ..], var = d_var[3 p ..], and e = emission, a = albedo, n = normal, z = depth of d_features[p].  D = the flag
+ * RTX_DENOISE_DEMODULATE; V = (d_var != NULL).
+ *
+ * Preparation, per pixel and channel k:
+ *     D:      u_k = a_k > albedo_min ? (c_k - e_k) / a_k : (c_k - e_k)        V: v_k = a_k > albedo_min ? var_k / (a_k * a_k) : var_k
+ *     not D:  u_k = c_k                                                      V: v_k = var_k
+ *     V:      nv = (v_0 + v_1) + v_2            -- taken again from the new v after every pass
+ *
+ * Pass i = 0 .. passes - 1 has step s = 2^i and maps (u, v, nv) to (u', v', nv') for every pixel at once (all reads see the pass's
+ * input).  For centre p:
+ *   - a centre with a u_p component that is not finite keeps u' = u_p, v' = v_p.  Else:
+ *   - V: gv = g / gw with g = gw = +0.0 and, for dy = -1, 0, 1 (outer) and dx = -1, 0, 1 (inner), for every q = p + (dx, dy) inside
+ *     the frame: g = g + m * nv_q, gw = gw + m, m = {1, 2, 1}[dx + 1] * {1, 2, 1}[dy + 1];   cden = (sigma_color * sigma_color) * gv +
+ *     epsilon
+ *   - sc_k = sv_k = sw = +0.0, then for dy = -2 .. 2 (outer) and dx = -2 .. 2 (inner) the tap q = p + s * (dx, dy):
+ *       h  = b[dx + 2] * b[dy + 2], b = {1/16, 1/4, 3/8, 1/4, 1/16}                                  (dyadic: exact)
+ *       the centre tap (dx = dy = 0): w = h.  Any other tap: skipped when q is outside the frame, else
+ *       wn = 1 when normal_power_log2 == RTX_DENOISE_NO_NORMAL, else t = (n_p.x * n_q.x + n_p.y * n_q.y) + n_p.z * n_q.z;
+ *            t = t > 0 ? t : 0;  normal_power_log2 times: t = t * t;  wn = t
+ *       wz = 1 when sigma_depth == +inf; else, both z_p and z_q finite: r = (z_p - z_q) / (sigma_depth * (z_p + z_q)),
+ *            wz = 1 / (1 + r * r); neither finite: wz = 1; exactly one finite: wz = 0
+ *       wa = 1 when sigma_albedo == +inf; else d_k = a_p,k - a_q,k, da = (d_0 * d_0 + d_1 * d_1) + d_2 * d_2,
+ *            wa = 1 / (1 + da / (sigma_albedo * sigma_albedo))
+ *       wc = 1 when not V or sigma_color == +inf; else d_k = u_p,k - u_q,k, d2 = (d_0 * d_0 + d_1 * d_1) + d_2 * d_2,
+ *            wc = 1 / (1 + d2 / cden)
+ *       w  = (((h * wn) * wz) * wa) * wc
+ *       the tap is skipped when !(w > 0) (which removes a NaN weight too) or when a component of u_q is not finite; a tap that is
+ *       kept adds  sc_k = sc_k + w * u_q,k,   sw = sw + w,   V: sv_k = sv_k + (w * w) * v_q,k
+ *   - u'_k = sc_k / sw;   V: v'_k = sv_k / (sw * sw), nv' = (v'_0 + v'_1) + v'_2.     (The centre tap is always kept: sw >= 9/64.)
+ *
+ * After the last pass:  D: d_out[3 p + k] = a_k > albedo_min ? u_k * a_k + e_k : u_k + e_k  (the multiply is rounded, then the add);
+ * not D: d_out = u.  d_var_out (V only) likewise: D && a_k > albedo_min ? v_k * (a_k * a_k) : v_k.  With passes == 0 d_out is a byte
+ * copy of d_rgb and d_var_out one of d_var: no arithmetic at all.
+ *
+ * Buffers.  d_rgb, d_out: width * height * 3 doubles.  d_var (may be NULL: no colour term, no variance is tracked) and d_var_out (may
+ * be NULL; must be NULL when d_var is): the same.  d_features: width * height records.  d_work: rtx_denoise_work_bytes(width, height,
+ * params) bytes, 16-byte aligned (may be NULL when that is 0): the packed 128-byte pixel records {u, v, nv, z, n, a} of a pass's input
+ * and output -- one buffer for one pass, two for more.  The library allocates nothing and reads nothing it has not written itself in
+ * d_out, d_var_out and d_work.  rtx_denoise_device only enqueues on `stream` (a hipStream_t; NULL = the device's null stream): one
+ * preparation launch and one launch per pass.
+ * RTX_ERR_INVALID_ARGUMENT, decided before any device is looked for: a NULL params, d_rgb, d_features, d_out, or d_work where work
+ * bytes are needed; a d_var_out without d_var; a misaligned d_work; any overlap among the input, output and work buffers; width *
+ * height == 0 or >= 2^32 - 16; passes > RTX_DENOISE_MAX_PASSES; a flag bit other than RTX_DENOISE_DEMODULATE; normal_power_log2 > 8
+ * and not RTX_DENOISE_NO_NORMAL; reserved != 0; a sigma that is NaN or <= 0 (+inf is allowed: it deletes the term); epsilon or
+ * albedo_min NaN, negative or infinite.  rtx_denoise_work_bytes returns 0 for arguments the call would refuse.
+ * (DESIGN.md 3.14 "Denoising".) */
+#define RTX_DENOISE_MAX_PASSES 8
+#define RTX_DENOISE_DEMODULATE 1u
+#define RTX_DENOISE_NO_NORMAL  0xFFFFFFFFu
+typedef struct RtxDenoiseParams {
+    uint32_t passes;             /* 0..RTX_DENOISE_MAX_PASSES; pass i uses step 2^i */
+    uint32_t flags;              /* RTX_DENOISE_DEMODULATE or 0 */
+    uint32_t normal_power_log2;  /* 0..8: the clamped normal dot product is squared this many times; RTX_DENOISE_NO_NORMAL: no normal term */
+    uint32_t reserved;           /* must be 0 */
+    double   sigma_color;        /* > 0, in standard deviations of the pixel's own noise; +inf: no colour term */
+    double   sigma_depth;        /* > 0, relative depth difference at which the weight is 1/2; +inf: no depth term */
+    double   sigma_albedo;       /* > 0, albedo distance at which the weight is 1/2; +inf: no albedo term */
+    double   epsilon;            /* >= 0, finite: added to the colour term's denominator */
+    double   albedo_min;         /* >= 0, finite: channels with albedo at or below it are not demodulated */
+} RtxDenoiseParams;
+RTX_STATIC_ASSERT(sizeof(RtxDenoiseParams) == 56 && offsetof(RtxDenoiseParams, flags) == 4 && offsetof(RtxDenoiseParams, normal_power_log2) == 8 &&
+                  offsetof(RtxDenoiseParams, reserved) == 12 && offsetof(RtxDenoiseParams, sigma_color) == 16 &&
+                  offsetof(RtxDenoiseParams, sigma_depth) == 24 && offsetof(RtxDenoiseParams, sigma_albedo) == 32 &&
+                  offsetof(RtxDenoiseParams, epsilon) == 40 && offsetof(RtxDenoiseParams, albedo_min) == 48, "RtxDenoiseParams layout");
+
+/* The defaults (DESIGN.md 3.14 records how they were chosen): 5 passes, RTX_DENOISE_DEMODULATE, normal_power_log2 = 0, sigma_color = 2,
+ * sigma_depth = 0.1, sigma_albedo = 0.5, epsilon = 1e-10, albedo_min = 1e-3. */
+void     rtx_denoise_default_params(RtxDenoiseParams *out);
+uint64_t rtx_denoise_work_bytes(uint32_t width, uint32_t height, const RtxDenoiseParams *params);
+int32_t  rtx_denoise_device(const double *d_rgb, const double *d_var, const RtxPixelFeatures *d_features, uint32_t width, uint32_t height,
+                            const RtxDenoiseParams *params, double *d_out, double *d_var_out, void *d_work, int32_t device, void *stream);
+/* One-shot host form (device 0: allocates, copies, denoises, copies back), as rtx_closest_hits.  Every pointer is a HOST array; var and
+ * var_out may be NULL as above. */
+int32_t  rtx_denoise(const double *rgb, const double *var, const RtxPixelFeatures *features, uint32_t width, uint32_t height,
+                     const RtxDenoiseParams *params, double *out, double *var_out);
+
 /* Test hook (lab library; the product returns RTX_ERR_UNSUPPORTED -- same sources and flags, so the arithmetic it shows is the
  * product's): evaluates one f64 operation per element on the device (op 0: a/b, 1: sqrt(a),
  * 2: sin(a), 3: cos(a), 4 / 5: sincos(a)'s two results; 6: the packet walks' v_writelane -- out[i] = (int)b[0] in lane (int)b[1]

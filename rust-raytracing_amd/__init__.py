@@ -23,11 +23,13 @@ from .abi import (RTX_TUNE_NO_TILES, RTX_TUNE_NO_QNODES, RTX_TUNE_NO_PACKETS, RT
                   RTX_TUNE_TWO_STAGE, RTX_TUNE_BVH_MEDIAN, RTX_TUNE_TRI_LEAF_SHIFT, RTX_TUNE_THRESH_SHIFT, RTX_TUNE_PK_LDS_STACK, RTX_TUNE_NO_CUT, RTX_TUNE_INLINE_LEAVES, RTX_TUNE_HALVES, RTX_TUNE_NO_HALVES, RTX_TUNE_NO_TILE_LISTS)
 from .abi import (OBJECT_DTYPE, RTX_KERNEL_WAVEFRONT, RTX_KERNEL_AUTO, RTX_KERNEL_BVH, RTX_KERNEL_EXACT, RTX_KERNEL_MIXED, RTX_KERNEL_MIXED_VERIFY, RTX_KERNEL_BVH_REGROUP,
                   RTX_PLANE, RTX_SPHERE, RTX_TRIANGLE, RtxError, load_library, RAY_DTYPE, HIT_DTYPE, FEATURE_DTYPE)
+from .abi import DENOISE_PARAMS_DTYPE, RTX_DENOISE_DEMODULATE, RTX_DENOISE_MAX_PASSES, RTX_DENOISE_NO_NORMAL
 
 __all__ = ["LabKernel", "Vector3", "Material", "Sphere", "Plane", "Triangle", "Object", "Config", "Camera", "Scene",
            "SceneHandle", "RtxError", "device_count", "pack_objects", "OBJECT_DTYPE",
            "RTX_KERNEL_AUTO", "RTX_KERNEL_EXACT", "RTX_KERNEL_MIXED", "RTX_KERNEL_MIXED_VERIFY", "RTX_KERNEL_BVH", "RTX_KERNEL_BVH_REGROUP", "RTX_KERNEL_WAVEFRONT", "debug_host_scene",
-           "RAY_DTYPE", "HIT_DTYPE", "FEATURE_DTYPE", "make_rays"]
+           "RAY_DTYPE", "HIT_DTYPE", "FEATURE_DTYPE", "make_rays", "denoise", "denoise_params", "denoise_work_bytes", "DENOISE_PARAMS_DTYPE",
+           "RTX_DENOISE_DEMODULATE", "RTX_DENOISE_MAX_PASSES", "RTX_DENOISE_NO_NORMAL"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -339,6 +341,67 @@ def _split_hits(hits):
 def _split_features(f):
     """RtxPixelFeatures records -> (albedo, emission, normal, depth, coverage, object) numpy arrays"""
     return (f["albedo"].copy(), f["emission"].copy(), f["normal"].copy(), f["depth"].copy(), f["coverage"].copy(), f["object"].copy())
+
+
+def denoise_params(lib=None, **kw):
+    """One RtxDenoiseParams record (DENOISE_PARAMS_DTYPE, shape ()): the library's defaults (rtx_denoise_default_params) with the given
+    fields replaced.  Besides the struct's own fields: demodulate=True / False sets the flag, normal_power_log2=None means
+    RTX_DENOISE_NO_NORMAL, and a sigma of None means +inf (the term is off)."""
+    lib = lib or load_library()
+    p = np.zeros((), dtype=DENOISE_PARAMS_DTYPE)
+    lib.rtx_denoise_default_params(p.ctypes.data)
+    for k, v in kw.items():
+        if k == "demodulate":
+            p["flags"] = (int(p["flags"]) | RTX_DENOISE_DEMODULATE) if v else (int(p["flags"]) & ~RTX_DENOISE_DEMODULATE)
+        elif k == "normal_power_log2" and v is None:
+            p[k] = RTX_DENOISE_NO_NORMAL
+        elif k in ("sigma_color", "sigma_depth", "sigma_albedo") and v is None:
+            p[k] = np.inf
+        elif k in DENOISE_PARAMS_DTYPE.names:
+            p[k] = v
+        else:
+            raise TypeError("denoise: unknown parameter %r" % k)
+    return p
+
+
+def denoise_work_bytes(width, height, params=None):
+    """rtx_denoise_work_bytes: the work buffer SceneHandle.denoise_device needs (0 for arguments the call would refuse)"""
+    lib = load_library()
+    p = params if params is not None else denoise_params(lib)
+    return int(lib.rtx_denoise_work_bytes(int(width), int(height), p.ctypes.data))
+
+
+def _features_records(features, height, width):
+    """the tuple of Scene.features / SceneHandle.features, or RtxPixelFeatures records, -> a contiguous [height][width] record array"""
+    if isinstance(features, np.ndarray) and features.dtype == FEATURE_DTYPE:
+        f = np.ascontiguousarray(features).reshape(height, width)
+    else:
+        f = np.zeros((height, width), dtype=FEATURE_DTYPE)
+        names = ("albedo", "emission", "normal", "depth", "coverage", "object")
+        if len(features) != len(names):
+            raise ValueError("denoise: features must be the (albedo, emission, normal, depth, coverage, object) of features()")
+        for name, a in zip(names, features):
+            f[name] = np.asarray(a).reshape(f[name].shape)
+    return f
+
+
+def denoise(img, features, variance=None, **params):
+    """The edge-avoiding a-trous filter of include/rtx_hip.h ("Denoising") on a host frame (rtx_denoise: device 0, copies both ways).
+    img: (height, width, 3) float64; features: what Scene.features / SceneHandle.features returned for the same frame (or the
+    RtxPixelFeatures records); variance: the per-channel variance of the mean (Progressive.variance()), or None -- then there is no
+    colour term.  params: fields of RtxDenoiseParams over the library's defaults (denoise_params).  Returns the denoised frame, and
+    with a variance the pair (frame, filtered variance)."""
+    img = np.ascontiguousarray(img, dtype=np.float64)
+    height, width = img.shape[0], img.shape[1]
+    lib = load_library()
+    p = denoise_params(lib, **params)
+    f = _features_records(features, height, width)
+    var = None if variance is None else np.ascontiguousarray(variance, dtype=np.float64).reshape(img.shape)
+    out = np.zeros_like(img)
+    var_out = None if var is None else np.zeros_like(img)
+    abi.check(lib.rtx_denoise(img.ctypes.data, var.ctypes.data if var is not None else None, f.ctypes.data, width, height, p.ctypes.data,
+                              out.ctypes.data, var_out.ctypes.data if var_out is not None else None), lib)
+    return out if var is None else (out, var_out)
 
 
 class Scene:
@@ -872,6 +935,16 @@ class SceneHandle:
         f = d_out[:n * FEATURE_DTYPE.itemsize].cpu().numpy().view(FEATURE_DTYPE).reshape(int(height), int(width))
         return _split_features(f)
 
+    def denoise_device(self, width, height, d_rgb_ptr, d_features_ptr, d_out_ptr, d_work_ptr, d_var_ptr=None, d_var_out_ptr=None,
+                       stream=None, params=None, **kw):
+        """rtx_denoise_device on this handle's device: every pointer a device address of a full [height][width] frame (d_work_ptr:
+        denoise_work_bytes(width, height, params) bytes).  Only enqueues on `stream`.  params: a denoise_params record, or its fields
+        as keywords."""
+        p = params if params is not None else denoise_params(self._lib, **kw)
+        ptr = lambda a: C.c_void_p(int(a)) if a else None
+        self._check(self._lib.rtx_denoise_device(ptr(d_rgb_ptr), ptr(d_var_ptr), ptr(d_features_ptr), int(width), int(height), p.ctypes.data,
+                                                 ptr(d_out_ptr), ptr(d_var_out_ptr), ptr(d_work_ptr), self.device, ptr(stream)))
+
     def close(self):
         if self._h:
             h, self._h = self._h, C.c_void_p()
@@ -977,6 +1050,29 @@ class Progressive:
             raise ValueError("variance() needs moments=True")
         n = self.count.to(self.sum.dtype)[..., None]
         return ((self.sum_sq - self.sum * self.sum / n) / (n - 1.0) / n).cpu().numpy()
+
+    def denoise(self, **params):
+        """The frame so far through the denoiser, on the device: the mean, the variance of the mean (when moments=True and every pixel
+        has two samples or more; else no colour term) and the handle's pixel features (at its rays_per_pixel) go to
+        rtx_denoise_device.  params: fields of RtxDenoiseParams over the defaults (denoise_params).  -> numpy (h, w, 3)"""
+        import torch
+        dev = self.sum.device
+        n = self.count.to(self.sum.dtype)[..., None]
+        mean = (self.sum / n).contiguous()
+        var = None
+        if self.sum_sq is not None and int(self.count.min()) >= 2:
+            var = ((self.sum_sq - self.sum * self.sum / n) / (n - 1.0) / n).contiguous()
+        p = denoise_params(self._hnd._lib, **params)
+        npix = self.width * self.height
+        feat = torch.empty(npix * FEATURE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        work = torch.empty(max(int(self._hnd._lib.rtx_denoise_work_bytes(self.width, self.height, p.ctypes.data)), 16), dtype=torch.uint8, device=dev)
+        out = torch.empty_like(mean)
+        torch.cuda.synchronize(dev)
+        self._hnd.pixel_features(self.width, self.height, feat.data_ptr(), want_stats=True)
+        self._hnd.denoise_device(self.width, self.height, mean.data_ptr(), feat.data_ptr(), out.data_ptr(), work.data_ptr(),
+                                 d_var_ptr=var.data_ptr() if var is not None else None, params=p)
+        torch.cuda.synchronize(dev)
+        return out.cpu().numpy()
 
 
 HOST_SCENE_STATS = ("spheres", "triangles", "tri_filter_records", "tri_in_tree", "wide_nodes", "depth", "binary_nodes", "flags",

@@ -34,6 +34,7 @@ RTX_TUNE_KNOWN_MASK = (RTX_TUNE_LAB_MASK | RTX_TUNE_NO_TILES | RTX_TUNE_ONE_STAG
 RTX_UPDATE_AUTO, RTX_UPDATE_REBUILD, RTX_UPDATE_DEFORM = 0, 1, 2
 RTX_UPDATED_NOTHING, RTX_UPDATED_RECORDS, RTX_UPDATED_REFIT, RTX_UPDATED_REBUILT = 0, 1, 2, 3
 RTX_MULTI_HIT_MAX = 32                       # rtx_scene_multi_hits: 1 <= k <= this
+RTX_DENOISE_MAX_PASSES, RTX_DENOISE_DEMODULATE, RTX_DENOISE_NO_NORMAL = 8, 1, 0xFFFFFFFF   # RtxDenoiseParams
 RTX_OK, RTX_ERR_INVALID_ARGUMENT, RTX_ERR_NO_DEVICE, RTX_ERR_HIP, RTX_ERR_UNSUPPORTED, RTX_ERR_OUT_OF_MEMORY = range(6)
 
 # RtxObject, 136 bytes: one entry of Scene.objects (scene.rs:80; object.rs:9-15,78-86)
@@ -81,6 +82,12 @@ class RtxPixelFeatures(C.Structure):
                 ("coverage", C.c_double), ("object", C.c_int64)]
 
 
+class RtxDenoiseParams(C.Structure):
+    _fields_ = [("passes", C.c_uint32), ("flags", C.c_uint32), ("normal_power_log2", C.c_uint32), ("reserved", C.c_uint32),
+                ("sigma_color", C.c_double), ("sigma_depth", C.c_double), ("sigma_albedo", C.c_double), ("epsilon", C.c_double),
+                ("albedo_min", C.c_double)]
+
+
 # the same layouts as numpy records (arrays of rays / answers)
 RAY_DTYPE = np.dtype([("position", "<f8", (3,)), ("direction", "<f8", (3,))])
 HIT_DTYPE = np.dtype([("position", "<f8", (3,)), ("normal", "<f8", (3,)), ("distance", "<f8"), ("object", "<i8")])
@@ -88,6 +95,10 @@ FEATURE_DTYPE = np.dtype([("albedo", "<f8", (3,)), ("emission", "<f8", (3,)), ("
                           ("coverage", "<f8"), ("object", "<i8")])
 assert RAY_DTYPE.itemsize == C.sizeof(RtxRay) == 48 and HIT_DTYPE.itemsize == C.sizeof(RtxHit) == 64
 assert FEATURE_DTYPE.itemsize == C.sizeof(RtxPixelFeatures) == 96
+DENOISE_PARAMS_DTYPE = np.dtype([("passes", "<u4"), ("flags", "<u4"), ("normal_power_log2", "<u4"), ("reserved", "<u4"),
+                                 ("sigma_color", "<f8"), ("sigma_depth", "<f8"), ("sigma_albedo", "<f8"), ("epsilon", "<f8"),
+                                 ("albedo_min", "<f8")])
+assert DENOISE_PARAMS_DTYPE.itemsize == C.sizeof(RtxDenoiseParams) == 56
 
 
 # every symbol include/rtx_hip.h declares: (name, restype, argtypes)
@@ -141,6 +152,11 @@ SYMBOLS = [
                                                     C.c_void_p, C.c_void_p, C.POINTER(RtxStats)]),
     ("rtx_pixel_features", C.c_int32, [C.POINTER(RtxScene), C.c_uint32, C.c_uint32, C.c_void_p]),
     ("rtx_quantize_image_device", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("rtx_denoise_default_params", None, [C.c_void_p]),
+    ("rtx_denoise_work_bytes", C.c_uint64, [C.c_uint32, C.c_uint32, C.c_void_p]),
+    ("rtx_denoise_device", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_int32, C.c_void_p]),
+    ("rtx_denoise", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rtx_debug_math", C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
     ("rtx_debug_paths", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("rtx_debug_store_samples", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),

@@ -254,6 +254,10 @@ int32_t check_scene_args(const RtxScene *scene, const char *who)
     return check_config(scene->config);
 }
 
+}  // namespace
+
+RTX_HOST_BEGIN
+
 int32_t check_device(int32_t device, const char *who)
 {
     int n_dev = 0;
@@ -265,6 +269,10 @@ int32_t check_device(int32_t device, const char *who)
     if (!device_is_gfx950(device)) return fail(RTX_ERR_NO_DEVICE, "device is not gfx950 (MI355X); this library targets gfx950 only");
     return RTX_OK;
 }
+
+RTX_HOST_END
+
+namespace {
 
 // A handle on `device` holding an already packed scene (one pack serves every device of rtx_render_devices).
 int32_t create_handle(const RtxScene *scene, const PackedScene &p, int32_t device, RtxSceneHandle_ **out)
@@ -375,7 +383,10 @@ int32_t begin_launches(RtxSceneHandle_ *h, hipStream_t stream)
     return RTX_OK;
 }
 
-struct Range { const void *base; size_t bytes; };      // one of the caller's arrays (a null base: an optional one that was not given)
+}  // namespace
+
+RTX_HOST_BEGIN
+
 bool ranges_overlap(const Range *r, int n)
 {
     for (int i = 0; i < n; ++i)
@@ -386,7 +397,7 @@ bool ranges_overlap(const Range *r, int n)
     return false;
 }
 
-}  // namespace
+RTX_HOST_END
 
 extern "C" {
 

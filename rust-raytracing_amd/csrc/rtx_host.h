@@ -129,6 +129,9 @@ struct DoneGuard {
 
 // rtx_api.hip
 int usable_device_count();
+int32_t check_device(int32_t device, const char *who);      // a usable gfx950 `device`, or the status with the error text set
+struct Range { const void *base; size_t bytes; };            // one of the caller's arrays (a null base: an optional one that was not given)
+bool ranges_overlap(const Range *r, int n);
 void drop_update_tables(RtxSceneHandle_ *h);
 int32_t upload_packed(RtxSceneHandle_ *h, const PackedScene &p);
 int32_t check_watchdog(RtxSceneHandle_ *h, bool wait);

@@ -116,6 +116,26 @@ hipError_t launch_deinterleave_u8(const uint8_t *parts, uint8_t *full, uint32_t 
 // `* 256`, saturating `as u8` (scene.rs:175-178) of the n_rows x width pixels of a band in place order (before it travels: no flip)
 hipError_t launch_quantize_values(const double *rgb, uint8_t *rgb8, uint32_t width, uint32_t n_rows, hipStream_t stream);
 
+// ---- denoising (rtx_denoise_device; device text: rtx_denoise.h, host side: rtx_denoise.hip): two more launch-uniform forms of
+// epilogue_kernel -- the preparation (one pixel per thread: frame, variance and features -> the packed 128-byte records) and one
+// a-trous pass (a 16 x 16 tile of one sub-lattice per workgroup, staged with its halo in dynamic LDS, which the other forms do not ask for)
+struct QueryFeatures;
+enum : uint32_t { kDnDemodulate = 1u, kDnVariance = 2u, kDnColor = 4u, kDnDepth = 8u, kDnAlbedo = 16u, kDnNormal = 32u };
+struct DenoiseArgs {
+    const double *rgb, *var;       // the preparation's inputs (var: null without kDnVariance)
+    const QueryFeatures *feat;     // the preparation's guides; the last pass's emission
+    const double *src;             // a pass's input records
+    double *dst;                   // the records the preparation or a pass writes; null: the last pass, which writes ...
+    double *out, *var_out;         // ... the frame (and the variance, or null)
+    double sigma_color2, sigma_depth, sigma_albedo2, epsilon, albedo_min;      // (the squares: one rounded multiply on the host)
+    uint32_t width, height, step, flags;                      // flags: kDn* -- which terms exist
+    uint32_t normal_power_log2, sub_x, tiles_x, tiles;        // a pass's grid: sub-lattice = blockIdx / tiles (x fastest, sub_x =
+                                                              // min(step, width) of them per row), tile = blockIdx % tiles
+};
+hipError_t launch_denoise_prepare(const DenoiseArgs &d, hipStream_t stream);
+// one pass of step d.step; fills in the grid fields of its copy of d.  hipErrorInvalidValue: a grid of 2^31 workgroups or more
+hipError_t launch_denoise_pass(const DenoiseArgs &d, hipStream_t stream);
+
 // ---- ray queries (rtx_query.hip): closest_object for caller rays or for the pick buffer's zero-offset primary rays, or -- the
 // any-hit mode, a launch-uniform switch of the same kernel -- whether any object lies before a per-ray distance limit, or -- the
 // path mode, a third switch -- render_ray's colour of the path that starts with the ray, or -- the feature mode, a fourth -- the
