@@ -66,6 +66,13 @@ __device__ __forceinline__ bool query_dir_ok(V3 d)
     return fabs(n2 - 1.0) <= kQueryDirTol;                        // (NaN / inf components: false)
 }
 
+// the sphere leaves' ray for a tree that may hold none: idle (no sphere record passes) unless the tree has sphere leaves
+__device__ __forceinline__ void query_sphere_ray(const SceneView &sv, V3 pos, V3 dir, SphereRay &sr)
+{
+    sr.px = sr.py = sr.pz = sr.dx = sr.dy = sr.dz = sr.Kg = sr.K = 0.f; sr.c0 = __builtin_inff();
+    if (sv.bvh_flags & 1u) sphere_ray_from(sv, pos, dir, sr);
+}
+
 // every shape exactly (spheres, planes, then every triangle -- Scene.objects order decides ties through hit_consider)
 __device__ __forceinline__ void query_sweep(const SceneView &sv, const LeafArrays &la, const RayX &rx, bool spheres, bool tris, Hit &h,
                                             unsigned long long &exact)
@@ -228,8 +235,7 @@ __device__ __forceinline__ uint32_t query_any_ray(const SceneView &sv, const flo
     uint32_t nbox = 0, nleaf = 0;
     if constexpr (TRIS) {
         SphereRay sr;
-        sr.px = sr.py = sr.pz = sr.dx = sr.dy = sr.dz = sr.Kg = sr.K = 0.f; sr.c0 = __builtin_inff();
-        if (sv.bvh_flags & 1u) sphere_ray_from(sv, pos, dir, sr);
+        query_sphere_ray(sv, pos, dir, sr);
         TriFilterParams tpar;
         tri_filter_from_ray(sv, pos, dir, tpar);
         const bool plain = (sv.bvh_flags & 4u) != 0u;
@@ -314,8 +320,7 @@ __device__ __forceinline__ void query_closest_ray(const SceneView &sv, uint32_t 
         uint32_t nbox = 0, nleaf = 0;
         if constexpr (TRIS) {
             SphereRay sr;
-            sr.px = sr.py = sr.pz = sr.dx = sr.dy = sr.dz = sr.Kg = sr.K = 0.f; sr.c0 = __builtin_inff();
-            if (sv.bvh_flags & 1u) sphere_ray_from(sv, pos, dir, sr);
+            query_sphere_ray(sv, pos, dir, sr);
             TriFilterParams tpar;
             tri_filter_from_ray(sv, pos, dir, tpar);
             const bool plain = (sv.bvh_flags & 4u) != 0u;
@@ -801,8 +806,7 @@ __device__ __forceinline__ void query_multi_ray(const SceneView &sv, const float
     uint32_t nbox = 0, nleaf = 0;
     if constexpr (TRIS) {
         SphereRay sr;
-        sr.px = sr.py = sr.pz = sr.dx = sr.dy = sr.dz = sr.Kg = sr.K = 0.f; sr.c0 = __builtin_inff();
-        if (sv.bvh_flags & 1u) sphere_ray_from(sv, pos, dir, sr);
+        query_sphere_ray(sv, pos, dir, sr);
         TriFilterParams tpar;
         tri_filter_from_ray(sv, pos, dir, tpar);
         const bool plain = (sv.bvh_flags & 4u) != 0u;
@@ -1230,10 +1234,9 @@ __global__ __launch_bounds__(kBvhThreads) void debug_path_bounds_kernel(const Sc
     uint32_t flags = a.entries[i] != kNone ? kPbInTree : 0u;
     if (!walk) { out[0] = flags | kPbNoWalk; return; }
     if (!(flags & kPbInTree)) { out[0] = flags; return; }
-    // the ray as query_closest_ray prepares it
+    // the ray as the walks prepare it
     SphereRay sr;
-    sr.px = sr.py = sr.pz = sr.dx = sr.dy = sr.dz = sr.Kg = sr.K = 0.f; sr.c0 = __builtin_inff();
-    if (sv.bvh_flags & 1u) sphere_ray_from(sv, pos, dir, sr);
+    query_sphere_ray(sv, pos, dir, sr);
     TriFilterParams tpar;
     if (sv.bvh_flags & 2u) tri_filter_from_ray(sv, pos, dir, tpar); else tri_filter_idle(tpar);
     if (in32 || (a.form & 1u) == 0u) {

@@ -413,7 +413,8 @@ def test_near_ties_through_the_query_modes(gpu):
 @pytest.mark.parametrize("name", ["spheres200", "tris300", "mixed"])
 def test_a_one_byte_scratch_limit_changes_no_list(gpu, name):
     """one scene per tree kind, the inside and far10 regimes: with set_scratch_limit(1) the walk has no stack columns in memory and the
-    rays whose stack overflows are swept -- the same bytes as with the default limit, which is restored afterwards"""
+    rays whose stack overflows are swept -- the same bytes as with the default limit, which is restored afterwards; any_hits and
+    closest_hits under the limit are held to those lists (occluded == count > 0, the record == the list at k = 1)"""
     import torch
     auto, _ = _handles(name)
     for regime in ("inside", "far10"):
@@ -427,6 +428,12 @@ def test_a_one_byte_scratch_limit_changes_no_list(gpu, name):
                 small, small_cnt, st_small = run_multi(auto, rays, (None, lim)[j], k, torch)
                 assert st.kernel == gpu.RTX_KERNEL_BVH and st_small.kernel == gpu.RTX_KERNEL_BVH
                 assert small.tobytes() == rec.tobytes() and small_cnt.tobytes() == cnt.tobytes(), (name, regime, k, j)
+            # the any-hit and the closest-hit mode under the same limit, the first 256 rays: count > 0 of the list at 32, its first record
+            head = rays[:256].copy()
+            for j, t_max in enumerate((None, lim[:256])):
+                occ, _ = run_any(auto, head, t_max, torch)
+                assert np.array_equal(occ.astype(bool), ref[(KMAX, j)][1][:256] > 0), (name, regime, "any_hits", j)
+            assert run_closest_records(auto, head, torch).tobytes() == ref[(1, 0)][0][:256].reshape(-1).tobytes(), (name, regime, "closest_hits")
         finally:
             auto.set_scratch_limit(0)
         again, again_cnt, _ = run_multi(auto, rays, None, 3, torch)

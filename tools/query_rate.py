@@ -40,14 +40,18 @@ generators and the same parameters:
 The library is the package's (RTX_HIP_LIB selects another build, e.g. one of the parent commit: the legs it lacks are then skipped).
 
 The exact leg runs 2^--exact-rays of the rays (the sweep is ~n_objects tests per ray) and reports its rate on those.  One JSON line per
-scene and leg; the best of --reps timed runs after one warm-up.
+scene and leg; the best of --reps timed runs after one warm-up.  Every line of a query leg also carries the timed call's raw counters
+(segments, exact_tests, filter_tests, box_tests) and the sha256 of the buffers it wrote: equal between two builds of the library that
+compute the same thing, since a lane's work depends only on its own ray.
 """
 import argparse
+import hashlib
 import json
 import os
 import sys
 
 import numpy as np
+import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
@@ -94,6 +98,23 @@ def primary_rays(rtx, cam, width, height):
     return np.broadcast_to(np.array(list(c.position), dtype=np.float64), d.shape), d
 
 
+def raw_counts(st):
+    """the launch counters of the timed call as they are, for comparing two builds of the library: a lane's work depends only on its ray"""
+    return {"segments": int(st.segments), "exact_tests": int(st.exact_tests), "filter_tests": int(st.filter_tests), "box_tests": int(st.box_tests)}
+
+
+def digest(*tensors):
+    """sha256 of what the timed call wrote: the bytes of the device tensors in the order given, read back in 256 MiB pieces.
+    Outside the timed call, but every byte crosses to the host: 1 GiB per line of the 2^24-ray closest-hit legs, 4 GiB for multi4 and
+    16 GiB for multi16 -- seconds per line, most of these legs' wall time."""
+    h = hashlib.sha256()
+    for t in tensors:
+        b = t.contiguous().view(torch.uint8).reshape(-1)
+        for at in range(0, b.numel(), 1 << 28):
+            h.update(b[at:at + (1 << 28)].cpu().numpy())
+    return h.hexdigest()
+
+
 LEGS = ("incoherent", "pick", "exact", "any", "any_short", "any_aimed", "paths", "paths_1seg", "paths_pick", "render_pick", "paths_primary",
         "features", "accumulate", "samples_frame", "samples_sparse", "refine", "multi1", "multi4", "multi16", "multi4_pick", "peel4")
 REFINE = dict(base=8, step=8, cap=64, threshold=0.5, floor=0.01)
@@ -108,7 +129,6 @@ def main():
     ap.add_argument("--legs", default=",".join(LEGS))
     ap.add_argument("--spp", type=int, default=64, help="samples per pixel of the accumulate leg's frame")
     args = ap.parse_args()
-    import torch
 
     import rust_raytracing_amd as rtx
     from rust_raytracing_amd import scenes
@@ -171,7 +191,7 @@ def main():
                                       "mrays_per_s": round(st.segments / (st.trace_ms * 1e-3) / 1e6, 1), "kernel": int(st.kernel),
                                       "exact_tests_per_ray": round(st.exact_tests / st.segments, 2),
                                       "box_tests_per_ray": round(st.box_tests / st.segments, 2),
-                                      "coverage": round(float(f["coverage"].mean()), 4)}), flush=True)
+                                      "coverage": round(float(f["coverage"].mean()), 4), **raw_counts(st), "sha256": digest(d_hits[:k * 96])}), flush=True)
                     hnd.close()
                 continue
             if leg == "accumulate":
@@ -225,7 +245,8 @@ def main():
                                       "trace_ms": round(st.trace_ms, 3), "msamples_per_s": round(k / (st.trace_ms * 1e-3) / 1e6, 1),
                                       "msegments_per_s": round(st.segments / (st.trace_ms * 1e-3) / 1e6, 1), "kernel": int(st.kernel),
                                       "segments_per_sample": round(st.segments / k, 3),
-                                      "lit_fraction": round(float((d_rgb[:3 * k].view(-1, 3) != 0).any(dim=1).float().mean().item()), 4)}), flush=True)
+                                      "lit_fraction": round(float((d_rgb[:3 * k].view(-1, 3) != 0).any(dim=1).float().mean().item()), 4),
+                                      **raw_counts(st), "sha256": digest(d_rgb[:3 * k])}), flush=True)
                     if leg == "samples_frame" and bounces == 10:
                         st = best(lambda: hnd.render_rows(W, H, 0, 1, H, d_rgb.data_ptr()))
                         print(json.dumps({"scene": name, "leg": leg, "form": "render_rows at 1 spp", "samples": k, "segments": int(st.segments),
@@ -268,6 +289,7 @@ def main():
                         else:
                             tot.trace_ms += st.trace_ms; tot.segments += st.segments; tot.primary_rays += st.primary_rays
                             tot.trace_launches += st.trace_launches
+                            tot.exact_tests += st.exact_tests; tot.filter_tests += st.filter_tests; tot.box_tests += st.box_tests
                     assert tot.primary_rays == counts[0][1] and c[2] == 0, (tot.primary_rays, c)
                     return tot
 
@@ -284,13 +306,16 @@ def main():
                                   "trace_ms": round(st_base.trace_ms, 3), "resolve_ms": round(st_base.resolve_ms, 3),
                                   "selected_after_base": round(float((extra > 0).mean()), 4), **r}), flush=True)
                 for run in (1, 2):
-                    for form, fn in (("rtx_render_blocks_refine", refine), ("rtx_render_blocks_refine, a call per round", refine_calls),
-                                     ("rtx_scene_trace_samples", lambda: hnd.trace_samples(W, H, d_ids.data_ptr(), len(ids), d_rgb.data_ptr()))):
+                    for form, fn, wrote in (("rtx_render_blocks_refine", refine, (d_sums, d_extra)),
+                                            ("rtx_render_blocks_refine, a call per round", refine_calls, (d_sums, d_extra)),
+                                            ("rtx_scene_trace_samples", lambda: hnd.trace_samples(W, H, d_ids.data_ptr(), len(ids), d_rgb.data_ptr()),
+                                             (d_rgb,))):
                         st = best(fn)
                         print(json.dumps({"scene": name, "leg": leg, "form": form, "run": run, "pixels": counts[0][0], "samples": len(ids),
                                           "still_selected": counts[0][2], "segments": int(st.segments), "trace_ms": round(st.trace_ms, 3),
                                           "ns_per_sample": round(st.trace_ms * 1e6 / len(ids), 3),
-                                          "msegments_per_s": round(st.segments / (st.trace_ms * 1e-3) / 1e6, 1), "kernel": int(st.kernel)}), flush=True)
+                                          "msegments_per_s": round(st.segments / (st.trace_ms * 1e-3) / 1e6, 1), "kernel": int(st.kernel),
+                                          **raw_counts(st), "sha256": digest(*wrote)}), flush=True)
                 hnd.close()
                 continue
             if leg == "render_pick":
@@ -311,7 +336,8 @@ def main():
                                   "msegments_per_s": round(st.segments / (st.trace_ms * 1e-3) / 1e6, 1), "kernel": int(st.kernel),
                                   "segments_per_ray": round(st.segments / k, 3), "exact_tests_per_ray": round(st.exact_tests / k, 2),
                                   "box_tests_per_ray": round(st.box_tests / k, 2),
-                                  "lit_fraction": round(float((d_rgb[:3 * k].view(-1, 3) != 0).any(dim=1).float().mean().item()), 4)}), flush=True)
+                                  "lit_fraction": round(float((d_rgb[:3 * k].view(-1, 3) != 0).any(dim=1).float().mean().item()), 4),
+                                  **raw_counts(st), "sha256": digest(d_rgb[:3 * k])}), flush=True)
                 hnd.close()
                 continue
             if leg.startswith("any"):
@@ -322,7 +348,8 @@ def main():
                 print(json.dumps({"scene": name, "leg": leg, "rays": k, "trace_ms": round(st.trace_ms, 3),
                                   "mrays_per_s": round(k / (st.trace_ms * 1e-3) / 1e6, 1), "kernel": int(st.kernel),
                                   "exact_tests_per_ray": round(st.exact_tests / k, 2), "box_tests_per_ray": round(st.box_tests / k, 2),
-                                  "occluded_fraction": round(float(d_hits[:k].float().mean().item()), 4)}), flush=True)
+                                  "occluded_fraction": round(float(d_hits[:k].float().mean().item()), 4),
+                                  **raw_counts(st), "sha256": digest(d_hits[:k])}), flush=True)
                 hnd.close()
                 continue
             if leg.startswith("multi"):
@@ -339,7 +366,7 @@ def main():
                                   "mrays_per_s": round(k / (st.trace_ms * 1e-3) / 1e6, 1), "kernel": int(st.kernel),
                                   "exact_tests_per_ray": round(st.exact_tests / k, 2), "box_tests_per_ray": round(st.box_tests / k, 2),
                                   "entries_per_ray": round(float(cnt.mean()), 3), "full_fraction": round(float((cnt == kk).mean()), 4),
-                                  "empty_fraction": round(float((cnt == 0).mean()), 4)}), flush=True)
+                                  "empty_fraction": round(float((cnt == 0).mean()), 4), **raw_counts(st), "sha256": digest(d_multi, d_cnt)}), flush=True)
                 del d_multi, d_cnt
                 hnd.close()
                 continue
@@ -377,7 +404,7 @@ def main():
             print(json.dumps({"scene": name, "leg": leg, "rays": k, "trace_ms": round(st.trace_ms, 3),
                               "mrays_per_s": round(k / (st.trace_ms * 1e-3) / 1e6, 1), "kernel": int(st.kernel),
                               "exact_tests_per_ray": round(st.exact_tests / k, 2), "box_tests_per_ray": round(st.box_tests / k, 2),
-                              "hit_fraction": round(float((hits["object"] >= 0).mean()), 4)}), flush=True)
+                              "hit_fraction": round(float((hits["object"] >= 0).mean()), 4), **raw_counts(st), "sha256": digest(d_hits[:k * 64])}), flush=True)
             hnd.close()
 
 
