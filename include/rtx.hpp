@@ -529,6 +529,18 @@ public:
     {
         check(rtx_denoise_device(d_rgb, d_var, d_features, (uint32_t)width, (uint32_t)height, &params, d_out, d_var_out, d_work, device_, hip_stream));
     }
+    // temporal accumulation on this scene's device (rtx_temporal_accumulate_device; it reads no scene): this frame's d_rgb, d_var (or
+    // null) and pick buffer d_hits with the previous frame's accumulated d_hist_* (all null: the first frame), its camera and the
+    // uploaded rtx::temporal_tables of that camera -> d_out_rgb, d_out_var (or null), d_out_len, d_motion (or null).  Only enqueues.
+    void temporal_accumulate(std::size_t width, std::size_t height, const double *d_rgb, const double *d_var, const RtxHit *d_hits,
+                             const double *d_hist_rgb, const double *d_hist_var, const double *d_hist_len, const RtxHit *d_hist_hits,
+                             const RtxCamera *prev_camera, const double *d_prev_tables, const RtxTemporalParams &params, double *d_out_rgb,
+                             double *d_out_var, double *d_out_len, double *d_motion = nullptr, void *hip_stream = nullptr)
+    {
+        check(rtx_temporal_accumulate_device(d_rgb, d_var, d_hits, d_hist_rgb, d_hist_var, d_hist_len, d_hist_hits, prev_camera, d_prev_tables,
+                                             (uint32_t)width, (uint32_t)height, &params, d_out_rgb, d_out_var, d_out_len, d_motion, device_,
+                                             hip_stream));
+    }
 
 private:
     friend class Scene;
@@ -573,6 +585,54 @@ inline std::vector<double> denoise(const std::vector<double> &rgb, const std::ve
     if (var_out) var_out->assign(var.empty() ? 0 : rgb.size(), 0.0);
     int32_t rc = rtx_denoise(rgb.data(), var.empty() ? nullptr : var.data(), features.data(), (uint32_t)width, (uint32_t)height, &params,
                              out.data(), (var_out && !var.empty()) ? var_out->data() : nullptr);
+    if (rc != RTX_OK) throw Panic(rc, rtx_last_error());
+    return out;
+}
+
+// Temporal accumulation of include/rtx_hip.h ("Temporal accumulation"): the previous frames' samples, reprojected and blended in where
+// the same surface is still seen.
+inline RtxTemporalParams temporal_default_params()
+{
+    RtxTemporalParams p;
+    rtx_temporal_default_params(&p);
+    return p;
+}
+// the sines of a camera's pixel map, Tx[width + 1] then Ty[height + 1]: what Resident::temporal_accumulate takes, uploaded
+inline std::vector<double> temporal_tables(double fov, std::size_t width, std::size_t height)
+{
+    std::vector<double> t(width + height + 2);
+    int32_t rc = rtx_temporal_tables(fov, (uint32_t)width, (uint32_t)height, t.data());
+    if (rc != RTX_OK) throw Panic(rc, rtx_last_error());
+    return t;
+}
+// one frame's buffers on the host: what temporal_accumulate takes as its history and returns as the next one
+struct TemporalFrame {
+    std::vector<double> rgb, var, len;                      // var: empty when no variance is tracked
+    std::vector<RtxHit> hits;
+    std::vector<double> motion;                             // filled when asked for
+};
+// host form (rtx_temporal_accumulate: device 0, copies both ways): rgb [height][width][3], var (may be empty), this frame's pick buffer;
+// history: null on the first frame, else the previous call's result with the camera it was taken with
+inline TemporalFrame temporal_accumulate(const std::vector<double> &rgb, const std::vector<double> &var, const std::vector<RtxHit> &hits,
+                                         std::size_t width, std::size_t height, const TemporalFrame *history = nullptr,
+                                         const RtxCamera *prev_camera = nullptr,
+                                         const RtxTemporalParams &params = temporal_default_params(), bool want_motion = false)
+{
+    const std::size_t n = width * height;
+    if (rgb.size() != 3 * n || hits.size() != n || (!var.empty() && var.size() != 3 * n))
+        throw Panic(RTX_ERR_INVALID_ARGUMENT, "temporal_accumulate: rgb, var and hits must hold width * height pixels");
+    if (history && (history->rgb.size() != 3 * n || history->len.size() != n || history->hits.size() != n ||
+                    (!history->var.empty() && history->var.size() != 3 * n)))
+        throw Panic(RTX_ERR_INVALID_ARGUMENT, "temporal_accumulate: the history must hold width * height pixels");
+    TemporalFrame out;
+    out.rgb.resize(3 * n); out.len.resize(n); out.hits = hits;
+    if (!var.empty()) out.var.resize(3 * n);
+    if (want_motion) out.motion.resize(2 * n);
+    int32_t rc = rtx_temporal_accumulate(rgb.data(), var.empty() ? nullptr : var.data(), hits.data(), history ? history->rgb.data() : nullptr,
+                                         (history && !history->var.empty()) ? history->var.data() : nullptr,
+                                         history ? history->len.data() : nullptr, history ? history->hits.data() : nullptr, prev_camera,
+                                         (uint32_t)width, (uint32_t)height, &params, out.rgb.data(), var.empty() ? nullptr : out.var.data(),
+                                         out.len.data(), want_motion ? out.motion.data() : nullptr);
     if (rc != RTX_OK) throw Panic(rc, rtx_last_error());
     return out;
 }

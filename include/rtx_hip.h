@@ -640,7 +640,8 @@ int32_t rtx_quantize_image_device(const double *d_rgb, uint32_t width, uint32_t 
 
 /* Denoising a low-sample frame: an edge-avoiding a-trous (dilated B3-spline) wavelet filter over a full [y][x] f64 frame in device
  * memory, guided by the frame's RtxPixelFeatures and, when the caller has it, by the per-pixel variance of the mean, which is filtered
- * along with the colour (the spatial filter of SVGF, no temporal part).  What a 4 to 64 spp frame of rtx_render_blocks_accumulate goes
+ * along with the colour (the spatial filter of SVGF; its temporal part is rtx_temporal_accumulate_device, below, whose outputs feed
+ * this call unchanged).  What a 4 to 64 spp frame of rtx_render_blocks_accumulate goes
  * through before rtx_quantize_image_device.  The call takes no scene handle.  Only the FULL frame: a band cannot be filtered without
  * its neighbours' rows, so the bands of a multi-device render are gathered first; multi-device denoising is out of scope.
  *
@@ -722,6 +723,106 @@ int32_t  rtx_denoise_device(const double *d_rgb, const double *d_var, const RtxP
  * var_out may be NULL as above. */
 int32_t  rtx_denoise(const double *rgb, const double *var, const RtxPixelFeatures *features, uint32_t width, uint32_t height,
                      const RtxDenoiseParams *params, double *out, double *var_out);
+
+/* Temporal accumulation: a frame of a sequence on one resident scene (rtx_scene_set_camera, rtx_scene_update_objects,
+ * rtx_scene_set_visible between frames) takes over the previous frame's accumulated samples wherever the same surface is still seen.
+ * For every pixel: where was its surface point in the previous frame (reprojection through the previous camera), did the previous
+ * frame see the same surface there (object, normal and tangent-plane tests on the four surrounding pixels), and if so the history is
+ * blended in, with the variance of the mean and a history length carried along.  d_out_rgb and d_out_var are what rtx_denoise_device
+ * takes as d_rgb and d_var; d_out_rgb, d_out_var, d_out_len and this frame's d_hits are the next frame's history.  d_hits and
+ * d_hist_hits are pick buffers of rtx_scene_primary_hits (the sharp zero-offset rays: position, normal, object) of this and of the
+ * previous frame, both of the same width x height.  The call takes no scene handle, allocates nothing and only enqueues ONE launch on
+ * `stream` (a hipStream_t; NULL = the device's null stream).
+ *
+ * This comment is the specification: every operation below is one separately rounded f64 operation (IEEE add, subtract, multiply,
+ * divide, square root; never fused), in exactly the written order and bracketing, so plain Python floats (tests/temporal_model.py)
+ * give the same bits.  Comparisons with a NaN are false.  "finite" means neither NaN nor an infinity.  a . b = (a.x * b.x + a.y * b.y)
+ * + a.z * b.z.  Pixel p = (x, y), row 0 = the reference's row 0.
+ *
+ * Tables (rtx_temporal_tables; host only, no device is looked for): Tx[i] = sin(fov * (i / width - 0.5)), i = 0 .. width, followed by
+ * Ty[j] = sin(vfov * (j / height - 0.5)), j = 0 .. height, vfov = height / width * fov -- (width + 1) + (height + 1) doubles; the
+ * divisions are of the integers as doubles; sin is the host libm's.  These are the sines of the render's own pixel map (scene.rs:145,
+ * :153-157, :214-215; entry i is pixel i's own ray, one entry more than the image has pixels), from the same code.  The caller uploads
+ * them once per (fov, size).  RTX_ERR_INVALID_ARGUMENT: NULL tables, fov not in (0, pi] (pi: the double 3.141592653589793; beyond
+ * it the tables stop being monotone), width * height == 0 or >= 2^32 - 16.
+ *
+ * Per pixel, with P = d_hits[p].position, n = d_hits[p].normal, o = d_hits[p].object, c = d_rgb[3 p ..], v = d_var[3 p ..]
+ * (V = (d_var != NULL): the variance is tracked):
+ *  1. NO HISTORY when the call has none (the first frame: every d_hist_* is NULL), or o < 0, or a component of P is not finite, or
+ *     where a step below says so.  Then d_out_rgb = c, d_out_var = v, d_out_len = 1: copies of the bytes, no arithmetic (a NaN keeps
+ *     its payload, -0.0 its sign).
+ *  2. e = P - prev_camera->position (per component);  cc.x = e . row 0, cc.y = e . row 1, cc.z = e . row 2 of prev_camera->
+ *     to_cam_space, each as (e.x * r[0] + e.y * r[1]) + e.z * r[2] (camera.rs:51-53, mat/mul.rs:42-50).  !(cc.z > 0): no history (a
+ *     point behind the previous camera; the NaN matrix of a camera that looks along +-z).
+ *  3. The inverse of get_ray_dir, whose direction is proportional to (sin ax, sin ay, cos ax * cos ay), without inverse trigonometry:
+ *       a = cc.x * cc.x;  b = cc.y * cc.y;  L = (a + b) + cc.z * cc.z;  q = L * L - 4 * (a * b);  q = q > 0 ? q : 0
+ *       m = 2 / (L + sqrt(q));  k = sqrt(m);  sx = cc.x * k;  sy = cc.y * k
+ *     fx from Tx (n = width) and sx:  lo = 0, hi = n;  while (hi - lo > 1) { mid = (lo + hi) >> 1;  if (T[mid] <= s) lo = mid; else
+ *     hi = mid; }   den = T[lo + 1] - T[lo];   fx = lo + (den > 0 ? (s - T[lo]) / den : 0)   (the first and the last interval
+ *     extrapolate; a NaN s gives a NaN fx); fy likewise from Ty (n = height) and sy.
+ *     !(fx >= -0.5 && fx <= width - 0.5) or !(fy >= -0.5 && fy <= height - 0.5): no history.  An integer fx is a pixel's own ray
+ *     (pixels are sampled at their corners).  Between the pixels' own rays the interpolation is linear in the SINE, not in the angle:
+ *     fx is off by up to 1e-4 px at 1920 wide and fov pi/2, 0.02 px at 8 wide, and 0.25 px in the outermost columns at fov = pi,
+ *     where the sine is flat; the pixels' own rays come back to 1e-12 px (3e-10 px at fov = pi and 1920 wide).
+ *  4. i0 = floor(fx), tx = fx - i0, j0 = floor(fy), ty = fy - j0; sw = h_k = hv_k = hn = +0.0.  For dy = 0, 1 (outer) and dx = 0, 1
+ *     (inner) the tap q = (i0 + dx, j0 + dy) with w = {1 - tx, tx}[dx] * {1 - ty, ty}[dy] is kept when ALL of:  q is inside the
+ *     frame;  w > 0;  d_hist_hits[q].object == o;  d_hist_len[q] >= 1;  the three d_hist_rgb[3 q ..] are finite, and with V the three
+ *     d_hist_var[3 q ..];  with n_q = d_hist_hits[q].normal:  t = n . n_q,  t > 0  and  t * t >= normal_min2 * ((n . n) * (n_q . n_q));
+ *     with Q = d_hist_hits[q].position:  g = Q - P,  d = g . n,  d * d <= (plane_tol2 * (e . e)) * (n . n).  Here normal_min2 =
+ *     normal_min * normal_min and plane_tol2 = plane_tolerance * plane_tolerance, each one rounded multiply.  (No square root and no
+ *     division in a test.  A zero normal fails t > 0: such a pixel never takes history.  The plane test keeps a plane seen at a
+ *     grazing angle and drops the pixels an object moved by rtx_scene_update_objects has covered or uncovered.)  A kept tap adds
+ *       sw = sw + w;   h_k = h_k + w * hist_rgb_q,k;   V: hv_k = hv_k + w * hist_var_q,k;   hn = hn + w * hist_len_q
+ *  5. !(sw > min_weight): no history.  Else  N = hn / sw;  alpha = 1 / (N + 1);  alpha = alpha > alpha_min ? alpha : alpha_min;
+ *     beta = 1 - alpha;   d_out_rgb_k = beta * (h_k / sw) + alpha * c_k;   V: d_out_var_k = (beta * beta) * (hv_k / sw) + (alpha *
+ *     alpha) * v_k;   len = N + 1;  d_out_len = len < max_history ? len : max_history.
+ *  d_motion (may be NULL; 2 doubles per pixel): (fx, fy) for every pixel that passed step 3 -- whether or not a tap was then kept --
+ *  and the quiet NaN pair otherwise.  A current colour or variance that is not finite is blended as it is: the output is not finite,
+ *  and the next frame's taps drop it.  d_hist_len need not be finite (+inf: the history's weight is 1 - alpha_min).
+ * With a static camera and scene, alpha_min = 0 and a large max_history this is the running mean of the frames and d_out_var the
+ * variance of that mean.
+ *
+ * Buffers (all DEVICE memory): d_rgb, d_var (may be NULL), d_hist_rgb, d_hist_var, d_out_rgb, d_out_var (may be NULL): width * height * 3
+ * doubles; d_hits, d_hist_hits: width * height RtxHit; d_hist_len, d_out_len: width * height doubles; d_prev_tables: the tables of
+ * (prev_camera->fov, width, height); prev_camera: a HOST struct, read before the call returns -- only its fov (checked), position and
+ * to_cam_space.  Nothing of the first frame's NULL history, camera and tables is read.
+ * RTX_ERR_INVALID_ARGUMENT, decided before any device is looked for: NULL params, d_rgb, d_hits, d_out_rgb or d_out_len; a history
+ * that is only partly given (d_hist_rgb, d_hist_len, d_hist_hits, prev_camera and d_prev_tables go together); d_var without
+ * d_hist_var on a frame with history, or the reverse; d_out_var without d_var; any overlap among the inputs and outputs; width * height
+ * == 0 or >= 2^32 - 16; alpha_min not in [0, 1]; max_history NaN, < 1 or infinite; plane_tolerance NaN, negative or infinite;
+ * normal_min not in [0, 1]; min_weight not in [0, 1); flags or reserved != 0; prev_camera->fov not in (0, pi].
+ * Out of scope: per-object motion vectors (a moved object's history is dropped where the tests catch it and kept where the same
+ * surface is seen again); SVGF's 3 x 3 fallback search; multi-device frames (gather first, as for the denoiser); frames of different
+ * sizes.  (DESIGN.md 3.15 "Temporal accumulation".) */
+typedef struct RtxTemporalParams {
+    double   alpha_min;          /* in [0, 1]: the least weight of the new frame (0: the running mean) */
+    double   max_history;        /* >= 1, finite: where the history length stops growing */
+    double   plane_tolerance;    /* >= 0, finite: a tap's distance from the tangent plane, relative to the distance from the previous camera */
+    double   normal_min;         /* in [0, 1]: the least cosine between the two normals */
+    double   min_weight;         /* in [0, 1): the bilinear weight that must survive the tests */
+    uint32_t flags;              /* must be 0 */
+    uint32_t reserved;           /* must be 0 */
+} RtxTemporalParams;
+RTX_STATIC_ASSERT(sizeof(RtxTemporalParams) == 48 && offsetof(RtxTemporalParams, max_history) == 8 &&
+                  offsetof(RtxTemporalParams, plane_tolerance) == 16 && offsetof(RtxTemporalParams, normal_min) == 24 &&
+                  offsetof(RtxTemporalParams, min_weight) == 32 && offsetof(RtxTemporalParams, flags) == 40 &&
+                  offsetof(RtxTemporalParams, reserved) == 44, "RtxTemporalParams layout");
+
+/* The defaults (DESIGN.md 3.15 records how they were chosen): alpha_min = 0.5, max_history = 32, plane_tolerance = 0.005,
+ * normal_min = 0.9, min_weight = 0.01. */
+void     rtx_temporal_default_params(RtxTemporalParams *out);
+int32_t  rtx_temporal_tables(double fov, uint32_t width, uint32_t height, double *tables);
+int32_t  rtx_temporal_accumulate_device(const double *d_rgb, const double *d_var, const RtxHit *d_hits, const double *d_hist_rgb,
+                                        const double *d_hist_var, const double *d_hist_len, const RtxHit *d_hist_hits,
+                                        const RtxCamera *prev_camera, const double *d_prev_tables, uint32_t width, uint32_t height,
+                                        const RtxTemporalParams *params, double *d_out_rgb, double *d_out_var, double *d_out_len,
+                                        double *d_motion, int32_t device, void *stream);
+/* One-shot host form (device 0: allocates, copies, accumulates, copies back; builds the tables itself from prev_camera->fov).  Every
+ * pointer is a HOST array; the same arguments may be NULL, the same are refused. */
+int32_t  rtx_temporal_accumulate(const double *rgb, const double *var, const RtxHit *hits, const double *hist_rgb, const double *hist_var,
+                                 const double *hist_len, const RtxHit *hist_hits, const RtxCamera *prev_camera, uint32_t width,
+                                 uint32_t height, const RtxTemporalParams *params, double *out_rgb, double *out_var, double *out_len,
+                                 double *motion);
 
 /* Test hook (lab library; the product returns RTX_ERR_UNSUPPORTED -- same sources and flags, so the arithmetic it shows is the
  * product's): evaluates one f64 operation per element on the device (op 0: a/b, 1: sqrt(a),

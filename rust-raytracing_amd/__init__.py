@@ -23,13 +23,14 @@ from .abi import (RTX_TUNE_NO_TILES, RTX_TUNE_NO_QNODES, RTX_TUNE_NO_PACKETS, RT
                   RTX_TUNE_TWO_STAGE, RTX_TUNE_BVH_MEDIAN, RTX_TUNE_TRI_LEAF_SHIFT, RTX_TUNE_THRESH_SHIFT, RTX_TUNE_PK_LDS_STACK, RTX_TUNE_NO_CUT, RTX_TUNE_INLINE_LEAVES, RTX_TUNE_HALVES, RTX_TUNE_NO_HALVES, RTX_TUNE_NO_TILE_LISTS)
 from .abi import (OBJECT_DTYPE, RTX_KERNEL_WAVEFRONT, RTX_KERNEL_AUTO, RTX_KERNEL_BVH, RTX_KERNEL_EXACT, RTX_KERNEL_MIXED, RTX_KERNEL_MIXED_VERIFY, RTX_KERNEL_BVH_REGROUP,
                   RTX_PLANE, RTX_SPHERE, RTX_TRIANGLE, RtxError, load_library, RAY_DTYPE, HIT_DTYPE, FEATURE_DTYPE)
-from .abi import DENOISE_PARAMS_DTYPE, RTX_DENOISE_DEMODULATE, RTX_DENOISE_MAX_PASSES, RTX_DENOISE_NO_NORMAL
+from .abi import DENOISE_PARAMS_DTYPE, RTX_DENOISE_DEMODULATE, RTX_DENOISE_MAX_PASSES, RTX_DENOISE_NO_NORMAL, TEMPORAL_PARAMS_DTYPE
 
 __all__ = ["LabKernel", "Vector3", "Material", "Sphere", "Plane", "Triangle", "Object", "Config", "Camera", "Scene",
            "SceneHandle", "RtxError", "device_count", "pack_objects", "OBJECT_DTYPE",
            "RTX_KERNEL_AUTO", "RTX_KERNEL_EXACT", "RTX_KERNEL_MIXED", "RTX_KERNEL_MIXED_VERIFY", "RTX_KERNEL_BVH", "RTX_KERNEL_BVH_REGROUP", "RTX_KERNEL_WAVEFRONT", "debug_host_scene",
            "RAY_DTYPE", "HIT_DTYPE", "FEATURE_DTYPE", "make_rays", "denoise", "denoise_params", "denoise_work_bytes", "DENOISE_PARAMS_DTYPE",
-           "RTX_DENOISE_DEMODULATE", "RTX_DENOISE_MAX_PASSES", "RTX_DENOISE_NO_NORMAL"]
+           "RTX_DENOISE_DEMODULATE", "RTX_DENOISE_MAX_PASSES", "RTX_DENOISE_NO_NORMAL", "temporal_params", "temporal_tables",
+           "temporal_accumulate", "TEMPORAL_PARAMS_DTYPE", "Temporal"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -404,6 +405,68 @@ def denoise(img, features, variance=None, **params):
     return out if var is None else (out, var_out)
 
 
+def temporal_params(lib=None, **fields):
+    """One RtxTemporalParams record (TEMPORAL_PARAMS_DTYPE, shape ()): the library's defaults (rtx_temporal_default_params) with the
+    given fields replaced."""
+    lib = lib or load_library()
+    p = np.zeros((), dtype=TEMPORAL_PARAMS_DTYPE)
+    lib.rtx_temporal_default_params(p.ctypes.data)
+    for k, v in fields.items():
+        if k not in TEMPORAL_PARAMS_DTYPE.names:
+            raise TypeError("temporal: unknown parameter %r" % k)
+        p[k] = v
+    return p
+
+
+def temporal_tables(fov, width, height):
+    """rtx_temporal_tables: the sines of the pixel map of a camera with this fov on a width x height frame, Tx[width + 1] followed by
+    Ty[height + 1] (host only: no device is needed).  What temporal_accumulate_device takes, uploaded, as the previous camera's tables."""
+    lib = load_library()
+    t = np.zeros(max(int(width) + int(height) + 2, 0), dtype=np.float64)
+    abi.check(lib.rtx_temporal_tables(float(fov), int(width), int(height), t.ctypes.data), lib)
+    return t
+
+
+def _hit_records(hits, height, width):
+    """RtxHit records, or the (distance, object, position, normal) of SceneHandle.pick, -> a contiguous [height][width] record array"""
+    if isinstance(hits, np.ndarray) and hits.dtype == HIT_DTYPE:
+        return np.ascontiguousarray(hits).reshape(height, width)
+    distance, obj, position, normal = hits
+    h = np.zeros((height, width), dtype=HIT_DTYPE)
+    h["distance"], h["object"] = np.asarray(distance).reshape(height, width), np.asarray(obj).reshape(height, width)
+    h["position"], h["normal"] = np.asarray(position).reshape(height, width, 3), np.asarray(normal).reshape(height, width, 3)
+    return h
+
+
+def temporal_accumulate(img, hits, history=None, prev_camera=None, variance=None, want_motion=False, **params):
+    """Temporal accumulation of include/rtx_hip.h ("Temporal accumulation") on host arrays (rtx_temporal_accumulate: device 0, copies
+    both ways, builds the tables itself).  img: (height, width, 3) float64; hits: this frame's pick buffer (HIT_DTYPE records, or the
+    tuple of SceneHandle.pick); variance: the variance of the mean, or None.  history: None on the first frame, else the dict this call
+    returned for the previous frame ("rgb", "len", "hits" and, with a variance, "var"), with prev_camera the Camera (or RtxCamera) that
+    frame was taken with.  params: fields of RtxTemporalParams over the defaults.  Returns a dict with "rgb", "var" (or None), "len",
+    "hits" (this frame's, so the dict is the next call's history) and "motion" (or None)."""
+    img = np.ascontiguousarray(img, dtype=np.float64)
+    height, width = img.shape[0], img.shape[1]
+    lib = load_library()
+    p = temporal_params(lib, **params)
+    h = _hit_records(hits, height, width)
+    var = None if variance is None else np.ascontiguousarray(variance, dtype=np.float64).reshape(img.shape)
+    hist = [None] * 4
+    cam = None
+    if history is not None:
+        hist = [np.ascontiguousarray(history["rgb"], dtype=np.float64), None if history.get("var") is None else
+                np.ascontiguousarray(history["var"], dtype=np.float64), np.ascontiguousarray(history["len"], dtype=np.float64),
+                _hit_records(history["hits"], height, width)]
+        cam = prev_camera.to_c() if hasattr(prev_camera, "to_c") else prev_camera
+    out = {"rgb": np.zeros_like(img), "var": None if var is None else np.zeros_like(img), "len": np.zeros((height, width)), "hits": h,
+           "motion": np.zeros((height, width, 2)) if want_motion else None}
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    abi.check(lib.rtx_temporal_accumulate(ptr(img), ptr(var), ptr(h), ptr(hist[0]), ptr(hist[1]), ptr(hist[2]), ptr(hist[3]),
+                                          C.addressof(cam) if cam is not None else None, width, height, p.ctypes.data,
+                                          ptr(out["rgb"]), ptr(out["var"]), ptr(out["len"]), ptr(out["motion"])), lib)
+    return out
+
+
 class Scene:
     def __init__(self, config=None, camera=None):                   # Scene::new scene.rs:112-118 / Default :86-94
         self.config = config if config is not None else Config()
@@ -547,6 +610,7 @@ class SceneHandle:
         sc = _scene_c(scene.config, scene.camera, packed)
         self._check(self._lib.rtx_scene_upload(C.byref(sc), self.device, C.byref(self._h)))
         self._n_objects = len(packed)
+        self.camera = scene.camera                      # the camera the handle renders with (set_camera replaces it)
 
     def _check(self, status):
         abi.check(status, self._lib)                    # (the error string is thread-local in the library that set it)
@@ -565,6 +629,7 @@ class SceneHandle:
     def set_camera(self, camera):
         c = camera.to_c()
         self._check(self._lib.rtx_scene_set_camera(self._h, C.byref(c)))
+        self.camera = camera
 
     def append_objects(self, packed):
         """Scene::add_object (scene.rs:126-128) for a resident scene: `packed` is an OBJECT_DTYPE array (or a list of Objects)."""
@@ -945,6 +1010,28 @@ class SceneHandle:
         self._check(self._lib.rtx_denoise_device(ptr(d_rgb_ptr), ptr(d_var_ptr), ptr(d_features_ptr), int(width), int(height), p.ctypes.data,
                                                  ptr(d_out_ptr), ptr(d_var_out_ptr), ptr(d_work_ptr), self.device, ptr(stream)))
 
+    def temporal_accumulate_device(self, width, height, d_rgb_ptr, d_hits_ptr, d_out_rgb_ptr, d_out_len_ptr, d_var_ptr=None,
+                                   d_out_var_ptr=None, d_motion_ptr=None, history=None, stream=None, params=None, **kw):
+        """rtx_temporal_accumulate_device on this handle's device: every pointer a device address of a full [height][width] frame.
+        history: None (the first frame) or (d_hist_rgb_ptr, d_hist_var_ptr or None, d_hist_len_ptr, d_hist_hits_ptr, prev_camera,
+        d_prev_tables_ptr) -- prev_camera a Camera or an abi.RtxCamera, the tables those of temporal_tables(prev_camera.fov, width,
+        height), uploaded.  Only enqueues on `stream`.  params: a temporal_params record, or its fields as keywords."""
+        p = params if params is not None else temporal_params(self._lib, **kw)
+        ptr = lambda a: C.c_void_p(int(a)) if a else None
+        hist, cam = (None,) * 6, None
+        if history is not None:
+            hist = tuple(history)
+            cam = hist[4].to_c() if hasattr(hist[4], "to_c") else hist[4]
+        self._check(self._lib.rtx_temporal_accumulate_device(
+            ptr(d_rgb_ptr), ptr(d_var_ptr), ptr(d_hits_ptr), ptr(hist[0]), ptr(hist[1]), ptr(hist[2]), ptr(hist[3]),
+            C.addressof(cam) if cam is not None else None, ptr(hist[5]), int(width), int(height), p.ctypes.data, ptr(d_out_rgb_ptr),
+            ptr(d_out_var_ptr), ptr(d_out_len_ptr), ptr(d_motion_ptr), self.device, ptr(stream)))
+
+    def temporal(self, width, height, **params):
+        """A Temporal accumulator of a width x height frame sequence on this handle: frame(spp, camera) renders the next low-sample
+        frame and blends the previous frames' history in where the same surface is still seen.  params: fields of RtxTemporalParams."""
+        return Temporal(self, width, height, **params)
+
     def close(self):
         if self._h:
             h, self._h = self._h, C.c_void_p()
@@ -1062,6 +1149,127 @@ class Progressive:
         var = None
         if self.sum_sq is not None and int(self.count.min()) >= 2:
             var = ((self.sum_sq - self.sum * self.sum / n) / (n - 1.0) / n).contiguous()
+        p = denoise_params(self._hnd._lib, **params)
+        npix = self.width * self.height
+        feat = torch.empty(npix * FEATURE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        work = torch.empty(max(int(self._hnd._lib.rtx_denoise_work_bytes(self.width, self.height, p.ctypes.data)), 16), dtype=torch.uint8, device=dev)
+        out = torch.empty_like(mean)
+        torch.cuda.synchronize(dev)
+        self._hnd.pixel_features(self.width, self.height, feat.data_ptr(), want_stats=True)
+        self._hnd.denoise_device(self.width, self.height, mean.data_ptr(), feat.data_ptr(), out.data_ptr(), work.data_ptr(),
+                                 d_var_ptr=var.data_ptr() if var is not None else None, params=p)
+        torch.cuda.synchronize(dev)
+        return out.cpu().numpy()
+
+
+class Temporal:
+    """Temporal accumulation over a sequence of frames of one resident scene (SceneHandle.temporal): every frame(spp, camera) renders
+    spp new samples per pixel, takes the pick buffer and blends in the accumulated history of the previous frame through
+    rtx_temporal_accumulate_device.  The camera may move and objects may be updated, hidden or shown between frames.  Everything stays
+    on the handle's device; two sets of history buffers are used in turn.
+
+    Frame i (counted from the last reset()) renders the samples [i * spp, (i + 1) * spp) of every pixel through
+    rtx_render_blocks_accumulate, so frames do not repeat each other's random draws.  That call does not read the handle's
+    rays_per_pixel; it accepts any range that ends at or below 2^32 - 1, and frame() raises ValueError beyond it."""
+
+    def __init__(self, handle, width, height, **params):
+        import torch
+        self._hnd, self.width, self.height = handle, int(width), int(height)
+        self.params = temporal_params(handle._lib, **params)
+        self._dev = torch.device("cuda", handle.device)
+        self._tables = {}                          # fov -> the uploaded tables
+        self.reset()
+
+    def reset(self):
+        """forget the history: the next frame is a first frame (and frame_index, so the sample range, starts again at 0)"""
+        self._hist = None                          # (rgb, var or None, len, hits, camera, tables) of the last frame
+        self._motion = None
+        self.frame_index = 0
+        self.frame_mean = self.frame_variance = None
+
+    def _tables_for(self, fov):
+        import torch
+        t = self._tables.get(fov)
+        if t is None:
+            t = self._tables[fov] = torch.from_numpy(temporal_tables(fov, self.width, self.height)).to(self._dev)
+        return t
+
+    def frame(self, spp, camera=None):
+        """the next frame at spp samples per pixel -> numpy (h, w, 3), the accumulated mean.  spp >= 2 tracks the variance of the mean
+        ((sum_sq - sum^2 / n) / (n - 1) / n, Progressive's expression); a sequence keeps one spp (a change resets the history when it
+        switches the variance on or off).  frame_mean / frame_variance keep this frame's own torch tensors."""
+        import torch
+        spp = int(spp)
+        if spp < 1:
+            raise ValueError("frame(): spp must be at least 1")
+        begin = self.frame_index * spp
+        if begin + spp > 0xFFFFFFFF:
+            raise ValueError("frame(): the sample range ends beyond 2^32 - 1; reset() starts it again")
+        if camera is not None:
+            self._hnd.set_camera(camera)
+        cam = self._hnd.camera.to_c()              # (a copy: the Camera may change before the next frame reads it as the previous one)
+        h, w, dev = self.height, self.width, self._dev
+        s = torch.zeros((h, w, 3), dtype=torch.float64, device=dev)
+        q = torch.zeros((h, w, 3), dtype=torch.float64, device=dev) if spp >= 2 else None
+        hits = torch.empty(h * w * HIT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        self._hnd.render_accumulate(w, h, begin, spp, s.data_ptr(), q.data_ptr() if q is not None else None)
+        self._hnd.primary_hits(w, h, hits.data_ptr(), want_stats=True)
+        n = torch.full((), float(spp), dtype=torch.float64, device=dev)     # (a tensor: torch divides by a Python scalar with a reciprocal)
+        mean = (s / n).contiguous()
+        var = ((q - s * s / n) / (n - 1.0) / n).contiguous() if q is not None else None
+        hist = self._hist
+        if hist is not None and (hist[1] is None) != (var is None):
+            hist = None
+        out = torch.empty_like(mean)
+        out_var = torch.empty_like(mean) if var is not None else None
+        out_len = torch.empty((h, w), dtype=torch.float64, device=dev)
+        motion = torch.empty((h, w, 2), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        history = None
+        if hist is not None:
+            history = (hist[0].data_ptr(), hist[1].data_ptr() if hist[1] is not None else None, hist[2].data_ptr(), hist[3].data_ptr(),
+                       hist[4], hist[5].data_ptr())
+        self._hnd.temporal_accumulate_device(w, h, mean.data_ptr(), hits.data_ptr(), out.data_ptr(), out_len.data_ptr(),
+                                             d_var_ptr=var.data_ptr() if var is not None else None,
+                                             d_out_var_ptr=out_var.data_ptr() if out_var is not None else None,
+                                             d_motion_ptr=motion.data_ptr(), history=history, params=self.params)
+        torch.cuda.synchronize(dev)
+        self.frame_mean, self.frame_variance, self.frame_hits = mean, var, hits
+        self._hist = (out, out_var, out_len, hits, cam, self._tables_for(float(cam.fov)))
+        self._motion = motion
+        self.frame_index += 1
+        return out.cpu().numpy()
+
+    def _need(self):
+        if self._hist is None:
+            raise ValueError("no frame yet")
+        return self._hist
+
+    def mean(self):
+        """the accumulated mean -> numpy (h, w, 3)"""
+        return self._need()[0].cpu().numpy()
+
+    def variance(self):
+        """the variance of the accumulated mean -> numpy (h, w, 3), or None when spp == 1"""
+        v = self._need()[1]
+        return None if v is None else v.cpu().numpy()
+
+    def length(self):
+        """the history length of every pixel (1: this frame alone) -> numpy (h, w)"""
+        return self._need()[2].cpu().numpy()
+
+    def motion(self):
+        """where every pixel's surface point was in the previous frame, (fx, fy) in pixels; NaN where it was not -> numpy (h, w, 2)"""
+        self._need()
+        return self._motion.cpu().numpy()
+
+    def denoise(self, **params):
+        """The accumulated mean and its variance (when tracked; else no colour term) with the handle's pixel features (at its
+        rays_per_pixel) through rtx_denoise_device, on the device.  params: fields of RtxDenoiseParams.  -> numpy (h, w, 3)"""
+        import torch
+        mean, var = self._need()[0], self._need()[1]
+        dev = self._dev
         p = denoise_params(self._hnd._lib, **params)
         npix = self.width * self.height
         feat = torch.empty(npix * FEATURE_DTYPE.itemsize, dtype=torch.uint8, device=dev)

@@ -88,6 +88,11 @@ class RtxDenoiseParams(C.Structure):
                 ("albedo_min", C.c_double)]
 
 
+class RtxTemporalParams(C.Structure):
+    _fields_ = [("alpha_min", C.c_double), ("max_history", C.c_double), ("plane_tolerance", C.c_double), ("normal_min", C.c_double),
+                ("min_weight", C.c_double), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 # the same layouts as numpy records (arrays of rays / answers)
 RAY_DTYPE = np.dtype([("position", "<f8", (3,)), ("direction", "<f8", (3,))])
 HIT_DTYPE = np.dtype([("position", "<f8", (3,)), ("normal", "<f8", (3,)), ("distance", "<f8"), ("object", "<i8")])
@@ -99,6 +104,9 @@ DENOISE_PARAMS_DTYPE = np.dtype([("passes", "<u4"), ("flags", "<u4"), ("normal_p
                                  ("sigma_color", "<f8"), ("sigma_depth", "<f8"), ("sigma_albedo", "<f8"), ("epsilon", "<f8"),
                                  ("albedo_min", "<f8")])
 assert DENOISE_PARAMS_DTYPE.itemsize == C.sizeof(RtxDenoiseParams) == 56
+TEMPORAL_PARAMS_DTYPE = np.dtype([("alpha_min", "<f8"), ("max_history", "<f8"), ("plane_tolerance", "<f8"), ("normal_min", "<f8"),
+                                  ("min_weight", "<f8"), ("flags", "<u4"), ("reserved", "<u4")])
+assert TEMPORAL_PARAMS_DTYPE.itemsize == C.sizeof(RtxTemporalParams) == 48
 
 
 # every symbol include/rtx_hip.h declares: (name, restype, argtypes)
@@ -157,6 +165,10 @@ SYMBOLS = [
     ("rtx_denoise_device", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_int32, C.c_void_p]),
     ("rtx_denoise", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rtx_temporal_default_params", None, [C.c_void_p]),
+    ("rtx_temporal_tables", C.c_int32, [C.c_double, C.c_uint32, C.c_uint32, C.c_void_p]),
+    ("rtx_temporal_accumulate_device", C.c_int32, [C.c_void_p] * 9 + [C.c_uint32, C.c_uint32] + [C.c_void_p] * 5 + [C.c_int32, C.c_void_p]),
+    ("rtx_temporal_accumulate", C.c_int32, [C.c_void_p] * 8 + [C.c_uint32, C.c_uint32] + [C.c_void_p] * 5),
     ("rtx_debug_math", C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
     ("rtx_debug_paths", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("rtx_debug_store_samples", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),

@@ -533,17 +533,15 @@ static int32_t ensure_tables(RtxSceneHandle_ *h, uint32_t width, uint32_t height
             h->tables_doubles = have / sizeof(double);
         }
         const double fov = h->cam.fov;
-        const double vertical_fov = (double)height / (double)width * fov;             // scene.rs:145
+        const double vertical_fov = table_vertical_fov(fov, width, height);          // scene.rs:145
         double *sx = h->h_tables, *cx = sx + width, *sy = cx + width, *cy = sy + n_rows;
         for (uint32_t x = 0; x < width; ++x) {
-            double u = (double)x / (double)width;                                       // scene.rs:157
-            double angle_x = fov * (u - 0.5);                                           // scene.rs:214
+            double angle_x = table_angle(fov, x, width);                                // scene.rs:157, :214
             ::sincos(angle_x, &sx[x], &cx[x]);
         }
         for (uint32_t k = 0; k < n_rows; ++k) {
             const uint32_t kb = k / row_block;
-            double v = (double)(row_begin + kb * row_stride + (k - kb * row_block)) / (double)height;   // scene.rs:153 (image_row)
-            double angle_y = vertical_fov * (v - 0.5);                                  // scene.rs:215
+            double angle_y = table_angle(vertical_fov, row_begin + kb * row_stride + (k - kb * row_block), height);   // scene.rs:153 (image_row), :215
             ::sincos(angle_y, &sy[k], &cy[k]);
         }
         RTX_HIP_CHECK(hipMemcpyAsync(h->tables, h->h_tables, tdbl * sizeof(double), hipMemcpyHostToDevice, stream));

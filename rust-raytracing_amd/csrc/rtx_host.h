@@ -127,6 +127,15 @@ struct DoneGuard {
     }
 };
 
+// The angles of get_ray_dir's trig tables, in the reference's operation order: what the render's own tables (ensure_tables, rtx_api.hip)
+// and rtx_temporal_tables (rtx_temporal.hip) take the host libm's sines of -- one text, so the two cannot drift.
+inline double table_vertical_fov(double fov, uint32_t width, uint32_t height) { return (double)height / (double)width * fov; }   // scene.rs:145
+inline double table_angle(double fov, uint32_t i, uint32_t n)
+{
+    const double u = (double)i / (double)n;                 // scene.rs:153 (v, of the image row), :157 (u)
+    return fov * (u - 0.5);                                 // scene.rs:214-215
+}
+
 // rtx_api.hip
 int usable_device_count();
 int32_t check_device(int32_t device, const char *who);      // a usable gfx950 `device`, or the status with the error text set

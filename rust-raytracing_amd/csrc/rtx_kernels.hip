@@ -11,13 +11,14 @@
 //                       trace_exact_kernel.  Dead slots are refilled from a global ray queue with a
 //                       wave ballot + mbcnt prefix sum (one atomic per workgroup per round).
 //   resolve_kernel      left fold of a pixel's samples in sample order, then / rays_per_pixel.
-//   epilogue_kernel     render_to_image's quantize, the multi-device gather and the two forms of the denoiser (rtx_denoise.h), by a
-//                       launch-uniform form.
+//   epilogue_kernel     render_to_image's quantize, the multi-device gather, the two forms of the denoiser (rtx_denoise.h) and the
+//                       temporal accumulation (rtx_temporal.h), by a launch-uniform form.
 //
 // Compiled with -ffp-contract=off; the f32 filter uses explicit fmaf.
 #include "rtx_launch.h"
 #include "rtx_traverse.h"
 #include "rtx_denoise.h"
+#include "rtx_temporal.h"
 
 #include <cstdlib>
 
@@ -667,13 +668,16 @@ __device__ __forceinline__ uint8_t rust_as_u8(double v)
 //   per thread, moved as one load and one store: parts[p] (cap_rows rows each) holds band p of n: the blocks of `block` image rows
 //   b = p, p + n, ... in order.  flip: output row height - 1 - y (render_to_image, scene.rs:176).
 // form 16 / 17 -- rtx_denoise_device's preparation and one of its passes (rtx_denoise.h): everything they read is in `dn`, which the
-//   other forms pass zeroed; only form 17 is launched with dynamic LDS (kDnLdsBytes), so the movers' occupancy pays none for it.
-constexpr uint32_t kEpilogueDenoisePrepare = 16u, kEpilogueDenoisePass = 17u;
+//   other forms pass zeroed; of the two only form 17 is launched with dynamic LDS (kDnLdsBytes), so the movers' occupancy pays none for it.
+// form 18 -- rtx_temporal_accumulate_device (rtx_temporal.h): everything it reads is in `ta`, which the other forms pass zeroed; it is
+//   launched with dynamic LDS for its two sine tables when they fit kTemporalLdsBytes, else with none.
+constexpr uint32_t kEpilogueDenoisePrepare = 16u, kEpilogueDenoisePass = 17u, kEpilogueTemporal = 18u;
 extern __shared__ double epilogue_lds[];
 __global__ __launch_bounds__(256) void epilogue_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
                                                        uint32_t width, uint32_t height, uint32_t n, uint32_t cap_rows,
-                                                       uint32_t block, uint32_t flip, uint32_t form, DenoiseArgs dn)
+                                                       uint32_t block, uint32_t flip, uint32_t form, DenoiseArgs dn, TemporalArgs ta)
 {
+    if (form == kEpilogueTemporal) { temporal_accumulate(ta, epilogue_lds); return; }
     if (form == kEpilogueDenoisePass) { denoise_pass(dn, epilogue_lds); return; }
     if (form == kEpilogueDenoisePrepare) { denoise_prepare(dn); return; }
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -863,7 +867,7 @@ hipError_t launch_quantize(const double *rgb, uint8_t *rgb8, uint32_t width, uin
     uint64_t npix = (uint64_t)width * height;
     if (npix == 0) return hipSuccess;
     hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, stream,
-                       reinterpret_cast<const uint8_t *>(rgb), rgb8, width, height, 1u, 0u, 1u, 1u, 0u, DenoiseArgs{});
+                       reinterpret_cast<const uint8_t *>(rgb), rgb8, width, height, 1u, 0u, 1u, 1u, 0u, DenoiseArgs{}, TemporalArgs{});
     return hipGetLastError();
 }
 
@@ -872,7 +876,7 @@ hipError_t launch_quantize_values(const double *rgb, uint8_t *rgb8, uint32_t wid
     uint64_t npix = (uint64_t)width * n_rows;
     if (npix == 0) return hipSuccess;
     hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, stream,
-                       reinterpret_cast<const uint8_t *>(rgb), rgb8, width, n_rows, 1u, 0u, 1u, 0u, 0u, DenoiseArgs{});
+                       reinterpret_cast<const uint8_t *>(rgb), rgb8, width, n_rows, 1u, 0u, 1u, 0u, 0u, DenoiseArgs{}, TemporalArgs{});
     return hipGetLastError();
 }
 
@@ -882,7 +886,7 @@ hipError_t launch_deinterleave(const double *parts, double *full, uint32_t width
     const uint64_t total = (uint64_t)width * height * 3;
     if (total == 0) return hipSuccess;
     hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, stream,
-                       reinterpret_cast<const uint8_t *>(parts), reinterpret_cast<uint8_t *>(full), width, height, n, cap_rows, block, 0u, 8u, DenoiseArgs{});
+                       reinterpret_cast<const uint8_t *>(parts), reinterpret_cast<uint8_t *>(full), width, height, n, cap_rows, block, 0u, 8u, DenoiseArgs{}, TemporalArgs{});
     return hipGetLastError();
 }
 
@@ -892,7 +896,7 @@ hipError_t launch_deinterleave_u8(const uint8_t *parts, uint8_t *full, uint32_t 
     const uint64_t total = (uint64_t)width * height * 3;
     if (total == 0) return hipSuccess;
     hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, stream, parts, full, width,
-                       height, n, cap_rows, block, flip ? 1u : 0u, 1u, DenoiseArgs{});
+                       height, n, cap_rows, block, flip ? 1u : 0u, 1u, DenoiseArgs{}, TemporalArgs{});
     return hipGetLastError();
 }
 
@@ -901,7 +905,7 @@ hipError_t launch_denoise_prepare(const DenoiseArgs &d, hipStream_t stream)
     const uint64_t npix = (uint64_t)d.width * d.height;
     if (npix == 0) return hipSuccess;
     hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, stream, nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u,
-                       kEpilogueDenoisePrepare, d);
+                       kEpilogueDenoisePrepare, d, TemporalArgs{});
     return hipGetLastError();
 }
 
@@ -919,7 +923,19 @@ hipError_t launch_denoise_pass(const DenoiseArgs &d_, hipStream_t stream)
     if (blocks >= (1ull << 31)) return hipErrorInvalidValue;
     d.tiles = (uint32_t)tiles;
     hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)blocks), dim3(256), kDnLdsBytes, stream, nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u,
-                       kEpilogueDenoisePass, d);
+                       kEpilogueDenoisePass, d, TemporalArgs{});
+    return hipGetLastError();
+}
+
+hipError_t launch_temporal(const TemporalArgs &t_, hipStream_t stream)
+{
+    TemporalArgs t = t_;
+    const uint64_t npix = (uint64_t)t.width * t.height;
+    if (npix == 0) return hipSuccess;
+    const size_t table_bytes = ((size_t)t.width + 1u + (size_t)t.height + 1u) * sizeof(double);
+    t.tables_in_lds = ((t.flags & kTaHistory) != 0u && table_bytes <= kTemporalLdsBytes) ? 1u : 0u;
+    hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)((npix + 255) / 256)), dim3(256), t.tables_in_lds ? table_bytes : 0, stream, nullptr,
+                       nullptr, 0u, 0u, 0u, 0u, 0u, 0u, kEpilogueTemporal, DenoiseArgs{}, t);
     return hipGetLastError();
 }
 

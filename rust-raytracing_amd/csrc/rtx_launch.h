@@ -136,6 +136,26 @@ hipError_t launch_denoise_prepare(const DenoiseArgs &d, hipStream_t stream);
 // one pass of step d.step; fills in the grid fields of its copy of d.  hipErrorInvalidValue: a grid of 2^31 workgroups or more
 hipError_t launch_denoise_pass(const DenoiseArgs &d, hipStream_t stream);
 
+// ---- temporal accumulation (rtx_temporal_accumulate_device; device text: rtx_temporal.h, host side: rtx_temporal.hip): one more
+// launch-uniform form of epilogue_kernel, one pixel per thread, its arguments by value beside DenoiseArgs (the other forms pass them
+// zeroed).  The two sine tables are staged in dynamic LDS when (width + 1) + (height + 1) doubles fit kTemporalLdsBytes, else searched
+// in global memory with the same code.
+struct QueryHit;
+enum : uint32_t { kTaHistory = 1u, kTaVariance = 2u };
+constexpr size_t kTemporalLdsBytes = 32768;                   // 4096 table entries: up to e.g. 2560 x 1440; two workgroups per CU and more
+struct TemporalArgs {
+    const double *rgb, *var;                                  // this frame (var: null without kTaVariance)
+    const QueryHit *hits;
+    const double *hist_rgb, *hist_var, *hist_len;             // the previous frame (null without kTaHistory)
+    const QueryHit *hist_hits;
+    const double *tables;                                     // Tx[width + 1], Ty[height + 1] of the previous camera's fov
+    double *out_rgb, *out_var, *out_len, *motion;             // out_var, motion: may be null
+    double cam_pos[3], to_cam[9];                             // the previous camera
+    double alpha_min, max_history, plane_tol2, normal_min2, min_weight;        // (the squares: one rounded multiply on the host)
+    uint32_t width, height, flags, tables_in_lds;             // flags: kTa*
+};
+hipError_t launch_temporal(const TemporalArgs &t, hipStream_t stream);         // sets tables_in_lds in its copy of t
+
 // ---- ray queries (rtx_query.hip): closest_object for caller rays or for the pick buffer's zero-offset primary rays, or -- the
 // any-hit mode, a launch-uniform switch of the same kernel -- whether any object lies before a per-ray distance limit, or -- the
 // path mode, a third switch -- render_ray's colour of the path that starts with the ray, or -- the feature mode, a fourth -- the

@@ -109,6 +109,19 @@ pub struct RtxPixelFeatures {
     pub object: i64,
 }
 
+/// `RtxTemporalParams` (include/rtx_hip.h, "Temporal accumulation"): fill it with `rtx_temporal_default_params`.  48 bytes.
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct RtxTemporalParams {
+    pub alpha_min: f64,
+    pub max_history: f64,
+    pub plane_tolerance: f64,
+    pub normal_min: f64,
+    pub min_weight: f64,
+    pub flags: u32,
+    pub reserved: u32,
+}
+
 #[repr(C)]
 pub struct RtxSceneHandleOpaque {
     _private: [u8; 0],
@@ -155,6 +168,10 @@ extern "C" {
     pub fn rtx_pixel_features(scene: *const RtxScene, width: u32, height: u32, features: *mut RtxPixelFeatures) -> i32;
     pub fn rtx_debug_resolve_moments(records: *const f64, mask: *const u32, width: u32, n_rows: u32, tiles_x: u32, n_samples: u32, sum: *mut f64, sum_doubles: u64, sum_sq: *mut f64, sum_sq_doubles: u64) -> i32;
     pub fn rtx_quantize_image_device(d_rgb: *const f64, width: u32, height: u32, d_rgb8: *mut u8, device: i32, stream: *mut c_void) -> i32;
+    pub fn rtx_temporal_default_params(out: *mut RtxTemporalParams);
+    pub fn rtx_temporal_tables(fov: f64, width: u32, height: u32, tables: *mut f64) -> i32;
+    pub fn rtx_temporal_accumulate_device(d_rgb: *const f64, d_var: *const f64, d_hits: *const RtxHit, d_hist_rgb: *const f64, d_hist_var: *const f64, d_hist_len: *const f64, d_hist_hits: *const RtxHit, prev_camera: *const RtxCamera, d_prev_tables: *const f64, width: u32, height: u32, params: *const RtxTemporalParams, d_out_rgb: *mut f64, d_out_var: *mut f64, d_out_len: *mut f64, d_motion: *mut f64, device: i32, stream: *mut c_void) -> i32;
+    pub fn rtx_temporal_accumulate(rgb: *const f64, var: *const f64, hits: *const RtxHit, hist_rgb: *const f64, hist_var: *const f64, hist_len: *const f64, hist_hits: *const RtxHit, prev_camera: *const RtxCamera, width: u32, height: u32, params: *const RtxTemporalParams, out_rgb: *mut f64, out_var: *mut f64, out_len: *mut f64, motion: *mut f64) -> i32;
 }
 
 /// The reference reports failures by panicking (scene.rs:168, object.rs:38,50); so does the shim.
