@@ -541,6 +541,14 @@ public:
                                              (uint32_t)width, (uint32_t)height, &params, d_out_rgb, d_out_var, d_out_len, d_motion, device_,
                                              hip_stream));
     }
+    // rewinds a pick buffer on this scene's device (rtx_rewind_hits_device; it reads no scene): the n_hits records at d_hits, with every
+    // hit on one of the m moved objects (d_objects ascending, d_motions: rtx::object_motions, uploaded) replaced by the record of the
+    // same material point on the object's previous geometry -> d_out, which temporal_accumulate then takes as d_hits.  Only enqueues.
+    void rewind_hits(const RtxHit *d_hits, std::size_t n_hits, const std::int64_t *d_objects, const RtxObjectMotion *d_motions, std::size_t m,
+                     RtxHit *d_out, void *hip_stream = nullptr)
+    {
+        check(rtx_rewind_hits_device(d_hits, n_hits, d_objects, d_motions, m, 0u, d_out, device_, hip_stream));
+    }
 
 private:
     friend class Scene;
@@ -633,6 +641,42 @@ inline TemporalFrame temporal_accumulate(const std::vector<double> &rgb, const s
                                          history ? history->len.data() : nullptr, history ? history->hits.data() : nullptr, prev_camera,
                                          (uint32_t)width, (uint32_t)height, &params, out.rgb.data(), var.empty() ? nullptr : out.var.data(),
                                          out.len.data(), want_motion ? out.motion.data() : nullptr);
+    if (rc != RTX_OK) throw Panic(rc, rtx_last_error());
+    return out;
+}
+
+// What moved between two frames (rtx_object_motions; host only): the objects `indices` had the records `before` when the previous
+// frame's pick was taken and have the records `now` -- what update_objects was given since.  Of a repeated index the first `before` and
+// the last `now` count; unchanged geometry is left out.
+struct ObjectMotions {
+    std::vector<std::int64_t> objects;                      // ascending
+    std::vector<RtxObjectMotion> motions;
+};
+inline ObjectMotions object_motions(const std::vector<std::uint64_t> &indices, const std::vector<object::Object> &before,
+                                    const std::vector<object::Object> &now)
+{
+    if (indices.size() != before.size() || indices.size() != now.size())
+        throw std::invalid_argument("object_motions: indices, before and now differ in length");
+    Scene was, is;
+    for (const object::Object &o : before) was.add_object(o);
+    for (const object::Object &o : now) is.add_object(o);
+    const std::vector<RtxObject> pw = was.pack(), pi = is.pack();
+    ObjectMotions out;
+    out.objects.resize(indices.size());
+    out.motions.resize(indices.size());
+    std::uint64_t m = 0;
+    int32_t rc = rtx_object_motions(indices.data(), pw.data(), pi.data(), indices.size(), out.objects.data(), out.motions.data(), &m);
+    if (rc != RTX_OK) throw Panic(rc, rtx_last_error());
+    out.objects.resize(m);
+    out.motions.resize(m);
+    return out;
+}
+// host form (rtx_rewind_hits: device 0, copies both ways): a pick buffer, rewound on the moved objects
+inline std::vector<RtxHit> rewind_hits(const std::vector<RtxHit> &hits, const ObjectMotions &moved)
+{
+    std::vector<RtxHit> out(hits.size());
+    int32_t rc = rtx_rewind_hits(hits.data(), hits.size(), moved.objects.empty() ? nullptr : moved.objects.data(),
+                                 moved.motions.empty() ? nullptr : moved.motions.data(), moved.objects.size(), out.data());
     if (rc != RTX_OK) throw Panic(rc, rtx_last_error());
     return out;
 }

@@ -791,8 +791,8 @@ int32_t  rtx_denoise(const double *rgb, const double *var, const RtxPixelFeature
  * d_hist_var on a frame with history, or the reverse; d_out_var without d_var; any overlap among the inputs and outputs; width * height
  * == 0 or >= 2^32 - 16; alpha_min not in [0, 1]; max_history NaN, < 1 or infinite; plane_tolerance NaN, negative or infinite;
  * normal_min not in [0, 1]; min_weight not in [0, 1); flags or reserved != 0; prev_camera->fov not in (0, pi].
- * Out of scope: per-object motion vectors (a moved object's history is dropped where the tests catch it and kept where the same
- * surface is seen again); SVGF's 3 x 3 fallback search; multi-device frames (gather first, as for the denoiser); frames of different
+ * Per-object motion is not part of this call: a moved object's history is dropped where the tests catch it, unless d_hits was first
+ * rewound by rtx_rewind_hits_device (below).  Out of scope: SVGF's 3 x 3 fallback search; multi-device frames (gather first, as for the denoiser); frames of different
  * sizes.  (DESIGN.md 3.15 "Temporal accumulation".) */
 typedef struct RtxTemporalParams {
     double   alpha_min;          /* in [0, 1]: the least weight of the new frame (0: the running mean) */
@@ -823,6 +823,89 @@ int32_t  rtx_temporal_accumulate(const double *rgb, const double *var, const Rtx
                                  const double *hist_len, const RtxHit *hist_hits, const RtxCamera *prev_camera, uint32_t width,
                                  uint32_t height, const RtxTemporalParams *params, double *out_rgb, double *out_var, double *out_len,
                                  double *motion);
+
+/* Rewinding a pick buffer: the step before rtx_temporal_accumulate_device in a frame in which objects MOVED (rtx_scene_update_objects
+ * between the two frames).  The accumulation reprojects a pixel's CURRENT surface point; a moved object was somewhere else when the
+ * previous pick was taken, so its history is dropped or -- after a sideways move -- taken from another point of its surface.  This call
+ * replaces every hit on a moved object by the record of the SAME MATERIAL POINT on the object's geometry of the previous frame: the
+ * position and Object::normal_at that geometry has there.  The rewound buffer is what the accumulation takes as d_hits (it reads only
+ * position, normal and object); its d_motion then holds true screen-space motion, object motion included.  The UNREWOUND pick stays
+ * the next frame's d_hist_hits, which is why there is no in-place form.  The call takes no scene handle, allocates nothing and only
+ * enqueues ONE launch on `stream` (a hipStream_t; NULL = the device's null stream).
+ *
+ * This comment is the specification, under the rules of the temporal comment above: every operation is one separately rounded f64
+ * operation (add, subtract, multiply, divide, square root; never fused) in the written order and bracketing, so plain Python floats
+ * (tests/rewind_model.py) give the same bits; comparisons with a NaN are false; "finite" is neither NaN nor an infinity;
+ * a . b = (a.x * b.x + a.y * b.y) + a.z * b.z;  |a| = sqrt((a.x * a.x + a.y * a.y) + a.z * a.z);  norm(a) = (a.x / |a|, a.y / |a|,
+ * a.z / |a|), three true divisions (vector.rs:97-107).
+ *
+ * d_objects holds the m indices of the moved objects, STRICTLY ASCENDING; d_motions[k] belongs to d_objects[k].  Per hit
+ * H = d_hits[p], with o = H.object and P = H.position, in this order:
+ *  1. UNMOVED when m == 0 or o < 0: d_out[p] = the 64 bytes of H (a NaN keeps its payload).  Else the search
+ *       lo = 0, hi = m;  while (hi - lo > 1) { mid = (lo + hi) >> 1;  if (d_objects[mid] <= o) lo = mid; else hi = mid; }
+ *     UNMOVED when d_objects[lo] != o.  Else M = d_motions[lo].  (A list that is not ascending is the caller's error in the device
+ *     form: the hit is rewound by whichever entry the search ends on, or not at all; no index outside [0, m) is read.)
+ *  2. LOST -- d_out[p] = H with object = -1, every other byte copied, so that step 1 of the accumulation gives "no history" -- when
+ *     M.kind is RTX_MOTION_LOST or none of the three shape kinds (M.reserved is not read); when a component of P is not finite; where
+ *     step 3 says so; when a component of the rewound P' is not finite.
+ *  3. P', by M.kind, from now = M.now and before = M.before (the words of RtxObject.geom; the device never compares the two):
+ *     sphere (c = now[0..2], r = now[3]; c' = before[0..2], r' = before[3]):   s = r' / r;  !(s > 0) or s infinite: LOST (a zero, negative
+ *       or NaN radius on either side; a ratio that overflows);   g = P - c;   P'_k = c'_k + g_k * s.
+ *     plane (q = now[0..2]; q' = before[0..2]):   t = q' - q;   P'_k = P_k + t_k.   The translation of the anchor: a plane that turned
+ *       gets its previous normal in step 4, and the accumulation's own normal test decides.
+ *     triangle (A, B, C = now[0..2], [3..5], [6..8]; A', B', C' of before):   e1 = B - A;  e2 = C - A;  w = P - A;   d11 = e1 . e1;
+ *       d12 = e1 . e2;  d22 = e2 . e2;  w1 = w . e1;  w2 = w . e2;   det = d11 * d22 - d12 * d12;   !(det > 0) or det infinite: LOST;
+ *       u = (d22 * w1 - d12 * w2) / det;   v = (d11 * w2 - d12 * w1) / det;   e1' = B' - A';  e2' = C' - A';
+ *       P'_k = (A'_k + u * e1'_k) + v * e2'_k.   (u, v) are P's affine coordinates in the plane of the current triangle (the least-squares
+ *       ones where rounding left P off it); the reference's phantom hits outside the triangle extend affinely, which is intended.
+ *  4. n' = Object::normal_at(P') of the object with geometry `before`, in the reference's order (object.rs:37-39 over sphere.rs:31-33,
+ *     plane.rs:33-35, triangle.rs:104-107): the shape's normal, normalised AGAIN --
+ *       sphere:  norm(norm(P' - c'));    plane:  norm(before[3..5]);    triangle:  norm(norm(e1' x e2')),
+ *       a x b = (a.y * b.z - a.z * b.y,  a.z * b.x - a.x * b.z,  a.x * b.y - a.y * b.x).
+ *     A normal that is not finite is written as it comes (the accumulation's t > 0 test drops such a pixel).
+ *  5. d_out[p] = { position = P', normal = n', distance = H.distance (this frame's ray's; the accumulation does not read it),
+ *     object = o }.
+ * With before == now bitwise: a plane's P' == P as values and as bits except that a component -0.0 comes back as +0.0 (t = +0.0); a
+ * sphere's P'_k = c_k + (P_k - c_k) (s == 1 exactly), which is P_k to within 2^-53 * (|P_k - c_k| + |P'_k|) but not always its bits;
+ * a triangle's P' is the projection of P onto its plane, through u and v.  rtx_object_motions leaves such entries out.
+ *
+ * Buffers (DEVICE memory): d_hits, d_out: n_hits RtxHit, both 16-BYTE ALIGNED (every hipMalloc'd array and every whole-record offset
+ * into one is; the records move as 16-byte vectors) -- an RtxHit array that is only 8-byte aligned is refused, here, not in the
+ * accumulation; d_objects: m int64; d_motions: m RtxObjectMotion (8-byte aligned).  With m == 0 both lists may be NULL and the call
+ * is a copy.  RTX_ERR_INVALID_ARGUMENT, decided before any device is looked for: NULL d_hits or d_out, or one that is not 16-byte
+ * aligned; m > 0 with a NULL d_objects or d_motions; n_hits == 0 or >= 2^32 - 16; m >= 2^31; flags != 0; any overlap among the
+ * inputs and the output.
+ * Out of scope: a device-side record of what moved; the rotation of a plane about its anchor; skinned or camera-relative motion.
+ * (DESIGN.md 3.16 "Rewinding moved objects".) */
+#define RTX_MOTION_LOST 0xFFFFFFFFu   /* RtxObjectMotion.kind: the object has no previous geometry to rewind to (none of RTX_SPHERE .. RTX_TRIANGLE) */
+typedef struct RtxObjectMotion {
+    uint32_t kind;               /* RTX_SPHERE | RTX_PLANE | RTX_TRIANGLE: the object's kind in both frames; or RTX_MOTION_LOST */
+    uint32_t reserved;           /* must be 0 */
+    double   now[9];             /* RtxObject.geom as resident when d_hits was picked */
+    double   before[9];          /* RtxObject.geom when the previous frame's pick (d_hist_hits) was taken */
+} RtxObjectMotion;
+RTX_STATIC_ASSERT(sizeof(RtxObjectMotion) == 152 && offsetof(RtxObjectMotion, reserved) == 4 && offsetof(RtxObjectMotion, now) == 8 &&
+                  offsetof(RtxObjectMotion, before) == 80, "RtxObjectMotion layout");
+
+int32_t  rtx_rewind_hits_device(const RtxHit *d_hits, uint64_t n_hits, const int64_t *d_objects, const RtxObjectMotion *d_motions,
+                                uint64_t m, uint32_t flags, RtxHit *d_out, int32_t device, void *stream);
+/* One-shot host form (device 0: allocates, copies, rewinds, copies back).  Every pointer is a HOST array of any alignment; flags are 0.
+ * Refused as the device form refuses, and additionally: a list that is not strictly ascending, a kind that is none of the three shapes
+ * and not RTX_MOTION_LOST, a reserved word that is not 0. */
+int32_t  rtx_rewind_hits(const RtxHit *hits, uint64_t n_hits, const int64_t *objects, const RtxObjectMotion *motions, uint64_t m,
+                         RtxHit *out);
+/* What a caller handed to rtx_scene_update_objects since the previous frame -> the sorted list the two calls above take.  Host only: no
+ * device is looked for.  Entry i says that object indices[i] had the record before[i] and now has now[i]; only kind and geom are
+ * read.  before[i].kind == RTX_MOTION_LOST says that the object was hidden, or did not exist, when the previous pick was taken.  Of an
+ * index that is given more than once, the FIRST entry's `before` and the LAST entry's `now` are kept (several updates between two
+ * frames, in call order).  Then, per index: the kinds differ, or `before` is RTX_MOTION_LOST: kind = RTX_MOTION_LOST, now and before
+ * all 0.  Else, when the geometry words the kind reads (sphere 4, plane 6, triangle 9) are bitwise the same in both: the index is left
+ * out (a material update moves nothing).  Else kind = the kind, now and before = all 9 words of the two geom arrays.  reserved = 0.
+ * The output is in ascending index order; *m_out entries (at most n; objects_out and motions_out hold n) are written.
+ * RTX_ERR_INVALID_ARGUMENT: n > 0 with a NULL indices, before, now, objects_out or motions_out; NULL m_out; n >= 2^31; an index
+ * >= 2^63; a now[i].kind that is none of the three shapes; a before[i].kind that is none of them and not RTX_MOTION_LOST. */
+int32_t  rtx_object_motions(const uint64_t *indices, const RtxObject *before, const RtxObject *now, uint64_t n, int64_t *objects_out,
+                            RtxObjectMotion *motions_out, uint64_t *m_out);
 
 /* Test hook (lab library; the product returns RTX_ERR_UNSUPPORTED -- same sources and flags, so the arithmetic it shows is the
  * product's): evaluates one f64 operation per element on the device (op 0: a/b, 1: sqrt(a),

@@ -24,13 +24,15 @@ from .abi import (RTX_TUNE_NO_TILES, RTX_TUNE_NO_QNODES, RTX_TUNE_NO_PACKETS, RT
 from .abi import (OBJECT_DTYPE, RTX_KERNEL_WAVEFRONT, RTX_KERNEL_AUTO, RTX_KERNEL_BVH, RTX_KERNEL_EXACT, RTX_KERNEL_MIXED, RTX_KERNEL_MIXED_VERIFY, RTX_KERNEL_BVH_REGROUP,
                   RTX_PLANE, RTX_SPHERE, RTX_TRIANGLE, RtxError, load_library, RAY_DTYPE, HIT_DTYPE, FEATURE_DTYPE)
 from .abi import DENOISE_PARAMS_DTYPE, RTX_DENOISE_DEMODULATE, RTX_DENOISE_MAX_PASSES, RTX_DENOISE_NO_NORMAL, TEMPORAL_PARAMS_DTYPE
+from .abi import OBJECT_MOTION_DTYPE, RTX_MOTION_LOST
 
 __all__ = ["LabKernel", "Vector3", "Material", "Sphere", "Plane", "Triangle", "Object", "Config", "Camera", "Scene",
            "SceneHandle", "RtxError", "device_count", "pack_objects", "OBJECT_DTYPE",
            "RTX_KERNEL_AUTO", "RTX_KERNEL_EXACT", "RTX_KERNEL_MIXED", "RTX_KERNEL_MIXED_VERIFY", "RTX_KERNEL_BVH", "RTX_KERNEL_BVH_REGROUP", "RTX_KERNEL_WAVEFRONT", "debug_host_scene",
            "RAY_DTYPE", "HIT_DTYPE", "FEATURE_DTYPE", "make_rays", "denoise", "denoise_params", "denoise_work_bytes", "DENOISE_PARAMS_DTYPE",
            "RTX_DENOISE_DEMODULATE", "RTX_DENOISE_MAX_PASSES", "RTX_DENOISE_NO_NORMAL", "temporal_params", "temporal_tables",
-           "temporal_accumulate", "TEMPORAL_PARAMS_DTYPE", "Temporal"]
+           "temporal_accumulate", "TEMPORAL_PARAMS_DTYPE", "Temporal", "object_motions", "rewind_hits", "OBJECT_MOTION_DTYPE",
+           "RTX_MOTION_LOST"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -464,6 +466,47 @@ def temporal_accumulate(img, hits, history=None, prev_camera=None, variance=None
     abi.check(lib.rtx_temporal_accumulate(ptr(img), ptr(var), ptr(h), ptr(hist[0]), ptr(hist[1]), ptr(hist[2]), ptr(hist[3]),
                                           C.addressof(cam) if cam is not None else None, width, height, p.ctypes.data,
                                           ptr(out["rgb"]), ptr(out["var"]), ptr(out["len"]), ptr(out["motion"])), lib)
+    return out
+
+
+def object_motions(indices, before, now):
+    """rtx_object_motions (host only: no device is needed): what a caller handed to update_objects since the previous frame -> the
+    (objects, motions) pair rewind_hits takes: int64 indices in ascending order and their OBJECT_MOTION_DTYPE records.  before / now:
+    OBJECT_DTYPE arrays (or lists of Objects), entry i the record object indices[i] had and has; before[i]["kind"] == RTX_MOTION_LOST
+    says it was hidden or absent.  Of a repeated index the first `before` and the last `now` count; a changed kind or a lost `before`
+    gives an RTX_MOTION_LOST record; bitwise unchanged geometry (a material update) is left out."""
+    lib = load_library()
+    pk = lambda a: np.ascontiguousarray(a if isinstance(a, np.ndarray) else pack_objects(a), dtype=OBJECT_DTYPE).reshape(-1)
+    was, is_ = pk(before), pk(now)
+    idx = np.ascontiguousarray(np.asarray(indices, dtype=np.uint64).reshape(-1))
+    if not len(idx) == len(was) == len(is_):
+        raise ValueError("object_motions: %d indices for %d and %d objects" % (len(idx), len(was), len(is_)))
+    n = len(idx)
+    objects, motions, m = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=OBJECT_MOTION_DTYPE), C.c_uint64(0)
+    ptr = lambda a: a.ctypes.data if len(a) else None
+    abi.check(lib.rtx_object_motions(ptr(idx), ptr(was), ptr(is_), n, ptr(objects), ptr(motions), C.byref(m)), lib)
+    return objects[:m.value].copy(), motions[:m.value].copy()
+
+
+def _motion_lists(objects, motions):
+    objects = np.ascontiguousarray(np.asarray(objects, dtype=np.int64).reshape(-1))
+    motions = np.ascontiguousarray(np.asarray(motions, dtype=OBJECT_MOTION_DTYPE).reshape(-1))
+    if len(objects) != len(motions):
+        raise ValueError("rewind_hits: %d objects for %d motions" % (len(objects), len(motions)))
+    return objects, motions
+
+
+def rewind_hits(hits, objects, motions):
+    """rtx_rewind_hits on host arrays (device 0, copies both ways): hits, HIT_DTYPE records of this frame's pick buffer (any shape) ->
+    the records of the same material points on the moved objects' previous geometry (include/rtx_hip.h, "Rewinding a pick buffer");
+    (objects, motions) as object_motions returns them."""
+    lib = load_library()
+    h = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    objects, motions = _motion_lists(objects, motions)
+    out = np.zeros_like(h)
+    m = len(objects)
+    abi.check(lib.rtx_rewind_hits(h.ctypes.data if h.size else None, h.size, objects.ctypes.data if m else None,
+                                  motions.ctypes.data if m else None, m, out.ctypes.data if h.size else None), lib)
     return out
 
 
@@ -1027,10 +1070,20 @@ class SceneHandle:
             C.addressof(cam) if cam is not None else None, ptr(hist[5]), int(width), int(height), p.ctypes.data, ptr(d_out_rgb_ptr),
             ptr(d_out_var_ptr), ptr(d_out_len_ptr), ptr(d_motion_ptr), self.device, ptr(stream)))
 
-    def temporal(self, width, height, **params):
+    def rewind_hits_device(self, n_hits, d_hits_ptr, d_out_ptr, d_objects_ptr=None, d_motions_ptr=None, m=0, stream=None):
+        """rtx_rewind_hits_device on this handle's device: n_hits RtxHit records at d_hits_ptr -> d_out_ptr (both 16-byte aligned),
+        rewound by the m ascending int64 indices at d_objects_ptr and their RtxObjectMotion records at d_motions_ptr (object_motions,
+        uploaded).  Only enqueues on `stream`."""
+        ptr = lambda a: C.c_void_p(int(a)) if a else None
+        self._check(self._lib.rtx_rewind_hits_device(ptr(d_hits_ptr), int(n_hits), ptr(d_objects_ptr), ptr(d_motions_ptr), int(m), 0,
+                                                     ptr(d_out_ptr), self.device, ptr(stream)))
+
+    def temporal(self, width, height, objects=None, **params):
         """A Temporal accumulator of a width x height frame sequence on this handle: frame(spp, camera) renders the next low-sample
-        frame and blends the previous frames' history in where the same surface is still seen.  params: fields of RtxTemporalParams."""
-        return Temporal(self, width, height, **params)
+        frame and blends the previous frames' history in where the same surface is still seen.  objects: the packed object list the
+        handle holds (OBJECT_DTYPE) -- with it Temporal.update_objects moves objects AND keeps their history (the frame's pick is
+        rewound, rtx_rewind_hits_device).  params: fields of RtxTemporalParams."""
+        return Temporal(self, width, height, objects=objects, **params)
 
     def close(self):
         if self._h:
@@ -1172,10 +1225,13 @@ class Temporal:
     rtx_render_blocks_accumulate, so frames do not repeat each other's random draws.  That call does not read the handle's
     rays_per_pixel; it accepts any range that ends at or below 2^32 - 1, and frame() raises ValueError beyond it."""
 
-    def __init__(self, handle, width, height, **params):
+    def __init__(self, handle, width, height, objects=None, **params):
         import torch
         self._hnd, self.width, self.height = handle, int(width), int(height)
         self.params = temporal_params(handle._lib, **params)
+        # the resident object list as update_objects() has left it (None: update_objects is not offered, `moved` is given to frame())
+        self._objects = None if objects is None else np.array(objects if isinstance(objects, np.ndarray) else pack_objects(objects), dtype=OBJECT_DTYPE)
+        self._moved = {}                           # index -> (record at the last frame, record now), since the last frame
         self._dev = torch.device("cuda", handle.device)
         self._tables = {}                          # fov -> the uploaded tables
         self.reset()
@@ -1184,8 +1240,30 @@ class Temporal:
         """forget the history: the next frame is a first frame (and frame_index, so the sample range, starts again at 0)"""
         self._hist = None                          # (rgb, var or None, len, hits, camera, tables) of the last frame
         self._motion = None
+        self._moved = {}
         self.frame_index = 0
-        self.frame_mean = self.frame_variance = None
+        self.frame_mean = self.frame_variance = self.frame_rewound = None
+
+    def update_objects(self, indices, packed, mode="auto"):
+        """SceneHandle.update_objects, remembered: the next frame() rewinds its pick on these objects to where they were at the last
+        frame, so their pixels keep their history.  Several updates between two frames fold as rtx_object_motions folds a repeated
+        index.  Needs the object list (SceneHandle.temporal(w, h, objects=...)).  Returns how the update ran.
+        Not tracked: visibility.  An object that was hidden (SceneHandle.hide) or absent when the last frame was taken has no previous
+        geometry on screen; update_objects cannot say so, and such an object is rewound from the record this list held, or not at
+        all, and the accumulation's own tests decide.  Give frame() the list yourself for it: moved=(indices, before, now) with
+        before[i]["kind"] = RTX_MOTION_LOST."""
+        if self._objects is None:
+            raise ValueError("update_objects: the Temporal was made without the object list (temporal(w, h, objects=packed))")
+        arr = np.ascontiguousarray(packed if isinstance(packed, np.ndarray) else pack_objects(packed), dtype=OBJECT_DTYPE).reshape(-1)
+        idx = [int(i) for i in np.asarray(indices).reshape(-1)]
+        if len(idx) != len(arr) or any(i < 0 or i >= len(self._objects) for i in idx):
+            raise ValueError("update_objects: %d indices for %d objects, or an index outside the list" % (len(idx), len(arr)))
+        how = self._hnd.update_objects(idx, arr, mode=mode)
+        for i, rec in zip(idx, arr):
+            first = self._moved[i][0] if i in self._moved else self._objects[i].copy()
+            self._moved[i] = (first, rec.copy())
+            self._objects[i] = rec
+        return how
 
     def _tables_for(self, fov):
         import torch
@@ -1194,8 +1272,12 @@ class Temporal:
             t = self._tables[fov] = torch.from_numpy(temporal_tables(fov, self.width, self.height)).to(self._dev)
         return t
 
-    def frame(self, spp, camera=None):
-        """the next frame at spp samples per pixel -> numpy (h, w, 3), the accumulated mean.  spp >= 2 tracks the variance of the mean
+    def frame(self, spp, camera=None, moved=None):
+        """the next frame at spp samples per pixel -> numpy (h, w, 3), the accumulated mean.  moved: what moved since the last frame,
+        as (indices, before_packed, now_packed) or a ready (objects, motions) pair of object_motions; None: what update_objects() of
+        this Temporal was given since then (nothing: the pick is used as it is, no rewind is launched).  With something moved the
+        frame's pick is rewound into a second buffer (frame_rewound), which the accumulation reads; the unrewound pick stays
+        frame_hits and is the next frame's history.  spp >= 2 tracks the variance of the mean
         ((sum_sq - sum^2 / n) / (n - 1) / n, Progressive's expression); a sequence keeps one spp (a change resets the history when it
         switches the variance on or off).  frame_mean / frame_variance keep this frame's own torch tensors."""
         import torch
@@ -1221,6 +1303,19 @@ class Temporal:
         hist = self._hist
         if hist is not None and (hist[1] is None) != (var is None):
             hist = None
+        if moved is None and self._moved:
+            keys = sorted(self._moved)
+            moved = (keys, np.array([self._moved[i][0] for i in keys], dtype=OBJECT_DTYPE),
+                     np.array([self._moved[i][1] for i in keys], dtype=OBJECT_DTYPE))
+        self._moved = {}
+        seen = hits                                # what the accumulation reads as d_hits
+        if moved is not None:
+            objects, motions = object_motions(*moved) if len(moved) == 3 else _motion_lists(*moved)
+            if len(objects) and hist is not None:
+                d_obj, d_mot = torch.from_numpy(objects).to(dev), torch.from_numpy(motions.view(np.uint8).reshape(-1)).to(dev)
+                seen = torch.empty_like(hits)
+                torch.cuda.synchronize(dev)
+                self._hnd.rewind_hits_device(h * w, hits.data_ptr(), seen.data_ptr(), d_obj.data_ptr(), d_mot.data_ptr(), len(objects))
         out = torch.empty_like(mean)
         out_var = torch.empty_like(mean) if var is not None else None
         out_len = torch.empty((h, w), dtype=torch.float64, device=dev)
@@ -1230,12 +1325,13 @@ class Temporal:
         if hist is not None:
             history = (hist[0].data_ptr(), hist[1].data_ptr() if hist[1] is not None else None, hist[2].data_ptr(), hist[3].data_ptr(),
                        hist[4], hist[5].data_ptr())
-        self._hnd.temporal_accumulate_device(w, h, mean.data_ptr(), hits.data_ptr(), out.data_ptr(), out_len.data_ptr(),
+        self._hnd.temporal_accumulate_device(w, h, mean.data_ptr(), seen.data_ptr(), out.data_ptr(), out_len.data_ptr(),
                                              d_var_ptr=var.data_ptr() if var is not None else None,
                                              d_out_var_ptr=out_var.data_ptr() if out_var is not None else None,
                                              d_motion_ptr=motion.data_ptr(), history=history, params=self.params)
         torch.cuda.synchronize(dev)
         self.frame_mean, self.frame_variance, self.frame_hits = mean, var, hits
+        self.frame_rewound = seen if seen is not hits else None
         self._hist = (out, out_var, out_len, hits, cam, self._tables_for(float(cam.fov)))
         self._motion = motion
         self.frame_index += 1

@@ -93,6 +93,13 @@ class RtxTemporalParams(C.Structure):
                 ("min_weight", C.c_double), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+RTX_MOTION_LOST = 0xFFFFFFFF                    # RtxObjectMotion.kind: no previous geometry to rewind to
+
+
+class RtxObjectMotion(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("reserved", C.c_uint32), ("now", C.c_double * 9), ("before", C.c_double * 9)]
+
+
 # the same layouts as numpy records (arrays of rays / answers)
 RAY_DTYPE = np.dtype([("position", "<f8", (3,)), ("direction", "<f8", (3,))])
 HIT_DTYPE = np.dtype([("position", "<f8", (3,)), ("normal", "<f8", (3,)), ("distance", "<f8"), ("object", "<i8")])
@@ -107,6 +114,8 @@ assert DENOISE_PARAMS_DTYPE.itemsize == C.sizeof(RtxDenoiseParams) == 56
 TEMPORAL_PARAMS_DTYPE = np.dtype([("alpha_min", "<f8"), ("max_history", "<f8"), ("plane_tolerance", "<f8"), ("normal_min", "<f8"),
                                   ("min_weight", "<f8"), ("flags", "<u4"), ("reserved", "<u4")])
 assert TEMPORAL_PARAMS_DTYPE.itemsize == C.sizeof(RtxTemporalParams) == 48
+OBJECT_MOTION_DTYPE = np.dtype([("kind", "<u4"), ("reserved", "<u4"), ("now", "<f8", (9,)), ("before", "<f8", (9,))])
+assert OBJECT_MOTION_DTYPE.itemsize == C.sizeof(RtxObjectMotion) == 152
 
 
 # every symbol include/rtx_hip.h declares: (name, restype, argtypes)
@@ -169,6 +178,10 @@ SYMBOLS = [
     ("rtx_temporal_tables", C.c_int32, [C.c_double, C.c_uint32, C.c_uint32, C.c_void_p]),
     ("rtx_temporal_accumulate_device", C.c_int32, [C.c_void_p] * 9 + [C.c_uint32, C.c_uint32] + [C.c_void_p] * 5 + [C.c_int32, C.c_void_p]),
     ("rtx_temporal_accumulate", C.c_int32, [C.c_void_p] * 8 + [C.c_uint32, C.c_uint32] + [C.c_void_p] * 5),
+    ("rtx_rewind_hits_device", C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_int32,
+                                           C.c_void_p]),
+    ("rtx_rewind_hits", C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    ("rtx_object_motions", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rtx_debug_math", C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
     ("rtx_debug_paths", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("rtx_debug_store_samples", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),

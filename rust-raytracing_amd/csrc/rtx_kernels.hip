@@ -11,14 +11,15 @@
 //                       trace_exact_kernel.  Dead slots are refilled from a global ray queue with a
 //                       wave ballot + mbcnt prefix sum (one atomic per workgroup per round).
 //   resolve_kernel      left fold of a pixel's samples in sample order, then / rays_per_pixel.
-//   epilogue_kernel     render_to_image's quantize, the multi-device gather, the two forms of the denoiser (rtx_denoise.h) and the
-//                       temporal accumulation (rtx_temporal.h), by a launch-uniform form.
+//   epilogue_kernel     render_to_image's quantize, the multi-device gather, the two forms of the denoiser (rtx_denoise.h), the
+//                       temporal accumulation (rtx_temporal.h) and the rewind of a pick buffer (rtx_rewind.h), by a launch-uniform form.
 //
 // Compiled with -ffp-contract=off; the f32 filter uses explicit fmaf.
 #include "rtx_launch.h"
 #include "rtx_traverse.h"
 #include "rtx_denoise.h"
 #include "rtx_temporal.h"
+#include "rtx_rewind.h"
 
 #include <cstdlib>
 
@@ -671,12 +672,16 @@ __device__ __forceinline__ uint8_t rust_as_u8(double v)
 //   other forms pass zeroed; of the two only form 17 is launched with dynamic LDS (kDnLdsBytes), so the movers' occupancy pays none for it.
 // form 18 -- rtx_temporal_accumulate_device (rtx_temporal.h): everything it reads is in `ta`, which the other forms pass zeroed; it is
 //   launched with dynamic LDS for its two sine tables when they fit kTemporalLdsBytes, else with none.
-constexpr uint32_t kEpilogueDenoisePrepare = 16u, kEpilogueDenoisePass = 17u, kEpilogueTemporal = 18u;
+// form 19 -- rtx_rewind_hits_device (rtx_rewind.h): everything it reads is in `rw`, which the other forms pass zeroed; it is launched
+//   with dynamic LDS for its list of moved objects when that fits kTemporalLdsBytes, else with none.
+constexpr uint32_t kEpilogueDenoisePrepare = 16u, kEpilogueDenoisePass = 17u, kEpilogueTemporal = 18u, kEpilogueRewind = 19u;
 extern __shared__ double epilogue_lds[];
 __global__ __launch_bounds__(256) void epilogue_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
                                                        uint32_t width, uint32_t height, uint32_t n, uint32_t cap_rows,
-                                                       uint32_t block, uint32_t flip, uint32_t form, DenoiseArgs dn, TemporalArgs ta)
+                                                       uint32_t block, uint32_t flip, uint32_t form, DenoiseArgs dn, TemporalArgs ta,
+                                                       RewindArgs rw)
 {
+    if (form == kEpilogueRewind) { rewind_hits(rw, epilogue_lds); return; }
     if (form == kEpilogueTemporal) { temporal_accumulate(ta, epilogue_lds); return; }
     if (form == kEpilogueDenoisePass) { denoise_pass(dn, epilogue_lds); return; }
     if (form == kEpilogueDenoisePrepare) { denoise_prepare(dn); return; }
@@ -867,7 +872,7 @@ hipError_t launch_quantize(const double *rgb, uint8_t *rgb8, uint32_t width, uin
     uint64_t npix = (uint64_t)width * height;
     if (npix == 0) return hipSuccess;
     hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, stream,
-                       reinterpret_cast<const uint8_t *>(rgb), rgb8, width, height, 1u, 0u, 1u, 1u, 0u, DenoiseArgs{}, TemporalArgs{});
+                       reinterpret_cast<const uint8_t *>(rgb), rgb8, width, height, 1u, 0u, 1u, 1u, 0u, DenoiseArgs{}, TemporalArgs{}, RewindArgs{});
     return hipGetLastError();
 }
 
@@ -876,7 +881,7 @@ hipError_t launch_quantize_values(const double *rgb, uint8_t *rgb8, uint32_t wid
     uint64_t npix = (uint64_t)width * n_rows;
     if (npix == 0) return hipSuccess;
     hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, stream,
-                       reinterpret_cast<const uint8_t *>(rgb), rgb8, width, n_rows, 1u, 0u, 1u, 0u, 0u, DenoiseArgs{}, TemporalArgs{});
+                       reinterpret_cast<const uint8_t *>(rgb), rgb8, width, n_rows, 1u, 0u, 1u, 0u, 0u, DenoiseArgs{}, TemporalArgs{}, RewindArgs{});
     return hipGetLastError();
 }
 
@@ -886,7 +891,7 @@ hipError_t launch_deinterleave(const double *parts, double *full, uint32_t width
     const uint64_t total = (uint64_t)width * height * 3;
     if (total == 0) return hipSuccess;
     hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, stream,
-                       reinterpret_cast<const uint8_t *>(parts), reinterpret_cast<uint8_t *>(full), width, height, n, cap_rows, block, 0u, 8u, DenoiseArgs{}, TemporalArgs{});
+                       reinterpret_cast<const uint8_t *>(parts), reinterpret_cast<uint8_t *>(full), width, height, n, cap_rows, block, 0u, 8u, DenoiseArgs{}, TemporalArgs{}, RewindArgs{});
     return hipGetLastError();
 }
 
@@ -896,7 +901,7 @@ hipError_t launch_deinterleave_u8(const uint8_t *parts, uint8_t *full, uint32_t 
     const uint64_t total = (uint64_t)width * height * 3;
     if (total == 0) return hipSuccess;
     hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, stream, parts, full, width,
-                       height, n, cap_rows, block, flip ? 1u : 0u, 1u, DenoiseArgs{}, TemporalArgs{});
+                       height, n, cap_rows, block, flip ? 1u : 0u, 1u, DenoiseArgs{}, TemporalArgs{}, RewindArgs{});
     return hipGetLastError();
 }
 
@@ -905,7 +910,7 @@ hipError_t launch_denoise_prepare(const DenoiseArgs &d, hipStream_t stream)
     const uint64_t npix = (uint64_t)d.width * d.height;
     if (npix == 0) return hipSuccess;
     hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, stream, nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u,
-                       kEpilogueDenoisePrepare, d, TemporalArgs{});
+                       kEpilogueDenoisePrepare, d, TemporalArgs{}, RewindArgs{});
     return hipGetLastError();
 }
 
@@ -923,7 +928,7 @@ hipError_t launch_denoise_pass(const DenoiseArgs &d_, hipStream_t stream)
     if (blocks >= (1ull << 31)) return hipErrorInvalidValue;
     d.tiles = (uint32_t)tiles;
     hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)blocks), dim3(256), kDnLdsBytes, stream, nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u,
-                       kEpilogueDenoisePass, d, TemporalArgs{});
+                       kEpilogueDenoisePass, d, TemporalArgs{}, RewindArgs{});
     return hipGetLastError();
 }
 
@@ -935,7 +940,18 @@ hipError_t launch_temporal(const TemporalArgs &t_, hipStream_t stream)
     const size_t table_bytes = ((size_t)t.width + 1u + (size_t)t.height + 1u) * sizeof(double);
     t.tables_in_lds = ((t.flags & kTaHistory) != 0u && table_bytes <= kTemporalLdsBytes) ? 1u : 0u;
     hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)((npix + 255) / 256)), dim3(256), t.tables_in_lds ? table_bytes : 0, stream, nullptr,
-                       nullptr, 0u, 0u, 0u, 0u, 0u, 0u, kEpilogueTemporal, DenoiseArgs{}, t);
+                       nullptr, 0u, 0u, 0u, 0u, 0u, 0u, kEpilogueTemporal, DenoiseArgs{}, t, RewindArgs{});
+    return hipGetLastError();
+}
+
+hipError_t launch_rewind(const RewindArgs &r_, hipStream_t stream)
+{
+    RewindArgs r = r_;
+    if (r.n == 0) return hipSuccess;
+    const size_t list_bytes = (size_t)r.m * sizeof(long long);
+    r.list_in_lds = (r.m != 0u && list_bytes <= kTemporalLdsBytes) ? 1u : 0u;
+    hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)(((uint64_t)r.n + 255) / 256)), dim3(256), r.list_in_lds ? list_bytes : 0, stream, nullptr,
+                       nullptr, 0u, 0u, 0u, 0u, 0u, 0u, kEpilogueRewind, DenoiseArgs{}, TemporalArgs{}, r);
     return hipGetLastError();
 }
 

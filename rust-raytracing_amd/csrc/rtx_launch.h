@@ -156,6 +156,21 @@ struct TemporalArgs {
 };
 hipError_t launch_temporal(const TemporalArgs &t, hipStream_t stream);         // sets tables_in_lds in its copy of t
 
+// ---- rewinding a pick buffer (rtx_rewind_hits_device; device text: rtx_rewind.h, host side: rtx_rewind.hip): one more launch-uniform
+// form of epilogue_kernel, one hit per thread, its arguments by value beside TemporalArgs (the other forms pass them zeroed).  The
+// sorted list of moved objects is staged in dynamic LDS when its m * 8 bytes fit kTemporalLdsBytes (the budget of form 18's tables),
+// else searched in global memory with the same code.
+struct RewindMotion { uint32_t kind, reserved; double now[9], before[9]; };    // = RtxObjectMotion
+static_assert(sizeof(RewindMotion) == 152, "RewindMotion");
+struct RewindArgs {
+    const QueryHit *hits;                                     // n records, 16-byte aligned
+    QueryHit *out;
+    const long long *objects;                                 // m indices, ascending (null when m == 0)
+    const RewindMotion *motions;
+    uint32_t n, m, list_in_lds, pad;
+};
+hipError_t launch_rewind(const RewindArgs &r, hipStream_t stream);             // sets list_in_lds in its copy of r
+
 // ---- ray queries (rtx_query.hip): closest_object for caller rays or for the pick buffer's zero-offset primary rays, or -- the
 // any-hit mode, a launch-uniform switch of the same kernel -- whether any object lies before a per-ray distance limit, or -- the
 // path mode, a third switch -- render_ray's colour of the path that starts with the ray, or -- the feature mode, a fourth -- the

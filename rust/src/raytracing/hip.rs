@@ -122,6 +122,19 @@ pub struct RtxTemporalParams {
     pub reserved: u32,
 }
 
+/// `RtxObjectMotion.kind` of an object with no previous geometry to rewind to (include/rtx_hip.h, "Rewinding a pick buffer").
+pub const RTX_MOTION_LOST: u32 = 0xFFFF_FFFF;
+
+/// `RtxObjectMotion`: one moved object's geometry now and when the previous frame's pick was taken.  152 bytes.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtxObjectMotion {
+    pub kind: u32,
+    pub reserved: u32,
+    pub now: [f64; 9],
+    pub before: [f64; 9],
+}
+
 #[repr(C)]
 pub struct RtxSceneHandleOpaque {
     _private: [u8; 0],
@@ -171,6 +184,9 @@ extern "C" {
     pub fn rtx_temporal_default_params(out: *mut RtxTemporalParams);
     pub fn rtx_temporal_tables(fov: f64, width: u32, height: u32, tables: *mut f64) -> i32;
     pub fn rtx_temporal_accumulate_device(d_rgb: *const f64, d_var: *const f64, d_hits: *const RtxHit, d_hist_rgb: *const f64, d_hist_var: *const f64, d_hist_len: *const f64, d_hist_hits: *const RtxHit, prev_camera: *const RtxCamera, d_prev_tables: *const f64, width: u32, height: u32, params: *const RtxTemporalParams, d_out_rgb: *mut f64, d_out_var: *mut f64, d_out_len: *mut f64, d_motion: *mut f64, device: i32, stream: *mut c_void) -> i32;
+    pub fn rtx_rewind_hits_device(d_hits: *const RtxHit, n_hits: u64, d_objects: *const i64, d_motions: *const RtxObjectMotion, m: u64, flags: u32, d_out: *mut RtxHit, device: i32, stream: *mut c_void) -> i32;
+    pub fn rtx_rewind_hits(hits: *const RtxHit, n_hits: u64, objects: *const i64, motions: *const RtxObjectMotion, m: u64, out: *mut RtxHit) -> i32;
+    pub fn rtx_object_motions(indices: *const u64, before: *const RtxObject, now: *const RtxObject, n: u64, objects_out: *mut i64, motions_out: *mut RtxObjectMotion, m_out: *mut u64) -> i32;
     pub fn rtx_temporal_accumulate(rgb: *const f64, var: *const f64, hits: *const RtxHit, hist_rgb: *const f64, hist_var: *const f64, hist_len: *const f64, hist_hits: *const RtxHit, prev_camera: *const RtxCamera, width: u32, height: u32, params: *const RtxTemporalParams, out_rgb: *mut f64, out_var: *mut f64, out_len: *mut f64, motion: *mut f64) -> i32;
 }
 
