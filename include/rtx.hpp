@@ -529,6 +529,16 @@ public:
     {
         check(rtx_denoise_device(d_rgb, d_var, d_features, (uint32_t)width, (uint32_t)height, &params, d_out, d_var_out, d_work, device_, hip_stream));
     }
+    // guided upsampling on this scene's device (rtx_upsample_device; it reads no scene): the low frame d_lo_rgb[height / s][width / s][3]
+    // (s = params.factor; d_lo_var its variance of the mean, or null) with the guides of the low and of the width x height output frame
+    // (pixel_features at both sizes, the same camera) -> d_out[height][width][3] (and d_var_out, or null).  One launch, only enqueued.
+    void upsample(std::size_t width, std::size_t height, const double *d_lo_rgb, const double *d_lo_var, const RtxPixelFeatures *d_lo_features,
+                  const RtxPixelFeatures *d_features, const RtxUpsampleParams &params, double *d_out, double *d_var_out,
+                  void *hip_stream = nullptr)
+    {
+        check(rtx_upsample_device(d_lo_rgb, d_lo_var, d_lo_features, d_features, (uint32_t)width, (uint32_t)height, &params, d_out, d_var_out,
+                                  device_, hip_stream));
+    }
     // temporal accumulation on this scene's device (rtx_temporal_accumulate_device; it reads no scene): this frame's d_rgb, d_var (or
     // null) and pick buffer d_hits with the previous frame's accumulated d_hist_* (all null: the first frame), its camera and the
     // uploaded rtx::temporal_tables of that camera -> d_out_rgb, d_out_var (or null), d_out_len, d_motion (or null).  Only enqueues.
@@ -593,6 +603,33 @@ inline std::vector<double> denoise(const std::vector<double> &rgb, const std::ve
     if (var_out) var_out->assign(var.empty() ? 0 : rgb.size(), 0.0);
     int32_t rc = rtx_denoise(rgb.data(), var.empty() ? nullptr : var.data(), features.data(), (uint32_t)width, (uint32_t)height, &params,
                              out.data(), (var_out && !var.empty()) ? var_out->data() : nullptr);
+    if (rc != RTX_OK) throw Panic(rc, rtx_last_error());
+    return out;
+}
+
+// The guided upsampling of include/rtx_hip.h ("Guided upsampling"): a frame rendered at 1 / factor of the output size, reconstructed at
+// the output size under the guides of both sizes.
+inline RtxUpsampleParams upsample_default_params()
+{
+    RtxUpsampleParams p;
+    rtx_upsample_default_params(&p);
+    return p;
+}
+// host form (rtx_upsample: device 0, copies both ways): lo_rgb [height / s][width / s][3] and lo_features of the low frame, features of
+// the width x height output frame (both from Scene::pixel_features, the same camera), lo_var (may be empty) the low frame's variance of
+// the mean -> the output frame; var_out (optional, needs lo_var): its variance
+inline std::vector<double> upsample(const std::vector<double> &lo_rgb, const std::vector<RtxPixelFeatures> &lo_features,
+                                    const std::vector<RtxPixelFeatures> &features, std::size_t width, std::size_t height,
+                                    const RtxUpsampleParams &params = upsample_default_params(), const std::vector<double> &lo_var = {},
+                                    std::vector<double> *var_out = nullptr)
+{
+    const std::size_t s = params.factor ? params.factor : 1, n_lo = (width / s) * (height / s);
+    if (lo_rgb.size() != 3 * n_lo || lo_features.size() != n_lo || features.size() != width * height || (!lo_var.empty() && lo_var.size() != lo_rgb.size()))
+        throw Panic(RTX_ERR_INVALID_ARGUMENT, "upsample: lo_rgb, lo_var and lo_features must hold (width / factor) * (height / factor) pixels, features width * height");
+    std::vector<double> out(3 * width * height);
+    if (var_out) var_out->assign(lo_var.empty() ? 0 : out.size(), 0.0);
+    int32_t rc = rtx_upsample(lo_rgb.data(), lo_var.empty() ? nullptr : lo_var.data(), lo_features.data(), features.data(), (uint32_t)width,
+                              (uint32_t)height, &params, out.data(), (var_out && !lo_var.empty()) ? var_out->data() : nullptr);
     if (rc != RTX_OK) throw Panic(rc, rtx_last_error());
     return out;
 }

@@ -793,7 +793,7 @@ int32_t  rtx_denoise(const double *rgb, const double *var, const RtxPixelFeature
  * normal_min not in [0, 1]; min_weight not in [0, 1); flags or reserved != 0; prev_camera->fov not in (0, pi].
  * Per-object motion is not part of this call: a moved object's history is dropped where the tests catch it, unless d_hits was first
  * rewound by rtx_rewind_hits_device (below).  Out of scope: SVGF's 3 x 3 fallback search; multi-device frames (gather first, as for the denoiser); frames of different
- * sizes.  (DESIGN.md 3.15 "Temporal accumulation".) */
+ * sizes (rtx_upsample_device, below, takes a low frame to the display's size after this call).  (DESIGN.md 3.15 "Temporal accumulation".) */
 typedef struct RtxTemporalParams {
     double   alpha_min;          /* in [0, 1]: the least weight of the new frame (0: the running mean) */
     double   max_history;        /* >= 1, finite: where the history length stops growing */
@@ -906,6 +906,94 @@ int32_t  rtx_rewind_hits(const RtxHit *hits, uint64_t n_hits, const int64_t *obj
  * >= 2^63; a now[i].kind that is none of the three shapes; a before[i].kind that is none of them and not RTX_MOTION_LOST. */
 int32_t  rtx_object_motions(const uint64_t *indices, const RtxObject *before, const RtxObject *now, uint64_t n, int64_t *objects_out,
                             RtxObjectMotion *motions_out, uint64_t *m_out);
+
+/* Guided upsampling: a frame rendered at 1/s of the output resolution (wl x hl = width / s x height / s, the same camera) is
+ * reconstructed at width x height, guided by the RtxPixelFeatures of both sizes (a joint bilateral upsampling: the four low pixels
+ * around an output pixel, tent weights times the denoiser's normal, depth and albedo weights).  What makes the construction exact is the
+ * reference's pixel map: render() gives pixel x of a w-wide frame the angle fov * (x / w - 0.5) -- pixel corners -- with
+ * vfov = h / w * fov, so pixel (X, Y) of the wl x hl frame has the zero-offset ray of pixel (s X, s Y) of the width x height frame bit
+ * for bit (X / wl and s X / width are correctly rounded quotients of the same rational, and so are hl / wl and height / width): the low
+ * frame is a sampling of the output frame's own lattice {(s X, s Y)}.  That identity needs s to divide both sizes, which is why any
+ * other width or height is refused.  Only the lens jitter of the two frames differs (the RNG key uses y * width + x).
+ * The call takes no scene handle, allocates nothing and only enqueues ONE launch on `stream` (a hipStream_t; NULL = the device's null
+ * stream).  d_lo_rgb is what rtx_render_blocks_accumulate, rtx_temporal_accumulate_device or rtx_denoise_device left of the low frame,
+ * d_lo_var its variance of the mean; d_out feeds rtx_quantize_image_device.
+ *
+ * This comment is the specification: every operation below is one separately rounded f64 operation (IEEE add, subtract, multiply,
+ * divide; never fused), in exactly the written order and bracketing, so plain numpy (tests/upsample_model.py) gives the same bits.
+ * Comparisons with a NaN are false.  "finite" means neither NaN nor an infinity.  s = factor; D = the flag RTX_UPSAMPLE_DEMODULATE;
+ * V = (d_lo_var != NULL).  The output pixel is p = (x, y) with a = albedo, e = emission, n = normal, z = depth of d_features[y * width
+ * + x]; low pixel Q = (X, Y) has a_Q, e_Q, n_Q, z_Q of d_lo_features[Y * wl + X], c_Q = d_lo_rgb[3 (Y * wl + X) ..], var_Q likewise.
+ *
+ * A tap's values, per channel k (the denoiser's preparation):
+ *     D:      u_Q,k = a_Q,k > albedo_min ? (c_Q,k - e_Q,k) / a_Q,k : c_Q,k - e_Q,k
+ *             V: v_Q,k = a_Q,k > albedo_min ? var_Q,k / (a_Q,k * a_Q,k) : var_Q,k
+ *     not D:  u_Q,k = c_Q,k                                       V: v_Q,k = var_Q,k
+ * Channel k of tap Q is USABLE when u_Q,k is finite and, under D, a_Q,k > albedo_min (a channel whose albedo is zero carries no
+ * irradiance, only c - e, which is about 0).
+ *
+ * X0 = x / s, Y0 = y / s (integer division), rx = x - s * X0, ry = y - s * Y0, fx = (double)rx / (double)s, fy = (double)ry / (double)s.
+ *   - A lattice pixel (rx == 0 && ry == 0): u_k = u_Q,k and v_k = v_Q,k of Q = (X0, Y0), moved without arithmetic, where the channel is
+ *     usable; else u_k = v_k = +0.0.
+ *   - Any other pixel: tc_k = tw_k = tv_k = sc_k = sw_k = sv_k = +0.0, then for j = 0, 1 (outer) and i = 0, 1 (inner) the tap
+ *     Q = (X0 + i, Y0 + j):
+ *       h  = (i ? fx : 1 - fx) * (j ? fy : 1 - fy)                                                      (the tent weight)
+ *       the tap is skipped when Q lies outside the low frame or h == 0; else
+ *       wn, wz, wa = the denoiser's three weights (above: "wn = 1 when normal_power_log2 == RTX_DENOISE_NO_NORMAL, else ...", "wz = 1
+ *            when sigma_depth == +inf; else ...", "wa = 1 when sigma_albedo == +inf; else ..."), word for word, with n_p, z_p, a_p =
+ *            n, z, a of the output pixel and n_q, z_q, a_q = n_Q, z_Q, a_Q
+ *       w  = ((h * wn) * wz) * wa
+ *       per usable channel k:  tc_k = tc_k + h * u_Q,k,  tw_k = tw_k + h,  V: tv_k = tv_k + (h * h) * v_Q,k
+ *       and, when w > 0, also: sc_k = sc_k + w * u_Q,k,  sw_k = sw_k + w,  V: sv_k = sv_k + (w * w) * v_Q,k
+ *     then per channel k:
+ *       sw_k > min_weight * tw_k:   u_k = sc_k / sw_k,  V: v_k = sv_k / (sw_k * sw_k)       (the guided sum)
+ *       else tw_k > 0:              u_k = tc_k / tw_k,  V: v_k = tv_k / (tw_k * tw_k)       (the tent sum: no tap resembles p enough)
+ *       else:                       u_k = v_k = +0.0                                        (no usable tap)
+ * Output.  D: d_out[3 p + k] = a_k > albedo_min ? u_k * a_k + e_k : e_k (the multiply is rounded, then the add); V: d_var_out[3 p + k]
+ * = a_k > albedo_min ? v_k * (a_k * a_k) : +0.0.  Not D: d_out = u, d_var_out = v.  The second arm under D is e_k, not the denoiser's
+ * u_k + e_k: a surface whose albedo is zero in a channel returns exactly its emission there (render_ray multiplies the light by the base
+ * colour), and a pixel whose samples all miss has a = e = 0, so a black channel and a missed pixel come out as the render would give
+ * them, whatever their neighbours hold.  With s == 1 every pixel is a lattice pixel: without D, d_out is a byte copy of d_lo_rgb
+ * wherever that is finite.
+ * d_var_out is the variance of the weighted mean of independent taps; neighbouring OUTPUT pixels share taps, and the result ignores
+ * that correlation: it is not the variance a filter over d_out may assume independent.
+ *
+ * Buffers.  d_lo_rgb: wl * hl * 3 doubles; d_lo_var (may be NULL) the same; d_lo_features: wl * hl records; d_features: width * height
+ * records; d_out: width * height * 3 doubles; d_var_out (may be NULL; must be NULL when d_lo_var is) the same.
+ * RTX_ERR_INVALID_ARGUMENT, decided before any device is looked for: a NULL params, d_lo_rgb, d_lo_features, d_features or d_out; a
+ * d_var_out without d_lo_var; any overlap among the inputs and outputs; width * height == 0 or >= 2^32 - 16; factor == 0 or >
+ * RTX_UPSAMPLE_MAX_FACTOR; width or height not a multiple of factor; a flag bit other than RTX_UPSAMPLE_DEMODULATE; reserved != 0;
+ * normal_power_log2 > 8 and not RTX_DENOISE_NO_NORMAL; a sigma that is NaN or <= 0 (+inf is allowed: it deletes the term, no
+ * arithmetic); albedo_min or min_weight NaN, negative or infinite.
+ * Out of scope: factors that are not integers or do not divide the frame; multi-device frames (gather first); more than 2 x 2 taps;
+ * upsampling history or pick buffers.  (DESIGN.md 3.17 "Guided upsampling".) */
+#define RTX_UPSAMPLE_MAX_FACTOR 8
+#define RTX_UPSAMPLE_DEMODULATE 1u
+typedef struct RtxUpsampleParams {
+    uint32_t factor;             /* s, 1..RTX_UPSAMPLE_MAX_FACTOR: output pixels per low pixel along each axis */
+    uint32_t flags;              /* RTX_UPSAMPLE_DEMODULATE or 0 */
+    uint32_t normal_power_log2;  /* 0..8 or RTX_DENOISE_NO_NORMAL, the denoiser's meaning */
+    uint32_t reserved;           /* must be 0 */
+    double   sigma_depth;        /* > 0, relative depth difference at which the weight is 1/2; +inf: no depth term */
+    double   sigma_albedo;       /* > 0, albedo distance at which the weight is 1/2; +inf: no albedo term */
+    double   albedo_min;         /* >= 0, finite: channels with albedo at or below it are not demodulated and carry no irradiance */
+    double   min_weight;         /* >= 0, finite: below this share of the tent weight the guided sum is not trusted */
+} RtxUpsampleParams;
+RTX_STATIC_ASSERT(sizeof(RtxUpsampleParams) == 48 && offsetof(RtxUpsampleParams, flags) == 4 && offsetof(RtxUpsampleParams, normal_power_log2) == 8 &&
+                  offsetof(RtxUpsampleParams, reserved) == 12 && offsetof(RtxUpsampleParams, sigma_depth) == 16 &&
+                  offsetof(RtxUpsampleParams, sigma_albedo) == 24 && offsetof(RtxUpsampleParams, albedo_min) == 32 &&
+                  offsetof(RtxUpsampleParams, min_weight) == 40, "RtxUpsampleParams layout");
+
+/* The defaults (DESIGN.md 3.17 records how they were chosen): factor 2, RTX_UPSAMPLE_DEMODULATE, normal_power_log2 = 2, sigma_depth =
+ * 0.05, sigma_albedo = 0.5, albedo_min = 1e-3, min_weight = 1e-3. */
+void     rtx_upsample_default_params(RtxUpsampleParams *out);
+int32_t  rtx_upsample_device(const double *d_lo_rgb, const double *d_lo_var, const RtxPixelFeatures *d_lo_features,
+                             const RtxPixelFeatures *d_features, uint32_t width, uint32_t height, const RtxUpsampleParams *params,
+                             double *d_out, double *d_var_out, int32_t device, void *stream);
+/* One-shot host form (device 0: allocates, copies, upsamples, copies back), as rtx_denoise.  Every pointer is a HOST array; lo_var and
+ * var_out may be NULL as above. */
+int32_t  rtx_upsample(const double *lo_rgb, const double *lo_var, const RtxPixelFeatures *lo_features, const RtxPixelFeatures *features,
+                      uint32_t width, uint32_t height, const RtxUpsampleParams *params, double *out, double *var_out);
 
 /* Test hook (lab library; the product returns RTX_ERR_UNSUPPORTED -- same sources and flags, so the arithmetic it shows is the
  * product's): evaluates one f64 operation per element on the device (op 0: a/b, 1: sqrt(a),

@@ -25,6 +25,7 @@ from .abi import (OBJECT_DTYPE, RTX_KERNEL_WAVEFRONT, RTX_KERNEL_AUTO, RTX_KERNE
                   RTX_PLANE, RTX_SPHERE, RTX_TRIANGLE, RtxError, load_library, RAY_DTYPE, HIT_DTYPE, FEATURE_DTYPE)
 from .abi import DENOISE_PARAMS_DTYPE, RTX_DENOISE_DEMODULATE, RTX_DENOISE_MAX_PASSES, RTX_DENOISE_NO_NORMAL, TEMPORAL_PARAMS_DTYPE
 from .abi import OBJECT_MOTION_DTYPE, RTX_MOTION_LOST
+from .abi import UPSAMPLE_PARAMS_DTYPE, RTX_UPSAMPLE_DEMODULATE, RTX_UPSAMPLE_MAX_FACTOR
 
 __all__ = ["LabKernel", "Vector3", "Material", "Sphere", "Plane", "Triangle", "Object", "Config", "Camera", "Scene",
            "SceneHandle", "RtxError", "device_count", "pack_objects", "OBJECT_DTYPE",
@@ -32,7 +33,7 @@ __all__ = ["LabKernel", "Vector3", "Material", "Sphere", "Plane", "Triangle", "O
            "RAY_DTYPE", "HIT_DTYPE", "FEATURE_DTYPE", "make_rays", "denoise", "denoise_params", "denoise_work_bytes", "DENOISE_PARAMS_DTYPE",
            "RTX_DENOISE_DEMODULATE", "RTX_DENOISE_MAX_PASSES", "RTX_DENOISE_NO_NORMAL", "temporal_params", "temporal_tables",
            "temporal_accumulate", "TEMPORAL_PARAMS_DTYPE", "Temporal", "object_motions", "rewind_hits", "OBJECT_MOTION_DTYPE",
-           "RTX_MOTION_LOST"]
+           "RTX_MOTION_LOST", "upsample", "upsample_params", "UPSAMPLE_PARAMS_DTYPE", "RTX_UPSAMPLE_DEMODULATE", "RTX_UPSAMPLE_MAX_FACTOR"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -404,6 +405,48 @@ def denoise(img, features, variance=None, **params):
     var_out = None if var is None else np.zeros_like(img)
     abi.check(lib.rtx_denoise(img.ctypes.data, var.ctypes.data if var is not None else None, f.ctypes.data, width, height, p.ctypes.data,
                               out.ctypes.data, var_out.ctypes.data if var_out is not None else None), lib)
+    return out if var is None else (out, var_out)
+
+
+def upsample_params(lib=None, **fields):
+    """One RtxUpsampleParams record (UPSAMPLE_PARAMS_DTYPE, shape ()): the library's defaults (rtx_upsample_default_params) with the
+    given fields replaced.  Besides the struct's own fields: demodulate=True / False sets the flag, normal_power_log2=None means
+    RTX_DENOISE_NO_NORMAL, and a sigma of None means +inf (the term is off)."""
+    lib = lib or load_library()
+    p = np.zeros((), dtype=UPSAMPLE_PARAMS_DTYPE)
+    lib.rtx_upsample_default_params(p.ctypes.data)
+    for k, v in fields.items():
+        if k == "demodulate":
+            p["flags"] = (int(p["flags"]) | RTX_UPSAMPLE_DEMODULATE) if v else (int(p["flags"]) & ~RTX_UPSAMPLE_DEMODULATE)
+        elif k == "normal_power_log2" and v is None:
+            p[k] = RTX_DENOISE_NO_NORMAL
+        elif k in ("sigma_depth", "sigma_albedo") and v is None:
+            p[k] = np.inf
+        elif k in UPSAMPLE_PARAMS_DTYPE.names:
+            p[k] = v
+        else:
+            raise TypeError("upsample: unknown parameter %r" % k)
+    return p
+
+
+def upsample(lo_rgb, lo_features, features, factor, variance=None, **params):
+    """The guided upsampling of include/rtx_hip.h ("Guided upsampling") on host arrays (rtx_upsample: device 0, copies both ways).
+    lo_rgb: the (hl, wl, 3) float64 low frame; lo_features / features: what Scene.features / SceneHandle.features returned for the low
+    frame and for the (hl * factor, wl * factor) output frame of the same camera (or the RtxPixelFeatures records); variance: the low
+    frame's per-channel variance of the mean, or None.  params: fields of RtxUpsampleParams over the library's defaults
+    (upsample_params).  Returns the output frame, and with a variance the pair (frame, variance)."""
+    lo = np.ascontiguousarray(lo_rgb, dtype=np.float64)
+    hl, wl, s = lo.shape[0], lo.shape[1], int(factor)
+    height, width = hl * s, wl * s
+    lib = load_library()
+    p = upsample_params(lib, factor=s, **params)
+    fl = _features_records(lo_features, hl, wl)
+    f = _features_records(features, height, width)
+    var = None if variance is None else np.ascontiguousarray(variance, dtype=np.float64).reshape(lo.shape)
+    out = np.zeros((height, width, 3))
+    var_out = None if var is None else np.zeros((height, width, 3))
+    abi.check(lib.rtx_upsample(lo.ctypes.data, var.ctypes.data if var is not None else None, fl.ctypes.data, f.ctypes.data, width, height,
+                               p.ctypes.data, out.ctypes.data, var_out.ctypes.data if var_out is not None else None), lib)
     return out if var is None else (out, var_out)
 
 
@@ -1053,6 +1096,46 @@ class SceneHandle:
         self._check(self._lib.rtx_denoise_device(ptr(d_rgb_ptr), ptr(d_var_ptr), ptr(d_features_ptr), int(width), int(height), p.ctypes.data,
                                                  ptr(d_out_ptr), ptr(d_var_out_ptr), ptr(d_work_ptr), self.device, ptr(stream)))
 
+    def upsample_device(self, width, height, d_lo_rgb_ptr, d_lo_features_ptr, d_features_ptr, d_out_ptr, d_lo_var_ptr=None,
+                        d_var_out_ptr=None, stream=None, params=None, **kw):
+        """rtx_upsample_device on this handle's device: width x height is the OUTPUT frame; the low frame and its features are
+        (height / factor) x (width / factor).  Every pointer a device address.  One launch, only enqueued on `stream`.  params: an
+        upsample_params record, or its fields as keywords (factor among them)."""
+        p = params if params is not None else upsample_params(self._lib, **kw)
+        ptr = lambda a: C.c_void_p(int(a)) if a else None
+        self._check(self._lib.rtx_upsample_device(ptr(d_lo_rgb_ptr), ptr(d_lo_var_ptr), ptr(d_lo_features_ptr), ptr(d_features_ptr),
+                                                  int(width), int(height), p.ctypes.data, ptr(d_out_ptr), ptr(d_var_out_ptr), self.device,
+                                                  ptr(stream)))
+
+    def _upsample_frame(self, lo, var, factor, params, return_features=False):
+        """Progressive.upsample / Temporal.upsample: the low frame `lo` (hl, wl, 3; a torch tensor on this handle's device, or a host
+        array) and its variance (or None) with this handle's pixel features at both sizes through rtx_upsample_device -> the
+        (hl * factor, wl * factor, 3) torch frame, on the device.  return_features=True: -> (frame, low features, output features),
+        the two RtxPixelFeatures buffers of the call as uint8 tensors; otherwise they are freed with the call."""
+        import torch
+        s = int(factor)
+        if not isinstance(lo, torch.Tensor):
+            lo = torch.from_numpy(np.ascontiguousarray(lo, dtype=np.float64))
+        lo = lo.to(device=torch.device("cuda", self.device), dtype=torch.float64)
+        if lo.dim() != 3 or lo.shape[2] != 3:
+            raise ValueError("upsample: the low frame must be (height, width, 3)")
+        hl, wl = int(lo.shape[0]), int(lo.shape[1])
+        h, w = hl * s, wl * s
+        dev = lo.device
+        p = upsample_params(self._lib, factor=s, **params)
+        lo = lo.contiguous()
+        var = None if var is None else var.contiguous()
+        feat_lo = torch.empty(hl * wl * FEATURE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        feat = torch.empty(h * w * FEATURE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        out = torch.empty((h, w, 3), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        self.pixel_features(wl, hl, feat_lo.data_ptr(), want_stats=True)
+        self.pixel_features(w, h, feat.data_ptr(), want_stats=True)
+        self.upsample_device(w, h, lo.data_ptr(), feat_lo.data_ptr(), feat.data_ptr(), out.data_ptr(),
+                             d_lo_var_ptr=var.data_ptr() if var is not None else None, params=p)
+        torch.cuda.synchronize(dev)
+        return (out, feat_lo, feat) if return_features else out
+
     def temporal_accumulate_device(self, width, height, d_rgb_ptr, d_hits_ptr, d_out_rgb_ptr, d_out_len_ptr, d_var_ptr=None,
                                    d_out_var_ptr=None, d_motion_ptr=None, history=None, stream=None, params=None, **kw):
         """rtx_temporal_accumulate_device on this handle's device: every pointer a device address of a full [height][width] frame.
@@ -1191,10 +1274,11 @@ class Progressive:
         n = self.count.to(self.sum.dtype)[..., None]
         return ((self.sum_sq - self.sum * self.sum / n) / (n - 1.0) / n).cpu().numpy()
 
-    def denoise(self, **params):
+    def denoise(self, on_device=False, **params):
         """The frame so far through the denoiser, on the device: the mean, the variance of the mean (when moments=True and every pixel
         has two samples or more; else no colour term) and the handle's pixel features (at its rays_per_pixel) go to
-        rtx_denoise_device.  params: fields of RtxDenoiseParams over the defaults (denoise_params).  -> numpy (h, w, 3)"""
+        rtx_denoise_device.  params: fields of RtxDenoiseParams over the defaults (denoise_params).  -> numpy (h, w, 3), or with
+        on_device=True the torch tensor on the device"""
         import torch
         dev = self.sum.device
         n = self.count.to(self.sum.dtype)[..., None]
@@ -1212,7 +1296,23 @@ class Progressive:
         self._hnd.denoise_device(self.width, self.height, mean.data_ptr(), feat.data_ptr(), out.data_ptr(), work.data_ptr(),
                                  d_var_ptr=var.data_ptr() if var is not None else None, params=p)
         torch.cuda.synchronize(dev)
-        return out.cpu().numpy()
+        return out if on_device else out.cpu().numpy()
+
+    def upsample(self, factor, frame=None, return_features=False, **params):
+        """This frame as the low frame of a (height * factor, width * factor) output: the mean so far with the variance of the mean
+        (when moments=True and every pixel has two samples or more), or `frame` -- a torch tensor on the device, e.g.
+        denoise(on_device=True), or a host array -- without a variance, and the handle's pixel features at both sizes (at its
+        rays_per_pixel) go to rtx_upsample_device.
+        params: fields of RtxUpsampleParams over the defaults (upsample_params).  -> torch (h * factor, w * factor, 3) on the device;
+        return_features=True: -> (frame, low features, output features), the call's two RtxPixelFeatures buffers as uint8 tensors"""
+        if frame is not None:
+            lo, var = frame, None
+        else:
+            n = self.count.to(self.sum.dtype)[..., None]
+            lo, var = self.sum / n, None
+            if self.sum_sq is not None and int(self.count.min()) >= 2:
+                var = (self.sum_sq - self.sum * self.sum / n) / (n - 1.0) / n
+        return self._hnd._upsample_frame(lo, var, factor, params, return_features)
 
 
 class Temporal:
@@ -1360,9 +1460,10 @@ class Temporal:
         self._need()
         return self._motion.cpu().numpy()
 
-    def denoise(self, **params):
+    def denoise(self, on_device=False, **params):
         """The accumulated mean and its variance (when tracked; else no colour term) with the handle's pixel features (at its
-        rays_per_pixel) through rtx_denoise_device, on the device.  params: fields of RtxDenoiseParams.  -> numpy (h, w, 3)"""
+        rays_per_pixel) through rtx_denoise_device, on the device.  params: fields of RtxDenoiseParams.  -> numpy (h, w, 3), or with
+        on_device=True the torch tensor on the device"""
         import torch
         mean, var = self._need()[0], self._need()[1]
         dev = self._dev
@@ -1376,7 +1477,18 @@ class Temporal:
         self._hnd.denoise_device(self.width, self.height, mean.data_ptr(), feat.data_ptr(), out.data_ptr(), work.data_ptr(),
                                  d_var_ptr=var.data_ptr() if var is not None else None, params=p)
         torch.cuda.synchronize(dev)
-        return out.cpu().numpy()
+        return out if on_device else out.cpu().numpy()
+
+    def upsample(self, factor, frame=None, return_features=False, **params):
+        """The accumulated frame as the low frame of a (height * factor, width * factor) output: the accumulated mean with its variance
+        (when tracked), or `frame` -- a torch tensor on the device, e.g. denoise(on_device=True), or a host array -- without a variance, and
+        the handle's pixel features at both sizes through rtx_upsample_device.  params: fields of RtxUpsampleParams.  -> torch
+        (h * factor, w * factor, 3) on the device; return_features=True: -> (frame, low features, output features)"""
+        if frame is not None:
+            lo, var = frame, None
+        else:
+            lo, var = self._need()[:2]
+        return self._hnd._upsample_frame(lo, var, factor, params, return_features)
 
 
 HOST_SCENE_STATS = ("spheres", "triangles", "tri_filter_records", "tri_in_tree", "wide_nodes", "depth", "binary_nodes", "flags",

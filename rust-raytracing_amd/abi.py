@@ -35,6 +35,7 @@ RTX_UPDATE_AUTO, RTX_UPDATE_REBUILD, RTX_UPDATE_DEFORM = 0, 1, 2
 RTX_UPDATED_NOTHING, RTX_UPDATED_RECORDS, RTX_UPDATED_REFIT, RTX_UPDATED_REBUILT = 0, 1, 2, 3
 RTX_MULTI_HIT_MAX = 32                       # rtx_scene_multi_hits: 1 <= k <= this
 RTX_DENOISE_MAX_PASSES, RTX_DENOISE_DEMODULATE, RTX_DENOISE_NO_NORMAL = 8, 1, 0xFFFFFFFF   # RtxDenoiseParams
+RTX_UPSAMPLE_MAX_FACTOR, RTX_UPSAMPLE_DEMODULATE = 8, 1                                     # RtxUpsampleParams
 RTX_OK, RTX_ERR_INVALID_ARGUMENT, RTX_ERR_NO_DEVICE, RTX_ERR_HIP, RTX_ERR_UNSUPPORTED, RTX_ERR_OUT_OF_MEMORY = range(6)
 
 # RtxObject, 136 bytes: one entry of Scene.objects (scene.rs:80; object.rs:9-15,78-86)
@@ -88,6 +89,11 @@ class RtxDenoiseParams(C.Structure):
                 ("albedo_min", C.c_double)]
 
 
+class RtxUpsampleParams(C.Structure):
+    _fields_ = [("factor", C.c_uint32), ("flags", C.c_uint32), ("normal_power_log2", C.c_uint32), ("reserved", C.c_uint32),
+                ("sigma_depth", C.c_double), ("sigma_albedo", C.c_double), ("albedo_min", C.c_double), ("min_weight", C.c_double)]
+
+
 class RtxTemporalParams(C.Structure):
     _fields_ = [("alpha_min", C.c_double), ("max_history", C.c_double), ("plane_tolerance", C.c_double), ("normal_min", C.c_double),
                 ("min_weight", C.c_double), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
@@ -114,6 +120,9 @@ assert DENOISE_PARAMS_DTYPE.itemsize == C.sizeof(RtxDenoiseParams) == 56
 TEMPORAL_PARAMS_DTYPE = np.dtype([("alpha_min", "<f8"), ("max_history", "<f8"), ("plane_tolerance", "<f8"), ("normal_min", "<f8"),
                                   ("min_weight", "<f8"), ("flags", "<u4"), ("reserved", "<u4")])
 assert TEMPORAL_PARAMS_DTYPE.itemsize == C.sizeof(RtxTemporalParams) == 48
+UPSAMPLE_PARAMS_DTYPE = np.dtype([("factor", "<u4"), ("flags", "<u4"), ("normal_power_log2", "<u4"), ("reserved", "<u4"),
+                                  ("sigma_depth", "<f8"), ("sigma_albedo", "<f8"), ("albedo_min", "<f8"), ("min_weight", "<f8")])
+assert UPSAMPLE_PARAMS_DTYPE.itemsize == C.sizeof(RtxUpsampleParams) == 48
 OBJECT_MOTION_DTYPE = np.dtype([("kind", "<u4"), ("reserved", "<u4"), ("now", "<f8", (9,)), ("before", "<f8", (9,))])
 assert OBJECT_MOTION_DTYPE.itemsize == C.sizeof(RtxObjectMotion) == 152
 
@@ -182,6 +191,10 @@ SYMBOLS = [
                                            C.c_void_p]),
     ("rtx_rewind_hits", C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     ("rtx_object_motions", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rtx_upsample_default_params", None, [C.c_void_p]),
+    ("rtx_upsample_device", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int32, C.c_void_p]),
+    ("rtx_upsample", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rtx_debug_math", C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
     ("rtx_debug_paths", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("rtx_debug_store_samples", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),

@@ -25,10 +25,10 @@ LAB_LIB = os.path.join(HERE, "librtx_hip_lab.so")
 OBJ_DIR = os.path.join(HERE, "build")
 SOURCES = ["rtx_kernels.hip", "rtx_bvh_spheres.hip", "rtx_bvh_mesh.hip", "rtx_wavefront.hip", "rtx_query.hip", "rtx_update.hip", "rtx_pack.hip",
            "rtx_api.hip", "rtx_api_update.hip", "rtx_api_debug.hip", "rtx_denoise.hip", "rtx_temporal.hip",
-           "rtx_rewind.hip"]
+           "rtx_rewind.hip", "rtx_upsample.hip"]
 HEADERS = ["rtx_math.h", "rtx_scene.h", "rtx_bvh.h", "rtx_device.h", "rtx_traverse.h", "rtx_mesh_step.h", "rtx_wavefront.h",
            "rtx_launch.h", "rtx_refit.h", "rtx_pack.h", "rtx_host.h", "rtx_spk_units.h", "rtx_spk_pool.h", "rtx_denoise.h", "rtx_temporal.h",
-           "rtx_rewind.h"]
+           "rtx_rewind.h", "rtx_upsample.h"]
 # -ffp-contract=off: the exact path must round like the reference (Rust never fuses a*b+c);
 # the f32 filter asks for FMAs explicitly.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",

@@ -19,6 +19,30 @@ constexpr size_t kDnLdsBytes = (size_t)kDnPlanes * kDnStaged * sizeof(double);  
 __device__ __forceinline__ bool dn_finite(double x) { return __builtin_fabs(x) < __builtin_inf(); }
 __device__ __forceinline__ double dn_b3(int i) { return i == 2 ? 0.375 : ((i == 1 || i == 3) ? 0.25 : 0.0625); }
 
+// The three guide weights of a tap q against the centre p, in the header's words; the upsampler (rtx_upsample.h) takes the same three.
+__device__ __forceinline__ double dn_weight_normal(const double np[3], double nq0, double nq1, double nq2, uint32_t power_log2)
+{
+    double t = (np[0] * nq0 + np[1] * nq1) + np[2] * nq2;
+    t = t > 0.0 ? t : 0.0;
+    for (uint32_t j = 0; j < power_log2; ++j) t = t * t;
+    return t;
+}
+__device__ __forceinline__ double dn_weight_depth(double zp, bool zp_fin, double zq, double sigma_depth)
+{
+    const bool zq_fin = dn_finite(zq);
+    if (zp_fin && zq_fin) {
+        const double r = (zp - zq) / (sigma_depth * (zp + zq));
+        return 1.0 / (1.0 + r * r);
+    }
+    return (zp_fin == zq_fin) ? 1.0 : 0.0;
+}
+__device__ __forceinline__ double dn_weight_albedo(const double ap[3], double aq0, double aq1, double aq2, double sigma_albedo2)
+{
+    const double d0 = ap[0] - aq0, d1 = ap[1] - aq1, d2 = ap[2] - aq2;
+    const double da = (d0 * d0 + d1 * d1) + d2 * d2;
+    return 1.0 / (1.0 + da / sigma_albedo2);
+}
+
 // form kEpilogueDenoisePrepare: one pixel per thread, (rgb, var, features) -> the record
 __device__ __forceinline__ void denoise_prepare(const DenoiseArgs &d)
 {
@@ -112,27 +136,9 @@ __device__ __forceinline__ void denoise_pass(const DenoiseArgs &d, double *lds)
                     const long long qx = x + dx * s, qy = y + dy * s;
                     if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
                     double wn = 1.0, wz = 1.0, wa = 1.0, wc = 1.0;
-                    if (d.flags & kDnNormal) {
-                        double t = (np[0] * lds[7 * N + c] + np[1] * lds[8 * N + c]) + np[2] * lds[9 * N + c];
-                        t = t > 0.0 ? t : 0.0;
-                        for (uint32_t j = 0; j < d.normal_power_log2; ++j) t = t * t;
-                        wn = t;
-                    }
-                    if (d.flags & kDnDepth) {
-                        const double zq = lds[6 * N + c];
-                        const bool zq_fin = dn_finite(zq);
-                        if (zp_fin && zq_fin) {
-                            const double r = (zp - zq) / (d.sigma_depth * (zp + zq));
-                            wz = 1.0 / (1.0 + r * r);
-                        } else {
-                            wz = (zp_fin == zq_fin) ? 1.0 : 0.0;
-                        }
-                    }
-                    if (d.flags & kDnAlbedo) {
-                        const double d0 = ap[0] - lds[10 * N + c], d1 = ap[1] - lds[11 * N + c], d2 = ap[2] - lds[12 * N + c];
-                        const double da = (d0 * d0 + d1 * d1) + d2 * d2;
-                        wa = 1.0 / (1.0 + da / d.sigma_albedo2);
-                    }
+                    if (d.flags & kDnNormal) wn = dn_weight_normal(np, lds[7 * N + c], lds[8 * N + c], lds[9 * N + c], d.normal_power_log2);
+                    if (d.flags & kDnDepth) wz = dn_weight_depth(zp, zp_fin, lds[6 * N + c], d.sigma_depth);
+                    if (d.flags & kDnAlbedo) wa = dn_weight_albedo(ap, lds[10 * N + c], lds[11 * N + c], lds[12 * N + c], d.sigma_albedo2);
                     if (d.flags & kDnColor) {
                         const double d0 = up[0] - lds[0 * N + c], d1 = up[1] - lds[1 * N + c], d2 = up[2] - lds[2 * N + c];
                         const double dd = (d0 * d0 + d1 * d1) + d2 * d2;

@@ -12,7 +12,8 @@
 //                       wave ballot + mbcnt prefix sum (one atomic per workgroup per round).
 //   resolve_kernel      left fold of a pixel's samples in sample order, then / rays_per_pixel.
 //   epilogue_kernel     render_to_image's quantize, the multi-device gather, the two forms of the denoiser (rtx_denoise.h), the
-//                       temporal accumulation (rtx_temporal.h) and the rewind of a pick buffer (rtx_rewind.h), by a launch-uniform form.
+//                       temporal accumulation (rtx_temporal.h), the rewind of a pick buffer (rtx_rewind.h) and the guided upsampling
+//                       (rtx_upsample.h), by a launch-uniform form.
 //
 // Compiled with -ffp-contract=off; the f32 filter uses explicit fmaf.
 #include "rtx_launch.h"
@@ -20,6 +21,7 @@
 #include "rtx_denoise.h"
 #include "rtx_temporal.h"
 #include "rtx_rewind.h"
+#include "rtx_upsample.h"
 
 #include <cstdlib>
 
@@ -674,13 +676,17 @@ __device__ __forceinline__ uint8_t rust_as_u8(double v)
 //   launched with dynamic LDS for its two sine tables when they fit kTemporalLdsBytes, else with none.
 // form 19 -- rtx_rewind_hits_device (rtx_rewind.h): everything it reads is in `rw`, which the other forms pass zeroed; it is launched
 //   with dynamic LDS for its list of moved objects when that fits kTemporalLdsBytes, else with none.
+// form 20 -- rtx_upsample_device (rtx_upsample.h): everything it reads is in `up`, which the other forms pass zeroed; it is launched
+//   with no LDS.
 constexpr uint32_t kEpilogueDenoisePrepare = 16u, kEpilogueDenoisePass = 17u, kEpilogueTemporal = 18u, kEpilogueRewind = 19u;
+constexpr uint32_t kEpilogueUpsample = 20u;
 extern __shared__ double epilogue_lds[];
 __global__ __launch_bounds__(256) void epilogue_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
                                                        uint32_t width, uint32_t height, uint32_t n, uint32_t cap_rows,
                                                        uint32_t block, uint32_t flip, uint32_t form, DenoiseArgs dn, TemporalArgs ta,
-                                                       RewindArgs rw)
+                                                       RewindArgs rw, UpsampleArgs up)
 {
+    if (form == kEpilogueUpsample) { upsample_pixel(up); return; }
     if (form == kEpilogueRewind) { rewind_hits(rw, epilogue_lds); return; }
     if (form == kEpilogueTemporal) { temporal_accumulate(ta, epilogue_lds); return; }
     if (form == kEpilogueDenoisePass) { denoise_pass(dn, epilogue_lds); return; }
@@ -872,7 +878,7 @@ hipError_t launch_quantize(const double *rgb, uint8_t *rgb8, uint32_t width, uin
     uint64_t npix = (uint64_t)width * height;
     if (npix == 0) return hipSuccess;
     hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, stream,
-                       reinterpret_cast<const uint8_t *>(rgb), rgb8, width, height, 1u, 0u, 1u, 1u, 0u, DenoiseArgs{}, TemporalArgs{}, RewindArgs{});
+                       reinterpret_cast<const uint8_t *>(rgb), rgb8, width, height, 1u, 0u, 1u, 1u, 0u, DenoiseArgs{}, TemporalArgs{}, RewindArgs{}, UpsampleArgs{});
     return hipGetLastError();
 }
 
@@ -881,7 +887,7 @@ hipError_t launch_quantize_values(const double *rgb, uint8_t *rgb8, uint32_t wid
     uint64_t npix = (uint64_t)width * n_rows;
     if (npix == 0) return hipSuccess;
     hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, stream,
-                       reinterpret_cast<const uint8_t *>(rgb), rgb8, width, n_rows, 1u, 0u, 1u, 0u, 0u, DenoiseArgs{}, TemporalArgs{}, RewindArgs{});
+                       reinterpret_cast<const uint8_t *>(rgb), rgb8, width, n_rows, 1u, 0u, 1u, 0u, 0u, DenoiseArgs{}, TemporalArgs{}, RewindArgs{}, UpsampleArgs{});
     return hipGetLastError();
 }
 
@@ -891,7 +897,7 @@ hipError_t launch_deinterleave(const double *parts, double *full, uint32_t width
     const uint64_t total = (uint64_t)width * height * 3;
     if (total == 0) return hipSuccess;
     hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, stream,
-                       reinterpret_cast<const uint8_t *>(parts), reinterpret_cast<uint8_t *>(full), width, height, n, cap_rows, block, 0u, 8u, DenoiseArgs{}, TemporalArgs{}, RewindArgs{});
+                       reinterpret_cast<const uint8_t *>(parts), reinterpret_cast<uint8_t *>(full), width, height, n, cap_rows, block, 0u, 8u, DenoiseArgs{}, TemporalArgs{}, RewindArgs{}, UpsampleArgs{});
     return hipGetLastError();
 }
 
@@ -901,7 +907,7 @@ hipError_t launch_deinterleave_u8(const uint8_t *parts, uint8_t *full, uint32_t 
     const uint64_t total = (uint64_t)width * height * 3;
     if (total == 0) return hipSuccess;
     hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, stream, parts, full, width,
-                       height, n, cap_rows, block, flip ? 1u : 0u, 1u, DenoiseArgs{}, TemporalArgs{}, RewindArgs{});
+                       height, n, cap_rows, block, flip ? 1u : 0u, 1u, DenoiseArgs{}, TemporalArgs{}, RewindArgs{}, UpsampleArgs{});
     return hipGetLastError();
 }
 
@@ -910,7 +916,7 @@ hipError_t launch_denoise_prepare(const DenoiseArgs &d, hipStream_t stream)
     const uint64_t npix = (uint64_t)d.width * d.height;
     if (npix == 0) return hipSuccess;
     hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, stream, nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u,
-                       kEpilogueDenoisePrepare, d, TemporalArgs{}, RewindArgs{});
+                       kEpilogueDenoisePrepare, d, TemporalArgs{}, RewindArgs{}, UpsampleArgs{});
     return hipGetLastError();
 }
 
@@ -928,7 +934,7 @@ hipError_t launch_denoise_pass(const DenoiseArgs &d_, hipStream_t stream)
     if (blocks >= (1ull << 31)) return hipErrorInvalidValue;
     d.tiles = (uint32_t)tiles;
     hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)blocks), dim3(256), kDnLdsBytes, stream, nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u,
-                       kEpilogueDenoisePass, d, TemporalArgs{}, RewindArgs{});
+                       kEpilogueDenoisePass, d, TemporalArgs{}, RewindArgs{}, UpsampleArgs{});
     return hipGetLastError();
 }
 
@@ -940,7 +946,7 @@ hipError_t launch_temporal(const TemporalArgs &t_, hipStream_t stream)
     const size_t table_bytes = ((size_t)t.width + 1u + (size_t)t.height + 1u) * sizeof(double);
     t.tables_in_lds = ((t.flags & kTaHistory) != 0u && table_bytes <= kTemporalLdsBytes) ? 1u : 0u;
     hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)((npix + 255) / 256)), dim3(256), t.tables_in_lds ? table_bytes : 0, stream, nullptr,
-                       nullptr, 0u, 0u, 0u, 0u, 0u, 0u, kEpilogueTemporal, DenoiseArgs{}, t, RewindArgs{});
+                       nullptr, 0u, 0u, 0u, 0u, 0u, 0u, kEpilogueTemporal, DenoiseArgs{}, t, RewindArgs{}, UpsampleArgs{});
     return hipGetLastError();
 }
 
@@ -951,7 +957,16 @@ hipError_t launch_rewind(const RewindArgs &r_, hipStream_t stream)
     const size_t list_bytes = (size_t)r.m * sizeof(long long);
     r.list_in_lds = (r.m != 0u && list_bytes <= kTemporalLdsBytes) ? 1u : 0u;
     hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)(((uint64_t)r.n + 255) / 256)), dim3(256), r.list_in_lds ? list_bytes : 0, stream, nullptr,
-                       nullptr, 0u, 0u, 0u, 0u, 0u, 0u, kEpilogueRewind, DenoiseArgs{}, TemporalArgs{}, r);
+                       nullptr, 0u, 0u, 0u, 0u, 0u, 0u, kEpilogueRewind, DenoiseArgs{}, TemporalArgs{}, r, UpsampleArgs{});
+    return hipGetLastError();
+}
+
+hipError_t launch_upsample(const UpsampleArgs &u, hipStream_t stream)
+{
+    const uint64_t npix = (uint64_t)u.width * u.height;
+    if (npix == 0) return hipSuccess;
+    hipLaunchKernelGGL(epilogue_kernel, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, stream, nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u,
+                       kEpilogueUpsample, DenoiseArgs{}, TemporalArgs{}, RewindArgs{}, u);
     return hipGetLastError();
 }
 

@@ -171,6 +171,19 @@ struct RewindArgs {
 };
 hipError_t launch_rewind(const RewindArgs &r, hipStream_t stream);             // sets list_in_lds in its copy of r
 
+// ---- guided upsampling (rtx_upsample_device; device text: rtx_upsample.h, host side: rtx_upsample.hip): one more launch-uniform form
+// of epilogue_kernel, one output pixel per thread, its arguments by value beside RewindArgs (the other forms pass them zeroed).  It asks
+// for no LDS: the low taps are gathered through the cache.
+struct UpsampleArgs {
+    const double *lo_rgb, *lo_var;                            // the low frame (lo_var: null without kDnVariance)
+    const QueryFeatures *lo_feat, *feat;                      // the guides of the low and of the output frame
+    double *out, *var_out;                                    // var_out: may be null
+    double sigma_depth, sigma_albedo2, albedo_min, min_weight;                 // (the square: one rounded multiply on the host)
+    uint32_t width, height, lo_width, lo_height;              // width = factor * lo_width, height = factor * lo_height
+    uint32_t factor, flags, normal_power_log2, pad;           // flags: kDnDemodulate, kDnVariance, kDnDepth, kDnAlbedo, kDnNormal
+};
+hipError_t launch_upsample(const UpsampleArgs &u, hipStream_t stream);
+
 // ---- ray queries (rtx_query.hip): closest_object for caller rays or for the pick buffer's zero-offset primary rays, or -- the
 // any-hit mode, a launch-uniform switch of the same kernel -- whether any object lies before a per-ray distance limit, or -- the
 // path mode, a third switch -- render_ray's colour of the path that starts with the ray, or -- the feature mode, a fourth -- the

@@ -135,6 +135,22 @@ pub struct RtxObjectMotion {
     pub before: [f64; 9],
 }
 
+/// `RtxUpsampleParams` (include/rtx_hip.h, "Guided upsampling"): fill it with `rtx_upsample_default_params`.  48 bytes.
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct RtxUpsampleParams {
+    pub factor: u32,
+    pub flags: u32,
+    pub normal_power_log2: u32,
+    pub reserved: u32,
+    pub sigma_depth: f64,
+    pub sigma_albedo: f64,
+    pub albedo_min: f64,
+    pub min_weight: f64,
+}
+pub const RTX_UPSAMPLE_MAX_FACTOR: u32 = 8;
+pub const RTX_UPSAMPLE_DEMODULATE: u32 = 1;
+
 #[repr(C)]
 pub struct RtxSceneHandleOpaque {
     _private: [u8; 0],
@@ -187,6 +203,9 @@ extern "C" {
     pub fn rtx_rewind_hits_device(d_hits: *const RtxHit, n_hits: u64, d_objects: *const i64, d_motions: *const RtxObjectMotion, m: u64, flags: u32, d_out: *mut RtxHit, device: i32, stream: *mut c_void) -> i32;
     pub fn rtx_rewind_hits(hits: *const RtxHit, n_hits: u64, objects: *const i64, motions: *const RtxObjectMotion, m: u64, out: *mut RtxHit) -> i32;
     pub fn rtx_object_motions(indices: *const u64, before: *const RtxObject, now: *const RtxObject, n: u64, objects_out: *mut i64, motions_out: *mut RtxObjectMotion, m_out: *mut u64) -> i32;
+    pub fn rtx_upsample_default_params(out: *mut RtxUpsampleParams);
+    pub fn rtx_upsample_device(d_lo_rgb: *const f64, d_lo_var: *const f64, d_lo_features: *const RtxPixelFeatures, d_features: *const RtxPixelFeatures, width: u32, height: u32, params: *const RtxUpsampleParams, d_out: *mut f64, d_var_out: *mut f64, device: i32, stream: *mut c_void) -> i32;
+    pub fn rtx_upsample(lo_rgb: *const f64, lo_var: *const f64, lo_features: *const RtxPixelFeatures, features: *const RtxPixelFeatures, width: u32, height: u32, params: *const RtxUpsampleParams, out: *mut f64, var_out: *mut f64) -> i32;
     pub fn rtx_temporal_accumulate(rgb: *const f64, var: *const f64, hits: *const RtxHit, hist_rgb: *const f64, hist_var: *const f64, hist_len: *const f64, hist_hits: *const RtxHit, prev_camera: *const RtxCamera, width: u32, height: u32, params: *const RtxTemporalParams, out_rgb: *mut f64, out_var: *mut f64, out_len: *mut f64, motion: *mut f64) -> i32;
 }
 
